@@ -11,6 +11,10 @@ are resident in HBM before the timed region.  Batches shard across GPUs with no 
 collective (weak scaling); the only RCCL call is the tiny residual-norm all-reduce.
 
 Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).
+
+A plain run sets up, warms up, times the --steps iterations, writes the outputs of the last one if --dump-outputs is given and
+prints the line.  Everything else it can measure -- the event-bracketed warm-up pass and the kernels sampled in the timed region
+(roofline, level0_kernels, hbm_path, --breakdown), the CPU baseline, the secondary configurations -- runs with --full only.
 """
 import argparse
 import json
@@ -416,6 +420,9 @@ def train_main(args, rank, world, dev, dist):
         same = bool(flag.item() == 1.0)
     if rank == 0:
         fwd_flop = 2.0 * unet_macs(n) * B * unroll
+        extra = {}
+        if args.dump_outputs:   # what the last training step leaves a caller: the updated weights, its gradient and loss
+            extra["outputs"] = dump_outputs(args.dump_outputs, {"weights": w[None], "gradient": g[None], "loss": o["loss"].reshape(1, -1)})
         print(json.dumps({
             "metric": f"training sample-iterations/sec (whole node), {n}^2 domain, batch={B} per GPU x {unroll} unrolled iterations",
             "value": round(world * B * unroll * K / dt, 1), "unit": "sample-iterations/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -425,7 +432,7 @@ def train_main(args, rank, world, dev, dist):
                                    "backward + gradient all-reduce (one 193 KB bucket, RCCL) + Adam", "options": args.opt,
                        "parallelism": f"dp{world} (each rank its own replay batch; one gradient all-reduce per step)"},
             "approx_tflops_forward_plus_backward": round(world * 3 * fwd_flop * K / dt / 1e12, 2), "loss_rank0": float(o["loss"][0]),
-            "replicas_bit_identical_after_run": same}), flush=True)
+            "replicas_bit_identical_after_run": same, **extra}), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -476,6 +483,31 @@ def spawn_ranks(n: int) -> int:
 
 
 STEP_COMPULSORY_BYTES_256 = 3751936.0   # read 4[(2+2+1) N^2 + 2 sum N_d^2] + write 4[(2+2) N^2 + 2 sum N_d^2] at N = 256
+SETTLE_STATE_ITERS = 640                # the settling loop's iterations the timed steps start after (a multiple of its 32)
+DUMP_CAP_BYTES = 60 * 10 ** 6           # --dump-outputs: array data in all (the files, headers included, stay under 64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: every array (leading dimension = the batch) as ``out_dir/<name>.npy`` in float32.  Beyond DUMP_CAP_BYTES in all, the
+    same fixed, seeded subset of batch entries of every array is written (whole samples, so each one kept compares field for field); an array
+    whose single sample is still too large is cut to a seeded subset of its elements.  Returns {name: shape written} and the batch entries kept."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    batch = min(a.shape[0] for a in host.values())
+    per_sample = sum(a[:1].nbytes for a in host.values())
+    keep = np.arange(batch)
+    if per_sample * batch > DUMP_CAP_BYTES:
+        rng = np.random.default_rng(DUMP_SEED)
+        keep = np.sort(rng.choice(batch, max(1, min(batch, DUMP_CAP_BYTES // per_sample)), replace=False))
+        host = {k: a[keep] for k, a in host.items()}
+        total = sum(a.nbytes for a in host.values())
+        if total > DUMP_CAP_BYTES:
+            frac = DUMP_CAP_BYTES / total
+            host = {k: a.reshape(-1)[np.sort(rng.choice(a.size, max(1, int(a.size * frac)), replace=False))] for k, a in host.items()}
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "arrays": {k: list(a.shape) for k, a in host.items()}, "batch_entries": keep.tolist()}
 
 
 def main():
@@ -495,14 +527,24 @@ def main():
                     help="library tuning knob for A/B runs (hn_set_option): deep=0, side_stream=0, ...")
     ap.add_argument("--settle", type=float, default=None, metavar="SECONDS",
                     help="keep the loop running untimed for this long right before the timed region (clock settling; default 0.3 s "
-                         "when --steps < 200, else 0); the iterations it adds are reported as warmup_extra / effective_warmup")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short 512^2 / bf16x3 side measurements")
-    ap.add_argument("--breakdown", action="store_true", help="also print the per-kernel time table (stderr)")
+                         "when --steps < 200, else 0; when on, at least 640 iterations, and the timed steps start from the state after "
+                         "exactly 640); the iterations it adds are reported as warmup_extra / effective_warmup")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the event-bracketed warm-up pass and the kernels sampled in the timed region "
+                         "(roofline, level0_kernels, hbm_path), the CPU baseline and the secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short 512^2 / bf16x3 side measurements")
+    ap.add_argument("--breakdown", action="store_true", help="with --full: also print the per-kernel time table (stderr)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--train", action="store_true",
                     help="time the data-parallel TRAINING step instead (96^2, batch 32 per GPU, 10 unrolled iterations, gradient all-reduce over RCCL); "
                          "a separate JSON line, not the headline metric")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full (it reads the event-bracketed warm-up pass)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)      # plain `python bench.py --gpus N`: this process never touches a GPU, its N children do
@@ -545,22 +587,25 @@ def main():
         eng.set_option(name, int(value))
     rmse = torch.zeros(max(K, W, 32), B, device=dev)
 
-    # warm-up, W untimed steps (at least 11): all but the last 8 with every kernel bracketed by events to find the
-    # dominant one (>= 3 passes: the first launch of a kernel is not representative), the last 8 as the timed region
+    # warm-up, W untimed steps (at least 11): all but the last 8 (with --full: with every kernel bracketed by events to find the
+    # dominant one; >= 3 passes: the first launch of a kernel is not representative), the last 8 as the timed region
     # will run them (graph replays)
+    full = args.full
     W1 = max(W - 8, 3)
-    eng.profile_enable(None)
+    if full:
+        eng.profile_enable(None)
     eng.step(wf, res, st, k_sq, src, W1, rmse_hist=rmse[:W1])
     torch.cuda.synchronize()
-    prof = eng.profile_collect()
-    pmin = eng.profile_min()    # shortest launch per kernel: the host cannot keep up with ~70 API calls per step
-    # candidates for the roofline block: the two longest kernels of the main chain in the fully bracketed warm-up pass; BOTH are sampled in
-    # the timed region and the block describes whichever is longer there (VERDICT r4 #5a; the other one is reported beside it when it is
-    # within 5 %).  The side-stream kernels (conv_state*) and the pair bracket are not candidates.
-    chain = {k: v for k, v in pmin.items() if not k.startswith("conv_state") and k != "spectral_pair"}
-    cand = sorted(chain, key=chain.get, reverse=True)[:2] if chain else ["decode0"]
-    cand_ids = [[i for i in range(eng.KERNEL_IDS) if eng.kernel_name(i) == k][0] for k in cand]
-    eng.profile_enable([])
+    if full:
+        prof = eng.profile_collect()
+        pmin = eng.profile_min()    # shortest launch per kernel: the host cannot keep up with ~70 API calls per step
+        # candidates for the roofline block: the two longest kernels of the main chain in the fully bracketed warm-up pass; BOTH are sampled in
+        # the timed region and the block describes whichever is longer there (VERDICT r4 #5a; the other one is reported beside it when it is
+        # within 5 %).  The side-stream kernels (conv_state*) and the pair bracket are not candidates.
+        chain = {k: v for k, v in pmin.items() if not k.startswith("conv_state") and k != "spectral_pair"}
+        cand = sorted(chain, key=chain.get, reverse=True)[:2] if chain else ["decode0"]
+        cand_ids = [[i for i in range(eng.KERNEL_IDS) if eng.kernel_name(i) == k][0] for k in cand]
+        eng.profile_enable([])
     # everything the timed region touches runs once before it: the captured iteration (graph instantiation), the
     # first reduction / collective of the process (code-object loads cost milliseconds on first use)
     eng.step(wf, res, st, k_sq, src, 8, rmse_hist=rmse[:8])   # (the first replays of a freshly instantiated graph are slow)
@@ -579,15 +624,26 @@ def main():
     # the settling loop comes LAST, straight in front of the barrier: a few hundred microseconds of idle GPU (the reduction above
     # ends in a host read-back) are enough for the clocks to drop, and the first ~10 ms afterwards then run ~9 % slow --
     # invisible at --steps 300, a tenth of a --steps 20 measurement
-    extra, t_w = 0, time.perf_counter()
+    # The loop runs at least SETTLE_STATE_ITERS iterations, and the timed steps start from the state after exactly that many of them,
+    # however long the loop runs on: with the same arguments every run times (and --dump-outputs writes) the same iterations of the
+    # same inputs, from a state as far along as a 0.3 s loop leaves the headline workload (the data affects speed by ~1 %).
+    extra, t_w, start = 0, time.perf_counter(), None
     settle_s = args.settle if args.settle is not None else (0.3 if K < 200 else 0.0)
-    while time.perf_counter() - t_w < settle_s:
+    while settle_s > 0 and (time.perf_counter() - t_w < settle_s or extra < SETTLE_STATE_ITERS):
         eng.step(wf, res, st, k_sq, src, 32, rmse_hist=rmse[:min(32, rmse.shape[0])] if rmse.shape[0] >= 32 else None)
         torch.cuda.synchronize()
         extra += 32
-    pair_id = [i for i in range(eng.KERNEL_IDS) if eng.kernel_name(i) == "spectral_pair"][0]
-    eng.profile_enable(cand_ids + [pair_id])          # host-side state only: the two candidate kernels and the spectral pair, sampled
-    eng.profile_stride(stride)
+        if extra == SETTLE_STATE_ITERS:
+            start = (wf.clone(), res.clone(), st.clone())
+    settled = min(extra, SETTLE_STATE_ITERS)
+    if start is not None:
+        for buf, saved in zip((wf, res, st), start):   # device copies on the launch stream (the same buffers: captured graphs stay valid)
+            buf.copy_(saved)
+        del start
+    if full:
+        pair_id = [i for i in range(eng.KERNEL_IDS) if eng.kernel_name(i) == "spectral_pair"][0]
+        eng.profile_enable(cand_ids + [pair_id])      # host-side state only: the two candidate kernels and the spectral pair, sampled
+        eng.profile_stride(stride)
     replays0, eager0 = eng.counter("graph_replays"), eng.counter("eager_iterations")
 
     barrier()
@@ -600,11 +656,15 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
-    collected = eng.profile_collect()
-    pair_ms, pair_cnt = collected.get("spectral_pair", (0.0, 0))
     replays, eager = eng.counter("graph_replays") - replays0, eng.counter("eager_iterations") - eager0
-    eng.profile_enable([])
-    eng.profile_stride(1)
+    if full:
+        collected = eng.profile_collect()
+        pair_ms, pair_cnt = collected.get("spectral_pair", (0.0, 0))
+        eng.profile_enable([])
+        eng.profile_stride(1)
+    dumped = None
+    if args.dump_outputs and rank == 0:               # what a caller of Engine.step receives: the state updated in place, the last RMSE row
+        dumped = dump_outputs(args.dump_outputs, {"wavefield": wf, "residual": res, "hidden_states": st, "residual_rmse": rmse[K - 1]})
 
     if rank == 0:
         macs, byts_k = kernel_macs(n), kernel_bytes(n)
@@ -645,7 +705,7 @@ def main():
                 r.pop("hbm_view")
             return r
 
-        sampled = sorted(((k,) + collected[k] for k in cand if collected.get(k, (0.0, 0))[1]), key=lambda t: -(t[1] / t[2]))
+        sampled = sorted(((k,) + collected[k] for k in cand if collected.get(k, (0.0, 0))[1]), key=lambda t: -(t[1] / t[2])) if full else []
         roof = None
         if sampled:
             roof = kernel_roof(*sampled[0])
@@ -663,7 +723,7 @@ def main():
                             "unit": "TFLOP/s", "frac": round(total_flops * K / dt / 1e12 / peak, 4),
                             "note": "whole iteration: UNet FLOPs of the reference layers / time per step (the spectral pair's 0.5 GFLOP not counted)"}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (torchrun pins OMP threads to 1 per rank)
+        if full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (torchrun pins OMP threads to 1 per rank)
             cpu = cpu_baseline(torch.from_numpy(sos_np), n, loc)
         final_rmse = rmse[K - 1].float().cpu().numpy()
         cfg_name = {(256, 32): "BASELINE configs[1]", (512, 16): "BASELINE configs[3]"}.get((n, B), "non-BASELINE shape")
@@ -683,10 +743,13 @@ def main():
             "sample_iterations_per_s": round(world * B * K / dt, 1),
             "unet_tflops": round(total_flops * K / dt / 1e12, 2),
             "residual_rmse_after_timed_steps": {"median": float(np.median(final_rmse)), "max": float(worst.max().item()),
-                                                "iterations_from_zero_wavefield": W1 + 8 + extra + K},
+                                                "iterations_from_zero_wavefield": W1 + 8 + settled + K},
             "roofline": roof,
             "cpu_baseline": cpu,
+            "full": full,
         }
+        if dumped is not None:
+            line["outputs"] = dumped
         # whole-step HBM view: compulsory bytes of one fused sample-iteration x batch x iterations/s against the HBM peak.
         # The step is compute-bound (fused arithmetic intensity 281 FLOP/B): at the fp32 peak the figure could reach ~7 %.
         step_bytes = STEP_COMPULSORY_BYTES_256 * (n / 256.0) ** 2 * B
@@ -698,24 +761,25 @@ def main():
             roof["flops_note"] = ("achieved / frac use the CREDITED FLOPs: the reference layers' (decode0: conv 16->8, conv 8->8, 1x1 8->2 = 228.6 MFLOP per sample "
                                   "at 256^2); `executed` is what the kernel's lanes compute (conv1 on the 18 x 66 mid tile of every 16 x 64 output tile; decode0's "
                                   "final 3x3 + 1x1 composed into one 2-channel 3x3)")
-        # every level-0 kernel of the main chain: shortest event-bracketed launch of the warm-up pass.  Durations only (VERDICT r4 #5c): each carries
-        # ~5-8 us of event overhead, so no rate is derived from them -- the rocprofv3 durations of the same command are in profiles/r5_kernel_stats.csv
-        line["level0_kernels_note"] = ("shortest launch per kernel in the warm-up pass in which EVERY kernel is bracketed by an event pair; each figure carries ~5-8 us of "
-                                       "event overhead (compare roofline.avg_launch_us, sampled in the timed region); rocprofv3 durations: profiles/r5_kernel_stats.csv")
-        line["level0_kernels"] = [{"kernel": k, "bracketed_us": round(pmin[k] * 1e3, 2), "gflop_credited": round(2.0 * macs[k] * B / per_step / 1e9, 3)}
-                                  for k in ("inc", "conv_signal0", "inc_conv_signal0", "down0", "up0", "decode0") if k in pmin and k in macs and pmin[k] > 0]
-        # secondary line for the HBM-bound part of the path (north_star: "achieved HBM GB/s for the FFT path"):
-        # compulsory bytes of get_residual (5 planes per sample) over the shortest bracketed launches of the two
-        # spectral kernels in the fully bracketed warm-up pass
-        sp_us = (pmin.get("spectral_cols", 0.0) + pmin.get("spectral_rows", 0.0)) * 1e3
-        if pair_cnt:   # both passes under one event pair, sampled in the timed region like the dominant kernel
-            sp_us = pair_ms / pair_cnt * 1e3
-        if sp_us > 0:
-            sp_bytes = spectral_bytes(n) * B
-            line["hbm_path"] = {"kernels": ["spectral_cols", "spectral_rows"], "bound": "hbm", "bytes_per_step": sp_bytes,
-                                "timing": f"one event pair around both kernels, {pair_cnt} samples in the timed region" if pair_cnt else "shortest bracketed launches of the warm-up pass",
-                                "us_per_step": round(sp_us, 2), "achieved": round(sp_bytes / (sp_us * 1e-6) / 1e9, 1),
-                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(sp_bytes / (sp_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
+        if full:
+            # every level-0 kernel of the main chain: shortest event-bracketed launch of the warm-up pass.  Durations only (VERDICT r4 #5c): each carries
+            # ~5-8 us of event overhead, so no rate is derived from them -- the rocprofv3 durations of the same command are in profiles/r5_kernel_stats.csv
+            line["level0_kernels_note"] = ("shortest launch per kernel in the warm-up pass in which EVERY kernel is bracketed by an event pair; each figure carries ~5-8 us of "
+                                           "event overhead (compare roofline.avg_launch_us, sampled in the timed region); rocprofv3 durations: profiles/r5_kernel_stats.csv")
+            line["level0_kernels"] = [{"kernel": k, "bracketed_us": round(pmin[k] * 1e3, 2), "gflop_credited": round(2.0 * macs[k] * B / per_step / 1e9, 3)}
+                                      for k in ("inc", "conv_signal0", "inc_conv_signal0", "down0", "up0", "decode0") if k in pmin and k in macs and pmin[k] > 0]
+            # secondary line for the HBM-bound part of the path (north_star: "achieved HBM GB/s for the FFT path"):
+            # compulsory bytes of get_residual (5 planes per sample) over the shortest bracketed launches of the two
+            # spectral kernels in the fully bracketed warm-up pass
+            sp_us = (pmin.get("spectral_cols", 0.0) + pmin.get("spectral_rows", 0.0)) * 1e3
+            if pair_cnt:   # both passes under one event pair, sampled in the timed region like the dominant kernel
+                sp_us = pair_ms / pair_cnt * 1e3
+            if sp_us > 0:
+                sp_bytes = spectral_bytes(n) * B
+                line["hbm_path"] = {"kernels": ["spectral_cols", "spectral_rows"], "bound": "hbm", "bytes_per_step": sp_bytes,
+                                    "timing": f"one event pair around both kernels, {pair_cnt} samples in the timed region" if pair_cnt else "shortest bracketed launches of the warm-up pass",
+                                    "us_per_step": round(sp_us, 2), "achieved": round(sp_bytes / (sp_us * 1e-6) / 1e9, 1),
+                                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(sp_bytes / (sp_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
         if args.breakdown:
             # event brackets around EVERY kernel stall the stream (the host cannot issue ~70 API calls per
             # step fast enough), so the average over-states a kernel that follows a host gap; the shortest
@@ -729,7 +793,7 @@ def main():
                       f"{fl / (us * 1e-6) / 1e12 if fl else 0:7.1f} TFLOP/s   (bracketed avg {ms / max(1, c) * 1e3:8.1f} us)", file=sys.stderr)
             print(f"  sum of per-kernel minima {tot:.1f} us/step (warm-up pass, all kernels bracketed; "
                   f"conv_state* run on the side stream, overlapped)", file=sys.stderr)
-        if world == 1 and not args.no_secondary and (n, B, prec) == (256, 32, "fp32"):
+        if full and world == 1 and not args.no_secondary and (n, B, prec) == (256, 32, "fp32"):
             # driver-visible side measurements: same process, a few seconds each
             line["secondary"] = [secondary(solver, dev, 256, 32, "fp32", 300, 20, loc=loc, seed=rank, readme_first=True,
                                            label="the HEADLINE workload again, 300 timed steps after 20 (VERDICT r3 #10: the driver's --steps 20 "

@@ -142,11 +142,11 @@ def test_lightning_checkpoint_reader(tmp_path, weights, hparams):
     assert torch.equal(s.f.inc.double_conv[0].weight, weights["inc.double_conv.0.weight"])
     with pytest.raises(RuntimeError):
         IterativeSolver.load_from_checkpoint(str(path), strict=True, test_data_path=None)
-    ref = "/root/reference/trained_models/jcp_paper_trained_weights.ckpt"
-    if os.path.exists(ref):
-        s2 = IterativeSolver.load_from_checkpoint(ref, strict=False, test_data_path=None)
-        for k, v in weights.items():
-            assert torch.equal(s2.f.state_dict()[k], v), k
+    # the reference's shipped (MIT-licensed) Lightning-0.9 file itself, kept as a fixture: the exported weights are its tensors
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jcp_paper_trained_weights.ckpt")
+    s2 = IterativeSolver.load_from_checkpoint(ref, strict=False, test_data_path=None)
+    for k, v in weights.items():
+        assert torch.equal(s2.f.state_dict()[k], v), k
 
 
 def test_phantoms():

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/quick
 rm -rf $O; mkdir -p $O
-BENCH="python3 $R/bench.py --steps 40 --warmup 12 --no-cpu-baseline --no-secondary $*"
+BENCH="python3 $R/bench.py --full --steps 40 --warmup 12 --no-cpu-baseline --no-secondary $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- $BENCH > $O/kt.log 2>&1
 python3 $R/tools/kstats.py $O/kt | sort -k5 -n -r | head -24
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_INSTS_LDS SQ_BUSY_CYCLES --output-format csv -d $O/pmc -- $BENCH > /dev/null 2>&1

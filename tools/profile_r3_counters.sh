@@ -7,7 +7,7 @@ rm -rf $O; mkdir -p $O
 rocprofv3 -L 2>/dev/null | grep -o "TCC_[A-Z0-9_]*" | sort -u | tr '\n' ' ' > $O/tcc_counters_available.txt
 ARGS="--steps 24 --warmup 12 --no-cpu-baseline --no-secondary"
 for v in xcd noxcd; do
-  if [ $v = xcd ]; then PROG="python3 $R/bench.py $ARGS"; else PROG="python3 $R/tools/run_with_lib.py $R/tools/lib_noxcd.so $ARGS"; fi
+  if [ $v = xcd ]; then PROG="python3 $R/bench.py --full $ARGS"; else PROG="python3 $R/tools/run_with_lib.py $R/tools/lib_noxcd.so $ARGS"; fi
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${v}_fetch -- $PROG > /dev/null 2>&1
   rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${v}_write -- $PROG > /dev/null 2>&1
   rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/${v}_hit -- $PROG > /dev/null 2>&1

@@ -6,6 +6,6 @@ for rep in 1 2; do
 for prec in fp16 bf16x3; do
 for o in "deep=2 side_sync=1" "deep=1 side_sync=1" "deep=1 side_sync=0"; do
   set -- $o
-  python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-secondary --precision $prec --opt $1 --opt $2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('256x32 $prec $o', d['value'], d['residual_rmse_after_timed_steps']['median'])"
-  python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --size 512 --batch 16 --precision $prec --opt $1 --opt $2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('512x16 $prec $o', d['value'])"
+  python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-secondary --precision $prec --opt $1 --opt $2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('256x32 $prec $o', d['value'], d['residual_rmse_after_timed_steps']['median'])"
+  python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --size 512 --batch 16 --precision $prec --opt $1 --opt $2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('512x16 $prec $o', d['value'])"
 done; done; done

@@ -9,5 +9,5 @@ for m in eager graph lanes; do
   python3 tools/kstats.py $O/kt_$m | grep -E "k_dc_asm|k_deepx|k_dc_mfma_s<8, 2" | cut -c1-150
   find $O/kt_$m -name "*kernel_trace.csv" -delete; find $O/kt_$m -name "*agent_info.csv" -delete
 done
-for i in 1 2; do python bench.py --gpus 1 --steps 300 --warmup 20 > $O/bench_$i.json 2> $O/bench_$i.err; python3 -c "
+for i in 1 2; do python bench.py --full --gpus 1 --steps 300 --warmup 20 > $O/bench_$i.json 2> $O/bench_$i.err; python3 -c "
 import json,sys; d=json.load(open('$O/bench_$i.json')); print('bench', d['value'], d['roofline'].get('dominant', d['roofline'].get('kernel')), d['roofline']['frac'])"; done

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${TM:-tm}; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --steps 40 --warmup 12 --no-cpu-baseline --no-secondary "$@" > $O/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --full --steps 40 --warmup 12 --no-cpu-baseline --no-secondary "$@" > $O/log.txt 2>&1
 python3 - <<PY | tee $O/timeline.txt
 import csv, glob
 rows = []
