@@ -325,11 +325,13 @@ def single_step(wf, k_sq, res, states, w, source, t: SpectralTables, depth: int 
 
 
 def solve(sos: Tensor, w: Dict[str, Tensor], source: Tensor, t: SpectralTables, num_iterations: int,
-          omega: float = 1.0, depth: int = 4, keep: str = "rmse"):
+          omega: float = 1.0, depth: int = 4, keep: str = "rmse", act: str = "prelu", state_depth: Optional[int] = None):
     """helmnet/hybridnet.py:654-697 (IterativeSolver.forward).
 
     keep = "rmse" returns the per-iteration per-sample RMSE trace instead of
     the full residual list (the reference keeps every residual tensor).
+    ``act`` / ``state_depth`` are passed to every ``single_step`` (HybridNet's
+    activation_function / state_depth hyperparameters).
     """
     k_sq, wf = get_initials(sos, omega)
     n = sos.shape[-1]
@@ -337,7 +339,7 @@ def solve(sos: Tensor, w: Dict[str, Tensor], source: Tensor, t: SpectralTables, 
     res = get_residual(wf, k_sq, source, t)
     trace = []
     for _ in range(num_iterations):
-        wf, res, states = single_step(wf, k_sq, res, states, w, source, t, depth)
+        wf, res, states = single_step(wf, k_sq, res, states, w, source, t, depth, act, state_depth=state_depth)
         trace.append(test_loss_function(res) if keep == "rmse" else res)
     return {"wavefield": wf, "residual": res, "states": states, "trace": trace}
 

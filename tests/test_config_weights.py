@@ -1,0 +1,90 @@
+"""The seeded fresh-weight helper (tests/config_weights.py), the oracle against the REFERENCE on those networks (tests/golden/configs.npz,
+made by tests/golden/make_golden_configs.py) and the oracle's solve() for networks other than the shipped checkpoint.  CPU only."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from config_weights import (GOLDEN_B, GOLDEN_CONFIGS, GOLDEN_INPUT_SEED, GOLDEN_N, GPU_CONFIGS, config_input, config_weights, slope_plan,
+                            tape_check)
+from helmnet_amd.engine import pack_weights, weight_shapes
+from oracle import helmnet_oracle as O
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3, 4, 5, 6])
+def test_fresh_weights_have_the_blob_shapes_and_are_reproducible(depth):
+    w = config_weights(depth, 700 + depth, "A")
+    shapes = weight_shapes(depth)
+    assert list(w) == list(shapes) and all(w[k].shape == shapes[k] and w[k].dtype == np.float32 for k in w)
+    again = config_weights(depth, 700 + depth, "A")
+    assert all(np.array_equal(w[k], again[k]) for k in w)
+    assert pack_weights(w, depth).size == sum(int(np.prod(s)) for s in shapes.values())
+    # without state below level 1: the reference's layout (8-channel conv_signal, no conv_state), packed as its stateful equivalent
+    sd = config_weights(depth, 700 + depth, "A", state_depth=1)
+    assert not any(k.startswith(f"enc.{d}.conv_state") for d in range(1, depth) for k in sd)
+    assert pack_weights(sd, depth, state_depth=1).size == pack_weights(w, depth).size
+    relu = config_weights(depth, 700 + depth, None, act="relu")
+    assert not any(k.endswith(".double_conv.1.weight") for k in relu)
+
+
+def test_every_layer_runs_both_slope_branches_across_the_two_plans():
+    """Plans A and B swap the slopes above 1 and the negative ones, so every PReLU layer (and so every kernel family) meets both."""
+    n = sum(k.endswith(".double_conv.1.weight") for k in weight_shapes(6))
+    a, b = slope_plan("A", n), slope_plan("B", n)
+    for sa, sb in zip(a, b):
+        assert (sa > 1 and sb < 0) or (sa < 0 and sb > 1), (sa, sb)
+    w = config_weights(4, 1, "B")
+    assert {v[0] for k, v in w.items() if k.endswith(".double_conv.1.weight")} == {np.float32(-0.4), np.float32(1.6), np.float32(3.0)}
+
+
+def test_oracle_solve_passes_activation_and_state_depth_through():
+    """O.solve(act=..., state_depth=...) is the loop of single_step with the same arguments; the defaults keep the shipped network's loop."""
+    n, depth, sd = 32, 4, 2
+    w = {k: torch.from_numpy(v) for k, v in config_weights(depth, 11, "A", state_depth=sd).items()}
+    sos = torch.from_numpy(1.0 + np.random.default_rng(5).random((2, 1, n, n)).astype(np.float32))
+    src = O.point_source_map(n, [4, 16], 10.0)
+    t = O.SpectralTables(n, 8, 2, 1.0)
+    out = O.solve(sos, w, src, t, 3, depth=depth, act="prelu", state_depth=sd)
+    k_sq, wf = O.get_initials(sos, 1.0)
+    st = [torch.zeros(2, 2, m, m) for m in O.state_dims(n, depth)]
+    res = O.get_residual(wf, k_sq, src, t)
+    for _ in range(3):
+        wf, res, st = O.single_step(wf, k_sq, res, st, w, src, t, depth, "prelu", state_depth=sd)
+    assert torch.equal(out["wavefield"], wf) and torch.equal(out["residual"], res)
+    assert all(torch.equal(a, c) for a, c in zip(out["states"], st))
+    assert all(not s.any() for s in out["states"][sd:]) and out["states"][0].abs().max() > 0
+
+
+@pytest.fixture(scope="module")
+def g_cfg():
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "configs.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.mark.parametrize("tag", list(GOLDEN_CONFIGS))
+def test_oracle_at_other_depths_and_slopes_vs_reference_fixture(g_cfg, tag):
+    """architectures.py:317-465 at depths 1 - 6, PReLU slopes above 1 and below 0, relu / softplus and state_depth < depth: the oracle's
+    unet_forward against the reference's HybridNet on the same seeded weights and input; the tape shows every layer's slope branch in use."""
+    depth, seed, plan, act, sd = GOLDEN_CONFIGS[tag]
+    w = {k: torch.from_numpy(v) for k, v in config_weights(depth, seed, plan, act, sd, n=GOLDEN_N).items()}
+    x = config_input(GOLDEN_N, GOLDEN_B, depth, GOLDEN_INPUT_SEED)
+    tape = {}
+    d, st = O.unet_forward(torch.from_numpy(x["x6"]), O.unflatten_states(torch.from_numpy(x["states"]), GOLDEN_N, depth), w, depth, act,
+                           state_depth=sd, tape=tape)
+    want_d, want_s = g_cfg[f"{tag}_d"], g_cfg[f"{tag}_states"]
+    assert np.abs(d.numpy() - want_d).max() <= 1e-5 * np.abs(want_d).max()
+    assert np.abs(O.flatten_states(st).numpy() - want_s).max() <= 1e-5 * np.abs(want_s).max()
+    tape_check(tape)
+
+
+@pytest.mark.parametrize("tag", list(GPU_CONFIGS))
+def test_gpu_configurations_use_every_slope_branch(tag):
+    """The networks of tests/test_config_matrix.py at their own sizes (two samples of their inputs): >= 20 % negative pre-activations in the
+    first convolution of every DoubleConv, every layer's RMS within [0.1, 10]."""
+    depth, seed, plan, act, sd, n, b = GPU_CONFIGS[tag]
+    w = {k: torch.from_numpy(v) for k, v in config_weights(depth, seed, plan, act, sd, n=n).items()}
+    x = config_input(n, min(b, 2), depth, 9000 + n, wf_scale=1e-6)
+    tape = {}
+    O.unet_forward(torch.from_numpy(x["x6"]), O.unflatten_states(torch.from_numpy(x["states"]), n, depth), w, depth, act, state_depth=sd, tape=tape)
+    tape_check(tape)
