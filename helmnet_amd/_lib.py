@@ -25,6 +25,7 @@ HN_OPTION = {"lanes": 0, "side_stream": 1, "deep": 3, "spectral_pfa": 4, "spectr
              "graph": 100, "train_lanes": 101}   # 100 +: laboratory knobs (HN_EXP_*)
 HN_COUNTER = {"graph_replays": 0, "eager_iterations": 1, "graphs_captured": 2, "stream_probes": 3, "side_candidate": 4, "train_fwd_events": 5, "flag_sync_iterations": 6}
 ABI_VERSION = 7
+HN_VJP = {"continue": 1, "defer": 2}   # enum hn_vjp_flags (hn_step_vjp)
 
 # name -> (restype, argtypes); every symbol include/helmnet_hip.h declares
 SYMBOLS = {
@@ -56,6 +57,9 @@ SYMBOLS = {
     "hn_train_reserve": (c_int, [c_void_p, c_int, c_int]),
     "hn_train_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hn_step_vjp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_int, c_void_p]),
     "hn_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
                              c_float, c_float, c_int64, c_void_p]),
     "hn_rows_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),

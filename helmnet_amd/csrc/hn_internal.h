@@ -307,7 +307,18 @@ struct hn_ctx {
         bool captured = false;       // a call using this workspace has been captured into a HIP graph: growing it needs an explicit hn_train_reserve
         int last_batch = 0;          // samples of the last hn_train_grad call in this workspace (hn_train_peek)
         int sumsq_batch = 0;         // samples per row of sumsq (lane 0 holds the whole batch's rows)
+        // hn_step_vjp: the job-table rows are a ring of `ring` rows (0 = one row per unrolled iteration, hn_train_grad); a row's pinned copy is
+        // rewritten only once the copy that last read it has run (ring_copied)
+        static constexpr int kRing = 8;
+        int ring = 0;
+        hipEvent_t ring_copied[kRing]{};
+        bool ring_pending[kRing]{};
     } tr, tr_b;                      // tr_b: the second half of the batch when hn_train_grad runs as two lanes
+    // hn_step_vjp: the recomputed iteration's new states (discarded) and the per-sample source gradient of a broadcast source
+    float* vjp_buf = nullptr;
+    size_t vjp_floats = 0;
+    bool vjp_open = false;           // a call with HN_VJP_DEFER left partial sums in ctx->tr for the next HN_VJP_CONTINUE call
+    int vjp_batch = 0, vjp_n = 0;    // shape of that open sweep
     int opt_train_overlap = 2;     // HN_OPT_TRAIN_OVERLAP: weight-gradient launches on a side stream beside the next iteration's backward chain.  0: in line;
                                    // 1: side stream, same launches ([measured, r4] no gain: 9.58 vs 9.61 ms at batch 32 -- the overlap is real, 2.3 ms of kernel time per
                                    // step run concurrently, but the weight-gradient blocks hold the CUs' LDS and the chain's kernels slow down by as much); 2 (default):

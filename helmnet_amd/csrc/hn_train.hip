@@ -31,6 +31,7 @@
 //   * Everything is enqueued on the caller's stream (HN_OPT_TRAIN_LANES 2: the second half of the batch on an internal stream,
 //     forked and joined with events); the host waits only when the workspace has to grow, or for a job table of four calls ago
 //     to have left its pinned buffer.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -896,7 +897,7 @@ __global__ __launch_bounds__(512) void k_reduce_rows(const float* __restrict__ p
 // PReLU slope gradients: block j sums the rows[j] per-block partial sums of DoubleConv j (fixed order) into grad[off[j]]
 struct SlopeJobs { int rows[3 * kMaxDepth + 2]; int off[3 * kMaxDepth + 2]; };
 __global__ __launch_bounds__(256) void k_reduce_slopes(const double* __restrict__ part, int stride, SlopeJobs jobs, const double* __restrict__ part_b,
-                                                       int stride_b, SlopeJobs jobs_b, float* __restrict__ grad) {
+                                                       int stride_b, SlopeJobs jobs_b, float* __restrict__ grad, int accumulate) {
     __shared__ double s_red[4];
     const int j = blockIdx.x;
     double s = 0.0;
@@ -907,7 +908,10 @@ __global__ __launch_bounds__(256) void k_reduce_slopes(const double* __restrict_
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) grad[jobs.off[j]] = (float)((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+    if (threadIdx.x == 0) {
+        const float v = (float)((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+        grad[jobs.off[j]] = accumulate ? grad[jobs.off[j]] + v : v;
+    }
 }
 
 // ---- output layer: d = Conv1x1(8 -> 2)(y0); wf_next = wf + d / 1e3   (architectures.py:57-60, hybridnet.py:570) ----------
@@ -967,6 +971,38 @@ __global__ __launch_bounds__(256) void k_loss_seed(float* __restrict__ g, const 
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < total) g[i] = has_in ? fmaf(c, res[i], g[i]) : c * res[i];
     sync_hook_end(hook);
+}
+// hn_step_vjp's seed of iteration t, one pass over the iteration's tensors (and the first kernel of its chain, so it carries the hook as k_loss_seed does):
+//   g_res += g_res_h, g_wf += g_wf_h, g_st += g_st_h   (the caller's cotangents on slot t of the histories; NULL = none)
+// and, with the cotangent of res_t = L(wf_t) + k_sq wf_t - src in registers, the two parameter gradients of the residual operator:
+//   g_ksq[b] += sum_c g_res[b,c] wf_t[b,c],   g_src[b] -= g_res[b]   (per sample: src_sb = 2 n^2; fixed order, no atomics)
+struct VjpSeedArgs {
+    float *g_res, *g_wf, *g_st;
+    const float *g_res_h, *g_wf_h, *g_st_h, *wf_t;
+    float *g_ksq, *g_src;
+    long n2, px_total, st_total;
+};
+__global__ __launch_bounds__(256) void k_vjp_seed(VjpSeedArgs a, SyncHook hook) {
+    sync_hook_begin(hook);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.px_total) {
+        const long b = i / a.n2, p = i - b * a.n2, i0 = b * 2 * a.n2 + p, i1 = i0 + a.n2;
+        float r0 = a.g_res[i0], r1 = a.g_res[i1];
+        if (a.g_res_h != nullptr) { r0 += a.g_res_h[i0]; r1 += a.g_res_h[i1]; a.g_res[i0] = r0; a.g_res[i1] = r1; }
+        if (a.g_wf_h != nullptr) { a.g_wf[i0] += a.g_wf_h[i0]; a.g_wf[i1] += a.g_wf_h[i1]; }
+        if (a.g_ksq != nullptr) a.g_ksq[i] += r0 * a.wf_t[i0] + r1 * a.wf_t[i1];
+        if (a.g_src != nullptr) { a.g_src[i0] -= r0; a.g_src[i1] -= r1; }
+    }
+    if (a.g_st_h != nullptr && i < a.st_total) a.g_st[i] += a.g_st_h[i];
+    sync_hook_end(hook);
+}
+// out[j] += sum_b part[b][j] in the order b = 0 .. batch - 1 (the per-sample source gradient of a broadcast source map)
+__global__ __launch_bounds__(256) void k_vjp_src_reduce(const float* __restrict__ part, int batch, long count, float* __restrict__ out) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    float s = 0.f;
+    for (int b = 0; b < batch; ++b) s += part[(size_t)b * count + j];
+    out[j] += s;
 }
 // loss = scale * sum(sumsq) / count, summed in a fixed order by one wavefront
 __global__ void k_loss_finalize(const float* __restrict__ sumsq, int n, float scale_over_count, float* __restrict__ loss) {
@@ -1196,7 +1232,13 @@ struct Trainer {
     int side(int d) const { return n >> d; }
     long plane(int d) const { return (long)side(d) * side(d); }
     hn_ctx::TrainWs& T() const { return *ws; }
-    float* tape(int t, size_t off) const { return T().tape + (size_t)t * T().step_floats + off; }
+    float* tape(int t, size_t off) const { return T().tape + (size_t)(tape_ring > 0 ? t % tape_ring : t) * T().step_floats + off; }
+    // hn_step_vjp: iteration t's tape in slot t % tape_ring; no weight-gradient jobs without g_weights; the forward pass stops at the tape (the recomputed
+    // wavefield / residual are the caller's histories already); the last flush keeps the cap (the block -> row mapping, hence the bits, must not depend on
+    // where a caller's segments end); `seed` replaces the loss term
+    int tape_ring = 0;
+    bool want_wgrad = true, tape_only = false, keep_cap = false;
+    const VjpSeedArgs* seed = nullptr;
     TSrc feat(const float* p, int d, int nch = kFeat, int act_on_load = 0) const { return TSrc{p, nch * plane(d), plane(d), nch, 1.f, act_on_load}; }
     TDst featdst(float* p, int d, int nch = kFeat, int accum = 0) const { return TDst{p, nch * plane(d), plane(d), nch, 1.f, accum}; }
     static TSrc nosrc() { return TSrc{nullptr, 0, 0, 0, 1.f, 0}; }
@@ -1266,6 +1308,7 @@ struct Trainer {
     std::vector<Wg8Args> jobsk;
     size_t lds8 = 0, lds2 = 0;
     int wgrad3(const TSrc (&in)[3], TSrc g, int co, size_t grad_off, int d, size_t slope_off) {
+        if (!want_wgrad) return HN_OK;
         Wg3Args a{};
         for (int i = 0; i < 3; ++i) a.src[i] = in[i];
         a.g = g.p; a.g_sb = g.sb; a.g_sc = g.sc;
@@ -1302,13 +1345,17 @@ struct Trainer {
         auto& W = T();
         const size_t b8 = jobs8.size() * sizeof(Wg3Args), b2 = jobs2.size() * sizeof(Wg3Args), bk = jobsk.size() * sizeof(Wg8Args);
         if (b8 + b2 + bk > W.jobs_region) return fail(ctx, HN_ERR_STATE, "internal: weight-gradient job table overflow (%zu > %zu bytes)", b8 + b2 + bk, W.jobs_region);
+        if (b8 + b2 + bk == 0) return HN_OK;
         const int n8 = number_blocks(jobs8, wg_cap), n2 = number_blocks(jobs2, wg_cap / 4), nk = number_blocks(jobsk, wg_cap / 2);
-        unsigned char* h = W.jobs_host + ((size_t)W.jobs_set * W.jobs_rows + t) * W.jobs_region;
-        unsigned char* dv = W.jobs_dev + (size_t)t * W.jobs_region;
+        const int row = W.ring > 0 ? t % W.ring : t;
+        if (W.ring > 0 && W.ring_pending[row]) { HN_HIP(ctx, hipEventSynchronize(W.ring_copied[row])); W.ring_pending[row] = false; }
+        unsigned char* h = W.jobs_host + ((size_t)W.jobs_set * W.jobs_rows + row) * W.jobs_region;
+        unsigned char* dv = W.jobs_dev + (size_t)row * W.jobs_region;
         if (b8) std::memcpy(h, jobs8.data(), b8);
         if (b2) std::memcpy(h + b8, jobs2.data(), b2);
         if (bk) std::memcpy(h + b8 + b2, jobsk.data(), bk);
         HN_HIP(ctx, hipMemcpyAsync(dv, h, b8 + b2 + bk, hipMemcpyHostToDevice, s));
+        if (W.ring > 0) { HN_HIP(ctx, hipEventRecord(W.ring_copied[row], s)); W.ring_pending[row] = true; }
         const bool gen = act > HN_ACT_LEAKYRELU;
         const Wg3Args* d8 = reinterpret_cast<const Wg3Args*>(dv);
         const Wg3Args* d2 = reinterpret_cast<const Wg3Args*>(dv + b8);
@@ -1392,6 +1439,7 @@ struct Trainer {
     int slope_rows(int d) const { (void)d; return (int)T().slope_stride; }   // every row of the slot (unused rows are zero): the kernels of a slot differ in their tile counts
 
     void wgrad8(const float* sm, int d_small, const float* bg, size_t grad_off, int bias_from_big) {   // weight [4096] and bias [8] are adjacent in the blob
+        if (!want_wgrad) return;
         Wg8Args a{};
         a.bias_from_big = bias_from_big;
         a.sm = sm; a.sm_sb = kFeat * plane(d_small); a.sm_sc = plane(d_small); a.hs = a.ws = side(d_small);
@@ -1461,6 +1509,7 @@ struct Trainer {
             const TSrc in[3] = {feat(tape(t, W.o_u[d]), d), feat(tape(t, W.o_out[d]), d), nosrc()};
             if ((rc = dc_fwd(L.dec[d], in, tape(t, W.o_zdec[d]), featdst(tape(t, W.o_y[d]), d), d, &F3.dec[d])) != HN_OK) return rc;
         }
+        if (tape_only) return HN_OK;
         const long total = (long)B * p0;
         hipLaunchKernelGGL(k_outc_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, tape(t, W.o_y[0]), w + L.outc_w, w + L.outc_b, wf, wf_next, p0, total);
         return spec_apply(ctx, wf_next, res_next, ksq, src, src_batch, B, sumsq0 + (size_t)t * sumsq_stride, s);
@@ -1489,7 +1538,13 @@ struct Trainer {
             W.wg_flag_epoch[par] = 0; W.wg_pending[par] = false;
         }
         // this iteration's loss term, then the adjoint of the residual operator: G = g_wf + L^H(g_res) + ksq * g_res
-        hipLaunchKernelGGL(k_loss_seed, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, s, W.g_res, res_out, loss_c, 1, tot2, hk);
+        if (seed != nullptr) {   // hn_step_vjp: the caller's cotangents on this iteration's outputs, and the residual operator's parameter gradients
+            VjpSeedArgs a = *seed;
+            a.g_res = W.g_res; a.g_wf = W.g_wf[cur_wf]; a.g_st = W.g_st[cur_st];
+            const long nthr = a.px_total > a.st_total ? a.px_total : a.st_total;
+            hipLaunchKernelGGL(k_vjp_seed, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, a, hk);
+        } else
+            hipLaunchKernelGGL(k_loss_seed, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, s, W.g_res, res_out, loss_c, 1, tot2, hk);
         if (deferred_t >= 0) {
             // the weight-gradient launches of iteration t + 1, gate first: enqueued HERE, behind the kernel that stores their release word, so that every
             // store precedes its wait in submission order too (a tool or setting that runs kernels strictly in that order cannot starve the gate).
@@ -1597,7 +1652,7 @@ struct Trainer {
             for (int k = 0; k < 2; ++k)
                 if (W.wg_pending[k]) { HN_HIP(ctx, hipStreamWaitEvent(s, W.wg_done[k], 0)); W.wg_pending[k] = false; W.wg_flag_epoch[k] = 0; }
             const int cap = wg_cap;
-            wg_cap = 0;
+            if (!keep_cap) wg_cap = 0;
             rc = flush_wgrads(t, s);
             wg_cap = cap;
             if (rc != HN_OK) return rc;
@@ -1630,6 +1685,8 @@ void train_free_ws(hn_ctx::TrainWs& W) {
     if (W.jobs_host != nullptr) (void)hipHostFree(W.jobs_host);
     for (hipEvent_t e : W.jobs_copied)
         if (e != nullptr) (void)hipEventDestroy(e);
+    for (hipEvent_t e : W.ring_copied)
+        if (e != nullptr) (void)hipEventDestroy(e);
     W.wg_stream = nullptr;   // (one of ctx->picks[1 / 2]'s candidates: side_stream_for)
     if (W.st_fork != nullptr) (void)hipEventDestroy(W.st_fork);
     if (W.st_done != nullptr) (void)hipEventDestroy(W.st_done);
@@ -1642,9 +1699,10 @@ void train_free_ws(hn_ctx::TrainWs& W) {
 }
 
 // workspace W for `batch` samples x n_unroll iterations; sumsq rows of `sumsq_batch` samples (the first lane keeps the whole batch's)
-int train_reserve(hn_ctx* ctx, hn_ctx::TrainWs& W, int batch, int n_unroll, int sumsq_batch, bool allow_regrow_captured = false) {
+int train_reserve(hn_ctx* ctx, hn_ctx::TrainWs& W, int batch, int n_unroll, int sumsq_batch, bool allow_regrow_captured = false, int jobs_rows_min = 0) {
     const int n = ctx->tab.n, depth = ctx->depth;
-    if (W.tape != nullptr && W.n == n && W.depth == depth && batch <= W.batch && n_unroll <= W.n_unroll && sumsq_batch <= W.sumsq_batch) return HN_OK;
+    if (W.tape != nullptr && W.n == n && W.depth == depth && batch <= W.batch && n_unroll <= W.n_unroll && sumsq_batch <= W.sumsq_batch &&
+        jobs_rows_min <= W.jobs_rows) return HN_OK;
     // a graph captured from hn_train_grad points into this workspace (tape, gradient buffers, the pinned job tables it re-copies on every replay): growing it
     // would free that memory under the graph.  hn_train_reserve -- an explicit call -- is how the caller says the graph is gone
     if (W.captured && !allow_regrow_captured)
@@ -1655,6 +1713,8 @@ int train_reserve(hn_ctx* ctx, hn_ctx::TrainWs& W, int batch, int n_unroll, int 
     const int nb = fresh || batch > W.batch ? batch : W.batch;
     const int nu = !fresh && n_unroll < W.n_unroll ? W.n_unroll : n_unroll;
     const int nsq = !fresh && sumsq_batch < W.sumsq_batch ? W.sumsq_batch : sumsq_batch;
+    const int njr = std::max(std::max(nu, jobs_rows_min), fresh ? 0 : W.jobs_rows);
+    ctx->vjp_open = false;   // (the partial sums an open hn_step_vjp sweep left are freed)
     train_free_ws(W);
     auto plane = [&](int d) { return (size_t)(n >> d) * (n >> d); };
     size_t pos = 0;
@@ -1726,10 +1786,11 @@ int train_reserve(hn_ctx* ctx, hn_ctx::TrainWs& W, int batch, int n_unroll, int 
     W.sumsq_batch = nsq;
     // per iteration: 2 jobs per DoubleConv (3 depth + 2 of them) + 2 depth 8x8 jobs
     W.jobs_region = (size_t)(6 * depth + 4) * sizeof(Wg3Args) + (size_t)2 * depth * sizeof(Wg8Args);
-    W.jobs_rows = nu;
-    HN_HIP(ctx, hipHostMalloc((void**)&W.jobs_host, W.jobs_region * nu * hn_ctx::TrainWs::kJobSets, hipHostMallocDefault));
-    HN_HIP(ctx, hipMalloc((void**)&W.jobs_dev, W.jobs_region * nu));
+    W.jobs_rows = njr;
+    HN_HIP(ctx, hipHostMalloc((void**)&W.jobs_host, W.jobs_region * njr * hn_ctx::TrainWs::kJobSets, hipHostMallocDefault));
+    HN_HIP(ctx, hipMalloc((void**)&W.jobs_dev, W.jobs_region * njr));
     for (hipEvent_t& e : W.jobs_copied) HN_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t& e : W.ring_copied) HN_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     W.batch = nb; W.n_unroll = nu; W.n = n; W.depth = depth;
     return HN_OK;
 }
@@ -1744,9 +1805,56 @@ int train_ready(hn_ctx* ctx, int batch, int n_unroll) {
     return HN_OK;
 }
 
+// the weights in the layouts the training kernels read (ctx->tr: one copy for both lanes): 3x3 both arrangements (one launch), 8x8 matrix-core fragments,
+// 3x3 matrix-core fragments
+void pack_train_weights(hn_ctx* ctx, const RawLayout& L, const float* weights, hipStream_t s) {
+    const int depth = ctx->depth;
+    auto& W = ctx->tr;
+    Pack3Jobs jobs{};
+    auto add = [&](const RawDc& dc) {
+        jobs.off[jobs.n] = (int)dc.w1; jobs.o[jobs.n] = (short)dc.cm; jobs.i[jobs.n] = (short)dc.cin; ++jobs.n;
+        jobs.off[jobs.n] = (int)dc.w2; jobs.o[jobs.n] = (short)dc.co; jobs.i[jobs.n] = (short)dc.cm; ++jobs.n;
+    };
+    add(L.inc);
+    for (int d = 0; d < depth; ++d) { add(L.sig[d]); add(L.st[d]); }
+    for (int d = 0; d <= depth; ++d) add(L.dec[d]);
+    hipLaunchKernelGGL(k_pack3, dim3(cdiv(16 * 9 * 8, 256), jobs.n), dim3(256), 0, s, weights, W.w3, pk_off((long)L.total) + 2, jobs);
+    PackK8Jobs kj{};
+    for (int d = 0; d < depth; ++d) {
+        kj.off[4 * d + 0] = (int)L.down[d].w; kj.up[4 * d + 0] = 0;   // down, forward
+        kj.off[4 * d + 1] = (int)L.down[d].w; kj.up[4 * d + 1] = 1;   // down, backward-data: [out, in] read as [in, out] by the transposed kernel
+        kj.off[4 * d + 2] = (int)L.up[d].w;   kj.up[4 * d + 2] = 1;   // up, forward
+        kj.off[4 * d + 3] = (int)L.up[d].w;   kj.up[4 * d + 3] = 0;   // up, backward-data: [in, out] read as [out, in] by the convolution kernel
+    }
+    hipLaunchKernelGGL(k_pack_frag8, dim3(16, 4 * depth), dim3(256), 0, s, weights, W.k8, kj);
+    {
+        const F3Layout F = f3_layout(depth);
+        PackF3Jobs fj{};
+        auto put = [&](size_t raw, size_t dst, int cin, int rows, int mode, int cm) {
+            fj.raw[fj.n] = (int)raw; fj.dst[fj.n] = (int)dst; fj.cin[fj.n] = (short)cin; fj.rows[fj.n] = (short)rows; fj.mode[fj.n] = (short)mode; fj.cm[fj.n] = (short)cm; ++fj.n;
+        };
+        auto addf = [&](const RawDc& dc, const size_t (&o)[2], const size_t (&ob)[2]) {
+            put(dc.w1, o[0], dc.cin, dc.cin, 0, kFeat);
+            put(dc.w2, o[1], dc.cm, dc.cm, 0, kFeat);
+            put(dc.w2, ob[0], kFeat, kFeat, 1, kFeat);
+            put(dc.w1, ob[1], dc.cin, cdiv(dc.cin, kFeat) * kFeat, 2, kFeat);
+        };
+        addf(L.inc, F.inc, F.incb);
+        for (int d = 0; d < depth; ++d) addf(L.sig[d], F.sig[d], F.sigb[d]);
+        for (int d = 0; d <= depth; ++d) addf(L.dec[d], F.dec[d], F.decb[d]);
+        for (int d = 0; d < depth; ++d) {   // conv_state: [2][2][3][3] and [2][10][3][3]
+            put(L.st[d].w2, F.stb[d][0], kState, kState, 1, kState);
+            put(L.st[d].w1, F.stb[d][1], kFeat + kState, 2 * kState, 2, kState);
+        }
+        hipLaunchKernelGGL(k_pack_frag3, dim3(cdiv(16 * 192, 256), fj.n), dim3(256), 0, s, weights, W.f3, fj);
+    }
+}
+
 }  // namespace
 
 void train_free(hn_ctx* ctx) {
+    (void)hipFree(ctx->vjp_buf);
+    ctx->vjp_buf = nullptr; ctx->vjp_floats = 0; ctx->vjp_open = false;
     train_free_ws(ctx->tr);
     train_free_ws(ctx->tr_b);
     if (ctx->train_fork != nullptr) (void)hipEventDestroy(ctx->train_fork);
@@ -1788,6 +1896,7 @@ int hn_train_grad(hn_ctx* ctx, const float* weights, const float* wf, const floa
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     const int n = ctx->tab.n, depth = ctx->depth;
+    ctx->vjp_open = false;   // (this call re-zeroes the partial sums an open hn_step_vjp sweep keeps)
     // Two lanes: samples are independent (hybridnet.py:399-409 is a batched call), and at the training size the chain of ~800 launches
     // is latency-bound (a step of 16 samples takes 0.83 of the time of 32), so the two halves of the batch run as two chains on
     // two streams.  Each lane has its own workspace and partial-sum tables; the packed weights and the sumsq rows are shared.
@@ -1881,46 +1990,9 @@ int hn_train_grad(hn_ctx* ctx, const float* weights, const float* wf, const floa
     // the training pass is fp32 whatever arithmetic the context's inference path is set to (the 8x8 launchers read it)
     struct PrecisionGuard { hn_ctx* c; int saved; ~PrecisionGuard() { c->precision = saved; } } pg{ctx, ctx->precision};
     ctx->precision = HN_PREC_FP32;
-    {   // weights in the layouts the kernels read: 3x3 both arrangements (one launch), 8x8 matrix-core fragments
+    {   // weights in the layouts the kernels read
+        pack_train_weights(ctx, L, weights, s);
         auto& W = ctx->tr;
-        Pack3Jobs jobs{};
-        auto add = [&](const RawDc& dc) {
-            jobs.off[jobs.n] = (int)dc.w1; jobs.o[jobs.n] = (short)dc.cm; jobs.i[jobs.n] = (short)dc.cin; ++jobs.n;
-            jobs.off[jobs.n] = (int)dc.w2; jobs.o[jobs.n] = (short)dc.co; jobs.i[jobs.n] = (short)dc.cm; ++jobs.n;
-        };
-        add(L.inc);
-        for (int d = 0; d < depth; ++d) { add(L.sig[d]); add(L.st[d]); }
-        for (int d = 0; d <= depth; ++d) add(L.dec[d]);
-        hipLaunchKernelGGL(k_pack3, dim3(cdiv(16 * 9 * 8, 256), jobs.n), dim3(256), 0, s, weights, W.w3, pk_off((long)L.total) + 2, jobs);
-        PackK8Jobs kj{};
-        for (int d = 0; d < depth; ++d) {
-            kj.off[4 * d + 0] = (int)L.down[d].w; kj.up[4 * d + 0] = 0;   // down, forward
-            kj.off[4 * d + 1] = (int)L.down[d].w; kj.up[4 * d + 1] = 1;   // down, backward-data: [out, in] read as [in, out] by the transposed kernel
-            kj.off[4 * d + 2] = (int)L.up[d].w;   kj.up[4 * d + 2] = 1;   // up, forward
-            kj.off[4 * d + 3] = (int)L.up[d].w;   kj.up[4 * d + 3] = 0;   // up, backward-data: [in, out] read as [out, in] by the convolution kernel
-        }
-        hipLaunchKernelGGL(k_pack_frag8, dim3(16, 4 * depth), dim3(256), 0, s, weights, W.k8, kj);
-        {
-            const F3Layout F = f3_layout(depth);
-            PackF3Jobs fj{};
-            auto put = [&](size_t raw, size_t dst, int cin, int rows, int mode, int cm) {
-                fj.raw[fj.n] = (int)raw; fj.dst[fj.n] = (int)dst; fj.cin[fj.n] = (short)cin; fj.rows[fj.n] = (short)rows; fj.mode[fj.n] = (short)mode; fj.cm[fj.n] = (short)cm; ++fj.n;
-            };
-            auto addf = [&](const RawDc& dc, const size_t (&o)[2], const size_t (&ob)[2]) {
-                put(dc.w1, o[0], dc.cin, dc.cin, 0, kFeat);
-                put(dc.w2, o[1], dc.cm, dc.cm, 0, kFeat);
-                put(dc.w2, ob[0], kFeat, kFeat, 1, kFeat);
-                put(dc.w1, ob[1], dc.cin, cdiv(dc.cin, kFeat) * kFeat, 2, kFeat);
-            };
-            addf(L.inc, F.inc, F.incb);
-            for (int d = 0; d < depth; ++d) addf(L.sig[d], F.sig[d], F.sigb[d]);
-            for (int d = 0; d <= depth; ++d) addf(L.dec[d], F.dec[d], F.decb[d]);
-            for (int d = 0; d < depth; ++d) {   // conv_state: [2][2][3][3] and [2][10][3][3]
-                put(L.st[d].w2, F.stb[d][0], kState, kState, 1, kState);
-                put(L.st[d].w1, F.stb[d][1], kFeat + kState, 2 * kState, 2, kState);
-            }
-            hipLaunchKernelGGL(k_pack_frag3, dim3(cdiv(16 * 192, 256), fj.n), dim3(256), 0, s, weights, W.f3, fj);
-        }
         if ((rc = zero_async(ctx, W.sumsq, sizeof(float) * (size_t)n_unroll * batch, s)) != HN_OK) return rc;
     }
     if (lanes == 2) {   // the second lane starts behind the packed weights (and whatever the caller's stream held before)
@@ -2019,10 +2091,152 @@ int hn_train_grad(hn_ctx* ctx, const float* weights, const float* wf, const floa
             for (int d = 0; d <= depth; ++d) put(tr[l].slot_dec(d), L.dec[d], d);
         }
         hipLaunchKernelGGL(k_reduce_slopes, dim3(3 * depth + 2), dim3(256), 0, s, ws[0]->slope_part, (int)ws[0]->slope_stride, sj[0],
-                           lanes == 2 ? ws[1]->slope_part : nullptr, (int)ws[1]->slope_stride, sj[1], grad);
+                           lanes == 2 ? ws[1]->slope_part : nullptr, (int)ws[1]->slope_stride, sj[1], grad, 0);
     }
     HN_HIP(ctx, hipGetLastError());
     return check_async(ctx, "hn_train_grad");   // (what is up by now; hn_check_async_errors behind a synchronise sees the rest)
+}
+
+int hn_step_vjp(hn_ctx* ctx, const float* weights, const float* wf0, const float* res0, const float* states0, const float* k_sq, int src_batch, int batch,
+                int n_iter, const float* wf_hist, const float* res_hist, const float* st_hist, const float* g_wf_hist, const float* g_res_hist,
+                const float* g_st_hist, const float* g_wf_T, const float* g_res_T, const float* g_st_T, float* g_wf0, float* g_res0, float* g_st0,
+                float* g_k_sq, float* g_src, float* g_weights, int flags, void* stream) {
+    if (!ctx || !weights || !wf0 || !res0 || !states0 || !k_sq || !wf_hist || !res_hist || !st_hist)
+        return fail(ctx, HN_ERR_ARG, "hn_step_vjp: NULL argument (weights, the inputs and the three histories are required)");
+    int rc = train_ready(ctx, batch, n_iter);
+    if (rc != HN_OK) return rc;
+    if ((rc = check_async(ctx, "hn_step_vjp (an earlier call)")) != HN_OK) return rc;
+    if (src_batch != 1 && src_batch != batch) return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
+    if ((flags & ~(HN_VJP_CONTINUE | HN_VJP_DEFER)) != 0) return fail(ctx, HN_ERR_ARG, "hn_step_vjp: unknown flags 0x%x", flags);
+    if (ctx->precision != HN_PREC_FP32 && ctx->precision != HN_PREC_FP32_VALU)
+        return fail(ctx, HN_ERR_UNSUPPORTED, "hn_step_vjp: gradients are computed for the fp32 UNet only (the context is set to a 16-bit mode)");
+    const int n = ctx->tab.n, depth = ctx->depth;
+    if ((flags & HN_VJP_CONTINUE) && !(ctx->vjp_open && ctx->vjp_batch == batch && ctx->vjp_n == n))
+        return fail(ctx, HN_ERR_STATE, "hn_step_vjp: HN_VJP_CONTINUE without an open sweep of this shape (the previous call on this context must be an hn_step_vjp "
+                                      "with HN_VJP_DEFER, batch %d, n %d)", batch, n);
+    hipStream_t s = (hipStream_t)stream;
+    {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(s, &cap);
+        if (cap != hipStreamCaptureStatusNone)
+            return fail(ctx, HN_ERR_STATE, "hn_step_vjp cannot be captured into a HIP graph (it grows its workspace and paces its job tables on the host)");
+    }
+    DeviceGuard guard(ctx);
+    hn_ctx::TrainWs& W = ctx->tr;
+    // the tape of TWO iterations (the weight gradients of iteration t read slot t % 2 beside the recompute of t - 1), a ring of job-table rows.
+    // Two slots whatever n_iter is: the segments of one sweep (HN_VJP_DEFER / CONTINUE) then need the same workspace, so a short segment cannot
+    // leave it too small for the next one (growing it frees the partial sums the sweep keeps)
+    const int slots = 2;
+    if (W.captured) return fail(ctx, HN_ERR_STATE, "hn_step_vjp: a training step captured into a HIP graph uses the training workspace: call hn_train_reserve first");
+    if ((rc = train_reserve(ctx, W, batch, slots, batch, false, hn_ctx::TrainWs::kRing)) != HN_OK) return rc;
+    if ((flags & HN_VJP_CONTINUE) && !ctx->vjp_open)   // (a reserve that re-allocated the workspace closed the sweep: its partial sums are gone)
+        return fail(ctx, HN_ERR_STATE, "hn_step_vjp: HN_VJP_CONTINUE, but the training workspace was re-allocated since the HN_VJP_DEFER call");
+    const long p2 = 2L * n * n, pst = (long)kState * ctx->state_len;
+    const size_t fwf = (size_t)batch * p2, fst = (size_t)batch * pst;
+    const size_t need = fst + (src_batch == 1 ? fwf : 0);
+    if (need > ctx->vjp_floats) {
+        if (ctx->vjp_open && src_batch == 1) return fail(ctx, HN_ERR_STATE, "hn_step_vjp: internal: the open sweep's workspace would have to grow");
+        HN_HIP(ctx, hipDeviceSynchronize());
+        (void)hipFree(ctx->vjp_buf);
+        ctx->vjp_buf = nullptr; ctx->vjp_floats = 0;
+        HN_HIP(ctx, hipMalloc((void**)&ctx->vjp_buf, sizeof(float) * need));
+        ctx->vjp_floats = need;
+    }
+    float* st_scratch = ctx->vjp_buf;                                   // the recomputed iteration's new states (the caller's history holds them)
+    float* src_ps = src_batch == 1 && g_src != nullptr ? ctx->vjp_buf + fst : nullptr;   // per-sample source gradient, reduced over the batch at the end
+    const bool cont = (flags & HN_VJP_CONTINUE) != 0, defer = (flags & HN_VJP_DEFER) != 0;
+    // job-table set of this call (as hn_train_grad: eager calls rotate over sets 1 .. kJobSets - 1)
+    W.jobs_set = W.jobs_set % (hn_ctx::TrainWs::kJobSets - 1) + 1;
+    if (W.jobs_in_flight[W.jobs_set]) { HN_HIP(ctx, hipEventSynchronize(W.jobs_copied[W.jobs_set])); W.jobs_in_flight[W.jobs_set] = false; }
+    W.last_batch = batch;
+    struct RingGuard { hn_ctx::TrainWs& w; ~RingGuard() { w.ring = 0; } } rg{W};
+    W.ring = std::min(W.jobs_rows, (int)hn_ctx::TrainWs::kRing);
+    const RawLayout L = raw_layout(depth);
+    Trainer tr{ctx, s, weights, L, batch, n, depth, ctx->act_kind, (long)ctx->state_len, &W, nullptr, batch};
+    tr.F3 = f3_layout(depth);
+    tr.fused_fwd = (ctx->opt_train_fused & 1) != 0; tr.fused_bwd = (ctx->opt_train_fused & 2) != 0; tr.fused_state = (ctx->opt_train_fused & 4) != 0;
+    tr.tile_small = (ctx->opt_train_fused & 8) != 0; tr.mfma_bwd = (ctx->opt_train_fused & 16) != 0; tr.merge_state = (ctx->opt_train_fused & 32) != 0;
+    tr.tape_ring = slots; tr.tape_only = true; tr.keep_cap = true; tr.want_wgrad = g_weights != nullptr;
+    // the side stream of the weight-gradient launches (HN_OPT_TRAIN_OVERLAP) with event hand-overs: the device-word hand-overs of HN_OPT_SIDE_SYNC pair a
+    // release with the NEXT iteration's seed kernel, and here a recomputed forward pass runs in between
+    if ((rc = side_stream_for(ctx, 1, &s, 1, true, &W.wg_stream)) != HN_OK) return rc;
+    {
+        const long px = (long)batch * n * n;
+        const int mode = ctx->opt_train_overlap;
+        tr.flag_sync = false;
+        tr.overlap = mode == 1 || (mode == 2 && px >= 200000);
+        tr.side_state_fwd = mode == 2 && px >= 200000;
+        tr.wg_cap = mode == 2 && px >= 200000 && px < 1000000 ? (int)(px / HN_WG_CAP_DIV < 512 ? 512 : px / HN_WG_CAP_DIV) : 0;
+    }
+    struct PrecisionGuard { hn_ctx* c; int saved; ~PrecisionGuard() { c->precision = saved; } } pg{ctx, ctx->precision};
+    ctx->precision = HN_PREC_FP32;
+    pack_train_weights(ctx, L, weights, s);
+    if (g_weights != nullptr && !cont) {
+        if ((rc = zero_async(ctx, W.part, sizeof(float) * W.part_floats, s)) != HN_OK) return rc;
+        if ((rc = zero_async(ctx, W.slope_part, sizeof(double) * W.slope_stride * (3 * depth + 2), s)) != HN_OK) return rc;
+    }
+    if (src_ps != nullptr && !cont && (rc = zero_async(ctx, src_ps, sizeof(float) * fwf, s)) != HN_OK) return rc;
+    ctx->vjp_open = false;
+    // the carried cotangents start as the caller's ones on the last outputs (or zeros)
+    auto init = [&](float* dst, const float* from, size_t floats) -> int {
+        if (from != nullptr) { HN_HIP(ctx, hipMemcpyAsync(dst, from, sizeof(float) * floats, hipMemcpyDeviceToDevice, s)); return HN_OK; }
+        return zero_async(ctx, dst, sizeof(float) * floats, s);
+    };
+    if ((rc = init(W.g_wf[0], g_wf_T, fwf)) != HN_OK || (rc = init(W.g_res, g_res_T, fwf)) != HN_OK || (rc = init(W.g_st[0], g_st_T, fst)) != HN_OK) return rc;
+    auto in_wf = [&](int t) { return t == 0 ? wf0 : wf_hist + (size_t)(t - 1) * fwf; };
+    auto in_res = [&](int t) { return t == 0 ? res0 : res_hist + (size_t)(t - 1) * fwf; };
+    auto in_st = [&](int t) { return t == 0 ? states0 : st_hist + (size_t)(t - 1) * fst; };
+    auto join_streams = [&]() {
+        for (int k = 0; k < 2; ++k)
+            if (W.wg_pending[k]) { (void)hipStreamWaitEvent(s, W.wg_done[k], 0); W.wg_pending[k] = false; }
+        if (W.st_pending) { (void)hipStreamWaitEvent(s, W.st_done, 0); W.st_pending = false; }
+    };
+    int cur_wf = 0, cur_st = 0;
+    VjpSeedArgs seed{};
+    seed.n2 = (long)n * n; seed.px_total = (long)batch * n * n; seed.st_total = (long)fst;
+    tr.seed = &seed;
+    for (int t = n_iter - 1; t >= 0 && rc == HN_OK; --t) {
+        // 1. the activation tape of iteration t, recomputed from the forward's own (wf, res, states)_{t-1} into slot t % 2 -- once the weight
+        //    gradients of iteration t + 2, which read that slot, are done
+        const int par = t & 1;
+        if (W.wg_pending[par]) { HN_HIP(ctx, hipStreamWaitEvent(s, W.wg_done[par], 0)); W.wg_pending[par] = false; }
+        if ((rc = tr.forward_step(t, in_wf(t), in_res(t), in_st(t), nullptr, nullptr, st_scratch, k_sq, nullptr, 1)) != HN_OK) break;
+        if (W.st_pending) { HN_HIP(ctx, hipStreamWaitEvent(s, W.st_done, 0)); W.st_pending = false; }   // the hidden-state DoubleConvs' tape
+        // 2. - 4. seed (the caller's cotangents on slot t; g_k_sq, g_src), the residual adjoint, the UNet's backward sweep
+        seed.g_res_h = g_res_hist ? g_res_hist + (size_t)t * fwf : nullptr;
+        seed.g_wf_h = g_wf_hist ? g_wf_hist + (size_t)t * fwf : nullptr;
+        seed.g_st_h = g_st_hist ? g_st_hist + (size_t)t * fst : nullptr;
+        seed.wf_t = wf_hist + (size_t)t * fwf;
+        seed.g_ksq = g_k_sq;
+        seed.g_src = src_ps != nullptr ? src_ps : g_src;
+        rc = tr.backward_step(t, in_wf(t), in_res(t), in_st(t), nullptr, k_sq, 0.f, cur_wf, cur_st);
+    }
+    if (rc != HN_OK) { join_streams(); return rc; }
+    join_streams();
+    HN_HIP(ctx, hipEventRecord(W.jobs_copied[W.jobs_set], s));
+    W.jobs_in_flight[W.jobs_set] = true;
+    if (g_wf0) HN_HIP(ctx, hipMemcpyAsync(g_wf0, W.g_wf[cur_wf], sizeof(float) * fwf, hipMemcpyDeviceToDevice, s));
+    if (g_res0) HN_HIP(ctx, hipMemcpyAsync(g_res0, W.g_res, sizeof(float) * fwf, hipMemcpyDeviceToDevice, s));
+    if (g_st0) HN_HIP(ctx, hipMemcpyAsync(g_st0, W.g_st[cur_st], sizeof(float) * fst, hipMemcpyDeviceToDevice, s));
+    if (defer) {   // the partial sums stay in the workspace for the next call's HN_VJP_CONTINUE
+        ctx->vjp_open = true; ctx->vjp_batch = batch; ctx->vjp_n = n;
+    } else {
+        if (src_ps != nullptr)
+            hipLaunchKernelGGL(k_vjp_src_reduce, dim3((unsigned)((p2 + 255) / 256)), dim3(256), 0, s, src_ps, batch, p2, g_src);
+        if (g_weights != nullptr) {
+            hipLaunchKernelGGL(k_reduce_rows, dim3(cdiv((int)L.total, 64)), dim3(512), 0, s, W.part, kPartRows, (int)L.total, g_weights, 1);
+            if (ctx->act_kind == HN_ACT_PRELU) {
+                SlopeJobs sj{};
+                auto put = [&](int slot, const RawDc& dc, int d) { sj.rows[slot] = tr.slope_rows(d); sj.off[slot] = (int)dc.slope; };
+                put(tr.slot_inc(), L.inc, 0);
+                for (int d = 0; d < depth; ++d) { put(tr.slot_sig(d), L.sig[d], d); put(tr.slot_st(d), L.st[d], d); }
+                for (int d = 0; d <= depth; ++d) put(tr.slot_dec(d), L.dec[d], d);
+                hipLaunchKernelGGL(k_reduce_slopes, dim3(3 * depth + 2), dim3(256), 0, s, W.slope_part, (int)W.slope_stride, sj, nullptr, 0, sj, g_weights, 1);
+            }
+        }
+    }
+    HN_HIP(ctx, hipGetLastError());
+    return check_async(ctx, "hn_step_vjp");
 }
 
 int hn_train_set_forward_event(hn_ctx* ctx, void* event, float* sumsq_host, int64_t sumsq_capacity) {

@@ -381,6 +381,32 @@ class Engine:
             out.update(grad_wf=g_in[0], grad_res=g_in[1], grad_states=g_in[2])
         return out
 
+    def step_vjp(self, weights, wf0, res0, states0, k_sq, src_batch: int, wf_hist, res_hist, st_hist, g_wf_hist=None, g_res_hist=None,
+                 g_st_hist=None, g_wf_T=None, g_res_T=None, g_st_T=None, g_k_sq=None, g_src=None, g_weights=None, flags: int = 0) -> dict:
+        """hn_step_vjp: reverse mode of ``n_iter = wf_hist.shape[0]`` solver iterations, the histories of ``step`` being the tape.  Returns the
+        gradients with respect to wf0 / res0 / states0 (new tensors); ``g_k_sq`` [B,1,n,n], ``g_src`` [src_batch,2,n,n] and ``g_weights`` are
+        accumulated into when given.  ``flags``: sum of _lib.HN_VJP values (segments of one long solve, see the header)."""
+        b, T = wf0.shape[0], int(wf_hist.shape[0])
+        n_w = int(self.lib.hn_weight_count(8, self.depth, 2))
+        self._chk(weights, (n_w,), "weights")
+        for t, shape, name in ((wf0, (b, 2, self.n, self.n), "wavefield"), (res0, (b, 2, self.n, self.n), "residual"),
+                               (states0, (b, 2, self.state_len), "hidden state"), (k_sq, (b, 1, self.n, self.n), "k_sq"),
+                               (wf_hist, (T, b, 2, self.n, self.n), "wf_hist"), (res_hist, (T, b, 2, self.n, self.n), "res_hist"),
+                               (st_hist, (T, b, 2, self.state_len), "st_hist")):
+            self._chk(t, shape, name)
+        for t, shape, name in ((g_wf_hist, wf_hist.shape, "g_wf_hist"), (g_res_hist, res_hist.shape, "g_res_hist"), (g_st_hist, st_hist.shape, "g_st_hist"),
+                               (g_wf_T, wf0.shape, "g_wf_T"), (g_res_T, res0.shape, "g_res_T"), (g_st_T, states0.shape, "g_st_T"),
+                               (g_k_sq, k_sq.shape, "g_k_sq"), (g_src, (int(src_batch), 2, self.n, self.n), "g_src"), (g_weights, (n_w,), "g_weights")):
+            if t is not None:
+                self._chk(t, shape, name)
+        out = {"grad_wf": torch.empty_like(wf0), "grad_res": torch.empty_like(res0), "grad_states": torch.empty_like(states0)}
+        rc = self.lib.hn_step_vjp(self.ctx, _ptr(weights), _ptr(wf0), _ptr(res0), _ptr(states0), _ptr(k_sq), int(src_batch), b, T,
+                                  _ptr(wf_hist), _ptr(res_hist), _ptr(st_hist), _ptr(g_wf_hist), _ptr(g_res_hist), _ptr(g_st_hist),
+                                  _ptr(g_wf_T), _ptr(g_res_T), _ptr(g_st_T), _ptr(out["grad_wf"]), _ptr(out["grad_res"]), _ptr(out["grad_states"]),
+                                  _ptr(g_k_sq), _ptr(g_src), _ptr(g_weights), int(flags), self._stream())
+        _lib.check(rc, self.ctx, "hn_step_vjp")
+        return out
+
     def adam_step(self, weights, grad, exp_avg, exp_avg_sq, step: int, lr: float, betas=(0.9, 0.95), eps: float = 1e-8,
                   weight_decay: float = 0.0, clip_value: float = 0.0, trainable: Optional[torch.Tensor] = None):
         """clip_grad_value_ + torch.optim.Adam step (hybridnet.py:172-176, 250-258) on caller-owned flat device tensors, in place."""

@@ -66,6 +66,7 @@ class IterativeSolver(nn.Module):
         hp.pop("__class__", None)
         self.hparams = AttributeDict(hp)  # save_hyperparameters() equivalent (hybridnet.py:54)
         self._engine: Optional[Engine] = None
+        self._differentiable = False   # differentiable(True): the autograd path even when only the parameters require grad
         self._unet_precision = None   # None: the library default (fp32, or HN_UNET_IMPL at context creation)
         self.register_buffer("sigmas", None)
         self.set_laplacian()
@@ -143,6 +144,65 @@ class IterativeSolver(nn.Module):
         self.Lap.bind(self._engine)
         self.f.sync_weights(self._engine)
         return self._engine
+
+    # ------------------------------------------------------------------ autograd ---------
+    def differentiable(self, on: bool = True):
+        """Route forward / n_steps / single_step / get_residual / apply_laplacian through autograd (helmnet_amd.autograd) whenever grad mode
+        is on, even if no input tensor requires grad: weight gradients for a loss of the caller's own over plain inputs.  Off by default --
+        an un-frozen solver's parameters alone do not switch the (taping) autograd path on.  Returns self."""
+        self._differentiable = bool(on)
+        return self
+
+    def _wants_grad(self, *tensors, states: bool = False) -> bool:
+        """The autograd path: grad mode is on and an input tensor (or the source map, or with ``states`` a hidden state held in f) requires
+        grad -- or differentiable(True) was called."""
+        if not torch.is_grad_enabled():
+            return False
+        if self._differentiable:
+            return True
+        ts = [t for t in tensors if isinstance(t, torch.Tensor)] + [self.source]
+        if states:
+            ts += [enc.state for enc in self.f.enc if enc.state is not None]
+        return any(t.requires_grad for t in ts)
+
+    def _check_grad_precision(self, eng: Engine):
+        if eng.unet_precision not in ("fp32", "valu"):
+            raise NotImplementedError(f"gradients through the solver are computed for the fp32 UNet only (this solver runs {eng.unet_precision!r}; "
+                                      "call set_unet_precision('fp32'), or run under torch.no_grad())")
+
+    def _src_graph(self) -> torch.Tensor:
+        src = self.source.float()
+        return src if src.is_contiguous() else src.contiguous()
+
+    def _run_autograd(self, wf, res, k_sq, num_iterations, return_wavefields, return_states, residuals: str, checkpoint_every: int):
+        """_run on the autograd path (helmnet_amd.autograd.Solve): same outputs, carrying grad_fn."""
+        from .autograd import Solve, SolveSpec, weight_blob
+        eng = self.engine()
+        self._check_grad_precision(eng)
+        K = int(num_iterations)
+        st = self.f.get_states(flatten=True).float()
+        if K <= 0:
+            self.f.adopt_states(st)
+            return {"wavefields": [wf], "residuals": [res] if residuals in ("all", "last") else [], "states": [], "last_iteration": K - 1,
+                    "residual_norms": None, **({"last_residual": res} if residuals == "norms" else {})}
+        want_w = any(p.requires_grad for p in self.f.parameters())
+        with torch.set_grad_enabled(want_w):
+            blob = weight_blob(self.f)
+        stateless = [tuple(bd) for d, bd in enumerate(self.f.state_boundaries) if d >= self.f.state_depth]
+        spec = SolveSpec(eng, K, checkpoint_every, bool(return_wavefields), residuals == "all", bool(return_states), stateless)
+        wf_o, res_o, st_o, rmse = Solve.apply(spec, wf.float().contiguous(), res.float().contiguous(), st.contiguous(), k_sq.float().contiguous(),
+                                              self._src_graph(), blob)
+        self.f.adopt_states(st_o[-1])
+        out = {
+            "wavefields": list(wf_o.unbind(0)),
+            "residuals": list(res_o.unbind(0)) if residuals in ("all", "last") else [],
+            "states": list(st_o.unbind(0)) if return_states else [],
+            "last_iteration": K - 1,
+            "residual_norms": rmse,
+        }
+        if residuals == "norms":
+            out["last_residual"] = res_o[-1]
+        return out
 
     def set_unet_precision(self, mode: str):
         """Extension (BASELINE.json configs[4]): arithmetic of the UNet convolutions -- 'fp32' (the reference's,
@@ -276,17 +336,29 @@ class IterativeSolver(nn.Module):
         return self.source.detach().float().contiguous()
 
     def apply_laplacian(self, x: torch.Tensor):
+        if self._wants_grad(x):
+            from .autograd import Laplacian
+            return Laplacian.apply(self.engine(), x.float())
         return self.engine().laplacian(x.float().contiguous())
 
     def get_residual(self, x: torch.Tensor, k_sq: torch.Tensor):
+        if self._wants_grad(x, k_sq):
+            from .autograd import Residual
+            return Residual.apply(self.engine(), x.float(), k_sq.float(), self._src_graph())
         return self.engine().residual(x.float().contiguous(), k_sq.float().contiguous(), self._src())
 
     def single_step(self, wavefield, k_sq, residual, get_residual: bool = True):
         """One iteration on caller-held tensors (hybridnet.py:558-584); network states live in
-        ``self.f`` as in the reference.  Inputs are not modified."""
+        ``self.f`` as in the reference.  Inputs are not modified.  With an input (or a state held in f, or the source) requiring
+        grad the step is differentiable and the new states stored in f carry their grad_fn, so chained calls back-propagate through
+        the hidden states as in the reference."""
         eng = self.engine()
         if any(enc.state is None for enc in self.f.enc):
             raise ValueError("You must set or clear the state before using this module")
+        if self._wants_grad(wavefield, k_sq, residual, states=True):
+            out = self._run_autograd(wavefield, residual, k_sq, 1, False, False, "last", 1)
+            wf, res = out["wavefields"][0], out["residuals"][0]
+            return (wf, res) if get_residual else wf
         wf = wavefield.detach().float().clone().contiguous()
         res = residual.detach().float().clone().contiguous()
         st = self.f.get_states(flatten=True).float().contiguous().clone()
@@ -333,14 +405,25 @@ class IterativeSolver(nn.Module):
         return out
 
     def forward(self, sos_maps, return_wavefields=False, return_states=False, num_iterations=None,
-                stop_if_diverge=False, residuals: str = "all"):
+                stop_if_diverge=False, residuals: str = "all", checkpoint_every: int = 1):
         """hybridnet.py:654-697.  ``residuals``: "all" keeps every residual tensor like the
         reference (K x B x 2 x N x N floats), "norms" keeps only the per-iteration per-sample RMSE
-        (``out["residual_norms"]``), "last" only the final residual."""
+        (``out["residual_norms"]``), "last" only the final residual.
+
+        Differentiable (helmnet_amd.autograd) when grad mode is on and ``sos_maps``, the source map or a hidden state requires grad, or
+        after ``differentiable(True)``; weight gradients then reach f's parameters if they require grad.  The autograd path keeps the
+        wavefield / residual / state of every iteration as its tape -- with residuals="norms" too -- or, with ``checkpoint_every`` = c > 1,
+        those of every c-th iteration only: backward re-runs the segments in between (same gradients, bit for bit).  Without
+        gradients ``checkpoint_every`` is ignored."""
         if residuals not in ("all", "norms", "last"):
             raise ValueError("residuals must be 'all', 'norms' or 'last'")
         if num_iterations is None:
             num_iterations = self.hparams.max_iterations
+        if self._wants_grad(sos_maps):
+            k_sq, wf = self.get_initials(sos_maps.float())
+            self.f.clear_states(wf)
+            res = self.get_residual(wf, k_sq)
+            return self._run_autograd(wf, res, k_sq, num_iterations, return_wavefields, return_states, residuals, checkpoint_every)
         sos_maps = sos_maps.float().contiguous()
         k_sq, wf = self.get_initials(sos_maps)
         self.f.clear_states(wf)
@@ -349,8 +432,11 @@ class IterativeSolver(nn.Module):
         return self._run(wf, res, st, k_sq.contiguous(), num_iterations, return_wavefields, return_states, residuals)
 
     def n_steps(self, wavefield, k_sq, residual, num_iterations, return_wavefields=False, return_states=False,
-                residuals: str = "all"):
-        """hybridnet.py:586-623: continue from given wavefield / residual and the states held in f."""
+                residuals: str = "all", checkpoint_every: int = 1):
+        """hybridnet.py:586-623: continue from given wavefield / residual and the states held in f.  Differentiable as ``forward``
+        when an input, a state held in f or the source requires grad (``checkpoint_every``: see ``forward``)."""
+        if self._wants_grad(wavefield, k_sq, residual, states=True):
+            return self._run_autograd(wavefield, residual, k_sq, num_iterations, return_wavefields, return_states, residuals, checkpoint_every)
         wf = wavefield.detach().float().clone().contiguous()
         res = residual.detach().float().clone().contiguous()
         st = self.f.get_states(flatten=True).float().contiguous().clone()

@@ -302,6 +302,36 @@ int hn_train_grad(hn_ctx* ctx, const float* weights, const float* wf, const floa
                   const float* src, int src_batch, int batch, int n_unroll, float loss_scale, float* wf_hist, float* res_hist,
                   float* st_hist, float* loss, float* grad, float* grad_wf0, float* grad_res0, float* grad_st0, void* stream);
 
+/* ---- reverse mode of the solver loop (added within ABI v7: a new entry point, nothing existing changes, so HN_ABI_VERSION stays 7) ----
+ * hn_step_vjp: the vector-Jacobian product of n_iter iterations of hn_step (single_step, hybridnet.py:558-584, looped as in forward :654-697),
+ * i.e. what torch.autograd computes when the reference back-propagates through its solver.  Iteration t maps (wf, res, st)_{t-1} -> (wf, res, st)_t,
+ * where index -1 is (wf0, res0, states0) and index t is slot t of the histories hn_step wrote (all three required: they are the tape, the
+ * linearisation point of every iteration).  The UNet activations of each iteration are recomputed in reverse order by the training forward pass
+ * (hn_train_grad's kernels), so the workspace holds the activations of TWO iterations whatever n_iter is.
+ * Cotangents (device, NULL = zero): g_wf_hist / g_res_hist [n_iter,B,2,n,n] and g_st_hist [n_iter,B,2,L] on the histories; g_wf_T / g_res_T /
+ * g_st_T [B,...] on the last iteration's outputs (added to slot n_iter - 1: a caller that only uses the end passes no histories).
+ * Outputs: g_wf0 / g_res0 [B,2,n,n], g_st0 [B,2,L] OVERWRITTEN (NULL = skip); g_k_sq [B,1,n,n], g_src [src_batch,2,n,n] and g_weights
+ * [hn_weight_count] ACCUMULATED (+=; NULL = skip -- without g_weights no weight-gradient kernel runs).  The source map itself is not read
+ * (the residual is linear in it), only its batch: src_batch 1 (broadcast: the gradient is summed over the batch once, at the end, in sample
+ * order) or B.  weights: the blob in PyTorch layout, as hn_train_grad takes it.  Levels without state (zero-padded weights, see hn_train_grad)
+ * get a zero state gradient out of the kernels: their slots pass through the solver unchanged, so their cotangent is the caller's identity.
+ * flags (a caller that splits a long solve into segments -- re-running each with hn_step from a checkpoint -- and wants the bits of ONE call):
+ *   HN_VJP_DEFER    keep the weight / broadcast-source partial sums in the context's workspace instead of reducing them into g_weights / g_src;
+ *   HN_VJP_CONTINUE add to the partial sums the previous call left (it must have been an hn_step_vjp with HN_VJP_DEFER of the same batch and
+ *                   domain, with no other training call on the context in between and no re-allocation of its workspace; HN_ERR_STATE otherwise --
+ *                   the tape has two slots whatever n_iter is, so the segments of one sweep never re-allocate it).
+ *   Segments processed last to first with DEFER on all but the first segment and CONTINUE on all but the last segment give the gradients of one call
+ *   bit for bit.  The input gradients and g_k_sq need no flag: a segment's g_wf0 / g_res0 / g_st0 is the earlier segment's g_*_T.
+ * fp32 UNet arithmetic only (HN_PREC_FP32 / HN_PREC_FP32_VALU; HN_ERR_UNSUPPORTED in the 16-bit modes).  Bit-reproducible: fixed-order sums, no
+ * atomics.  The weight-gradient launches run beside the chain as HN_OPT_TRAIN_OVERLAP says, handed over with events (not the device words of
+ * HN_OPT_SIDE_SYNC); HN_EXP_TRAIN_LANES does not apply (one chain).  NOT capturable: under stream capture it returns HN_ERR_STATE before
+ * enqueuing anything (it may grow its workspace and paces its pinned job tables on the host). */
+enum hn_vjp_flags { HN_VJP_CONTINUE = 1, HN_VJP_DEFER = 2 };
+int hn_step_vjp(hn_ctx* ctx, const float* weights, const float* wf0, const float* res0, const float* states0, const float* k_sq, int src_batch,
+                int batch, int n_iter, const float* wf_hist, const float* res_hist, const float* st_hist, const float* g_wf_hist,
+                const float* g_res_hist, const float* g_st_hist, const float* g_wf_T, const float* g_res_T, const float* g_st_T, float* g_wf0,
+                float* g_res0, float* g_st0, float* g_k_sq, float* g_src, float* g_weights, int flags, void* stream);
+
 /* ABI v5.  `event` (a hipEvent_t, or NULL to clear): every later hn_train_grad on this context records it on the caller's stream BEHIND THE FORWARD SWEEP, i.e. when
  * wf_hist / res_hist / st_hist are complete and before the backward pass starts.  The reference's training_step decides from the residual of one
  * unrolled iteration which replay-buffer slots to refill (`res.pow(2).mean() < 1`, hybridnet.py:431-463) -- a host decision; with this event the host
