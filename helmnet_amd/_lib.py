@@ -64,6 +64,9 @@ SYMBOLS = {
                              c_float, c_float, c_int64, c_void_p]),
     "hn_rows_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "hn_rows_scatter": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "hn_stream_verdict": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_float, POINTER(c_void_p), c_void_p]),
+    "hn_stream_swap": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "hn_train_peek": (c_int64, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "hn_train_set_forward_event": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "hn_profile_enable": (c_int, [c_void_p, ctypes.c_uint64]),

@@ -424,6 +424,7 @@ void hn_destroy(hn_ctx* ctx) {
     (void)hipFree(ctx->sync_flags);
     (void)hipFree(ctx->inc_sigma_map);
     if (ctx->sync_err) (void)hipHostFree(ctx->sync_err);
+    stream_table_free(ctx);
     for (int j = 0; j < 8; ++j) {
         auto& sl = ctx->side[j];
         if (!sl.done) continue;
@@ -641,6 +642,7 @@ int hn_reserve(hn_ctx* ctx, int max_batch) {
     HN_HIP(ctx, hipMalloc((void**)&ctx->dx_done, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
     HN_HIP(ctx, hipMemset(ctx->dx_done, 0, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
     if (int rc_sync = ensure_sync_words(ctx); rc_sync != HN_OK) return rc_sync;
+    if (int rc_tab = stream_table_reserve(ctx, max_batch); rc_tab != HN_OK) return rc_tab;
     ctx->cap_batch = max_batch;
     return HN_OK;
 }

@@ -212,6 +212,10 @@ struct hn_ctx {
     int dca_dec_pad = 0;       // dynamic LDS of the next decode_0 launch on hn_dca.hip: 7168 (3 blocks per CU) while the gate kernel is resident, else 0
     int* sync_err = nullptr;          // host-mapped: a bounded device-side wait that gave up stores its code here (sticky; checked by hn_step)
     int* sync_err_dev = nullptr;
+    // hn_stream_verdict (hn_stream.hip): one record per slot, host-mapped like sync_err; sized with the workspace (hn_reserve), freed by hn_destroy
+    hn_stream_verdict_rec* stream_tab = nullptr;
+    hn_stream_verdict_rec* stream_tab_dev = nullptr;
+    int stream_tab_cap = 0;
     // the sigma channels' share of the input layer's conv1 as a per-domain map (hn_dca.hip: SigmaMap; built by hn_load_weights / hn_set_domain, whichever comes second)
     float2* inc_sigma_map = nullptr;   // [4 channel pairs][n][n]
     int inc_sigma_band = 0;            // the map is zero farther than this many pixels from the border
@@ -417,6 +421,8 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
 // of hn_residual with respect to the wavefield (training).  `add` may alias `out`.
 int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
 void train_free(hn_ctx* ctx);   // hn_train.hip
+int stream_table_reserve(hn_ctx* ctx, int slots);   // hn_stream.hip: the verdict table holds at least `slots` records (growing it synchronises the device)
+void stream_table_free(hn_ctx* ctx);
 
 // ---- matrix-core kernels (hn_mfma.hip) ----
 void pack_frag_3x3(const float* w_oihw, int cin, float* dst);  // -> [cin][3][64]

@@ -73,6 +73,29 @@ def gather_batch(local: torch.Tensor, total: int, dst: int = 0) -> Optional[torc
     return torch.cat([b[: hi - lo] for b, (lo, hi) in zip(bufs, sizes)], 0)
 
 
+def solve_many_sharded(solver, sos_maps: torch.Tensor, tol: float, source_maps: Optional[torch.Tensor] = None, **kwargs) -> dict:
+    """``IterativeSolver.solve_many`` on this rank's contiguous share of the N maps (``shard_bounds``).  Every rank streams its shard
+    on its own -- no exchange per chunk -- and the per-map ``iterations`` / ``status`` of the whole job are gathered once at the end
+    (``iterations_all`` / ``status_all``, [N] on every rank; the wavefields stay on the rank that solved them: ``gather_batch``)."""
+    total = int(sos_maps.shape[0])
+    rank, world = (dist.get_rank(), dist.get_world_size()) if _ready() else (0, 1)
+    lo, hi = shard_bounds(total, rank, world)
+    out = solver.solve_many(sos_maps[lo:hi], tol, source_maps=None if source_maps is None else source_maps[lo:hi], **kwargs)
+    out["shard"] = (lo, hi)
+    if not _ready():
+        out["iterations_all"], out["status_all"] = out["iterations"], out["status"]
+        return out
+    dev = solver.device if dist.get_backend() == "nccl" else torch.device("cpu")
+    sizes = [shard_bounds(total, r, world) for r in range(world)]
+    pad = torch.zeros(2, max(h - l for l, h in sizes), dtype=torch.int64, device=dev)
+    pad[0, : hi - lo], pad[1, : hi - lo] = out["iterations"].to(dev), out["status"].to(dev, torch.int64)
+    bufs = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(bufs, pad)
+    both = torch.cat([b[:, : h - l] for b, (l, h) in zip(bufs, sizes)], 1).cpu()
+    out["iterations_all"], out["status_all"] = both[0], both[1].to(torch.int8)
+    return out
+
+
 def solve_sharded(solve: Callable[[torch.Tensor, int], dict], sos_maps: torch.Tensor, num_iterations: int,
                   tol: Optional[float] = None, check_every: int = 50, gather: bool = False) -> dict:
     """Run ``solve(local_sos, n_iter)`` on this rank's shard of ``sos_maps``.

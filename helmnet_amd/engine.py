@@ -457,6 +457,45 @@ class Engine:
                                       (ctypes.c_void_p * n)(*ptrs), (ctypes.c_int64 * n)(*strides), self._stream())
         _lib.check(rc, self.ctx, "hn_rows_scatter")
 
+    # ---- a stream of maps solved to a tolerance (hn_stream_verdict / hn_stream_swap) ------------------------------------
+    VERDICT_DTYPE = np.dtype([("first_below", np.int32), ("bad", np.int32), ("last_rmse", np.float32)])   # struct hn_stream_verdict_rec
+
+    def stream_verdict(self, rmse_hist: torch.Tensor, tol: float, diverge_rmse: Optional[float] = None) -> np.ndarray:
+        """One launch over the [n_rows, batch] RMSE rows a chunk of ``step`` wrote.  Returns a VIEW (no copy) of the context's pinned table as a
+        structured array of ``batch`` records (first_below, bad, last_rmse): valid once the current stream has been synchronised and until the
+        next call.  ``diverge_rmse`` None: only NaN / Inf rows mark a slot as bad."""
+        n_rows, b = int(rmse_hist.shape[0]), int(rmse_hist.shape[1])
+        self._chk(rmse_hist, (n_rows, b), "rmse_hist")
+        table = ctypes.c_void_p()
+        rc = self.lib.hn_stream_verdict(self.ctx, _ptr(rmse_hist), n_rows, b, float(tol), float("inf") if diverge_rmse is None else float(diverge_rmse),
+                                        ctypes.byref(table), self._stream())
+        _lib.check(rc, self.ctx, "hn_stream_verdict")
+        raw = (ctypes.c_char * (self.VERDICT_DTYPE.itemsize * b)).from_address(table.value)
+        return np.frombuffer(raw, dtype=self.VERDICT_DTYPE, count=b)
+
+    def stream_swap(self, wf, res, states, k_sq, src, ops, sos_in=None, src_in=None, omega: float = 1.0, out_wf=None, out_res=None):
+        """Retire / move / refill slots of the batch arrays in one launch (hn_stream_swap).  ``ops``: rows of (slot, retire_map, move_from,
+        refill_map), -1 = none -- host integers, they travel in the kernel arguments.  ``sos_in`` [n_maps,1,n,n] / ``src_in`` [n_maps,2,n,n]
+        feed refills (``src_in`` only when ``src`` has one row per slot), ``out_wf`` / ``out_res`` [n_maps,2,n,n] receive retired slots."""
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, self.n, self.n), "wavefield")
+        self._chk(res, (b, 2, self.n, self.n), "residual")
+        self._chk(states, (b, 2, self.state_len), "hidden state")
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
+        self._chk(src, (src.shape[0], 2, self.n, self.n), "source")
+        n_maps = {int(t.shape[0]) for t in (sos_in, src_in, out_wf, out_res) if t is not None}
+        if len(n_maps) > 1:
+            raise ValueError(f"sos_in / src_in / out_wf / out_res disagree on the number of maps: {sorted(n_maps)}")
+        n_maps = n_maps.pop() if n_maps else 0
+        for t, ch, name in ((sos_in, 1, "sos_in"), (src_in, 2, "src_in"), (out_wf, 2, "out_wf"), (out_res, 2, "out_res")):
+            if t is not None:
+                self._chk(t, (n_maps, ch, self.n, self.n), name)
+        ops = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1, 4))
+        rc = self.lib.hn_stream_swap(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), int(src.shape[0]), b, int(ops.shape[0]),
+                                     ops.ctypes.data_as(ctypes.c_void_p), _ptr(sos_in), _ptr(src_in), n_maps, float(omega), _ptr(out_wf), _ptr(out_res),
+                                     self._stream())
+        _lib.check(rc, self.ctx, "hn_stream_swap")
+
     def set_train_forward_event(self, event: Optional[torch.cuda.Event], sumsq_host: Optional[torch.Tensor] = None) -> None:
         """hn_train_set_forward_event: ``event`` is recorded behind the forward sweep of every later ``train_grad`` (None clears it); ``sumsq_host``
         (a pinned fp32 host tensor) receives the [n_unroll, batch] table of per-sample sums of res^2 before the event fires."""

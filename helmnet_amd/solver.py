@@ -469,6 +469,87 @@ class IterativeSolver(nn.Module):
                 break
         return {"wavefield": wf, "residual": res, "residual_norms": torch.cat(traces, 0), "iterations": done, "converged": converged}
 
+    def solve_many(self, sos_maps, tol: float, max_iterations: int = None, slots: int = 32, check_every: int = 25,
+                   source_maps=None, diverge_rmse: float = None, keep_residuals: bool = False, norm_reduce=None) -> dict:
+        """Extension: solve a stream of N maps to a tolerance, every map stopping on its own (continuous batching; the workload of the
+        reference's evaluate.py, which runs its test set batch by batch for a fixed iteration count).  ``slots`` maps iterate at a time
+        in chunks of ``check_every``; after each chunk one launch judges every slot from the chunk's RMSE rows (``hn_stream_verdict``),
+        the host synchronises once, and one launch (``hn_stream_swap``) retires finished slots into the outputs, hands them the next
+        unsolved maps and, when none is left, moves the last active slots into the holes -- ``hn_step`` always runs a dense prefix.
+
+        ``sos_maps`` [N,1,n,n], any N (a host tensor is uploaded whole, once); ``source_maps`` None: the solver's one source map
+        (``self.source`` must be [1,2,n,n]), or [N,2,n,n], one per map.  A map is retired after the chunk in which its residual RMSE is
+        NaN / Inf or above ``diverge_rmse`` (status 2), else in which it was below ``tol`` at some iteration (status 0), else when it has
+        run ``max_iterations`` (status 1).  CHUNK GRANULARITY: the stop is decided per chunk and no extra history is kept, so the
+        wavefield and ``residual_norm`` returned are those at the END of that chunk and ``iterations`` is a multiple of ``check_every``
+        capped at ``max_iterations`` (helmnet_amd.stream_schedule has the rule for a ``max_iterations`` that is not a multiple); a
+        residual that dips below ``tol`` and rises again inside the chunk is reported as converged with the larger end-of-chunk norm.
+
+        Returns ``wavefields`` [N,2,n,n], ``residual_norm`` [N] (device), ``iterations`` int64 [N], ``status`` int8 [N] (host; 0 converged,
+        1 hit max_iterations, 2 diverged / non-finite), ``residuals`` [N,2,n,n] with ``keep_residuals``, ``sample_iterations`` (the sum over
+        chunks of active slots x chunk length: the work enqueued) and ``chunks``.  With ``slots`` <= 32 every map's result is bit-identical
+        to ``forward(sos[m:m+1], num_iterations=iterations[m])`` (fp32 UNet; INTEGRATION.md section 7 says where that stops holding).
+        ``norm_reduce`` (e.g. helmnet_amd.distributed.allreduce_residual_norms) is called ONCE, at the end, on the final norms
+        (``worst_residual_norm``): ranks stream their shards independently.  Runs without gradients -- an input that requires grad raises
+        (the differentiable path is ``forward``) -- and leaves the hidden states held in ``f`` untouched."""
+        import numpy as np
+        from .stream_schedule import StreamScheduler
+        if max_iterations is None:
+            max_iterations = self.hparams.max_iterations
+        for t in (sos_maps, source_maps):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError("solve_many runs without gradients: pass detached tensors (the differentiable path is forward())")
+        if not (float(tol) == float(tol)):
+            raise ValueError("tol is NaN")
+        with torch.no_grad():
+            eng = self.engine()
+            dev, n = eng.device, int(self.hparams.domain_size)
+            if sos_maps.dim() != 4 or tuple(sos_maps.shape[1:]) != (1, n, n):
+                raise ValueError(f"sos_maps must be [N, 1, {n}, {n}], got {tuple(sos_maps.shape)}")
+            N = int(sos_maps.shape[0])
+            sos_in = sos_maps.detach().to(dev, torch.float32).contiguous()
+            if source_maps is None:
+                src_in, src = None, self._src()
+                if src.shape[0] != 1:
+                    raise ValueError(f"the solver holds {src.shape[0]} source maps: pass source_maps=[N, 2, {n}, {n}] (one per map)")
+            else:
+                if tuple(source_maps.shape) != (N, 2, n, n):
+                    raise ValueError(f"source_maps must be [{N}, 2, {n}, {n}], got {tuple(source_maps.shape)}")
+                src_in = source_maps.detach().to(dev, torch.float32).contiguous()
+            sched = StreamScheduler(N, slots, max_iterations, check_every)
+            new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
+            out_wf = new(N, 2, n, n)
+            out_res = new(N, 2, n, n) if keep_residuals else None
+            S = min(sched.slots, N)
+            if S > 0:
+                eng.reserve(S)
+                wf, res, st, k_sq = new(S, 2, n, n), new(S, 2, n, n), new(S, 2, eng.state_len), new(S, 1, n, n)
+                if src_in is not None:
+                    src = new(S, 2, n, n)
+                rmse = new(sched.check_every * S)
+                omega = float(self.hparams.omega)
+                per_slot = src_in is not None
+                stream = torch.cuda.current_stream(dev)
+                eng.stream_swap(wf, res, st, k_sq, src, sched.initial_ops(), sos_in, src_in, omega)
+                while sched.active:
+                    a, chunk = sched.active, sched.next_chunk()
+                    hist = rmse[: chunk * a].view(chunk, a)
+                    eng.step(wf[:a], res[:a], st[:a], k_sq[:a], src[:a] if per_slot else src, chunk, rmse_hist=hist)
+                    table = eng.stream_verdict(hist, tol, diverge_rmse)
+                    stream.synchronize()
+                    eng.check_async_errors()
+                    ops = sched.advance(chunk, table.tolist())
+                    eng.stream_swap(wf, res, st, k_sq, src, ops, sos_in, src_in, omega, out_wf, out_res)
+            norms = torch.tensor(np.asarray(sched.residual_norm, dtype=np.float32), device=dev)
+            out = {"wavefields": out_wf, "iterations": torch.tensor(sched.iterations, dtype=torch.int64),
+                   "residual_norm": norms, "status": torch.tensor(sched.status, dtype=torch.int8),
+                   "sample_iterations": sched.sample_iterations, "chunks": sched.chunks}
+            if keep_residuals:
+                out["residuals"] = out_res
+            if norm_reduce is not None:
+                out["worst_residual_norm"] = norm_reduce(norms, "max")
+            return out
+
     def forward_variable_src(self, sos_maps, src_time_pairs, return_wavefields=False, return_states=False,
                              num_iterations=None, stop_if_diverge=False, residuals: str = "all"):
         """hybridnet.py:699-754: swap the source map at given iterations (the residual is recomputed

@@ -357,6 +357,37 @@ int hn_rows_gather(hn_ctx* ctx, int n_fields, const float* const* buffers, const
 int hn_rows_scatter(hn_ctx* ctx, int n_fields, float* const* buffers, const int64_t* row_floats, int64_t capacity, const int32_t* slots, int count,
                     const float* const* rows, const int64_t* rows_stride, void* stream);
 
+/* ---- a stream of maps solved to a tolerance (added within ABI v7: new entry points, nothing existing changes) ----
+ * The reference's evaluate.py runs a test set batch by batch for a fixed iteration count; a batch solved to a tolerance instead stops with its
+ * WORST map.  These two calls are what a scheduler needs to stop every map on its own and hand its slot of the batch to the next map
+ * (helmnet_amd.IterativeSolver.solve_many): the batch arrays wf / res [batch,2,n,n], states [batch,2,L], k_sq [batch,1,n,n] (and src
+ * [batch,2,n,n] when every map has its own source) are SLOTS, the maps of the job live in sos_in [n_maps,1,n,n] (and src_in [n_maps,2,n,n]).
+ * Both work in every hn_precision mode (no UNet arithmetic) and are NOT capturable: they read host lists / hand out a host table, and return
+ * HN_ERR_STATE under stream capture before enqueuing anything.
+ *
+ * hn_stream_verdict: one launch that reads the rmse_hist rows [n_rows, batch] a chunk of hn_step iterations wrote and leaves one record per slot
+ * in a pinned, host-mapped table of the context (sized by hn_reserve, grown on demand): first_below = first row whose RMSE is < tol (-1: none),
+ * last_rmse = the last row's RMSE, bad = 1 if any row is NaN / Inf or > diverge_rmse (pass +Inf for "never").  One thread walks one slot's column
+ * in row order: deterministic, no atomics.  *host_table is valid once `stream` has been synchronised and until the next call on this context.
+ *
+ * hn_stream_swap: retire and refill, one launch per 192 operations (the list travels in the kernel arguments like the slots of hn_rows_gather; a
+ * longer list is split).  ops: `count` HOST records; per record, in this order (-1 = none):
+ *   retire_map  out_wf[retire_map] = wf[slot], and out_res[retire_map] = res[slot] if out_res is not NULL;
+ *   move_from   the wf, res, states, k_sq (and, with src_batch == batch, src) rows of slot move_from are copied into slot (tail compaction);
+ *   refill_map  the slot becomes what IterativeSolver.forward starts from for map refill_map: k_sq = ((1 / sos) * omega)^2 in fp32 (the
+ *               arithmetic of get_initials, hybridnet.py:522-538), wf = 0, states = 0, res = k_sq * 0 - src (with src_batch == batch the slot's
+ *               src row is src_in[refill_map] first; else src is the one broadcast map) -- no spectral launch: L(0) = 0.
+ * HN_ERR_ARG for: a slot outside [0, batch) or a map outside [0, n_maps); a slot named by two records; two records retiring the same map; a
+ * move_from that is the record's own slot or a slot another record of the call moves into / refills; src_batch not in {1, batch}; a refill without
+ * sos_in, or without src_in when src_batch == batch (with batch == 1 a NULL src_in means the broadcast source); a retire without out_wf; rows or pointers that are not 16-byte multiples. */
+typedef struct hn_stream_verdict_rec { int32_t first_below; int32_t bad; float last_rmse; } hn_stream_verdict_rec;
+typedef struct hn_stream_op { int32_t slot, retire_map, move_from, refill_map; } hn_stream_op;
+int hn_stream_verdict(hn_ctx* ctx, const float* rmse_hist, int n_rows, int batch, float tol, float diverge_rmse,
+                      const hn_stream_verdict_rec** host_table, void* stream);
+int hn_stream_swap(hn_ctx* ctx, float* wf, float* res, float* states, float* k_sq, float* src, int src_batch, int batch,
+                   int count, const hn_stream_op* ops, const float* sos_in, const float* src_in, int64_t n_maps, float omega,
+                   float* out_wf, float* out_res, void* stream);
+
 /* One optimiser step on caller-owned device arrays of n floats: gradient value clipping to [-clip_value, clip_value]
  * (clip_value <= 0: none; torch.nn.utils.clip_grad_value_, hybridnet.py:172-176), then torch.optim.Adam as configured by the
  * reference (hybridnet.py:250-258: betas (0.9, 0.95), L2 weight decay added to the gradient, no amsgrad):
