@@ -42,9 +42,6 @@ ProfScope::~ProfScope() {
 
 namespace {
 
-constexpr size_t dc_count(int cin, int cm, int co) { return (size_t)cm * cin * 9 + cm + 1 + (size_t)co * cm * 9 + co; }
-constexpr size_t k8_count() { return (size_t)kFeat * kFeat * 64 + kFeat; }
-
 // [cout][cin][kh][kw] -> [cin][kh][kw][cout]
 void repack_oihw(const float* src, float* dst, int co, int ci, int kk) {
     for (int o = 0; o < co; ++o)
@@ -58,37 +55,38 @@ void repack_iohw(const float* src, float* dst, int ci, int co, int kk) {
             for (int t = 0; t < kk; ++t) dst[((size_t)i * kk + t) * co + o] = src[((size_t)i * co + o) * kk + t];
 }
 
-struct Packer {
-    const float* src;
-    std::vector<float>& dst;
-    float* dev;
-    int act;
-    size_t pos = 0;
-    DcW dc(int cin, int cm, int co) {
-        DcW w;
-        w.act = act;
-        w.w1q = w.wa = w.wa2 = nullptr;   // set by hn_load_weights for the 8-channel DoubleConvs
-        repack_oihw(src + pos, dst.data() + pos, cm, cin, 9);
-        w.w1 = dev + pos; pos += (size_t)cm * cin * 9;
-        std::memcpy(dst.data() + pos, src + pos, sizeof(float) * cm);
-        w.b1 = dev + pos; pos += cm;
-        dst[pos] = src[pos];
-        w.slope = dev + pos; pos += 1;
-        repack_oihw(src + pos, dst.data() + pos, co, cm, 9);
-        w.w2 = dev + pos; pos += (size_t)co * cm * 9;
-        std::memcpy(dst.data() + pos, src + pos, sizeof(float) * co);
-        w.b2 = dev + pos; pos += co;
-        return w;
+// One DoubleConv / 8x8 convolution of the raw blob `src`, re-packed into `dst` at the same offsets; the result points into `dev`, where `dst` is uploaded to
+DcW pack_dc(const float* src, float* dst, const float* dev, const RawDc& r, int act) {
+    repack_oihw(src + r.w1, dst + r.w1, r.cm, r.cin, 9);
+    std::memcpy(dst + r.b1, src + r.b1, sizeof(float) * r.cm);
+    dst[r.slope] = src[r.slope];
+    repack_oihw(src + r.w2, dst + r.w2, r.co, r.cm, 9);
+    std::memcpy(dst + r.b2, src + r.b2, sizeof(float) * r.co);
+    DcW w{};   // (w1q, wa, wa2: hn_load_weights, for the 8-channel DoubleConvs)
+    w.w1 = dev + r.w1; w.b1 = dev + r.b1; w.slope = dev + r.slope; w.w2 = dev + r.w2; w.b2 = dev + r.b2;
+    w.act = act;
+    return w;
+}
+K8W pack_k8(const float* src, float* dst, const float* dev, const RawK8& r, bool transposed) {
+    if (transposed) repack_iohw(src + r.w, dst + r.w, kFeat, kFeat, 64);
+    else repack_oihw(src + r.w, dst + r.w, kFeat, kFeat, 64);
+    std::memcpy(dst + r.b, src + r.b, sizeof(float) * kFeat);
+    return K8W{dev + r.w, dev + r.b};
+}
+
+// The fragment arena on the host: add() appends a zero-filled block and notes the pointer that is to lead to it, resolve() sets those pointers once the
+// arena is on the device.
+struct Arena {
+    std::vector<float> host;
+    std::vector<std::pair<const float**, size_t>> slots;
+    size_t add(size_t floats, const float** slot) {
+        const size_t o = host.size();
+        host.resize(o + floats);
+        slots.emplace_back(slot, o);
+        return o;
     }
-    K8W k8(bool transposed) {
-        K8W w;
-        if (transposed) repack_iohw(src + pos, dst.data() + pos, kFeat, kFeat, 64);
-        else repack_oihw(src + pos, dst.data() + pos, kFeat, kFeat, 64);
-        w.w = dev + pos; pos += (size_t)kFeat * kFeat * 64;
-        std::memcpy(dst.data() + pos, src + pos, sizeof(float) * kFeat);
-        w.b = dev + pos; pos += kFeat;
-        return w;
-    }
+    float* at(size_t o) { return host.data() + o; }   // (valid until the next add)
+    void resolve(const float* dev) const { for (const auto& sl : slots) *sl.first = dev + sl.second; }
 };
 
 // pack host weights (PyTorch layout) with `fill`, upload them, run `go` on the stream, wait, free
@@ -442,12 +440,7 @@ void hn_destroy(hn_ctx* ctx) {
 
 size_t hn_weight_count(int features, int depth, int state_ch) {
     if (features != kFeat || state_ch != kState || depth < 1 || depth > kMaxDepth) return 0;
-    size_t n = dc_count(kInCh, kFeat, kFeat);
-    n += (size_t)depth * (dc_count(kFeat + kState, kFeat, kFeat) + k8_count() + dc_count(kFeat + kState, kState, kState));
-    n += (size_t)depth * dc_count(2 * kFeat, kFeat, kFeat) + dc_count(kFeat, kFeat, kFeat);
-    n += (size_t)depth * k8_count();
-    n += (size_t)2 * kFeat + 2;
-    return n;
+    return raw_layout(depth).total;
 }
 
 int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int features, int depth, int state_ch, int act_kind) {
@@ -457,128 +450,73 @@ int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int feature
     if (depth < 1 || depth > kMaxDepth) return fail(ctx, HN_ERR_UNSUPPORTED, "depth %d outside [1, %d]", depth, kMaxDepth);
     if (act_kind < HN_ACT_PRELU || act_kind > HN_ACT_SOFTPLUS)
         return fail(ctx, HN_ERR_UNSUPPORTED, "activation kind %d is not implemented (hn_act: prelu .. softplus)", act_kind);
-    const size_t want = hn_weight_count(features, depth, state_ch);
-    if (n_floats != want) return fail(ctx, HN_ERR_ARG, "weight blob has %zu floats, expected %zu", n_floats, want);
+    const RawLayout L = raw_layout(depth);
+    if (n_floats != L.total) return fail(ctx, HN_ERR_ARG, "weight blob has %zu floats, expected %zu", n_floats, L.total);
     DeviceGuard guard(ctx);
     HN_HIP(ctx, hipDeviceSynchronize());  // nothing may still read the old weights
     clear_step_graphs(ctx);
     (void)hipFree(ctx->wdev);
     ctx->wdev = nullptr;
-    HN_HIP(ctx, hipMalloc((void**)&ctx->wdev, want * sizeof(float)));
-    std::vector<float> packed(want);
-    Packer p{blob, packed, ctx->wdev, act_kind};
+    HN_HIP(ctx, hipMalloc((void**)&ctx->wdev, L.total * sizeof(float)));
     ctx->act_kind = act_kind;
     for (int co = 0; co < kFeat; ++co)      // inc.conv1.weight [8][6][3][3]: the sigma channels 4, 5 (hn_dca.hip: SigmaMap)
         for (int c = 0; c < 2; ++c)
-            for (int t = 0; t < 9; ++t) ctx->inc_w_sigma[(co * 2 + c) * 9 + t] = blob[((size_t)co * kInCh + 4 + c) * 9 + t];
-    ctx->inc = p.dc(kInCh, kFeat, kFeat);
-    for (int d = 0; d < depth; ++d) {
-        ctx->sig[d] = p.dc(kFeat + kState, kFeat, kFeat);
-        ctx->down[d] = p.k8(false);
-        ctx->st[d] = p.dc(kFeat + kState, kState, kState);
-    }
-    for (int d = 0; d <= depth; ++d) ctx->dec[d] = p.dc(d < depth ? 2 * kFeat : kFeat, kFeat, kFeat);
-    for (int d = 0; d < depth; ++d) ctx->up[d] = p.k8(true);
-    repack_oihw(blob + p.pos, packed.data() + p.pos, 2, kFeat, 1);  // outc [2][8] -> [8][2]
-    ctx->outc_w = ctx->wdev + p.pos; p.pos += 2 * kFeat;
-    packed[p.pos] = blob[p.pos]; packed[p.pos + 1] = blob[p.pos + 1];
-    ctx->outc_b = ctx->wdev + p.pos; p.pos += 2;
-    if (p.pos != want) return fail(ctx, HN_ERR_ARG, "internal: packed %zu of %zu floats", p.pos, want);
-    HN_HIP(ctx, hipMemcpy(ctx->wdev, packed.data(), want * sizeof(float), hipMemcpyHostToDevice));
-    {   // A-operand fragments for the matrix-core kernels, built from the original OIHW tensors
-        std::vector<float> fr;
-        std::vector<size_t> off, offq, offa, offd2;   // offq / offa: conv1 of every 8-channel DoubleConv re-packed for hn_dcv.hip / hn_dca.hip, in blob order   // offq: the vector-pipe re-pack of conv1 of every 8-channel DoubleConv, in blob order; offu: its
-                                               // two convolutions in the Winograd domain (hn_wino.hip)
-        size_t pos = 0;
-        auto dc = [&](int cin, int cm, int co) {  // returns offsets of (frag1, frag2) or (npos, npos)
-            const float* w1 = blob + pos; pos += (size_t)cm * cin * 9 + cm + 1;
-            const float* w2 = blob + pos; pos += (size_t)co * cm * 9 + co;
-            if (cm != kFeat || co != kFeat) {   // conv_state: fp32 fragments with the two channels in rows 0..3 of M
-                off.push_back(fr.size()); fr.resize(fr.size() + (size_t)cin * 3 * 64); pack_frag_3x3_c2(w1, cin, fr.data() + off.back());
-                off.push_back(fr.size()); fr.resize(fr.size() + (size_t)cm * 3 * 64); pack_frag_3x3_c2(w2, cm, fr.data() + off.back());
+            for (int t = 0; t < 9; ++t) ctx->inc_w_sigma[(co * 2 + c) * 9 + t] = blob[L.inc.w1 + ((size_t)co * kInCh + 4 + c) * 9 + t];
+    // One walk over the blob fills both uploads: the re-packed fp32 weights (wdev, same offsets as the blob) and the arena (fragdev) with every layer's
+    // other packings, built from the original OIHW tensors.  Each block's pointer is a named member of its layer's record; nothing reads the arena by position.
+    std::vector<float> packed(L.total);
+    Arena fr;
+    auto frag3 = [&](const float* w, int cin, Frag& f) {   // matrix-core A fragments of a 3x3 convolution: fp32, split-bf16, fp16
+        pack_frag_3x3(w, cin, fr.at(fr.add((size_t)cin * 3 * 64, &f.f32)));
+        pack_frag_3x3_split(w, cin, fr.at(fr.add(frag_3x3_split_floats(cin), &f.bf16)));
+        pack_frag_3x3_half(w, cin, fr.at(fr.add(frag_3x3_half_floats(cin), &f.f16)));
+    };
+    for_each_layer(depth,
+        [&](int, int, int, const RawDc& r, DcLayer& l) {
+            l = DcLayer{};
+            l.w = pack_dc(blob, packed.data(), ctx->wdev, r, act_kind);
+            const float *w1 = blob + r.w1, *w2 = blob + r.w2;
+            if (r.cm != kFeat || r.co != kFeat) {   // conv_state: fp32 fragments with the two channels in rows 0..3 of M
+                pack_frag_3x3_c2(w1, r.cin, fr.at(fr.add((size_t)r.cin * 3 * 64, &l.f1.f32)));
+                pack_frag_3x3_c2(w2, r.cm, fr.at(fr.add((size_t)r.cm * 3 * 64, &l.f2.f32)));
                 return;
             }
-            offq.push_back(fr.size()); fr.resize(fr.size() + (size_t)cin * 72); pack_valu_q(w1, cin, fr.data() + offq.back());
-            {
-                static const float inc_scale_a[kInCh] = {1.f, 1.f, 1000.f, 1000.f, 1.f, 1.f};
-                offa.push_back(fr.size()); fr.resize(fr.size() + (size_t)cin * 72); pack_dca(w1, cin, cin == kInCh ? inc_scale_a : nullptr, fr.data() + offa.back());
-                offa.push_back(fr.size()); fr.resize(fr.size() + (size_t)kFeat * 72); pack_dca(w2, kFeat, nullptr, fr.data() + offa.back());
-            }
-            // each fp32 fragment block is followed by its split-bf16 and fp16 twins (launch_dc8 relies on this order)
-            off.push_back(fr.size()); fr.resize(fr.size() + (size_t)cin * 3 * 64); pack_frag_3x3(w1, cin, fr.data() + off.back());
-            { const size_t o = fr.size(); fr.resize(o + frag_3x3_split_floats(cin)); pack_frag_3x3_split(w1, cin, fr.data() + o); }
-            { const size_t o = fr.size(); fr.resize(o + frag_3x3_half_floats(cin)); pack_frag_3x3_half(w1, cin, fr.data() + o); }
-            off.push_back(fr.size()); fr.resize(fr.size() + (size_t)kFeat * 3 * 64); pack_frag_3x3(w2, kFeat, fr.data() + off.back());
-            { const size_t o = fr.size(); fr.resize(o + frag_3x3_split_floats(kFeat)); pack_frag_3x3_split(w2, kFeat, fr.data() + o); }
-            { const size_t o = fr.size(); fr.resize(o + frag_3x3_half_floats(kFeat)); pack_frag_3x3_half(w2, kFeat, fr.data() + o); }
-        };
-        auto k8 = [&](bool up) {
-            off.push_back(fr.size()); fr.resize(fr.size() + (size_t)kFeat * kFeat * 64);
-            if (up) pack_frag_up(blob + pos, fr.data() + off.back()); else pack_frag_down(blob + pos, fr.data() + off.back());
-            {   // 16-bit twins (mixed-precision modes), right behind the fp32 block: 3-part bf16, then fp16
-                const size_t o = fr.size();
-                fr.resize(o + k8_split_floats() + k8_half_floats());
-                if (up) pack_frag_up_x16(blob + pos, fr.data() + o, fr.data() + o + k8_split_floats());
-                else pack_frag_down_x16(blob + pos, fr.data() + o, fr.data() + o + k8_split_floats());
-            }
-            // (behind the twins, which the 16-bit launchers address relative to the fp32 block) the column-pair packing of hn_deepx.hip
-            if (!up) { offd2.push_back(fr.size()); fr.resize(fr.size() + (size_t)kFeat * 2 * 10 * 64); pack_frag_down2(blob + pos, fr.data() + offd2.back()); }
-            pos += k8_count();
-        };
-        dc(kInCh, kFeat, kFeat);
-        for (int d = 0; d < depth; ++d) { dc(kFeat + kState, kFeat, kFeat); k8(false); dc(kFeat + kState, kState, kState); }
-        const size_t pos_dec0 = pos;
-        for (int d = 0; d <= depth; ++d) dc(d < depth ? 2 * kFeat : kFeat, kFeat, kFeat);
-        for (int d = 0; d < depth; ++d) k8(true);
-        // final layer: decode[0]'s second convolution composed with the 1x1 out-conv (one linear map, composed in float64)
-        size_t off_comp = 0, off_comp_b = 0, off_comp_v = 0;
-        {
-            const float* w2 = blob + pos_dec0 + (size_t)kFeat * 2 * kFeat * 9 + kFeat + 1;   // decode.0.double_conv.2.weight [8][8][3][3]
-            const float* b2 = w2 + (size_t)kFeat * kFeat * 9;
-            const float* wo = blob + want - (2 * kFeat + 2);                                  // outc.conv.weight [2][8], bias [2]
-            const float* bo = wo + 2 * kFeat;
-            off_comp = fr.size();
-            fr.resize(fr.size() + (size_t)kFeat * 5 * 64);
-            pack_frag_outc3x3(w2, b2, wo, bo, fr.data() + off_comp, nullptr);
-            off_comp_b = fr.size();
-            fr.resize(fr.size() + 4);
-            pack_frag_outc3x3(w2, b2, wo, bo, nullptr, fr.data() + off_comp_b);
-            off_comp_v = fr.size();
-            fr.resize(fr.size() + (size_t)kFeat * 9 * 2);
-            pack_outc3x3_valu(w2, wo, fr.data() + off_comp_v);
-        }
-        fr.resize((fr.size() + 3) / 4 * 4);   // 16-byte aligned
-        const size_t off_zero = fr.size();
-        fr.resize(fr.size() + 64, 0.f);       // the zero page out-of-image staging loads read (hn_dca.hip)
-        (void)hipFree(ctx->fragdev);
-        ctx->fragdev = nullptr;
-        HN_HIP(ctx, hipMalloc((void**)&ctx->fragdev, fr.size() * sizeof(float)));
-        HN_HIP(ctx, hipMemcpy(ctx->fragdev, fr.data(), fr.size() * sizeof(float), hipMemcpyHostToDevice));
-        size_t i = 0;
-        auto nxt = [&]() { const size_t o = off[i++]; return o == (size_t)-1 ? (const float*)nullptr : ctx->fragdev + o; };
-        ctx->f_inc[0] = nxt(); ctx->f_inc[1] = nxt();
-        for (int d = 0; d < depth; ++d) {
-            ctx->f_sig[d][0] = nxt(); ctx->f_sig[d][1] = nxt(); ctx->f_down[d] = nxt(); ctx->f_st[d][0] = nxt(); ctx->f_st[d][1] = nxt();
-        }
-        for (int d = 0; d <= depth; ++d) { ctx->f_dec[d][0] = nxt(); ctx->f_dec[d][1] = nxt(); }
-        for (int d = 0; d < depth; ++d) ctx->f_up[d] = nxt();
-        for (int d = 0; d < depth; ++d) ctx->f_down2[d] = ctx->fragdev + offd2[d];
-        {
-            size_t iq = 0;
-            ctx->inc.w1q = ctx->fragdev + offq[iq++];
-            for (int d = 0; d < depth; ++d) ctx->sig[d].w1q = ctx->fragdev + offq[iq++];
-            for (int d = 0; d <= depth; ++d) ctx->dec[d].w1q = ctx->fragdev + offq[iq++];
-            size_t ia = 0;
-            auto seta = [&](DcW& w) { w.wa = ctx->fragdev + offa[ia++]; w.wa2 = ctx->fragdev + offa[ia++]; };
-            seta(ctx->inc);
-            for (int d = 0; d < depth; ++d) seta(ctx->sig[d]);
-            for (int d = 0; d <= depth; ++d) seta(ctx->dec[d]);
-        }
-        ctx->zero_page = ctx->fragdev + off_zero;
-        ctx->f_dec0c = ctx->fragdev + off_comp;
-        ctx->dec0c_b = ctx->fragdev + off_comp_b;
-        ctx->v_dec0c = ctx->fragdev + off_comp_v;
+            static const float inc_scale_a[kInCh] = {1.f, 1.f, 1000.f, 1000.f, 1.f, 1.f};
+            pack_valu_q(w1, r.cin, fr.at(fr.add((size_t)r.cin * 72, &l.w.w1q)));   // conv1 for hn_dcv.hip; conv1 and conv2 for hn_dca.hip
+            pack_dca(w1, r.cin, r.cin == kInCh ? inc_scale_a : nullptr, fr.at(fr.add((size_t)r.cin * 72, &l.w.wa)));
+            pack_dca(w2, kFeat, nullptr, fr.at(fr.add((size_t)kFeat * 72, &l.w.wa2)));
+            frag3(w1, r.cin, l.f1);
+            frag3(w2, kFeat, l.f2);
+        },
+        [&](bool up, const RawK8& r, K8Layer& l) {
+            l = K8Layer{};
+            l.w = pack_k8(blob, packed.data(), ctx->wdev, r, up);
+            l.f.bias = l.w.b;
+            const float* w = blob + r.w;
+            (up ? pack_frag_up : pack_frag_down)(w, fr.at(fr.add((size_t)kFeat * kFeat * 64, &l.f.f32)));
+            const size_t split = fr.add(k8_split_floats(), &l.f.bf16), half = fr.add(k8_half_floats(), &l.f.f16);   // (mixed-precision modes)
+            (up ? pack_frag_up_x16 : pack_frag_down_x16)(w, fr.at(split), fr.at(half));
+            if (!up) pack_frag_down2(w, fr.at(fr.add((size_t)kFeat * 2 * 10 * 64, &l.f_pair)));
+        },
+        L, *ctx);
+    repack_oihw(blob + L.outc_w, packed.data() + L.outc_w, 2, kFeat, 1);  // outc [2][8] -> [8][2]
+    packed[L.outc_b] = blob[L.outc_b]; packed[L.outc_b + 1] = blob[L.outc_b + 1];
+    ctx->outc_w = ctx->wdev + L.outc_w;
+    ctx->outc_b = ctx->wdev + L.outc_b;
+    {   // final layer: decode[0]'s second convolution composed with the 1x1 out-conv (one linear map, composed in float64)
+        const float *w2 = blob + L.dec[0].w2, *b2 = blob + L.dec[0].b2, *wo = blob + L.outc_w, *bo = blob + L.outc_b;
+        pack_frag_outc3x3(w2, b2, wo, bo, fr.at(fr.add((size_t)kFeat * 5 * 64, &ctx->f_dec0c)), nullptr);
+        pack_frag_outc3x3(w2, b2, wo, bo, nullptr, fr.at(fr.add(4, &ctx->dec0c_b)));
+        pack_outc3x3_valu(w2, wo, fr.at(fr.add((size_t)kFeat * 9 * 2, &ctx->v_dec0c)));
     }
+    fr.host.resize((fr.host.size() + 3) / 4 * 4);   // 16-byte aligned
+    fr.add(64, &ctx->zero_page);                    // the zero page out-of-image staging loads read (hn_dca.hip)
+    HN_HIP(ctx, hipMemcpy(ctx->wdev, packed.data(), L.total * sizeof(float), hipMemcpyHostToDevice));
+    (void)hipFree(ctx->fragdev);
+    ctx->fragdev = nullptr;
+    HN_HIP(ctx, hipMalloc((void**)&ctx->fragdev, fr.host.size() * sizeof(float)));
+    HN_HIP(ctx, hipMemcpy(ctx->fragdev, fr.host.data(), fr.host.size() * sizeof(float), hipMemcpyHostToDevice));
+    fr.resolve(ctx->fragdev);
     if (ctx->have_weights && ctx->depth != depth) free_workspace(ctx);
     ctx->depth = depth;
     ctx->have_weights = true;
@@ -751,8 +689,10 @@ int hn_double_conv(hn_ctx* ctx, const float* x, int cin, int cout, const float* 
     const bool ok = (cout == kFeat && (cin == kInCh || cin == kFeat || cin == kFeat + kState || cin == 2 * kFeat)) || (cout == kState && cin == kFeat + kState);
     if (!ok) return fail(ctx, HN_ERR_UNSUPPORTED, "hn_double_conv: (cin, cout) = (%d, %d) is not one of (6,8) (8,8) (10,8) (16,8) (10,2)", cin, cout);
     DcW dw;
-    return with_temp_weights(ctx, dc_count(cin, cout, cout), (hipStream_t)stream,
-        [&](std::vector<float>& packed, float* dev) { Packer p{weights_host, packed, dev, act_kind}; dw = p.dc(cin, cout, cout); },
+    size_t n_floats = 0;
+    const RawDc r = raw_dc(n_floats, cin, cout, cout);
+    return with_temp_weights(ctx, n_floats, (hipStream_t)stream,
+        [&](std::vector<float>& packed, float* dev) { dw = pack_dc(weights_host, packed.data(), dev, r, act_kind); },
         [&]() { return module_double_conv(ctx, x, cin, cout, dw, out, batch, h, w, (hipStream_t)stream); });
 }
 
@@ -761,8 +701,10 @@ int hn_conv8x8(hn_ctx* ctx, const float* x, const float* weights_host, int trans
     if (batch < 1 || h < 1 || w < 1) return fail(ctx, HN_ERR_ARG, "hn_conv8x8: batch, h, w must be positive");
     if (!transposed && ((h | w) & 1)) return fail(ctx, HN_ERR_UNSUPPORTED, "hn_conv8x8: the stride-2 convolution needs even h, w (got %d, %d)", h, w);
     K8W kw;
-    return with_temp_weights(ctx, k8_count(), (hipStream_t)stream,
-        [&](std::vector<float>& packed, float* dev) { Packer p{weights_host, packed, dev, HN_ACT_PRELU}; kw = p.k8(transposed != 0); },
+    size_t n_floats = 0;
+    const RawK8 r = raw_k8(n_floats);
+    return with_temp_weights(ctx, n_floats, (hipStream_t)stream,
+        [&](std::vector<float>& packed, float* dev) { kw = pack_k8(weights_host, packed.data(), dev, r, transposed != 0); },
         [&]() { return module_conv8x8(ctx, x, kw, transposed != 0, out, batch, h, w, (hipStream_t)stream); });
 }
 

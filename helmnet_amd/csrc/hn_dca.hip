@@ -497,7 +497,7 @@ void launch_dc_asm(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const Dc
 bool dc_asm_pair_applies(const hn_ctx* ctx, Src wf, Src res, Src sig, Src x0, Src st, int H, int W, int batch, int ws_off) {
     if (!ctx->opt_dc_pair || ctx->pair_flags == nullptr || ctx->pair_done == nullptr) return false;
     const Src none{nullptr, 0, 0, 1.f};
-    if (!dc_asm_applies(ctx, ctx->inc.act, wf, res, sig, 0, H, W) || !dc_asm_applies(ctx, ctx->sig[0].act, x0, st, none, 1, H, W)) return false;
+    if (!dc_asm_applies(ctx, ctx->inc.w.act, wf, res, sig, 0, H, W) || !dc_asm_applies(ctx, ctx->sig[0].w.act, x0, st, none, 1, H, W)) return false;
     return H == ctx->tab.n && W == ctx->tab.n && (long)cdiv_(W, 64) * cdiv_(H, 16) * (ws_off + batch) <= ctx->pair_flags_cap;   // (the counters assume ONE tile grid per context)
 }
 
@@ -506,7 +506,7 @@ void launch_dc_asm_pair(hn_ctx* ctx, Src wf, Src res, Src sig, Dst x0_out, Src x
     const int gx = cdiv_(W, 64), gy = cdiv_(H, 16), T = gx * gy * batch;
     const SigmaMap sm = sigma_map_applies(ctx, sig, H, W) ? SigmaMap{ctx->inc_sigma_map, ctx->inc_sigma_band} : SigmaMap{nullptr, 0};
     const unsigned host_epoch = capturing ? 0u : 0x80000000u | ++ctx->pair_epoch;   // (0: derive it on the device)
-    hipLaunchKernelGGL(k_dc_asm_pair, dim3(2 * T), dim3(256), 0, s, wf, res, sig, x0_out, ctx->inc, x0, st, out0, ctx->sig[0], ctx->zero_page, H, W, gx, gy, T,
+    hipLaunchKernelGGL(k_dc_asm_pair, dim3(2 * T), dim3(256), 0, s, wf, res, sig, x0_out, ctx->inc.w, x0, st, out0, ctx->sig[0].w, ctx->zero_page, H, W, gx, gy, T,
                        ctx->pair_flags + (long)ws_off * gx * gy, ctx->pair_done + (long)ws_off * kCounterStride, host_epoch, ctx->sync_err_dev, sm);
 }
 

@@ -487,12 +487,13 @@ int launch_deep(hn_ctx* ctx, const float* x_in, long x_sb, const float* st_in, f
                 long y_sb, int batch, hipStream_t s, SyncHook hook) {
     const int d = ctx->depth - 1;
     DeepW w;
-    w.sig1 = ctx->f_sig[d][0]; w.sig1_b = ctx->sig[d].b1; w.sig_slope = ctx->sig[d].slope; w.sig2 = ctx->f_sig[d][1]; w.sig2_b = ctx->sig[d].b2;
-    w.st1 = ctx->f_st[d][0]; w.st1_b = ctx->st[d].b1; w.st_slope = ctx->st[d].slope; w.st2 = ctx->f_st[d][1]; w.st2_b = ctx->st[d].b2;
-    w.down = ctx->f_down[d]; w.down_b = ctx->down[d].b;
-    w.bot1 = ctx->f_dec[d + 1][0]; w.bot1_b = ctx->dec[d + 1].b1; w.bot_slope = ctx->dec[d + 1].slope; w.bot2 = ctx->f_dec[d + 1][1]; w.bot2_b = ctx->dec[d + 1].b2;
-    w.up = ctx->f_up[d]; w.up_b = ctx->up[d].b;
-    w.dec1 = ctx->f_dec[d][0]; w.dec1_b = ctx->dec[d].b1; w.dec_slope = ctx->dec[d].slope; w.dec2 = ctx->f_dec[d][1]; w.dec2_b = ctx->dec[d].b2;
+    const DcLayer &sig = ctx->sig[d], &st = ctx->st[d], &bot = ctx->dec[d + 1], &dec = ctx->dec[d];
+    w.sig1 = sig.f1.f32; w.sig1_b = sig.w.b1; w.sig_slope = sig.w.slope; w.sig2 = sig.f2.f32; w.sig2_b = sig.w.b2;
+    w.st1 = st.f1.f32; w.st1_b = st.w.b1; w.st_slope = st.w.slope; w.st2 = st.f2.f32; w.st2_b = st.w.b2;
+    w.down = ctx->down[d].f.f32; w.down_b = ctx->down[d].f.bias;
+    w.bot1 = bot.f1.f32; w.bot1_b = bot.w.b1; w.bot_slope = bot.w.slope; w.bot2 = bot.f2.f32; w.bot2_b = bot.w.b2;
+    w.up = ctx->up[d].f.f32; w.up_b = ctx->up[d].f.bias;
+    w.dec1 = dec.f1.f32; w.dec1_b = dec.w.b1; w.dec_slope = dec.w.slope; w.dec2 = dec.f2.f32; w.dec2_b = dec.w.b2;
     w.act = ctx->act_kind;
     if (!ctx->deep_attr_set) {   // 135.6 KB of dynamic LDS: above the default limit of a launch
         HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_deep32<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FLOATS * (int)sizeof(float)));

@@ -823,11 +823,12 @@ int launch_deepx(hn_ctx* ctx, int K, const float* states_in, float* states_out, 
     for (int k = 0; k < K; ++k) {
         const int d = d0 + k;
         DxLevel& w = a.lv[k];
-        w.sig1 = ctx->f_sig[d][0]; w.sig1_b = ctx->sig[d].b1; w.sig_slope = ctx->sig[d].slope; w.sig2 = ctx->f_sig[d][1]; w.sig2_b = ctx->sig[d].b2;
-        w.st1 = ctx->st[d].w1; w.st1_b = ctx->st[d].b1; w.st_slope = ctx->st[d].slope; w.st2 = ctx->st[d].w2; w.st2_b = ctx->st[d].b2;
-        w.down = ctx->f_down2[d]; w.down_b = ctx->down[d].b;
-        w.up = ctx->f_up[d]; w.up_b = ctx->up[d].b;
-        w.dec1 = ctx->f_dec[d][0]; w.dec1_b = ctx->dec[d].b1; w.dec_slope = ctx->dec[d].slope; w.dec2 = ctx->f_dec[d][1]; w.dec2_b = ctx->dec[d].b2;
+        const DcLayer &sig = ctx->sig[d], &st = ctx->st[d], &dec = ctx->dec[d];
+        w.sig1 = sig.f1.f32; w.sig1_b = sig.w.b1; w.sig_slope = sig.w.slope; w.sig2 = sig.f2.f32; w.sig2_b = sig.w.b2;
+        w.st1 = st.w.w1; w.st1_b = st.w.b1; w.st_slope = st.w.slope; w.st2 = st.w.w2; w.st2_b = st.w.b2;
+        w.down = ctx->down[d].f_pair; w.down_b = ctx->down[d].f.bias;
+        w.up = ctx->up[d].f.f32; w.up_b = ctx->up[d].f.bias;
+        w.dec1 = dec.f1.f32; w.dec1_b = dec.w.b1; w.dec_slope = dec.w.slope; w.dec2 = dec.f2.f32; w.dec2_b = dec.w.b2;
         w.st_in = states_in + ctx->state_off[d];
         w.st_out = states_out + ctx->state_off[d];
         w.g_out = ctx->buf_o[d] + (long)ws_off * kFeat * plane(d);
@@ -835,7 +836,8 @@ int launch_deepx(hn_ctx* ctx, int K, const float* states_in, float* states_out, 
         w.g_y = ctx->buf_y[d + 1] + (long)ws_off * kFeat * plane(d + 1);
         w.g_u = ctx->buf_a[d] + (long)ws_off * kFeat * plane(d);   // (x_d is dead once conv_signal_d has read it: the upsampled tensor takes its buffer, as in the layer-by-layer path)
     }
-    a.bot1 = ctx->f_dec[depth][0]; a.bot1_b = ctx->dec[depth].b1; a.bot_slope = ctx->dec[depth].slope; a.bot2 = ctx->f_dec[depth][1]; a.bot2_b = ctx->dec[depth].b2;
+    const DcLayer& bot = ctx->dec[depth];
+    a.bot1 = bot.f1.f32; a.bot1_b = bot.w.b1; a.bot_slope = bot.w.slope; a.bot2 = bot.f2.f32; a.bot2_b = bot.w.b2;
     a.x_in = ctx->buf_a[d0] + (long)ws_off * kFeat * plane(d0);
     a.y_out = ctx->buf_y[d0] + (long)ws_off * kFeat * plane(d0);
     a.wblob = ctx->wdev; a.wblob_floats = (int)hn_weight_count(kFeat, depth, kState);

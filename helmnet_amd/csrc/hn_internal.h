@@ -117,6 +117,63 @@ struct K8W {
     const float* b;
 };
 
+// ---- the raw (PyTorch-layout) weight blob: inc, per level conv_signal / down / conv_state, the decoders (the last one is the bottleneck), the ups, outc ----
+struct RawDc { size_t w1, b1, slope, w2, b2; int cin, cm, co; };   // offsets in floats: w1 [cm][cin][3][3], b1 [cm], slope [1], w2 [co][cm][3][3], b2 [co]
+struct RawK8 { size_t w, b; };                                      // w [8][8][8][8], b [8]
+inline RawDc raw_dc(size_t& pos, int cin, int cm, int co) {
+    RawDc d{};
+    d.cin = cin; d.cm = cm; d.co = co;
+    d.w1 = pos; pos += (size_t)cm * cin * 9;
+    d.b1 = pos; pos += cm;
+    d.slope = pos; pos += 1;
+    d.w2 = pos; pos += (size_t)co * cm * 9;
+    d.b2 = pos; pos += co;
+    return d;
+}
+inline RawK8 raw_k8(size_t& pos) { RawK8 k{}; k.w = pos; pos += (size_t)kFeat * kFeat * 64; k.b = pos; pos += kFeat; return k; }
+// The one place that knows the order of the layers in the blob.  `nets` are structs with the members inc, sig[], down[], st[], dec[], up[] (RawLayout, hn_ctx),
+// walked side by side: dc(cin, cm, co, nets.layer...) for every DoubleConv, k8(transposed, nets.layer...) for every 8x8 convolution; the out-conv follows.
+template <class FDc, class FK8, class... Net>
+void for_each_layer(int depth, FDc&& dc, FK8&& k8, Net&... nets) {
+    dc(kInCh, kFeat, kFeat, nets.inc...);
+    for (int d = 0; d < depth; ++d) {
+        dc(kFeat + kState, kFeat, kFeat, nets.sig[d]...);
+        k8(false, nets.down[d]...);
+        dc(kFeat + kState, kState, kState, nets.st[d]...);
+    }
+    for (int d = 0; d <= depth; ++d) dc(d < depth ? 2 * kFeat : kFeat, kFeat, kFeat, nets.dec[d]...);
+    for (int d = 0; d < depth; ++d) k8(true, nets.up[d]...);
+}
+struct RawLayout {
+    RawDc inc, sig[kMaxDepth], st[kMaxDepth], dec[kMaxDepth + 1];
+    RawK8 down[kMaxDepth], up[kMaxDepth];
+    size_t outc_w, outc_b, total;   // outc: weight [2][8], bias [2]
+};
+inline RawLayout raw_layout(int depth) {
+    RawLayout L{};
+    size_t pos = 0;
+    for_each_layer(depth, [&](int cin, int cm, int co, RawDc& d) { d = raw_dc(pos, cin, cm, co); }, [&](bool, RawK8& k) { k = raw_k8(pos); }, L);
+    L.outc_w = pos; pos += 2 * kFeat;
+    L.outc_b = pos; pos += 2;
+    L.total = pos;
+    return L;
+}
+
+// ---- host-side records of the loaded network: what a kernel takes by value plus that layer's matrix-core A-operand fragments (hn_mfma.hip) ----
+// One convolution's fragments: fp32 and its split-bf16 / fp16 twins.  No twins (nullptr): the launchers run the fp32 kernels whatever the precision mode.
+struct Frag { const float *f32, *bf16, *f16; };
+struct DcLayer {
+    DcW w;
+    Frag f1, f2;   // conv1 [cin][3][64], conv2 [cm][3][64]; conv_state: its two output channels in rows 0..3 of M, no twins (hn_deep.hip)
+};
+// an 8x8 convolution as launch_down / launch_up take it: fragments [8][8][64], their twins [8 blocks][parts][64 lanes][8 ci] (nullable, as above), the bias
+struct K8Frag { const float *f32, *bf16, *f16, *bias; };
+struct K8Layer {
+    K8W w;
+    K8Frag f;
+    const float* f_pair;   // `down` only: the column-pair packing of hn_deepx.hip, [8 ci][2 h][10 kx'][64]
+};
+
 struct SpecTables {
     int n = 0;
     bool pow2 = false;
@@ -148,16 +205,11 @@ struct hn_ctx {
     int depth = 0;
     int act_kind = HN_ACT_PRELU;
     float* wdev = nullptr;  // all re-packed weights
-    hn::DcW inc{}, sig[hn::kMaxDepth]{}, st[hn::kMaxDepth]{}, dec[hn::kMaxDepth + 1]{};
-    hn::K8W down[hn::kMaxDepth]{}, up[hn::kMaxDepth]{};
-    // MFMA A-operand fragments (hn_mfma.hip): [cin][3][64] per 3x3 conv, [8][8][64] per 8x8 conv
-    float* fragdev = nullptr;
-    const float *f_inc[2]{}, *f_sig[hn::kMaxDepth][2]{}, *f_dec[hn::kMaxDepth + 1][2]{};
-    const float *f_down[hn::kMaxDepth]{}, *f_up[hn::kMaxDepth]{};
-    const float* f_down2[hn::kMaxDepth]{};   // the 8x8 stride-2 convolution again in the column-pair packing of hn_deepx.hip: [8 ci][2 h][10 kx'][64]
+    hn::DcLayer inc{}, sig[hn::kMaxDepth]{}, st[hn::kMaxDepth]{}, dec[hn::kMaxDepth + 1]{};   // (their pointers lead into wdev and fragdev)
+    hn::K8Layer down[hn::kMaxDepth]{}, up[hn::kMaxDepth]{};
+    float* fragdev = nullptr;   // every re-packing of the weights beyond wdev: the layers' fragments and what follows here
     const float *f_dec0c = nullptr, *dec0c_b = nullptr;   // decode[0] conv2 composed with the out-conv: [8][5][64] row-triple fragments, bias [2]
     const float* v_dec0c = nullptr;   // the same composed convolution for the vector-pipe kernel: [8 cm][3][3][2] (hn_dcv.hip)
-    const float* f_st[hn::kMaxDepth][2]{};   // conv_state (2 output channels in rows 0..3 of M): [10][3][64], [2][3][64] (hn_deep.hip)
     bool deep_attr_set = false, pfa_attr_set = false, pfa_adj_attr_set = false;
     // arithmetic of the UNet convolutions (hn_set_unet_precision; default from HN_UNET_IMPL at hn_create only)
     int precision = HN_PREC_FP32;
@@ -440,8 +492,8 @@ size_t k8_half_floats();
 void pack_frag_down_x16(const float* w_oihw, float* dst_split, float* dst_half);
 void pack_frag_up_x16(const float* w_iohw, float* dst_split, float* dst_half);
 // kind: 0 inc (2+2+2 ch), 1 conv_signal (8+2), 2 bottleneck (8), 3 decoder (8+8; final_epi adds outc + wf update)
-int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w, const float* frag1, const float* frag2,
-               bool final_epi, float* d_out, float* wf, int H, int W, int batch, hipStream_t s);
+int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcLayer& l, bool final_epi, float* d_out, float* wf, int H, int W, int batch,
+               hipStream_t s);
 // training forward: the fused matrix-core DoubleConv with the pre-activation mid tensor stored to `z` ([B, 8, H, W]); fragments as pack_frag_3x3
 bool dc8_tape_applies(int H, int W);
 // Backward-data pass of an 8-channel DoubleConv (cin -> 8 -> 8) on the fp32 matrix core (hn_mfma.hip, k_dc_bwd_mfma_p): g_z = conv2^T(g) * act'(z),
@@ -474,9 +526,9 @@ int dc8_bwd_tiles(int H, int W, int batch);   // rows of slope_part a launch add
 int launch_dc8_bwd(hn_ctx* ctx, const McBwd& a, int cin, int H, int W, int batch, hipStream_t s);
 int launch_dc8_tape(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const float* frag1, const float* b1, const float* slope, const float* frag2,
                     const float* b2, int act, float* z, int H, int W, int batch, hipStream_t s);
-void launch_down(const hn_ctx* ctx, Src in, Dst out, const float* frag, const float* bias, int Hin, int Win, int batch, hipStream_t s,
+void launch_down(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s,
                  SyncHook hook = SyncHook{});   // hook: fp32 matrix-core kernels only (k_down_mfma)
-void launch_up(const hn_ctx* ctx, Src in, Dst out, const float* frag, const float* bias, int Hin, int Win, int batch, hipStream_t s, bool accumulate = false,
+void launch_up(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s, bool accumulate = false,
                SyncHook hook = SyncHook{});   // hook: fp32 matrix-core kernels only (k_up_mfma)
 
 // ---- vector-pipe DoubleConv of the big levels (hn_dcv.hip) ----

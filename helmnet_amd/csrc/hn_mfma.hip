@@ -2533,8 +2533,8 @@ void pack_frag_down(const float* w, float* dst) {
             }
 }
 // 16-bit fragments of the 8x8 convs (k_down_x16 / k_up_x16): [8 blocks][parts][64 lanes][8 ci]; block = kx (down) or
-// px * 4 + bb (up); lane -> (co, h | py = l & 1, q | a = l >> 4) as in the fp32 packers; the 3-part bf16 buffer
-// (k8_split_floats) is followed by the fp16 one (k8_half_floats).
+// px * 4 + bb (up); lane -> (co, h | py = l & 1, q | a = l >> 4) as in the fp32 packers; one buffer for the 3-part bf16
+// fragments (k8_split_floats), one for the fp16 ones (k8_half_floats).
 size_t k8_split_floats() { return (size_t)8 * 3 * 64 * 4; }
 size_t k8_half_floats() { return (size_t)8 * 64 * 4; }
 static void pack_k8_x16(const float* w, bool up, float* dst_split, float* dst_half) {
@@ -2572,8 +2572,9 @@ void pack_frag_up(const float* w, float* dst) {
                 }
 }
 
-int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w, const float* frag1, const float* frag2,
-               bool final_epi, float* d_out, float* wf, int H, int W, int batch, hipStream_t s) {
+int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcLayer& l, bool final_epi, float* d_out, float* wf, int H, int W, int batch,
+               hipStream_t s) {
+    const DcW& w = l.w;
     if (dc_asm_applies(ctx, w.act, a, b, c, kind, H, W)) {
         launch_dc_asm(ctx, kind, a, b, c, out, w, final_epi, d_out, wf, H, W, batch, s);
         return HN_OK;
@@ -2582,11 +2583,7 @@ int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w
         launch_dc_valu(ctx, kind, a, b, c, out, w, final_epi, d_out, wf, H, W, batch, s);
         return HN_OK;
     }
-    const int cin = kind == 0 ? kInCh : kind == 1 ? kFeat + kState : kind == 2 ? kFeat : 2 * kFeat;
-    // hn_load_weights stores the split-bf16 fragments right behind the fp32 ones
-    const float* s1 = frag1 + (size_t)cin * 3 * 64;      // split-bf16 twin, then the fp16 twin
-    const float* s2 = frag2 + (size_t)kFeat * 3 * 64;
-    const McW mw{frag1, w.b1, w.slope, frag2, w.b2, s1, s2, s1 + frag_3x3_split_floats(cin), s2 + frag_3x3_split_floats(kFeat), w.act};
+    const McW mw{l.f1.f32, w.b1, w.slope, l.f2.f32, w.b2, l.f1.bf16, l.f2.bf16, l.f1.f16, l.f2.f16, w.act};
     McEpi e{ctx->outc_w, ctx->outc_b, d_out, wf, ctx->f_dec0c, ctx->dec0c_b};
     e.wf_in = ctx->step_wf_in != nullptr ? ctx->step_wf_in : wf;
     const int x16 = (ctx->precision >= HN_PREC_BF16X3 && ctx->precision <= HN_PREC_BF16X2) ? ctx->precision : 0;
@@ -2665,16 +2662,16 @@ int launch_dc8_bwd_aux(hn_ctx* ctx, const McBwd& a, const McBwdAux& x, int H, in
     return HN_OK;
 }
 
-void launch_down(const hn_ctx* ctx, Src in, Dst out, const float* frag, const float* bias, int Hin, int Win, int batch, hipStream_t s, SyncHook hook) {
+void launch_down(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s, SyncHook hook) {
     const int Wout = Win / 2, Hout = Hin / 2;
+    const float *frag = w.f32, *bias = w.bias;
+    const int mode = w.f16 != nullptr ? ctx->precision : HN_PREC_FP32;   // (no twins: the caller's own fp32 fragments, hn_train.hip)
     // mixed-precision modes: levels 0 and 1 on the 16-bit matrix core; the 3-part split stays on the fp32 kernel
     // here (its 71 KB window and 288 MFMAs per wave measured 55 us against 48 us)
-    if (const int mode = ctx->precision; (mode == HN_PREC_FP16 || mode == HN_PREC_BF16X2) && Wout >= 64) {
+    if ((mode == HN_PREC_FP16 || mode == HN_PREC_BF16X2) && Wout >= 64) {
         const dim3 g(cdiv_(Wout, 16), cdiv_(Hout, 16), batch);
-        const float* split = frag + (size_t)kFeat * kFeat * 64;   // hn_load_weights stores the 16-bit twins behind the fp32 block
-        const float* half = split + k8_split_floats();
-        if (mode == 3) hipLaunchKernelGGL((k_down_x16<SplitBf16x2>), g, dim3(256), 0, s, in, out, split, bias, Hin, Win);
-        else hipLaunchKernelGGL((k_down_x16<HalfF16>), g, dim3(256), 0, s, in, out, half, bias, Hin, Win);
+        if (mode == 3) hipLaunchKernelGGL((k_down_x16<SplitBf16x2>), g, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win);
+        else hipLaunchKernelGGL((k_down_x16<HalfF16>), g, dim3(256), 0, s, in, out, w.f16, bias, Hin, Win);
         return;
     }
     // tile shape by level size: 64x16 outputs per block for the big levels, 32x16 at 64 < Wout... (more, shorter blocks
@@ -2690,15 +2687,15 @@ void launch_down(const hn_ctx* ctx, Src in, Dst out, const float* frag, const fl
     }
 }
 
-void launch_up(const hn_ctx* ctx, Src in, Dst out, const float* frag, const float* bias, int Hin, int Win, int batch, hipStream_t s, bool accumulate, SyncHook hook) {
+void launch_up(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s, bool accumulate, SyncHook hook) {
+    const float *frag = w.f32, *bias = w.bias;
+    const int mode = w.f16 != nullptr ? ctx->precision : HN_PREC_FP32;   // (as launch_down)
     // window rows -1 .. Hin-1
-    if (const int mode = ctx->precision; mode >= HN_PREC_BF16X3 && mode <= HN_PREC_BF16X2 && Win >= 64) {
+    if (mode >= HN_PREC_BF16X3 && mode <= HN_PREC_BF16X2 && Win >= 64) {
         const dim3 g(cdiv_(Win, 16), cdiv_(Hin + 1, 20), batch);
-        const float* split = frag + (size_t)kFeat * kFeat * 64;
-        const float* half = split + k8_split_floats();
-        if (mode == 1) hipLaunchKernelGGL((k_up_x16<SplitBf16>), g, dim3(256), 0, s, in, out, split, bias, Hin, Win, hook);
-        else if (mode == 3) hipLaunchKernelGGL((k_up_x16<SplitBf16x2>), g, dim3(256), 0, s, in, out, split, bias, Hin, Win, hook);
-        else hipLaunchKernelGGL((k_up_x16<HalfF16>), g, dim3(256), 0, s, in, out, half, bias, Hin, Win, hook);
+        if (mode == 1) hipLaunchKernelGGL((k_up_x16<SplitBf16>), g, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win, hook);
+        else if (mode == 3) hipLaunchKernelGGL((k_up_x16<SplitBf16x2>), g, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win, hook);
+        else hipLaunchKernelGGL((k_up_x16<HalfF16>), g, dim3(256), 0, s, in, out, w.f16, bias, Hin, Win, hook);
         return;
     }
     constexpr int up_small = 64;  // at and below: the all-channels-at-once kernel (few tiles, latency-bound)

@@ -44,42 +44,6 @@ namespace {
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 void select_gset(hn_ctx::TrainWs& W, int k);
 
-// ---- raw (PyTorch-layout) blob offsets, the order of hn_load_weights -------------------------------------------------
-struct RawDc { size_t w1, b1, slope, w2, b2; int cin, cm, co; };
-struct RawK8 { size_t w, b; };
-struct RawLayout {
-    RawDc inc, sig[kMaxDepth], st[kMaxDepth], dec[kMaxDepth + 1];
-    RawK8 down[kMaxDepth], up[kMaxDepth];
-    size_t outc_w, outc_b, total;
-};
-RawLayout raw_layout(int depth) {
-    RawLayout L{};
-    size_t pos = 0;
-    auto dc = [&](int cin, int cm, int co) {
-        RawDc d{};
-        d.cin = cin; d.cm = cm; d.co = co;
-        d.w1 = pos; pos += (size_t)cm * cin * 9;
-        d.b1 = pos; pos += cm;
-        d.slope = pos; pos += 1;
-        d.w2 = pos; pos += (size_t)co * cm * 9;
-        d.b2 = pos; pos += co;
-        return d;
-    };
-    auto k8 = [&]() { RawK8 k{}; k.w = pos; pos += (size_t)kFeat * kFeat * 64; k.b = pos; pos += kFeat; return k; };
-    L.inc = dc(kInCh, kFeat, kFeat);
-    for (int d = 0; d < depth; ++d) {
-        L.sig[d] = dc(kFeat + kState, kFeat, kFeat);
-        L.down[d] = k8();
-        L.st[d] = dc(kFeat + kState, kState, kState);
-    }
-    for (int d = 0; d <= depth; ++d) L.dec[d] = dc(d < depth ? 2 * kFeat : kFeat, kFeat, kFeat);
-    for (int d = 0; d < depth; ++d) L.up[d] = k8();
-    L.outc_w = pos; pos += 2 * kFeat;
-    L.outc_b = pos; pos += 2;
-    L.total = pos;
-    return L;
-}
-
 // ---- activations and their derivatives (architectures.py:5-44) ---------------------------------------------------------
 // GEN = false: the piecewise-linear activations only (prelu / relu / leakyrelu -- the shipped network).  The kernels are instantiated
 // for both: the smooth activations' code (expm1f, tanhf, erff, log1pf inlined at every staged element) made a 3x3 kernel 35 KB of
@@ -1250,7 +1214,8 @@ struct Trainer {
     const float* wfwd(size_t off) const { return ctx->tr.w3 + pk_off((long)off); }            // (packed weights: one copy, in the first lane's workspace)                // k_pack3: forward arrangement at the raw offset
     const float* wbwd(size_t off) const { return ctx->tr.w3 + pk_off((long)L.total) + 2 + pk_off((long)off); }      // backward-data arrangement behind it
     float* table(size_t col) const { return T().part + col; }                   // &table[0][col]; rows are L.total floats apart
-    const float* frag8(int d, int which) const { return ctx->tr.k8 + ((size_t)d * 4 + which) * 4096; }   // 0 down fwd, 1 down bwd-data, 2 up fwd, 3 up bwd-data
+    // this call's own fp32 fragments of an 8x8 convolution (no 16-bit twins: the fp32 kernels): 0 down fwd, 1 down bwd-data, 2 up fwd, 3 up bwd-data
+    K8Frag frag8(int d, int which, const float* bias) const { return K8Frag{ctx->tr.k8 + ((size_t)d * 4 + which) * 4096, nullptr, nullptr, bias}; }
 
     Conv3Args fwd_args(const TSrc (&src)[3], size_t w_off, size_t b_off, size_t slope_off, TDst dst, int d) const {
         Conv3Args a{};
@@ -1466,7 +1431,7 @@ struct Trainer {
             if ((rc = dc_fwd(L.sig[d], in_sig, tape(t, W.o_zsig[d]), featdst(tape(t, W.o_out[d]), d), d, &F3.sig[d])) != HN_OK) return rc;
             SyncHook hk;   // flag sync: conv_signal of the last level is complete when its `down` starts: the hidden-state launch may go
             if (flag_sync && fused_state && side_state_fwd && d == depth - 1) { fwd_epoch = ++ctx->sync_epoch; hk.store = ctx->sync_flags + 64; hk.store_epoch = fwd_epoch; }
-            launch_down(ctx, msrc(tape(t, W.o_out[d]), d), mdst(tape(t, W.o_x[d + 1]), d + 1), frag8(d, 0), w + L.down[d].b, side(d), side(d), B, s, hk);
+            launch_down(ctx, msrc(tape(t, W.o_out[d]), d), mdst(tape(t, W.o_x[d + 1]), d + 1), frag8(d, 0, w + L.down[d].b), side(d), side(d), B, s, hk);
         }
         {   // new_state_d = conv_state_d(cat[out_d, state_d]) (architectures.py:248) for every level at once: nothing of this iteration
             // reads the new states, so the levels' DoubleConvs are two launches (first convolutions, second convolutions) instead of 2 depth
@@ -1505,7 +1470,7 @@ struct Trainer {
         for (int d = depth - 1; d >= 0; --d) {
             SyncHook hk;   // flag sync: the iteration's new hidden states are complete when up_0 is
             if (flag_sync && fused_state && side_state_fwd && d == 0) { hk.wait = ctx->sync_flags + 96; hk.wait_epoch = fwd_epoch; hk.err = ctx->sync_err_dev; }
-            launch_up(ctx, msrc(tape(t, W.o_y[d + 1]), d + 1), mdst(tape(t, W.o_u[d]), d), frag8(d, 2), w + L.up[d].b, side(d + 1), side(d + 1), B, s, false, hk);
+            launch_up(ctx, msrc(tape(t, W.o_y[d + 1]), d + 1), mdst(tape(t, W.o_u[d]), d), frag8(d, 2, w + L.up[d].b), side(d + 1), side(d + 1), B, s, false, hk);
             const TSrc in[3] = {feat(tape(t, W.o_u[d]), d), feat(tape(t, W.o_out[d]), d), nosrc()};
             if ((rc = dc_fwd(L.dec[d], in, tape(t, W.o_zdec[d]), featdst(tape(t, W.o_y[d]), d), d, &F3.dec[d])) != HN_OK) return rc;
         }
@@ -1622,7 +1587,7 @@ struct Trainer {
                 if ((rc = dc_bwd(L.dec[d], slot_dec(d), in, tape(t, W.o_zdec[d]), feat(W.g_y[d], d), gin, d, &F3.decb[d])) != HN_OK) return rc;
             }
             // up[d]: backward-data = the stride-2 convolution kernel on the transposed-convolution weights read as [out, in, kh, kw]
-            launch_down(ctx, msrc(W.g_u[d], d), mdst(W.g_y[d + 1], d + 1), frag8(d, 3), ctx->tr.zero8, side(d), side(d), B, s);
+            launch_down(ctx, msrc(W.g_u[d], d), mdst(W.g_y[d + 1], d + 1), frag8(d, 3, ctx->tr.zero8), side(d), side(d), B, s);
             wgrad8(tape(t, W.o_y[d + 1]), d + 1, W.g_u[d], L.up[d].w, 1);
         }
         {
@@ -1633,7 +1598,7 @@ struct Trainer {
         for (int d = depth - 1; d >= 0; --d) {   // encoder, bottom up
             // down[d]: backward-data = the transposed-convolution kernel on the convolution weights read as [in, out, kh, kw];
             // added to the skip gradient
-            launch_up(ctx, msrc(W.g_x[d + 1], d + 1), mdst(W.g_out[d], d), frag8(d, 1), ctx->tr.zero8, side(d + 1), side(d + 1), B, s, true);
+            launch_up(ctx, msrc(W.g_x[d + 1], d + 1), mdst(W.g_out[d], d), frag8(d, 1, ctx->tr.zero8), side(d + 1), side(d + 1), B, s, true);
             wgrad8(W.g_x[d + 1], d + 1, tape(t, W.o_out[d]), L.down[d].w, 0);
             {   // conv_signal: out = DC(cat[x, state])
                 const TSrc in[3] = {feat(tape(t, W.o_x[d]), d), state_src(st_in, d), nosrc()};
@@ -1987,9 +1952,7 @@ int hn_train_grad(hn_ctx* ctx, const float* weights, const float* wf, const floa
         tr[l].wg_cap = mode == 2 && px >= 200000 && px < 1000000 ? (int)(px / HN_WG_CAP_DIV < 512 ? 512 : px / HN_WG_CAP_DIV) : 0;
     }
     const size_t fwf = (size_t)batch * p2, fst = (size_t)batch * pst;
-    // the training pass is fp32 whatever arithmetic the context's inference path is set to (the 8x8 launchers read it)
-    struct PrecisionGuard { hn_ctx* c; int saved; ~PrecisionGuard() { c->precision = saved; } } pg{ctx, ctx->precision};
-    ctx->precision = HN_PREC_FP32;
+    // (the training pass is fp32 whatever arithmetic the context's inference path is set to: it brings its own fragments, without 16-bit twins)
     {   // weights in the layouts the kernels read
         pack_train_weights(ctx, L, weights, s);
         auto& W = ctx->tr;
@@ -2168,8 +2131,6 @@ int hn_step_vjp(hn_ctx* ctx, const float* weights, const float* wf0, const float
         tr.side_state_fwd = mode == 2 && px >= 200000;
         tr.wg_cap = mode == 2 && px >= 200000 && px < 1000000 ? (int)(px / HN_WG_CAP_DIV < 512 ? 512 : px / HN_WG_CAP_DIV) : 0;
     }
-    struct PrecisionGuard { hn_ctx* c; int saved; ~PrecisionGuard() { c->precision = saved; } } pg{ctx, ctx->precision};
-    ctx->precision = HN_PREC_FP32;
     pack_train_weights(ctx, L, weights, s);
     if (g_weights != nullptr && !cont) {
         if ((rc = zero_async(ctx, W.part, sizeof(float) * W.part_floats, s)) != HN_OK) return rc;

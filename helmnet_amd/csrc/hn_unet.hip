@@ -470,8 +470,8 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
     } else {
     // inc: DoubleConv(6 -> 8 -> 8) on [wf, 1e3*res, sigmas]  (architectures.py:442, hybridnet.py:566)
     ProfScope ps(ctx, KID_INC, s);
-    if (mfma) launch_dc8(ctx, 0, in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), ctx->inc, ctx->f_inc[0], ctx->f_inc[1], false, nullptr, nullptr, n, n, batch, s);
-    else launch_dc<2, 2, 2, kFeat, kFeat, 0>(in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), ctx->inc, noepi, n, n, batch, s);
+    if (mfma) launch_dc8(ctx, 0, in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), ctx->inc, false, nullptr, nullptr, n, n, batch, s);
+    else launch_dc<2, 2, 2, kFeat, kFeat, 0>(in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), ctx->inc.w, noepi, n, n, batch, s);
     }
     // deferred join (hn_step): the hidden-state kernels of the PREVIOUS iteration are waited for here, behind the input layer (the
     // first reader of the new states is conv_signal_0 below; the side kernels read the skip buffers, which conv_signal_0 is also the
@@ -519,9 +519,9 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
             const Src so{states_in + ctx->state_off[e], 2 * L, L, 1.f};
             const Dst sn{states_out + ctx->state_off[e], 2 * L, L};
 #ifndef HN_EXP_REPEAT   // (the per-kernel probes of tools/energy_probe.py / cs_skip_probe.py launch every level on its own)
-            if (conv_state_applies(ctx, ctx->st[e], featsrc(ctx->buf_o[e], e), so, sn, me, me)) {
+            if (conv_state_applies(ctx, ctx->st[e].w, featsrc(ctx->buf_o[e], e), so, sn, me, me)) {
                 if (nb_levels == 0) first_level = e;
-                ba[nb_levels] = featsrc(ctx->buf_o[e], e); bb[nb_levels] = so; bo[nb_levels] = sn; bw[nb_levels] = ctx->st[e]; bh[nb_levels] = me;
+                ba[nb_levels] = featsrc(ctx->buf_o[e], e); bb[nb_levels] = so; bo[nb_levels] = sn; bw[nb_levels] = ctx->st[e].w; bh[nb_levels] = me;
                 ++nb_levels;
                 continue;
             }
@@ -529,8 +529,8 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
             ProfScope ps2(ctx, KID_STATE0 + 3 * e, side);
             HN_REP(KID_STATE0 + 3 * e) {
                 const Src oe = featsrc(ctx->buf_o[e], e);
-                if (conv_state_applies(ctx, ctx->st[e], oe, so, sn, me, me)) launch_conv_state(ctx, 1, &oe, &so, &sn, &ctx->st[e], &me, &me, batch, side);
-                else launch_dc<kFeat, kState, 0, kState, kState, 0>(featsrc(ctx->buf_o[e], e), so, none, sn, ctx->st[e], noepi, me, me, batch, side);
+                if (conv_state_applies(ctx, ctx->st[e].w, oe, so, sn, me, me)) launch_conv_state(ctx, 1, &oe, &so, &sn, &ctx->st[e].w, &me, &me, batch, side);
+                else launch_dc<kFeat, kState, 0, kState, kState, 0>(featsrc(ctx->buf_o[e], e), so, none, sn, ctx->st[e].w, noepi, me, me, batch, side);
             }
         }
         if (nb_levels > 0) {
@@ -558,17 +558,17 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
         if (!(pair && d == 0)) {
             ProfScope ps(ctx, KID_SIG0 + 3 * d, s);
             HN_REP(KID_SIG0 + 3 * d)
-            if (mfma) launch_dc8(ctx, 1, featsrc(ctx->buf_a[d], d), st_old, none, feat(ctx->buf_o[d], d), ctx->sig[d], ctx->f_sig[d][0],
-                                 ctx->f_sig[d][1], false, nullptr, nullptr, m, m, batch, s);
+            if (mfma) launch_dc8(ctx, 1, featsrc(ctx->buf_a[d], d), st_old, none, feat(ctx->buf_o[d], d), ctx->sig[d], false, nullptr, nullptr,
+                                 m, m, batch, s);
             else launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(featsrc(ctx->buf_a[d], d), st_old, none, feat(ctx->buf_o[d], d),
-                                                              ctx->sig[d], noepi, m, m, batch, s);
+                                                              ctx->sig[d].w, noepi, m, m, batch, s);
         }
         // state = conv_state(cat[out, state_old])                        (architectures.py:248)
         if (policy == 0) {
             ProfScope ps(ctx, KID_STATE0 + 3 * d, s);
             const Src od = featsrc(ctx->buf_o[d], d);
-            if (conv_state_applies(ctx, ctx->st[d], od, st_old, st_new, m, m)) launch_conv_state(ctx, 1, &od, &st_old, &st_new, &ctx->st[d], &m, &m, batch, s);
-            else launch_dc<kFeat, kState, 0, kState, kState, 0>(featsrc(ctx->buf_o[d], d), st_old, none, st_new, ctx->st[d],
+            if (conv_state_applies(ctx, ctx->st[d].w, od, st_old, st_new, m, m)) launch_conv_state(ctx, 1, &od, &st_old, &st_new, &ctx->st[d].w, &m, &m, batch, s);
+            else launch_dc<kFeat, kState, 0, kState, kState, 0>(featsrc(ctx->buf_o[d], d), st_old, none, st_new, ctx->st[d].w,
                                                                 noepi, m, m, batch, s);
         } else if (policy == 2) {
             int rc = release_states(d, d + 1, side_lane->ev[d]);
@@ -578,10 +578,10 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
         {
             ProfScope ps(ctx, KID_DOWN0 + 3 * d, s);
             HN_REP(KID_DOWN0 + 3 * d)
-            if (mfma) launch_down(ctx, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->f_down[d], ctx->down[d].b, m, m, batch, s);
+            if (mfma) launch_down(ctx, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].f, m, m, batch, s);
             else hipLaunchKernelGGL(k_down8x8, dim3(cdiv(m / 2, DownCfg::TW), cdiv(m / 2, DownCfg::TH), batch),
                                     dim3(DownCfg::NT), 0, s, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1),
-                                    ctx->down[d], m, m);
+                                    ctx->down[d].w, m, m);
         }
         if (d == 0 && after_down0 != nullptr) HN_HIP(ctx, hipEventRecord(after_down0, s));
         if (policy == 1 && d == n_enc - 1 && !rel_flag) {
@@ -623,9 +623,9 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
     if (!deep && !deepx) {
         ProfScope ps(ctx, KID_BOTTLENECK, s);
         if (mfma) launch_dc8(ctx, 2, featsrc(ctx->buf_a[depth], depth), none, none, feat(ctx->buf_y[depth], depth), ctx->dec[depth],
-                             ctx->f_dec[depth][0], ctx->f_dec[depth][1], false, nullptr, nullptr, n >> depth, n >> depth, batch, s);
+                             false, nullptr, nullptr, n >> depth, n >> depth, batch, s);
         else launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(featsrc(ctx->buf_a[depth], depth), none, none, feat(ctx->buf_y[depth], depth),
-                                                     ctx->dec[depth], noepi, n >> depth, n >> depth, batch, s);
+                                                     ctx->dec[depth].w, noepi, n >> depth, n >> depth, batch, s);
     }
     for (int d = n_enc - 1; d >= 0; --d) {
         const int m = n >> d;
@@ -633,25 +633,25 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
         {
             ProfScope ps(ctx, KID_UP0 + 2 * d, s);
             HN_REP(KID_UP0 + 2 * d)
-            if (mfma) launch_up(ctx, featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->f_up[d], ctx->up[d].b, m / 2, m / 2, batch, s, false,
+            if (mfma) launch_up(ctx, featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].f, m / 2, m / 2, batch, s, false,
                                 d == 0 ? join_hook : SyncHook{});
             else hipLaunchKernelGGL(k_up8x8, dim3(cdiv(m / 2, UpCfg::TW), cdiv(m / 2, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s,
-                                    featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d], m / 2, m / 2);
+                                    featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].w, m / 2, m / 2);
         }
         ProfScope ps(ctx, KID_DEC0 + 2 * d, s);
         // x = decode[d](cat[x, skip_d])                                  (architectures.py:458-460)
         HN_REP(KID_DEC0 + 2 * d)
         if (mfma) {
             launch_dc8(ctx, 3, featsrc(ctx->buf_a[d], d), featsrc(ctx->buf_o[d], d), none, d > 0 ? feat(ctx->buf_y[d], d) : Dst{nullptr, 0, 0},
-                       ctx->dec[d], ctx->f_dec[d][0], ctx->f_dec[d][1], d == 0, d_out, wf_update, m, m, batch, s);
+                       ctx->dec[d], d == 0, d_out, wf_update, m, m, batch, s);
         } else if (d > 0) {
             launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(featsrc(ctx->buf_a[d], d), featsrc(ctx->buf_o[d], d), none,
-                                                        feat(ctx->buf_y[d], d), ctx->dec[d], noepi, m, m, batch, s);
+                                                        feat(ctx->buf_y[d], d), ctx->dec[d].w, noepi, m, m, batch, s);
         } else {
             // + outc 1x1 (architectures.py:463) and wf <- d/1e3 + wf (hybridnet.py:570)
             const DcEpi e{ctx->outc_w, ctx->outc_b, d_out, wf_update, ctx->step_wf_in != nullptr ? ctx->step_wf_in : wf_update};
             launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(featsrc(ctx->buf_a[0], 0), featsrc(ctx->buf_o[0], 0), none,
-                                                        Dst{nullptr, 0, 0}, ctx->dec[0], e, m, m, batch, s);
+                                                        Dst{nullptr, 0, 0}, ctx->dec[0].w, e, m, m, batch, s);
         }
     }
     if (policy != 0) {  // the next iteration's conv_signal reads the new states
