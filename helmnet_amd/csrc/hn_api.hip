@@ -675,10 +675,13 @@ int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states
     DeviceGuard guard(ctx);
     if ((rc = hn_reserve(ctx, batch)) != HN_OK) return rc;
     const long plane = (long)ctx->tab.n * ctx->tab.n;
-    const Src wf{in6, kInCh * plane, plane, 1.f};
-    const Src res{in6 + 2 * plane, kInCh * plane, plane, 1.f};
-    const Src sig{in6 + 4 * plane, kInCh * plane, plane, 1.f};
-    return unet_forward(ctx, wf, res, sig, states_in, states_out, d_out, nullptr, batch, (hipStream_t)stream);
+    UnetCall c;
+    c.wf = Src{in6, kInCh * plane, plane, 1.f};
+    c.res = Src{in6 + 2 * plane, kInCh * plane, plane, 1.f};
+    c.sig = Src{in6 + 4 * plane, kInCh * plane, plane, 1.f};
+    c.states_in = states_in; c.states_out = states_out; c.d_out = d_out;
+    c.batch = batch; c.stream = (hipStream_t)stream;
+    return unet_forward(ctx, c);
 }
 
 int hn_double_conv(hn_ctx* ctx, const float* x, int cin, int cout, const float* weights_host, int act_kind, float* out,
@@ -876,11 +879,15 @@ int one_iteration(hn_ctx* ctx, const StepArgs& a, int parity, int b0, int nb, in
     const float* res_in = (io ? io->res_in : a.res) + fo;
     float* st_user = a.states + (size_t)b0 * kState * L;
     float* st_tmp = ctx->st_tmp + (size_t)b0 * kState * L;
-    const Src s_wf{wf_in, 2 * plane, plane, 1.f};
-    const Src s_res{res_in, 2 * plane, plane, 1e3f};     // 1e3 * residual (hybridnet.py:566)
-    const Src s_sig{ctx->tab.sigmas, 0, plane, 1.f};     // sigmas.repeat(B) without the copy
-    int rc = unet_forward(ctx, s_wf, s_res, s_sig, parity ? st_tmp : st_user, parity ? st_user : st_tmp, nullptr, wf_j, nb, sj, b0,
-                          stagger, ctx->opt_side_stream ? &ctx->side[lane] : nullptr, defer_join, wf_in != wf_j ? wf_in : nullptr);
+    UnetCall c;
+    c.wf = Src{wf_in, 2 * plane, plane, 1.f};
+    c.res = Src{res_in, 2 * plane, plane, 1e3f};     // 1e3 * residual (hybridnet.py:566)
+    c.sig = Src{ctx->tab.sigmas, 0, plane, 1.f};     // sigmas.repeat(B) without the copy
+    c.states_in = parity ? st_tmp : st_user; c.states_out = parity ? st_user : st_tmp;
+    c.wf_in = wf_in; c.wf_out = wf_j;
+    c.batch = nb; c.stream = sj; c.ws_off = b0;
+    c.after_down0 = stagger; c.side_lane = ctx->opt_side_stream ? &ctx->side[lane] : nullptr; c.defer_join = defer_join;
+    int rc = unet_forward(ctx, c);
     if (rc != HN_OK) return rc;
     const float* src_j = a.src_batch == 1 ? a.src : a.src + (size_t)b0 * 2 * plane;
     HN_REP(KID_SPEC_PAIR)
@@ -1089,9 +1096,9 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
 
 // Laboratory accessor (tools/deepx_check.py; not part of the ABI of include/helmnet_hip.h): the workspace tensor kind (0 x_d / upsampled, 1 skip out_d,
 // 2 decoder output y_d) of level d, [reserved batch][8][n_d][n_d] floats.
-int hn_debug_workspace(hn_ctx* ctx, int kind, int level, float** ptr, long* floats) {
+int hn_debug_workspace(hn_ctx* ctx, int which, int level, float** ptr, long* floats) {
     if (!ctx || !ptr || !floats || level < 0 || level > kMaxDepth) return HN_ERR_ARG;
-    float* p = kind == 0 ? ctx->buf_a[level] : kind == 1 ? (level < kMaxDepth ? ctx->buf_o[level] : nullptr) : ctx->buf_y[level];
+    float* p = which == 0 ? ctx->buf_a[level] : which == 1 ? (level < kMaxDepth ? ctx->buf_o[level] : nullptr) : ctx->buf_y[level];
     const long m = ctx->tab.n >> level;
     *ptr = p;
     *floats = p ? (long)ctx->cap_batch * kFeat * m * m : 0;

@@ -206,26 +206,27 @@ __global__ __launch_bounds__(256, 4) void k_conv_state(CsArgs args, const float*
 }  // namespace
 
 // a = out_d (8 channels), b = state_d (2 channels); everything else keeps the general kernel (k_double_conv, hn_unet.hip)
-bool conv_state_applies(const hn_ctx* ctx, const DcW& w, Src a, Src b, Dst out, int H, int W) {
-    if (!ctx->opt_state_kernel || ctx->zero_page == nullptr || ctx->wdev == nullptr || w.act > HN_ACT_LEAKYRELU) return false;
-    if (w.w1 < ctx->wdev || w.w1 - ctx->wdev > (1 << 28)) return false;   // (the kernel addresses the weights as offsets into the context's blob)
-    if (a.scale != 1.f || b.scale != 1.f || W < 64 || (W & 3) != 0) return false;
-    const bool aligned = (reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(b.p) | reinterpret_cast<uintptr_t>(out.p)) % 16 == 0 &&
-                         (a.sb % 4 | a.sc % 4 | b.sb % 4 | b.sc % 4 | out.sb % 4 | out.sc % 4) == 0;
+bool conv_state_applies(const hn_ctx* ctx, const StateLevel& v) {
+    if (!ctx->opt_state_kernel || ctx->zero_page == nullptr || ctx->wdev == nullptr || v.w.act > HN_ACT_LEAKYRELU) return false;
+    if (v.w.w1 < ctx->wdev || v.w.w1 - ctx->wdev > (1 << 28)) return false;   // (the kernel addresses the weights as offsets into the context's blob)
+    if (v.a.scale != 1.f || v.b.scale != 1.f || v.W < 64 || (v.W & 3) != 0) return false;
+    const bool aligned = (reinterpret_cast<uintptr_t>(v.a.p) | reinterpret_cast<uintptr_t>(v.b.p) | reinterpret_cast<uintptr_t>(v.out.p)) % 16 == 0 &&
+                         (v.a.sb % 4 | v.a.sc % 4 | v.b.sb % 4 | v.b.sc % 4 | v.out.sb % 4 | v.out.sc % 4) == 0;
     return aligned;
 }
 
 // one launch for up to kMaxDepth levels (each checked with conv_state_applies); levels in the order given: the largest first
-void launch_conv_state(hn_ctx* ctx, int n, const Src* a, const Src* b, const Dst* out, const DcW* w, const int* H, const int* W, int batch, hipStream_t s) {
+void launch_conv_state(const hn_ctx* ctx, int n, const StateLevel* lv, int batch, hipStream_t s) {
     CsArgs args{};
     args.n = n;
     int tiles = 0;
     for (int l = 0; l < n; ++l) {
         CsLevel& L = args.lv[l];
-        L.a = a[l]; L.b = b[l]; L.out = out[l];
-        L.ow1 = (int)(w[l].w1 - ctx->wdev); L.ob1 = (int)(w[l].b1 - ctx->wdev); L.oslope = (int)(w[l].slope - ctx->wdev);
-        L.ow2 = (int)(w[l].w2 - ctx->wdev); L.ob2 = (int)(w[l].b2 - ctx->wdev);
-        L.H = H[l]; L.W = W[l]; L.gx = (W[l] + 63) / 64; L.gy = (H[l] + 15) / 16;
+        const StateLevel& v = lv[l];
+        L.a = v.a; L.b = v.b; L.out = v.out;
+        L.ow1 = (int)(v.w.w1 - ctx->wdev); L.ob1 = (int)(v.w.b1 - ctx->wdev); L.oslope = (int)(v.w.slope - ctx->wdev);
+        L.ow2 = (int)(v.w.w2 - ctx->wdev); L.ob2 = (int)(v.w.b2 - ctx->wdev);
+        L.H = v.H; L.W = v.W; L.gx = (v.W + 63) / 64; L.gy = (v.H + 15) / 16;
         L.tile0 = tiles; L.tiles = L.gx * L.gy * batch;
         tiles += L.tiles;
     }

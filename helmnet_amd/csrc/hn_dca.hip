@@ -459,37 +459,40 @@ static bool sigma_map_applies(const hn_ctx* ctx, Src c, int H, int W) {
     return ctx->opt_inc_sigma_map && ctx->inc_sigma_map != nullptr && c.p == ctx->tab.sigmas && c.sb == 0 && c.sc == (long)H * W && H == ctx->tab.n && W == ctx->tab.n;
 }
 
-bool dc_asm_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, int kind, int H, int W) {
+bool dc_asm_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, DcKind kind, int H, int W) {
     if (ctx->precision != HN_PREC_FP32 || ctx->opt_dc_valu < 3 || ctx->zero_page == nullptr) return false;
     if (act > HN_ACT_LEAKYRELU) return false;           // the smooth activations keep hn_dcv.hip's GEN instances
-    if (kind == 2) return false;                         // (the bottleneck lives at the deepest level)
-    if (ctx->opt_dc_valu == 3 && kind == 1) return false;   // 3: inc + decoder here, conv_signal on the matrix core; 4: all three
+    if (kind == DcKind::Bottleneck) return false;       // (the bottleneck lives at the deepest level)
+    if (ctx->opt_dc_valu == 3 && kind == DcKind::Signal) return false;   // 3: inc + decoder here, conv_signal on the matrix core; 4: all three
     // the input layer's weights carry the reference's 1e3 on the residual channels (hybridnet.py:566); any other scaling takes the other kernels
-    const bool scales_ok = kind == 0 ? (a.scale == 1.f && b.scale == 1000.f && c.scale == 1.f) : (a.scale == 1.f && b.scale == 1.f && c.scale == 1.f);
+    const bool inc = kind == DcKind::Inc;
+    const bool scales_ok = inc ? (a.scale == 1.f && b.scale == 1000.f && c.scale == 1.f) : (a.scale == 1.f && b.scale == 1.f && c.scale == 1.f);
     const bool off32 = 8.0 * (double)H * (double)W * 4.0 < 4.0e9;
-    const bool aligned = (reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(b.p) | (kind == 0 ? reinterpret_cast<uintptr_t>(c.p) : 0)) % 16 == 0 &&
-                         (a.sb % 4 | a.sc % 4 | b.sb % 4 | b.sc % 4 | (kind == 0 ? (c.sb % 4 | c.sc % 4) : 0)) == 0;
+    const bool aligned = (reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(b.p) | (inc ? reinterpret_cast<uintptr_t>(c.p) : 0)) % 16 == 0 &&
+                         (a.sb % 4 | a.sc % 4 | b.sb % 4 | b.sc % 4 | (inc ? (c.sb % 4 | c.sc % 4) : 0)) == 0;
 #ifndef HN_DCA_MIN_W
 #define HN_DCA_MIN_W 256
 #endif
     return W >= HN_DCA_MIN_W && (W & 3) == 0 && off32 && scales_ok && aligned;
 }
 
-void launch_dc_asm(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w, bool final_epi, float* d_out, float* wf, int H, int W,
-                   int batch, hipStream_t s) {
-    const VcEpi e{d_out, wf, ctx->v_dec0c, ctx->dec0c_b, ctx->step_wf_in != nullptr ? ctx->step_wf_in : wf};
+void launch_dc_asm(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s) {
+    const FinalEpi f = fin ? *fin : FinalEpi{};
+    const VcEpi e{f.d_out, f.wf_out, ctx->v_dec0c, ctx->dec0c_b, f.wf_in};
     switch (kind) {
-        case 0:                                                                                           // inc
+        case DcKind::Inc:
             if (sigma_map_applies(ctx, c, H, W)) launch<2, 2, 0, 0>(a, b, Src{nullptr, 0, 0, 1.f}, out, w, e, ctx->zero_page, H, W, batch, s, 0, SigmaMap{ctx->inc_sigma_map, ctx->inc_sigma_band});
             else launch<2, 2, 2, 0>(a, b, c, out, w, e, ctx->zero_page, H, W, batch, s);
             break;
-        case 1: launch<kFeat, kState, 0, 0>(a, b, c, out, w, e, ctx->zero_page, H, W, batch, s); break;      // conv_signal
-        default:
-            // decoder (+ out-conv, wavefield update).  With the side stream's gate wave resident (flag sync, hn_internal.h) the kernel runs at 3 blocks per CU:
+        case DcKind::Signal: launch<kFeat, kState, 0, 0>(a, b, c, out, w, e, ctx->zero_page, H, W, batch, s); break;
+        case DcKind::Bottleneck: break;   // (dc_asm_applies never takes it)
+        case DcKind::Decoder:
+            // (+ out-conv, wavefield update: FinalEpi).  With the side stream's gate wave resident (flag sync, hn_internal.h) the kernel runs at 3 blocks per CU:
             // at 4 (every VGPR of every SIMD) the gate's wave costs one CU a block slot and the kernel a ragged third round (70 -> 74 us); at 3 the decoder is as
             // fast as at 4 [measured, r5: DESIGN_NOTEBOOK Part I] and the gate fits beside it: +0.9 .. 1.1 % it/s at 256^2 x 32 (-0.5 % at 512^2, where no gate exists)
-            if (final_epi) launch<kFeat, kFeat, 0, 1>(a, b, c, out, w, e, ctx->zero_page, H, W, batch, s, ctx->dca_dec_pad);
+            if (fin) launch<kFeat, kFeat, 0, 1>(a, b, c, out, w, e, ctx->zero_page, H, W, batch, s, f.lds_pad);
             else launch<kFeat, kFeat, 0, 0>(a, b, c, out, w, e, ctx->zero_page, H, W, batch, s);
+            break;
     }
 }
 
@@ -497,7 +500,7 @@ void launch_dc_asm(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const Dc
 bool dc_asm_pair_applies(const hn_ctx* ctx, Src wf, Src res, Src sig, Src x0, Src st, int H, int W, int batch, int ws_off) {
     if (!ctx->opt_dc_pair || ctx->pair_flags == nullptr || ctx->pair_done == nullptr) return false;
     const Src none{nullptr, 0, 0, 1.f};
-    if (!dc_asm_applies(ctx, ctx->inc.w.act, wf, res, sig, 0, H, W) || !dc_asm_applies(ctx, ctx->sig[0].w.act, x0, st, none, 1, H, W)) return false;
+    if (!dc_asm_applies(ctx, ctx->inc.w.act, wf, res, sig, DcKind::Inc, H, W) || !dc_asm_applies(ctx, ctx->sig[0].w.act, x0, st, none, DcKind::Signal, H, W)) return false;
     return H == ctx->tab.n && W == ctx->tab.n && (long)cdiv_(W, 64) * cdiv_(H, 16) * (ws_off + batch) <= ctx->pair_flags_cap;   // (the counters assume ONE tile grid per context)
 }
 

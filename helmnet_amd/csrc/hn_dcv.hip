@@ -300,31 +300,33 @@ void pack_valu_q(const float* w, int cin, float* dst) {
                 for (int j = 0; j < 4; ++j) dst[(((size_t)ci * 2 + q) * 9 + t) * 4 + j] = w[((size_t)(4 * q + j) * cin + ci) * 9 + t];
 }
 
-bool dc_valu_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, int kind, int H, int W) {
+bool dc_valu_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, DcKind kind, int H, int W) {
     if (ctx->precision != HN_PREC_FP32 || !ctx->opt_dc_valu) return false;
     // HN_OPT_DC_VALU 1 (default): inc and the decoder on the vector pipe, conv_signal on the matrix core; 2: all three on the vector
     // pipe.  [measured on four boxes, 3 x 300 steps each] all-vector 1808 / 1987 / 1873 / 1929 it/s, all-matrix 1884 / 1902 / 1904 /
     // 1894, this mix 1887 / 1982 / 1925 / 1919: the packed-FMA kernels pull the shader clock down (median 2.22-2.30 GHz in the loop
     // instead of a held 2.40, tools/clock_probe.py) by an amount that depends on the box, and every other kernel pays for it.
-    if ((ctx->opt_dc_valu == 1 || ctx->opt_dc_valu == 3) && kind == 1) return false;   // (3 / 4: hn_dca.hip takes what it can; the rest falls through to here)
+    if ((ctx->opt_dc_valu == 1 || ctx->opt_dc_valu == 3) && kind == DcKind::Signal) return false;   // (3 / 4: hn_dca.hip takes what it can; the rest falls through to here)
 #ifdef HN_EXP_MFMA_KINDS
-    if ((HN_EXP_MFMA_KINDS >> kind) & 1) return false;   // A/B: these DoubleConv kinds stay on the matrix core
+    if ((HN_EXP_MFMA_KINDS >> (int)kind) & 1) return false;   // A/B: these DoubleConv kinds stay on the matrix core
 #endif
     (void)act;
     const bool scaled = a.scale != 1.f || b.scale != 1.f || c.scale != 1.f;
     const bool off32 = 8.0 * (double)H * (double)W * 4.0 < 4.0e9;
-    return W >= 256 && (W & 1) == 0 && off32 && (!scaled || kind == 0) && kind != 2;   // kind 2 (bottleneck) lives at the deepest level
+    return W >= 256 && (W & 1) == 0 && off32 && (!scaled || kind == DcKind::Inc) && kind != DcKind::Bottleneck;   // (the bottleneck lives at the deepest level)
 }
 
-void launch_dc_valu(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w, bool final_epi, float* d_out, float* wf, int H,
-                    int W, int batch, hipStream_t s) {
-    const VcEpi e{d_out, wf, ctx->v_dec0c, ctx->dec0c_b, ctx->step_wf_in != nullptr ? ctx->step_wf_in : wf};
+void launch_dc_valu(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s) {
+    const FinalEpi f = fin ? *fin : FinalEpi{};
+    const VcEpi e{f.d_out, f.wf_out, ctx->v_dec0c, ctx->dec0c_b, f.wf_in};
     switch (kind) {
-        case 0: launch<2, 2, 2, 0>(a, b, c, out, w, e, H, W, batch, s); break;              // inc
-        case 1: launch<kFeat, kState, 0, 0>(a, b, c, out, w, e, H, W, batch, s); break;      // conv_signal
-        default:
-            if (final_epi) launch<kFeat, kFeat, 0, 1>(a, b, c, out, w, e, H, W, batch, s);  // decoder (+ out-conv, wavefield update)
+        case DcKind::Inc: launch<2, 2, 2, 0>(a, b, c, out, w, e, H, W, batch, s); break;
+        case DcKind::Signal: launch<kFeat, kState, 0, 0>(a, b, c, out, w, e, H, W, batch, s); break;
+        case DcKind::Bottleneck: break;   // (dc_valu_applies never takes it)
+        case DcKind::Decoder:
+            if (fin) launch<kFeat, kFeat, 0, 1>(a, b, c, out, w, e, H, W, batch, s);  // (+ out-conv, wavefield update)
             else launch<kFeat, kFeat, 0, 0>(a, b, c, out, w, e, H, W, batch, s);
+            break;
     }
 }
 

@@ -100,9 +100,9 @@ __device__ __forceinline__ float act_general(float x, int act) {
 }
 // d act(x) / dx (the backward kernels); GEN = false: the piecewise-linear kinds (torch: the slope applies at x == 0)
 template <bool GEN>
-__device__ __forceinline__ float act_grad(float x, int kind, float slope) {
+__device__ __forceinline__ float act_grad(float x, int act, float slope) {
     if (!GEN) return x > 0.f ? 1.f : slope;
-    switch (kind) {
+    switch (act) {
         case HN_ACT_CELU: return x > 0.f ? 1.f : expf(x);
         case HN_ACT_TANH: { const float t = tanhf(x); return 1.f - t * t; }
         case HN_ACT_GELU: return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
@@ -259,9 +259,6 @@ struct hn_ctx {
     int opt_side_sync = 1;     // HN_OPT_SIDE_SYNC: 1 device words between the iterations of one hn_step call, 0 events everywhere
     unsigned* sync_flags = nullptr;   // device, 256 words: 0 release / 32 join of hn_step; 64, 96 forward and 128, 160 backward sweep of hn_train_grad
     unsigned sync_epoch = 0;   // (compared wrap-around safe)
-    const float* step_wf_in = nullptr;   // argument of the NEXT decode_0 launch: the wavefield its update starts from when that is not the buffer it writes
-                               // (hn_step's zero-copy wavefield history: reads slot it - 1, writes slot it); set and cleared by unet_forward
-    int dca_dec_pad = 0;       // dynamic LDS of the next decode_0 launch on hn_dca.hip: 7168 (3 blocks per CU) while the gate kernel is resident, else 0
     int* sync_err = nullptr;          // host-mapped: a bounded device-side wait that gave up stores its code here (sticky; checked by hn_step)
     int* sync_err_dev = nullptr;
     // hn_stream_verdict (hn_stream.hip): one record per slot, host-mapped like sync_err; sized with the workspace (hn_reserve), freed by hn_destroy
@@ -491,9 +488,13 @@ size_t k8_split_floats();
 size_t k8_half_floats();
 void pack_frag_down_x16(const float* w_oihw, float* dst_split, float* dst_half);
 void pack_frag_up_x16(const float* w_iohw, float* dst_split, float* dst_half);
-// kind: 0 inc (2+2+2 ch), 1 conv_signal (8+2), 2 bottleneck (8), 3 decoder (8+8; final_epi adds outc + wf update)
-int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcLayer& l, bool final_epi, float* d_out, float* wf, int H, int W, int batch,
-               hipStream_t s);
+// The 8-channel DoubleConvs by their channel groups: inc (2+2+2), conv_signal (8+2), bottleneck (8), decoder (8+8)
+enum class DcKind { Inc, Signal, Bottleneck, Decoder };
+// decode_0's epilogue (a Decoder launch with a non-null FinalEpi; null: a plain DoubleConv): the 1x1 out-conv, d stored to d_out (nullable), and the wavefield
+// update wf_out = wf_in + d / 1e3 (wf_out nullable; wf_in == wf_out: in place; hn_step's zero-copy wavefield history reads slot it - 1 and writes slot it).
+// lds_pad: dynamic LDS of the launch on hn_dca.hip: 7168 (3 blocks per CU) while the side stream's gate kernel is resident, else 0
+struct FinalEpi { float* d_out; float* wf_out; const float* wf_in; int lds_pad; };
+void launch_dc8(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcLayer& l, const FinalEpi* fin, int H, int W, int batch, hipStream_t s);
 // training forward: the fused matrix-core DoubleConv with the pre-activation mid tensor stored to `z` ([B, 8, H, W]); fragments as pack_frag_3x3
 bool dc8_tape_applies(int H, int W);
 // Backward-data pass of an 8-channel DoubleConv (cin -> 8 -> 8) on the fp32 matrix core (hn_mfma.hip, k_dc_bwd_mfma_p): g_z = conv2^T(g) * act'(z),
@@ -524,7 +525,7 @@ int launch_dc8_bwd_aux(hn_ctx* ctx, const McBwd& a, const McBwdAux& x, int H, in
 bool dc8_bwd_applies(int H, int W);
 int dc8_bwd_tiles(int H, int W, int batch);   // rows of slope_part a launch adds to
 int launch_dc8_bwd(hn_ctx* ctx, const McBwd& a, int cin, int H, int W, int batch, hipStream_t s);
-int launch_dc8_tape(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const float* frag1, const float* b1, const float* slope, const float* frag2,
+void launch_dc8_tape(DcKind kind, Src a, Src b, Src c, Dst out, const float* frag1, const float* b1, const float* slope, const float* frag2,
                     const float* b2, int act, float* z, int H, int W, int batch, hipStream_t s);
 void launch_down(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s,
                  SyncHook hook = SyncHook{});   // hook: fp32 matrix-core kernels only (k_down_mfma)
@@ -534,18 +535,17 @@ void launch_up(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int
 // ---- vector-pipe DoubleConv of the big levels (hn_dcv.hip) ----
 void pack_valu_q(const float* w_oihw, int cin, float* dst);            // conv1 [8][cin][3][3] -> [cin][2][9][4]
 void pack_outc3x3_valu(const float* w2, const float* wo, float* dst);   // conv2 composed with the out-conv -> [8 cm][3][3][2]
-bool dc_valu_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, int kind, int H, int W);
-void launch_dc_valu(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w, bool final_epi, float* d_out, float* wf, int H,
-                    int W, int batch, hipStream_t s);
+bool dc_valu_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, DcKind kind, int H, int W);
+void launch_dc_valu(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s);
 
 // ---- the same with a hand-scheduled conv1 loop and LDS-direct staging (hn_dca.hip) ----
 void pack_dca(const float* w_oihw, int cin, const float* scale, float* dst);   // conv1 [8][cin][3][3] -> [cin][3 kx][3 ky][8]
-bool dc_asm_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, int kind, int H, int W);
-void launch_dc_asm(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcW& w, bool final_epi, float* d_out, float* wf, int H, int W,
-                   int batch, hipStream_t s);
+bool dc_asm_applies(const hn_ctx* ctx, int act, Src a, Src b, Src c, DcKind kind, int H, int W);
+void launch_dc_asm(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s);
 // ---- hidden-state DoubleConv as a streaming kernel (hn_cs.hip) ----
-bool conv_state_applies(const hn_ctx* ctx, const DcW& w, Src a, Src b, Dst out, int H, int W);
-void launch_conv_state(hn_ctx* ctx, int n, const Src* a, const Src* b, const Dst* out, const DcW* w, const int* H, const int* W, int batch, hipStream_t s);   // n levels, one launch
+struct StateLevel { Src a, b; Dst out; DcW w; int H, W; };   // one level's conv_state: a = out_d (8 channels), b = state_d (2 channels)
+bool conv_state_applies(const hn_ctx* ctx, const StateLevel& v);
+void launch_conv_state(const hn_ctx* ctx, int n, const StateLevel* lv, int batch, hipStream_t s);   // n levels, one launch
 // inc and conv_signal_0 as ONE launch with a flag per tile (k_dc_asm_pair): x0_out / x0 are the same tensor as inc's output and conv_signal's input
 bool dc_asm_pair_applies(const hn_ctx* ctx, Src wf, Src res, Src sig, Src x0, Src st, int H, int W, int batch, int ws_off);
 void launch_dc_asm_pair(hn_ctx* ctx, Src wf, Src res, Src sig, Dst x0_out, Src x0, Src st, Dst out0, int H, int W, int batch, int ws_off, bool capturing, hipStream_t s);
@@ -562,13 +562,20 @@ int deepx_levels(const hn_ctx* ctx, int batch);   // 2 / 1 / 0: levels the kerne
 int launch_deepx(hn_ctx* ctx, int levels, const float* states_in, float* states_out, int ws_off, int batch, hipStream_t s, SyncHook hook = SyncHook{});
 
 // ---- unet (hn_unet.hip) ----
-// One HybridNet forward.  wf/res/sigma sources are generic views; if wf_update != nullptr the
-// wavefield is updated (wf_update = wf_prev + d / 1e3; in place when wf_prev is nullptr) by the last kernel; if d_out != nullptr d is stored.
-int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* states_in, float* states_out,
-                 float* d_out, float* wf_update, int batch, hipStream_t s, int ws_off = 0, hipEvent_t after_down0 = nullptr,
-                 hn_ctx::SideLane* side_lane = nullptr, bool defer_join = false, const float* wf_prev = nullptr);
-// wf_prev (with wf_update): the update reads the old wavefield THERE and writes wf_update (in_wf should view the same tensor); nullptr: in place
-// make stream s wait for the hidden-state kernels of the previous unet_forward(..., defer_join = true) on this lane
+// One HybridNet forward.
+struct UnetCall {
+    Src wf{}, res{}, sig{};               // the input layer's three channel groups, generic views
+    const float* states_in = nullptr; float* states_out = nullptr;
+    float* d_out = nullptr;               // non-null: d is stored
+    float* wf_out = nullptr; const float* wf_in = nullptr;   // wf_out non-null: the last kernel updates the wavefield, wf_out = wf_in + d / 1e3 (wf views the tensor at wf_in; wf_in == wf_out: in place)
+    int batch = 0, ws_off = 0;            // ws_off: first sample slot of the workspace this call may use (sub-batches on parallel streams)
+    hipStream_t stream = nullptr;
+    hipEvent_t after_down0 = nullptr;     // non-null: recorded behind down_0 (hn_step staggers its pipeline lanes on it)
+    hn_ctx::SideLane* side_lane = nullptr;   // non-null: the hidden-state kernels may leave the main chain for this lane's side stream
+    bool defer_join = false;              // leave the side stream unjoined: the next call on this lane (or side_join) waits for it
+};
+int unet_forward(hn_ctx* ctx, const UnetCall& c);
+// make stream s wait for the hidden-state kernels of the previous unet_forward with defer_join on this lane
 int side_join(hn_ctx* ctx, hn_ctx::SideLane* side_lane, hipStream_t s);
 bool side_flags_apply(hn_ctx* ctx, hipStream_t s);
 // flag sync, the side stream's halves (hn_unet.hip): a one-wave kernel that holds stream s until *flag has reached epoch / a one-thread kernel that stores it

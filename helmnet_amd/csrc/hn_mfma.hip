@@ -2572,49 +2572,39 @@ void pack_frag_up(const float* w, float* dst) {
                 }
 }
 
-int launch_dc8(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const DcLayer& l, bool final_epi, float* d_out, float* wf, int H, int W, int batch,
-               hipStream_t s) {
+void launch_dc8(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcLayer& l, const FinalEpi* fin, int H, int W, int batch, hipStream_t s) {
     const DcW& w = l.w;
-    if (dc_asm_applies(ctx, w.act, a, b, c, kind, H, W)) {
-        launch_dc_asm(ctx, kind, a, b, c, out, w, final_epi, d_out, wf, H, W, batch, s);
-        return HN_OK;
-    }
-    if (dc_valu_applies(ctx, w.act, a, b, c, kind, H, W)) {
-        launch_dc_valu(ctx, kind, a, b, c, out, w, final_epi, d_out, wf, H, W, batch, s);
-        return HN_OK;
-    }
+    if (dc_asm_applies(ctx, w.act, a, b, c, kind, H, W)) return launch_dc_asm(ctx, kind, a, b, c, out, w, fin, H, W, batch, s);
+    if (dc_valu_applies(ctx, w.act, a, b, c, kind, H, W)) return launch_dc_valu(ctx, kind, a, b, c, out, w, fin, H, W, batch, s);
     const McW mw{l.f1.f32, w.b1, w.slope, l.f2.f32, w.b2, l.f1.bf16, l.f2.bf16, l.f1.f16, l.f2.f16, w.act};
-    McEpi e{ctx->outc_w, ctx->outc_b, d_out, wf, ctx->f_dec0c, ctx->dec0c_b};
-    e.wf_in = ctx->step_wf_in != nullptr ? ctx->step_wf_in : wf;
+    const FinalEpi f = fin ? *fin : FinalEpi{};
+    McEpi e{ctx->outc_w, ctx->outc_b, f.d_out, f.wf_out, ctx->f_dec0c, ctx->dec0c_b};
+    e.wf_in = f.wf_in;
     const int x16 = (ctx->precision >= HN_PREC_BF16X3 && ctx->precision <= HN_PREC_BF16X2) ? ctx->precision : 0;
     switch (kind) {
-        case 0: launch_dc_mfma<2, 2, 2, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;          // inc
-        case 1: launch_dc_mfma<kFeat, kState, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;  // conv_signal
-        case 2: launch_dc_mfma<kFeat, 0, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;       // bottleneck
-        case 3:
-            if (final_epi) launch_dc_mfma<kFeat, kFeat, 0, 1>(x16, a, b, c, out, mw, e, H, W, batch, s);
+        case DcKind::Inc: launch_dc_mfma<2, 2, 2, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Signal: launch_dc_mfma<kFeat, kState, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Bottleneck: launch_dc_mfma<kFeat, 0, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Decoder:
+            if (fin) launch_dc_mfma<kFeat, kFeat, 0, 1>(x16, a, b, c, out, mw, e, H, W, batch, s);
             else launch_dc_mfma<kFeat, kFeat, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s);
             break;
-        default: return fail(ctx, HN_ERR_ARG, "internal: bad DoubleConv kind %d", kind);
     }
-    return HN_OK;
 }
 
 // Training forward (hn_train.hip): a whole 8-channel DoubleConv on the fp32 matrix core from fragments packed for THIS call's weights,
 // the pre-activation mid tensor stored to the tape by the kernel that computes it.
 bool dc8_tape_applies(int H, int W) { return (W & 1) == 0 && 8.0 * (double)H * (double)W * 4.0 < 4.0e9; }
-int launch_dc8_tape(hn_ctx* ctx, int kind, Src a, Src b, Src c, Dst out, const float* frag1, const float* b1, const float* slope, const float* frag2,
+void launch_dc8_tape(DcKind kind, Src a, Src b, Src c, Dst out, const float* frag1, const float* b1, const float* slope, const float* frag2,
                     const float* b2, int act, float* z, int H, int W, int batch, hipStream_t s) {
     const McW mw{frag1, b1, slope, frag2, b2, nullptr, nullptr, nullptr, nullptr, act};
     const McEpi e{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, z, (long)kFeat * H * W, (long)H * W};
     switch (kind) {
-        case 0: launch_dc_mfma<2, 2, 2, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
-        case 1: launch_dc_mfma<kFeat, kState, 0, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
-        case 2: launch_dc_mfma<kFeat, 0, 0, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
-        case 3: launch_dc_mfma<kFeat, kFeat, 0, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
-        default: return fail(ctx, HN_ERR_ARG, "internal: bad DoubleConv kind %d", kind);
+        case DcKind::Inc: launch_dc_mfma<2, 2, 2, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Signal: launch_dc_mfma<kFeat, kState, 0, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Bottleneck: launch_dc_mfma<kFeat, 0, 0, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Decoder: launch_dc_mfma<kFeat, kFeat, 0, 0>(0, a, b, c, out, mw, e, H, W, batch, s); break;
     }
-    return HN_OK;
 }
 
 bool dc8_bwd_applies(int H, int W) { return (W & 1) == 0 && H > 0; }

@@ -49,9 +49,9 @@ void select_gset(hn_ctx::TrainWs& W, int k);
 // for both: the smooth activations' code (expm1f, tanhf, erff, log1pf inlined at every staged element) made a 3x3 kernel 35 KB of
 // instructions, which every launch of the latency-bound training step fetched cold.
 template <bool GEN>
-__device__ __forceinline__ float act_fwd(float x, int kind, float slope) {
-    if (!GEN || kind <= HN_ACT_LEAKYRELU) return x > 0.f ? x : slope * x;
-    return act_general(x, kind);
+__device__ __forceinline__ float act_fwd(float x, int act, float slope) {
+    if (!GEN || act <= HN_ACT_LEAKYRELU) return x > 0.f ? x : slope * x;
+    return act_general(x, act);
 }
 
 // A channel group of an implicit concatenation: element (b, c, y, x) at p[b*sb + c*sc + y*W + x]
@@ -1250,10 +1250,11 @@ struct Trainer {
         // (one launch instead of two, at 0.4-0.6 of the fp32 peak instead of 0.16; VERDICT r3 #2a)
         if (fused_fwd && f3 != nullptr && dc.cm == kFeat && dc.co == kFeat && dc8_tape_applies(side(d), side(d)) && out.scale == 1.f && !out.accum &&
             in[0].act == 0 && in[1].act == 0 && in[2].act == 0) {
-            const int kind = dc.cin == kInCh ? 0 : dc.cin == kFeat + kState ? 1 : dc.cin == kFeat ? 2 : 3;
+            const DcKind kind = dc.cin == kInCh ? DcKind::Inc : dc.cin == kFeat + kState ? DcKind::Signal : dc.cin == kFeat ? DcKind::Bottleneck : DcKind::Decoder;
             auto ms = [](const TSrc& t) { return Src{t.p, t.sb, t.sc, t.scale}; };
-            return launch_dc8_tape(ctx, kind, ms(in[0]), ms(in[1]), ms(in[2]), Dst{out.p, out.sb, out.sc}, ctx->tr.f3 + (*f3)[0], w + dc.b1, w + dc.slope,
-                                   ctx->tr.f3 + (*f3)[1], w + dc.b2, act, z, side(d), side(d), B, s);
+            launch_dc8_tape(kind, ms(in[0]), ms(in[1]), ms(in[2]), Dst{out.p, out.sb, out.sc}, ctx->tr.f3 + (*f3)[0], w + dc.b1, w + dc.slope,
+                            ctx->tr.f3 + (*f3)[1], w + dc.b2, act, z, side(d), side(d), B, s);
+            return HN_OK;
         }
         if (small_level(d) && dc.cm == kFeat && dc.co == kFeat) {   // both convolutions in one launch (k_dc_small)
             const TSrc mid[3] = {feat(z, d, dc.cm, 1), nosrc(), nosrc()};
@@ -2225,7 +2226,7 @@ int hn_adam_step(hn_ctx* ctx, float* weights, const float* grad, float* exp_avg,
     return HN_OK;
 }
 
-int64_t hn_train_peek(hn_ctx* ctx, int kind, int level, float* out, int64_t max_floats, void* stream) {
+int64_t hn_train_peek(hn_ctx* ctx, int which, int level, float* out, int64_t max_floats, void* stream) {
     if (!ctx || !out) return fail(ctx, HN_ERR_ARG, "hn_train_peek: NULL argument");
     if (ctx->tr.tape == nullptr) return fail(ctx, HN_ERR_STATE, "hn_train_peek: hn_train_grad has not run");
     const int depth = ctx->tr.depth;
@@ -2240,7 +2241,7 @@ int64_t hn_train_peek(hn_ctx* ctx, int kind, int level, float* out, int64_t max_
         if (W.tape == nullptr || W.last_batch == 0) continue;
         const float* p = nullptr;
         size_t ch = kFeat;
-        switch (kind) {
+        switch (which) {
             case 0: p = W.tape + W.o_x[level]; break;
             case 1: if (enc) p = W.tape + W.o_zsig[level]; break;
             case 2: if (enc) p = W.tape + W.o_out[level]; break;
@@ -2255,7 +2256,7 @@ int64_t hn_train_peek(hn_ctx* ctx, int kind, int level, float* out, int64_t max_
             case 22: p = W.g_y[level]; break;
             default: break;
         }
-        if (p == nullptr) return fail(ctx, HN_ERR_ARG, "hn_train_peek: no tensor of kind %d at level %d", kind, level);
+        if (p == nullptr) return fail(ctx, HN_ERR_ARG, "hn_train_peek: no tensor of kind %d at level %d", which, level);
         const int64_t count = (int64_t)((size_t)W.last_batch * ch * plane);
         const int64_t room = max_floats - total;
         const int64_t ncopy = count < room ? count : (room > 0 ? room : 0);

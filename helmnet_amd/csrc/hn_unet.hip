@@ -436,12 +436,10 @@ __global__ void k_sync_gate(const unsigned* flag, unsigned epoch, int* err) {
 
 }  // namespace
 
-int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* states_in, float* states_out,
-                 float* d_out, float* wf_update, int batch, hipStream_t s, int ws_off, hipEvent_t after_down0,
-                 hn_ctx::SideLane* side_lane, bool defer_join, const float* wf_prev) {
-    const int n = ctx->tab.n, depth = ctx->depth;
-    struct WfIn { hn_ctx* c; ~WfIn() { c->step_wf_in = nullptr; } } wf_in_guard{ctx};   // (read by the decode_0 launchers below)
-    ctx->step_wf_in = wf_update != nullptr ? wf_prev : nullptr;
+int unet_forward(hn_ctx* ctx, const UnetCall& c) {
+    const int n = ctx->tab.n, depth = ctx->depth, batch = c.batch, ws_off = c.ws_off;
+    const hipStream_t s = c.stream;
+    hn_ctx::SideLane* const side_lane = c.side_lane;
     const long L = ctx->state_len;
     const Src none{nullptr, 0, 0, 1.f};
     const DcEpi noepi{nullptr, nullptr, nullptr, nullptr};
@@ -451,6 +449,45 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
     // ws_off: first sample slot of the workspace this call may use (sub-batches on parallel streams)
     auto feat = [&](float* p, int d) { return Dst{p + (long)ws_off * kFeat * plane(d), kFeat * plane(d), plane(d)}; };
     auto featsrc = [&](const float* p, int d) { return Src{p + (long)ws_off * kFeat * plane(d), kFeat * plane(d), plane(d), 1.f}; };
+    auto st_old = [&](int d) { return Src{c.states_in + ctx->state_off[d], 2 * L, L, 1.f}; };
+    // state = conv_state(cat[out, state_old]) of level d                  (architectures.py:248)
+    auto state_level = [&](int d) {
+        return StateLevel{featsrc(ctx->buf_o[d], d), st_old(d), Dst{c.states_out + ctx->state_off[d], 2 * L, L}, ctx->st[d].w, n >> d, n >> d};
+    };
+    // One DoubleConv of level d: the matrix-core / vector-pipe launchers (launch_dc8) or, in HN_PREC_FP32_VALU, the direct kernel above.
+    // fin (decode_0 only): + outc 1x1 (architectures.py:463) and wf <- d/1e3 + wf (hybridnet.py:570)
+    auto dc = [&](DcKind kind, int d, Src a, Src b, Src c3, Dst out, const FinalEpi* fin) {
+        const DcLayer& l = kind == DcKind::Inc ? ctx->inc : kind == DcKind::Signal ? ctx->sig[d] : ctx->dec[d];
+        const int m = n >> d;
+        if (mfma) return launch_dc8(ctx, kind, a, b, c3, out, l, fin, m, m, batch, s);
+        switch (kind) {
+            case DcKind::Inc: launch_dc<2, 2, 2, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s); break;
+            case DcKind::Signal: launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s); break;
+            case DcKind::Bottleneck: launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s); break;
+            case DcKind::Decoder:
+                if (fin == nullptr) launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s);
+                else launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(a, b, c3, out, l.w, DcEpi{ctx->outc_w, ctx->outc_b, fin->d_out, fin->wf_out, fin->wf_in}, m, m, batch, s);
+                break;
+        }
+    };
+    // x_{d+1} = down(out_d) / u_d = up[d](y_{d+1}): the matrix-core kernels or the direct ones above
+    auto down = [&](int d) {
+        const int m = n >> d;
+        if (mfma) launch_down(ctx, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].f, m, m, batch, s);
+        else hipLaunchKernelGGL(k_down8x8, dim3(cdiv(m / 2, DownCfg::TW), cdiv(m / 2, DownCfg::TH), batch), dim3(DownCfg::NT), 0, s,
+                                featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].w, m, m);
+    };
+    auto up = [&](int d, const SyncHook& hook) {
+        const int m = n >> d;
+        if (mfma) launch_up(ctx, featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].f, m / 2, m / 2, batch, s, false, hook);
+        else hipLaunchKernelGGL(k_up8x8, dim3(cdiv(m / 2, UpCfg::TW), cdiv(m / 2, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s,
+                                featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].w, m / 2, m / 2);
+    };
+    // one level's conv_state on stream st: the streaming kernel (hn_cs.hip) where it applies, else the general kernel
+    auto conv_state = [&](const StateLevel& v, hipStream_t st) {
+        if (conv_state_applies(ctx, v)) launch_conv_state(ctx, 1, &v, batch, st);
+        else launch_dc<kFeat, kState, 0, kState, kState, 0>(v.a, v.b, none, v.out, v.w, noepi, v.H, v.W, batch, st);
+    };
 
     // inc and conv_signal_0 as ONE launch with a flag per tile (hn_dca.hip, k_dc_asm_pair) where both run on the hand-scheduled kernel -- eagerly, under
     // stream capture (where it derives its epoch on the device) and in every pipeline lane (flags and counters per sample slot)
@@ -458,20 +495,18 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
     const bool not_capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
     (void)hipGetLastError();
     const bool eager = not_capturing && ws_off == 0 && ctx->opt_lanes == 1 && side_lane != nullptr;   // hn_step's single lane, launched kernel by kernel (flag sync below)
-    const bool pair = mfma && dc_asm_pair_applies(ctx, in_wf, in_res, in_sig, featsrc(ctx->buf_a[0], 0), Src{states_in + ctx->state_off[0], 2 * L, L, 1.f}, n, n, batch, ws_off);
+    const bool pair = mfma && dc_asm_pair_applies(ctx, c.wf, c.res, c.sig, featsrc(ctx->buf_a[0], 0), st_old(0), n, n, batch, ws_off);
     if (pair) {
         if (side_lane != nullptr) {   // (deferred join: conv_signal_0 reads the new states)
             int rc = side_join(ctx, side_lane, s);
             if (rc != HN_OK) return rc;
         }
-        const Src st0{states_in + ctx->state_off[0], 2 * L, L, 1.f};
         ProfScope ps(ctx, KID_INC_SIG0, s);
-        HN_REP(KID_INC_SIG0) launch_dc_asm_pair(ctx, in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), featsrc(ctx->buf_a[0], 0), st0, feat(ctx->buf_o[0], 0), n, n, batch, ws_off, !not_capturing, s);
+        HN_REP(KID_INC_SIG0) launch_dc_asm_pair(ctx, c.wf, c.res, c.sig, feat(ctx->buf_a[0], 0), featsrc(ctx->buf_a[0], 0), st_old(0), feat(ctx->buf_o[0], 0), n, n, batch, ws_off, !not_capturing, s);
     } else {
-    // inc: DoubleConv(6 -> 8 -> 8) on [wf, 1e3*res, sigmas]  (architectures.py:442, hybridnet.py:566)
-    ProfScope ps(ctx, KID_INC, s);
-    if (mfma) launch_dc8(ctx, 0, in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), ctx->inc, false, nullptr, nullptr, n, n, batch, s);
-    else launch_dc<2, 2, 2, kFeat, kFeat, 0>(in_wf, in_res, in_sig, feat(ctx->buf_a[0], 0), ctx->inc.w, noepi, n, n, batch, s);
+        // inc: DoubleConv(6 -> 8 -> 8) on [wf, 1e3*res, sigmas]  (architectures.py:442, hybridnet.py:566)
+        ProfScope ps(ctx, KID_INC, s);
+        dc(DcKind::Inc, 0, c.wf, c.res, c.sig, feat(ctx->buf_a[0], 0), nullptr);
     }
     // deferred join (hn_step): the hidden-state kernels of the PREVIOUS iteration are waited for here, behind the input layer (the
     // first reader of the new states is conv_signal_0 below; the side kernels read the skip buffers, which conv_signal_0 is also the
@@ -495,54 +530,50 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
     const int policy = side != nullptr ? ctx->opt_side_stream : 0;
     // flag sync (hn_internal.h: sync_flags): in an iteration whose join may be deferred (all but the last of an hn_step call) the join is one thread of
     // up_0 polling a word, and, where the deep kernel exists to carry the store, the release is a word too: no event packet touches the main stream
-    const bool flags = eager && defer_join && policy == 1 && ctx->opt_side_sync == 1 && ctx->sync_flags != nullptr && mfma && n_enc >= 1;   // (r6: the 16-bit modes too)
+    const bool flags = eager && c.defer_join && policy == 1 && ctx->opt_side_sync == 1 && ctx->sync_flags != nullptr && mfma && n_enc >= 1;   // (r6: the 16-bit modes too)
     const bool rel_flag = flags && (deep || deepx);   // otherwise the release stays an event record (no other kernel sits where the store belongs)
     const unsigned sync_epoch = flags ? ++ctx->sync_epoch : 0u;
-    auto release_states = [&](int d0, int d1, hipEvent_t ev) -> int {
+    // where the hidden-state kernels leave the main chain: never (policy 0: each level in line behind its conv_signal); per level (policy 2); behind the last
+    // layer-by-layer `down` (policy 1 with an event record); in front of the bottleneck / decoder, i.e. behind the deep kernel where there is one (policy 3, and
+    // policy 1 with the deep kernel carrying the release word)
+    enum class Release { Never, PerLevel, LastDown, BehindDeep };
+    const Release release = policy == 0 ? Release::Never : policy == 2 ? Release::PerLevel : policy == 3 || rel_flag ? Release::BehindDeep : Release::LastDown;
+    auto release_states = [&](int d0, int d1) -> int {
         if (rel_flag) {   // (the kernel that stores the release word has been enqueued)
             hipLaunchKernelGGL(k_sync_gate, dim3(1), dim3(64), 0, side, ctx->sync_flags, sync_epoch, ctx->sync_err_dev);
         } else {
-            HN_HIP(ctx, hipEventRecord(ev, s));
-            HN_HIP(ctx, hipStreamWaitEvent(side, ev, 0));
+            HN_HIP(ctx, hipEventRecord(side_lane->ev[d0], s));
+            HN_HIP(ctx, hipStreamWaitEvent(side, side_lane->ev[d0], 0));
         }
         // the levels the streaming kernel takes (hn_cs.hip) share ONE launch, the largest first; the others keep the general kernel, one launch each
-        Src ba[kMaxDepth], bb[kMaxDepth];
-        Dst bo[kMaxDepth];
-        DcW bw[kMaxDepth];
-        int bh[kMaxDepth], nb_levels = 0, first_level = d0;
+        StateLevel merged[kMaxDepth];
+        int n_merged = 0, first_level = d0;
         for (int e = d0; e < d1; ++e) {
 #ifdef HN_EXP_SKIP_STATE   // timing experiment only (tools/r4_skip_state.sh): environment bit e skips conv_state_e -- the results are WRONG
             static const int exp_skip = getenv("HN_EXP_SKIP_STATE") ? std::atoi(getenv("HN_EXP_SKIP_STATE")) : 0;
             if (exp_skip >> e & 1) continue;
 #endif
-            const int me = n >> e;
-            const Src so{states_in + ctx->state_off[e], 2 * L, L, 1.f};
-            const Dst sn{states_out + ctx->state_off[e], 2 * L, L};
+            const StateLevel v = state_level(e);
 #ifndef HN_EXP_REPEAT   // (the per-kernel probes of tools/energy_probe.py / cs_skip_probe.py launch every level on its own)
-            if (conv_state_applies(ctx, ctx->st[e].w, featsrc(ctx->buf_o[e], e), so, sn, me, me)) {
-                if (nb_levels == 0) first_level = e;
-                ba[nb_levels] = featsrc(ctx->buf_o[e], e); bb[nb_levels] = so; bo[nb_levels] = sn; bw[nb_levels] = ctx->st[e].w; bh[nb_levels] = me;
-                ++nb_levels;
+            if (conv_state_applies(ctx, v)) {
+                if (n_merged == 0) first_level = e;
+                merged[n_merged++] = v;
                 continue;
             }
 #endif
             ProfScope ps2(ctx, KID_STATE0 + 3 * e, side);
-            HN_REP(KID_STATE0 + 3 * e) {
-                const Src oe = featsrc(ctx->buf_o[e], e);
-                if (conv_state_applies(ctx, ctx->st[e].w, oe, so, sn, me, me)) launch_conv_state(ctx, 1, &oe, &so, &sn, &ctx->st[e].w, &me, &me, batch, side);
-                else launch_dc<kFeat, kState, 0, kState, kState, 0>(featsrc(ctx->buf_o[e], e), so, none, sn, ctx->st[e].w, noepi, me, me, batch, side);
-            }
+            HN_REP(KID_STATE0 + 3 * e) conv_state(v, side);
         }
-        if (nb_levels > 0) {
+        if (n_merged > 0) {
             ProfScope ps2(ctx, KID_STATE0 + 3 * first_level, side);   // (the merged launch is accounted to its largest level)
-            launch_conv_state(ctx, nb_levels, ba, bb, bo, bw, bh, bh, batch, side);
+            launch_conv_state(ctx, n_merged, merged, batch, side);
         }
         if (flags) hipLaunchKernelGGL(k_sync_signal, dim3(1), dim3(64), 0, side, ctx->sync_flags + 32, sync_epoch);   // (... before up_0, which waits for it)
         return HN_OK;
     };
     SyncHook rel_hook, join_hook;
     if (flags) ++ctx->flag_sync_iterations;
-    ctx->dca_dec_pad = rel_flag ? 7168 : 0;   // (the gate wave is resident while decode_0 runs: hn_dca.hip, launch_dc_asm)
+    const FinalEpi fin{c.d_out, c.wf_out, c.wf_in, rel_flag ? 7168 : 0};   // (the gate wave is resident while decode_0 runs: hn_dca.hip, launch_dc_asm)
     if (rel_flag) { rel_hook.store = ctx->sync_flags; rel_hook.store_epoch = sync_epoch; }
     // (the deep kernel carries the release: its start = everything before it is complete.  [measured, r6: profiles/r6_release_point_ab.txt] the last
     // layer-by-layer `down` carrying it instead -- the hidden-state kernels one kernel earlier -- loses 2 % at 256^2 x 32 and 512^2 x 16; conv_state_0 alone
@@ -551,117 +582,66 @@ int unet_forward(hn_ctx* ctx, Src in_wf, Src in_res, Src in_sig, const float* st
     // 16-wavefront k_deepx that is 9 us faster alone: profiles/r6_release_late_ab.txt)
     if (flags) { join_hook.wait = ctx->sync_flags + 32; join_hook.wait_epoch = sync_epoch; join_hook.err = ctx->sync_err_dev; }
     for (int d = 0; d < n_enc; ++d) {
-        const int m = n >> d;
-        const Src st_old{states_in + ctx->state_off[d], 2 * L, L, 1.f};
-        const Dst st_new{states_out + ctx->state_off[d], 2 * L, L};
         // out = conv_signal(cat[x, state])                               (architectures.py:246-247)
         if (!(pair && d == 0)) {
             ProfScope ps(ctx, KID_SIG0 + 3 * d, s);
-            HN_REP(KID_SIG0 + 3 * d)
-            if (mfma) launch_dc8(ctx, 1, featsrc(ctx->buf_a[d], d), st_old, none, feat(ctx->buf_o[d], d), ctx->sig[d], false, nullptr, nullptr,
-                                 m, m, batch, s);
-            else launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(featsrc(ctx->buf_a[d], d), st_old, none, feat(ctx->buf_o[d], d),
-                                                              ctx->sig[d].w, noepi, m, m, batch, s);
+            HN_REP(KID_SIG0 + 3 * d) dc(DcKind::Signal, d, featsrc(ctx->buf_a[d], d), st_old(d), none, feat(ctx->buf_o[d], d), nullptr);
         }
         // state = conv_state(cat[out, state_old])                        (architectures.py:248)
-        if (policy == 0) {
+        if (release == Release::Never) {
             ProfScope ps(ctx, KID_STATE0 + 3 * d, s);
-            const Src od = featsrc(ctx->buf_o[d], d);
-            if (conv_state_applies(ctx, ctx->st[d].w, od, st_old, st_new, m, m)) launch_conv_state(ctx, 1, &od, &st_old, &st_new, &ctx->st[d].w, &m, &m, batch, s);
-            else launch_dc<kFeat, kState, 0, kState, kState, 0>(featsrc(ctx->buf_o[d], d), st_old, none, st_new, ctx->st[d].w,
-                                                                noepi, m, m, batch, s);
-        } else if (policy == 2) {
-            int rc = release_states(d, d + 1, side_lane->ev[d]);
+            conv_state(state_level(d), s);
+        } else if (release == Release::PerLevel) {
+            int rc = release_states(d, d + 1);
             if (rc != HN_OK) return rc;
         }
         // x = down(out)                                                  (architectures.py:252)
         {
             ProfScope ps(ctx, KID_DOWN0 + 3 * d, s);
-            HN_REP(KID_DOWN0 + 3 * d)
-            if (mfma) launch_down(ctx, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].f, m, m, batch, s);
-            else hipLaunchKernelGGL(k_down8x8, dim3(cdiv(m / 2, DownCfg::TW), cdiv(m / 2, DownCfg::TH), batch),
-                                    dim3(DownCfg::NT), 0, s, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1),
-                                    ctx->down[d].w, m, m);
+            HN_REP(KID_DOWN0 + 3 * d) down(d);
         }
-        if (d == 0 && after_down0 != nullptr) HN_HIP(ctx, hipEventRecord(after_down0, s));
-        if (policy == 1 && d == n_enc - 1 && !rel_flag) {
-            int rc = release_states(0, n_enc, side_lane->ev[0]);
+        if (d == 0 && c.after_down0 != nullptr) HN_HIP(ctx, hipEventRecord(c.after_down0, s));
+        if (release == Release::LastDown && d == n_enc - 1) {
+            int rc = release_states(0, n_enc);
             if (rc != HN_OK) return rc;
         }
     }
-    if (deepx) {
-        {
-            ProfScope ps(ctx, KID_DEEP, s);
-            int rc = HN_OK;
-            HN_REP(KID_DEEP) rc = launch_deepx(ctx, deepx, states_in, states_out, ws_off, batch, s, rel_hook);
-            if (rc != HN_OK) return rc;
-        }
-        if (rel_flag) {
-            int rc = release_states(0, n_enc, nullptr);
-            if (rc != HN_OK) return rc;
-        }
+    if (deep || deepx) {
+        const int d = depth - 1;   // (launch_deep: the one level it takes)
+        ProfScope ps(ctx, KID_DEEP, s);
+        int rc = HN_OK;
+        HN_REP(KID_DEEP)
+        rc = deepx ? launch_deepx(ctx, deepx, c.states_in, c.states_out, ws_off, batch, s, rel_hook)
+                   : launch_deep(ctx, ctx->buf_a[d] + (long)ws_off * kFeat * plane(d), kFeat * plane(d), c.states_in + ctx->state_off[d],
+                                 c.states_out + ctx->state_off[d], 2 * L, L, ctx->buf_y[d] + (long)ws_off * kFeat * plane(d), kFeat * plane(d), batch, s, rel_hook);
+        if (rc != HN_OK) return rc;
     }
-    if (deep) {
-        const int d = depth - 1;
-        {
-            ProfScope ps(ctx, KID_DEEP, s);
-            int rc = HN_OK;
-            HN_REP(KID_DEEP) rc = launch_deep(ctx, ctx->buf_a[d] + (long)ws_off * kFeat * plane(d), kFeat * plane(d), states_in + ctx->state_off[d],
-                                 states_out + ctx->state_off[d], 2 * L, L, ctx->buf_y[d] + (long)ws_off * kFeat * plane(d), kFeat * plane(d), batch, s, rel_hook);
-            if (rc != HN_OK) return rc;
-        }
-        if (rel_flag) {
-            int rc = release_states(0, n_enc, nullptr);
-            if (rc != HN_OK) return rc;
-        }
-    }
-    if (policy == 3) {
-        int rc = release_states(0, n_enc, side_lane->ev[0]);
+    if (release == Release::BehindDeep) {
+        int rc = release_states(0, n_enc);
         if (rc != HN_OK) return rc;
     }
     // bottleneck: decode[depth]                                          (architectures.py:453)
     if (!deep && !deepx) {
         ProfScope ps(ctx, KID_BOTTLENECK, s);
-        if (mfma) launch_dc8(ctx, 2, featsrc(ctx->buf_a[depth], depth), none, none, feat(ctx->buf_y[depth], depth), ctx->dec[depth],
-                             false, nullptr, nullptr, n >> depth, n >> depth, batch, s);
-        else launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(featsrc(ctx->buf_a[depth], depth), none, none, feat(ctx->buf_y[depth], depth),
-                                                     ctx->dec[depth].w, noepi, n >> depth, n >> depth, batch, s);
+        dc(DcKind::Bottleneck, depth, featsrc(ctx->buf_a[depth], depth), none, none, feat(ctx->buf_y[depth], depth), nullptr);
     }
     for (int d = n_enc - 1; d >= 0; --d) {
-        const int m = n >> d;
         // x = up[d](x)                                                   (architectures.py:456)
         {
             ProfScope ps(ctx, KID_UP0 + 2 * d, s);
-            HN_REP(KID_UP0 + 2 * d)
-            if (mfma) launch_up(ctx, featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].f, m / 2, m / 2, batch, s, false,
-                                d == 0 ? join_hook : SyncHook{});
-            else hipLaunchKernelGGL(k_up8x8, dim3(cdiv(m / 2, UpCfg::TW), cdiv(m / 2, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s,
-                                    featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].w, m / 2, m / 2);
+            HN_REP(KID_UP0 + 2 * d) up(d, d == 0 ? join_hook : SyncHook{});
         }
         ProfScope ps(ctx, KID_DEC0 + 2 * d, s);
-        // x = decode[d](cat[x, skip_d])                                  (architectures.py:458-460)
+        // x = decode[d](cat[x, skip_d]); decode_0 + outc + the wavefield update   (architectures.py:458-463, hybridnet.py:570)
         HN_REP(KID_DEC0 + 2 * d)
-        if (mfma) {
-            launch_dc8(ctx, 3, featsrc(ctx->buf_a[d], d), featsrc(ctx->buf_o[d], d), none, d > 0 ? feat(ctx->buf_y[d], d) : Dst{nullptr, 0, 0},
-                       ctx->dec[d], d == 0, d_out, wf_update, m, m, batch, s);
-        } else if (d > 0) {
-            launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(featsrc(ctx->buf_a[d], d), featsrc(ctx->buf_o[d], d), none,
-                                                        feat(ctx->buf_y[d], d), ctx->dec[d].w, noepi, m, m, batch, s);
-        } else {
-            // + outc 1x1 (architectures.py:463) and wf <- d/1e3 + wf (hybridnet.py:570)
-            const DcEpi e{ctx->outc_w, ctx->outc_b, d_out, wf_update, ctx->step_wf_in != nullptr ? ctx->step_wf_in : wf_update};
-            launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(featsrc(ctx->buf_a[0], 0), featsrc(ctx->buf_o[0], 0), none,
-                                                        Dst{nullptr, 0, 0}, ctx->dec[0].w, e, m, m, batch, s);
-        }
+        dc(DcKind::Decoder, d, featsrc(ctx->buf_a[d], d), featsrc(ctx->buf_o[d], d), none, d > 0 ? feat(ctx->buf_y[d], d) : Dst{nullptr, 0, 0}, d == 0 ? &fin : nullptr);
     }
-    if (policy != 0) {  // the next iteration's conv_signal reads the new states
-        if (!flags) {   // (flag sync: up_0 has waited for the join word)
-            HN_HIP(ctx, hipEventRecord(side_lane->done, side));
-            side_lane->pending = true;
-            if (!defer_join) {
-                int rc = side_join(ctx, side_lane, s);
-                if (rc != HN_OK) return rc;
-            }
+    if (release != Release::Never && !flags) {  // the next iteration's conv_signal reads the new states (flag sync: up_0 has waited for the join word)
+        HN_HIP(ctx, hipEventRecord(side_lane->done, side));
+        side_lane->pending = true;
+        if (!c.defer_join) {
+            int rc = side_join(ctx, side_lane, s);
+            if (rc != HN_OK) return rc;
         }
     }
     HN_HIP(ctx, hipGetLastError());
