@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <complex>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -193,7 +194,24 @@ struct SpecTables {
     float2* dense_t = nullptr; // dense_t[m*n + j] = M[j][m]
     float2* dense_adj_t = nullptr; // the same for the adjoint operator M^H (training, hn_train.hip)
     float* sigmas = nullptr;   // [2, n, n]
+    // float64 residual check (hn_f64.hip): what hn_set_domain was called with, and what the first float64 call on this domain builds from it
+    int pml = 0;
+    double sigma_max = 0.0, k = 0.0;
+    double* f64_tab = nullptr;   // [7][n]: Re g1, Im g1, g2 (first columns of the circulant D1, D2), then a and b as (re, im) pairs
+    double* f64_part = nullptr;  // [f64_part_cap] per-block sums of res^2
+    long f64_part_cap = 0;
 };
+// One axis' constants on the host: the fp32 wavenumber grid (Nyquist at -pi) with k2 = -(k1 * k1) squared in fp32, the PML profile, and the fp32-rounded
+// PML coefficients a = -gamma' / gamma^3, b = 1 / gamma^2 -- the values the reference holds in its fp32 buffers (and still holds after .double())
+struct AxisHost {
+    std::vector<float> k1, k2;
+    std::vector<double> sigma;
+    std::vector<float2> fa, fb;
+};
+AxisHost spec_axis_host(int n, int pml, double sigma_max, double k);
+// First columns of the circulant spectral derivative operators in float64: D1[j][m] = g1[(j - m) mod n], D2[j][m] = g2[(j - m) mod n] with
+// g1[d] = (1/n) sum_p i k1_p exp(2 pi i p d / n), g2 likewise from k2.  g2 is real; g1 is real but for the Nyquist term i k1[n/2] (-1)^d / n.
+void spec_circulant_host(const AxisHost& ax, std::vector<std::complex<double>>& g1, std::vector<std::complex<double>>& g2);
 
 }  // namespace hn
 
@@ -469,6 +487,9 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
 // out = L^H(g) + ksq * g [+ add]: the adjoint (conjugate transpose) of the residual operator, i.e. the vector-Jacobian product
 // of hn_residual with respect to the wavefield (training).  `add` may alias `out`.
 int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
+// ---- float64 residual check (hn_f64.hip) ----
+// out = L(wf) [+ ksq * wf - src] in float64 (out nullable) and / or rmse[b] = sqrt(mean over (c, h, w) of out^2) (nullable)
+int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s);
 void train_free(hn_ctx* ctx);   // hn_train.hip
 int stream_table_reserve(hn_ctx* ctx, int slots);   // hn_stream.hip: the verdict table holds at least `slots` records (growing it synchronises the device)
 void stream_table_free(hn_ctx* ctx);

@@ -1333,12 +1333,71 @@ int upload(hn_ctx* ctx, T** dst, const std::vector<T>& h) {
 
 void spec_free(SpecTables& t) {
     for (void* p : {(void*)t.tw, (void*)t.k1, (void*)t.k2, (void*)t.a, (void*)t.b, (void*)t.dense_t, (void*)t.dense_adj_t, (void*)t.sigmas, (void*)t.tw_q,
-                    (void*)t.k1_pfa, (void*)t.k2_pfa}) (void)hipFree(p);
+                    (void*)t.k1_pfa, (void*)t.k2_pfa, (void*)t.f64_tab, (void*)t.f64_part}) (void)hipFree(p);
     t = SpecTables{};
 }
 
 // Host-side construction of every constant, float64 then cast -- the formulas of
 // spectral.py:126-127 (k grid), :298-363 (sigma, gamma, a = -gamma' / gamma^3, b = 1 / gamma^2).
+AxisHost spec_axis_host(int n, int pml, double sigma_max, double k) {
+    AxisHost ax;
+    const double pi = 3.14159265358979323846;
+    // k grid: 2*pi*linspace(-0.5, 0.5, n, endpoint=False) rotated by n//2
+    std::vector<double> kd(n);
+    for (int i = 0; i < n; ++i) {
+        const int s = (i + n / 2) % n;
+        kd[i] = 2.0 * pi * (-0.5 + (double)s / n);
+    }
+    ax.k1.resize(n);
+    ax.k2.resize(n);
+    for (int i = 0; i < n; ++i) {
+        ax.k1[i] = (float)kd[i];
+        ax.k2[i] = -(ax.k1[i] * ax.k1[i]);  // fp32 square of the fp32 grid, as kx.pow(2) in the reference
+    }
+    ax.sigma.assign(n, 0.0);
+    std::vector<double> sigp(n, 0.0);
+    for (int i = 0; i < pml; ++i) {
+        const double q = std::fabs(1.0 - (double)i / pml);
+        const double so = sigma_max * (q * q);
+        const double sp = -2.0 * sigma_max * (1.0 - (double)i / pml) / pml;
+        ax.sigma[i] = so;
+        ax.sigma[n - 1 - i] = so;
+        sigp[i] = sp;
+        sigp[n - 1 - i] = -sp;
+    }
+    ax.fa.resize(n);
+    ax.fb.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const std::complex<double> inv_gamma = 1.0 / (std::complex<double>(1.0, 0.0) + std::complex<double>(0.0, 1.0 / k) * ax.sigma[i]);
+        const std::complex<double> gamma_prime = std::complex<double>(0.0, 1.0 / k) * sigp[i];
+        const std::complex<double> ca = (-gamma_prime) * (inv_gamma * (inv_gamma * inv_gamma));
+        const std::complex<double> cb = inv_gamma * inv_gamma;
+        ax.fa[i] = make_float2((float)ca.real(), (float)ca.imag());
+        ax.fb[i] = make_float2((float)cb.real(), (float)cb.imag());
+    }
+    return ax;
+}
+
+void spec_circulant_host(const AxisHost& ax, std::vector<std::complex<double>>& g1, std::vector<std::complex<double>>& g2) {
+    const int n = (int)ax.k1.size();
+    const double pi = 3.14159265358979323846;
+    std::vector<std::complex<double>> e(n);
+    for (int q = 0; q < n; ++q) e[q] = std::polar(1.0, 2.0 * pi * q / n);
+    // g1[d] = (1/n) sum_p i*k_p e[(p*d) mod n];  g2[d] = (1/n) sum_p k2_p e[(p*d) mod n], d = (j-m) mod n
+    g1.resize(n);
+    g2.resize(n);
+    for (int d = 0; d < n; ++d) {
+        std::complex<double> s1 = 0, s2 = 0;
+        for (int p = 0; p < n; ++p) {
+            const std::complex<double> w = e[(int)(((long)p * d) % n)];
+            s1 += std::complex<double>(0.0, (double)ax.k1[p]) * w;
+            s2 += (double)ax.k2[p] * w;
+        }
+        g1[d] = s1 / (double)n;
+        g2[d] = s2 / (double)n;
+    }
+}
+
 int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
     if (n < 16 || n > 2048) return fail(ctx, HN_ERR_ARG, "domain size %d outside [16, 2048]", n);
     if (pml < 1 || 2 * pml > n) return fail(ctx, HN_ERR_ARG, "PML size %d does not fit domain %d", pml, n);
@@ -1347,38 +1406,16 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
     SpecTables& t = ctx->tab;
     t.n = n;
     t.pow2 = (n & (n - 1)) == 0;
+    t.pml = pml;
+    t.sigma_max = sigma_max;
+    t.k = k;
     const double pi = 3.14159265358979323846;
-    // k grid: 2*pi*linspace(-0.5, 0.5, n, endpoint=False) rotated by n//2
-    std::vector<double> kd(n);
-    for (int i = 0; i < n; ++i) {
-        const int s = (i + n / 2) % n;
-        kd[i] = 2.0 * pi * (-0.5 + (double)s / n);
-    }
-    std::vector<float> k1(n), k2(n);
-    for (int i = 0; i < n; ++i) {
-        k1[i] = (float)kd[i];
-        k2[i] = -(k1[i] * k1[i]);  // fp32 square of the fp32 grid, as kx.pow(2) in the reference
-    }
-    std::vector<double> sigma(n, 0.0), sigp(n, 0.0);
-    for (int i = 0; i < pml; ++i) {
-        const double q = std::fabs(1.0 - (double)i / pml);
-        const double so = sigma_max * (q * q);
-        const double sp = -2.0 * sigma_max * (1.0 - (double)i / pml) / pml;
-        sigma[i] = so;
-        sigma[n - 1 - i] = so;
-        sigp[i] = sp;
-        sigp[n - 1 - i] = -sp;
-    }
-    std::vector<std::complex<double>> ca(n), cb(n);
-    std::vector<float2> fa(n), fb(n);
-    for (int i = 0; i < n; ++i) {
-        const std::complex<double> inv_gamma = 1.0 / (std::complex<double>(1.0, 0.0) + std::complex<double>(0.0, 1.0 / k) * sigma[i]);
-        const std::complex<double> gamma_prime = std::complex<double>(0.0, 1.0 / k) * sigp[i];
-        ca[i] = (-gamma_prime) * (inv_gamma * (inv_gamma * inv_gamma));
-        cb[i] = inv_gamma * inv_gamma;
-        fa[i] = make_float2((float)ca[i].real(), (float)ca[i].imag());
-        fb[i] = make_float2((float)cb[i].real(), (float)cb[i].imag());
-    }
+    const AxisHost ax = spec_axis_host(n, pml, sigma_max, k);
+    const std::vector<float>& k1 = ax.k1;
+    const std::vector<float>& k2 = ax.k2;
+    const std::vector<double>& sigma = ax.sigma;
+    const std::vector<float2>& fa = ax.fa;
+    const std::vector<float2>& fb = ax.fb;
     std::vector<float> sig((size_t)2 * n * n);
     for (int y = 0; y < n; ++y)
         for (int x = 0; x < n; ++x) {
@@ -1418,20 +1455,8 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
         if ((rc = upload(ctx, &t.b, fb)) != HN_OK) return rc;
     } else {
         // M[j][m] = (1/n) sum_p (a_j * i*k_p + b_j * k2_p) exp(2 pi i p (j - m) / n), k2_p = -(k_p^2)
-        std::vector<std::complex<double>> e(n);
-        for (int q = 0; q < n; ++q) e[q] = std::polar(1.0, 2.0 * pi * q / n);
-        // g1[d] = (1/n) sum_p i*k_p e[(p*d) mod n];  g2[d] = (1/n) sum_p k2_p e[(p*d) mod n], d = (j-m) mod n
-        std::vector<std::complex<double>> g1(n), g2(n);
-        for (int d = 0; d < n; ++d) {
-            std::complex<double> s1 = 0, s2 = 0;
-            for (int p = 0; p < n; ++p) {
-                const std::complex<double> w = e[(int)(((long)p * d) % n)];
-                s1 += std::complex<double>(0.0, (double)k1[p]) * w;
-                s2 += (double)k2[p] * w;
-            }
-            g1[d] = s1 / (double)n;
-            g2[d] = s2 / (double)n;
-        }
+        std::vector<std::complex<double>> g1, g2;
+        spec_circulant_host(ax, g1, g2);
         std::vector<float2> mt((size_t)n * n);
         for (int j = 0; j < n; ++j)
             for (int m = 0; m < n; ++m) {

@@ -218,13 +218,13 @@ class Engine:
         _lib.check(self.lib.hn_reserve(self.ctx, int(batch)), self.ctx, "hn_reserve")
 
     # ---- helpers -----------------------------------------------------------------------
-    def _chk(self, t: torch.Tensor, shape: Sequence[int], name: str) -> torch.Tensor:
+    def _chk(self, t: torch.Tensor, shape: Sequence[int], name: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a tensor")
         if t.device != self.device:
             raise ValueError(f"{name} is on {t.device}, engine is on {self.device}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dtype != dtype:
+            raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
         if tuple(t.shape) != tuple(shape):
             raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
         if not t.is_contiguous():
@@ -272,6 +272,26 @@ class Engine:
         out = torch.empty(b, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.hn_rmse(self.ctx, _ptr(res), _ptr(out), b, self._stream()), self.ctx, "hn_rmse")
         return out
+
+    # ---- the same operators in float64: the check the fp32 residual is measured against (hn_f64.hip) ----
+    def laplacian64(self, wf: torch.Tensor) -> torch.Tensor:
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, self.n, self.n), "wavefield", torch.float64)
+        out = torch.empty_like(wf)
+        _lib.check(self.lib.hn_laplacian_f64(self.ctx, _ptr(wf), _ptr(out), b, self._stream()), self.ctx, "hn_laplacian_f64")
+        return out
+
+    def residual64(self, wf: torch.Tensor, k_sq: torch.Tensor, src: torch.Tensor, want_res: bool = True, want_rmse: bool = True):
+        """(res [B,2,n,n] or None, rmse [B] or None), both float64; the RMSE is summed in a fixed order (bit-reproducible)."""
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, self.n, self.n), "wavefield", torch.float64)
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq", torch.float64)
+        self._chk(src, (src.shape[0], 2, self.n, self.n), "source", torch.float64)
+        res = torch.empty_like(wf) if want_res else None
+        rmse = torch.empty(b, device=self.device, dtype=torch.float64) if want_rmse else None
+        rc = self.lib.hn_residual_f64(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), src.shape[0], _ptr(res), _ptr(rmse), b, self._stream())
+        _lib.check(rc, self.ctx, "hn_residual_f64")
+        return res, rmse
 
     def unet(self, in6: torch.Tensor, states_in: torch.Tensor):
         b = in6.shape[0]

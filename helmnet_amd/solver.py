@@ -347,6 +347,36 @@ class IterativeSolver(nn.Module):
             return Residual.apply(self.engine(), x.float(), k_sq.float(), self._src_graph())
         return self.engine().residual(x.float().contiguous(), k_sq.float().contiguous(), self._src())
 
+    def get_residual64(self, wavefield: torch.Tensor, k_sq: torch.Tensor) -> torch.Tensor:
+        """The residual of ``get_residual`` evaluated in float64 on the GPU (the reference's ``solver.double().get_residual``), [B,2,n,n] float64.
+        fp32 inputs are up-cast exactly: the problem checked is the one with the fp32 ``k_sq`` and source the solver ran.  No gradients."""
+        return self._residual64(wavefield, k_sq, True, False)[0]
+
+    def _residual64(self, wavefield, k_sq, want_res: bool, want_rmse: bool):
+        for t in (wavefield, k_sq):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError("the float64 residual check runs without gradients: pass detached tensors")
+        return self.engine().residual64(wavefield.double().contiguous(), k_sq.double().contiguous(), self.source.detach().double().contiguous(),
+                                        want_res, want_rmse)
+
+    def verify(self, wavefield: torch.Tensor, sos_maps: Optional[torch.Tensor] = None, k_sq: Optional[torch.Tensor] = None) -> dict:
+        """How far the fp32 residual norm of ``wavefield`` can be trusted.  Pass exactly one of ``sos_maps`` / ``k_sq`` (the fp32 problem the solver ran).
+        Returns per sample: ``residual_norm64`` (float64 RMSE of the float64 residual), ``residual_norm32`` (what hn_residual + hn_rmse give) and
+        ``evaluator_error`` = RMSE of (fp32 residual - float64 residual), the floor below which an fp32 residual norm carries no information."""
+        if (sos_maps is None) == (k_sq is None):
+            raise ValueError("pass exactly one of sos_maps and k_sq")
+        for t in (wavefield, sos_maps, k_sq):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError("verify runs without gradients: pass detached tensors")
+        if k_sq is None:
+            k_sq = self.get_initials(sos_maps.float().contiguous())[0]
+        eng = self.engine()
+        wf32, k32 = wavefield.float().contiguous(), k_sq.float().contiguous()
+        res32 = eng.residual(wf32, k32, self._src())
+        res64, norm64 = self._residual64(wavefield, k32, True, True)
+        diff = res32.double() - res64
+        return {"residual_norm64": norm64, "residual_norm32": eng.rmse(res32), "evaluator_error": diff.pow(2).mean((1, 2, 3)).sqrt()}
+
     def single_step(self, wavefield, k_sq, residual, get_residual: bool = True):
         """One iteration on caller-held tensors (hybridnet.py:558-584); network states live in
         ``self.f`` as in the reference.  Inputs are not modified.  With an input (or a state held in f, or the source) requiring
@@ -443,12 +473,13 @@ class IterativeSolver(nn.Module):
         return self._run(wf, res, st, k_sq.float().contiguous(), num_iterations, return_wavefields, return_states, residuals)
 
     def solve_to_tolerance(self, sos_maps, tol: float, max_iterations: int = None, check_every: int = 50,
-                           norm_reduce=None) -> dict:
+                           norm_reduce=None, verify: bool = False) -> dict:
         """Extension (BASELINE.json configs[4], "convergence-to-tolerance"): iterate in chunks of
         ``check_every`` until the WORST per-sample residual RMSE (hybridnet.py:295-297) is below ``tol`` or
         ``max_iterations`` is reached.  One device-to-host read of a single float per chunk; with
         ``norm_reduce`` (e.g. helmnet_amd.distributed.allreduce_residual_norms) the test is global over ranks.
-        Returns wavefield, last residual, per-iteration RMSE trace [K, B], iterations run and whether it converged."""
+        Returns wavefield, last residual, per-iteration RMSE trace [K, B], iterations run and whether it converged.  ``verify=True`` adds the keys of
+        ``verify()`` for the final wavefield and ``converged64``: the worst float64 residual norm is below ``tol``."""
         if max_iterations is None:
             max_iterations = self.hparams.max_iterations
         sos_maps = sos_maps.float().contiguous()
@@ -467,7 +498,12 @@ class IterativeSolver(nn.Module):
             if float(worst) < tol:
                 converged = True
                 break
-        return {"wavefield": wf, "residual": res, "residual_norms": torch.cat(traces, 0), "iterations": done, "converged": converged}
+        out = {"wavefield": wf, "residual": res, "residual_norms": torch.cat(traces, 0), "iterations": done, "converged": converged}
+        if verify:
+            out.update(self.verify(wf, k_sq=k_sq))
+            worst64 = out["residual_norm64"].max() if norm_reduce is None else norm_reduce(out["residual_norm64"], "max")
+            out["converged64"] = bool(float(worst64) < tol)
+        return out
 
     def solve_many(self, sos_maps, tol: float, max_iterations: int = None, slots: int = 32, check_every: int = 25,
                    source_maps=None, diverge_rmse: float = None, keep_residuals: bool = False, norm_reduce=None) -> dict:

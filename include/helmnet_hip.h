@@ -228,6 +228,18 @@ int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, 
 /* rmse[B] = sqrt(mean_{c,h,w} res^2).  Replaces test_loss_function (hybridnet.py:295-297). */
 int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream);
 
+/* The same operator in float64, as an independent check of the fp32 residual: what the reference computes after solver.double()
+ * (apply_laplacian / get_residual, hybridnet.py:540-556, on fast_laplacian_with_pml, spectral.py:31-79 run under .double(): the fp32 tables'
+ * values, float64 arithmetic).  One code path for every legal domain size: dense circulant derivative operators on the f64 matrix instruction.
+ * Shapes and layout as for hn_laplacian / hn_residual, all tensors doubles.  wf must not overlap out / res (HN_ERR_ARG).
+ * hn_residual_f64: res[B,2,n,n] (may be NULL) and / or rmse[B] = sqrt(mean_{c,h,w} res^2) (may be NULL; not both, HN_ERR_ARG), the RMSE summed in a
+ * fixed order (bit-reproducible).  The first call on a domain builds and uploads the float64 tables (freed by the next hn_set_domain / hn_destroy), and
+ * an rmse call with a larger batch than any before grows a table of partial sums: such a call under stream capture returns HN_ERR_STATE before
+ * enqueuing anything; once they exist the calls are capturable.  Plain launches on the caller's stream.  HN_ERR_STATE before hn_set_domain. */
+int hn_laplacian_f64(hn_ctx* ctx, const double* wf, double* out, int batch, void* stream);
+int hn_residual_f64(hn_ctx* ctx, const double* wf, const double* k_sq, const double* src, int src_batch,
+                    double* res, double* rmse, int batch, void* stream);
+
 /* d[B,2,n,n] = HybridNet(in6[B,6,n,n]); the hidden states are read from `states_in` and the new
  * ones written to `states_out`, both in the reference's flat layout [B, 2, hn_state_len()]
  * (architectures.py:419-437).  states_in must not alias states_out.
