@@ -51,6 +51,9 @@ SYMBOLS = {
     "hn_laplacian_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_residual_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_unet": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "hn_unet_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "hn_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hn_double_conv": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_float), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hn_conv8x8": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hn_out_conv": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_void_p, c_int, c_int, c_int, c_void_p]),

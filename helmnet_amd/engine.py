@@ -293,6 +293,38 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_residual_f64")
         return res, rmse
 
+    # ---- the UNet and the solver loop in float64: the trajectory the fp32 / fp16 / bf16 modes are measured against (hn_unet_f64.hip) ----
+    def unet64(self, in6: torch.Tensor, states_in: torch.Tensor):
+        """(d [B,2,n,n], states_out [B,2,L]) = HybridNet(in6, states_in) in float64, the weights of the last load_weights up-cast."""
+        b = in6.shape[0]
+        self._chk(in6, (b, 6, self.n, self.n), "network input", torch.float64)
+        self._chk(states_in, (b, 2, self.state_len), "hidden state", torch.float64)
+        d = torch.empty(b, 2, self.n, self.n, device=self.device, dtype=torch.float64)
+        states_out = torch.empty_like(states_in)
+        rc = self.lib.hn_unet_f64(self.ctx, _ptr(in6), _ptr(states_in), _ptr(states_out), _ptr(d), b, self._stream())
+        _lib.check(rc, self.ctx, "hn_unet_f64")
+        return d, states_out
+
+    def step64(self, wf, res, states, k_sq, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
+        """n_iter solver iterations in float64; wf, res, states updated in place (``step`` with every tensor float64)."""
+        b, f64 = wf.shape[0], torch.float64
+        self._chk(wf, (b, 2, self.n, self.n), "wavefield", f64)
+        self._chk(res, (b, 2, self.n, self.n), "residual", f64)
+        self._chk(states, (b, 2, self.state_len), "hidden state", f64)
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq", f64)
+        self._chk(src, (src.shape[0], 2, self.n, self.n), "source", f64)
+        if res_hist is not None:
+            self._chk(res_hist, (n_iter, b, 2, self.n, self.n), "res_hist", f64)
+        if wf_hist is not None:
+            self._chk(wf_hist, (n_iter, b, 2, self.n, self.n), "wf_hist", f64)
+        if st_hist is not None:
+            self._chk(st_hist, (n_iter, b, 2, self.state_len), "st_hist", f64)
+        if rmse_hist is not None:
+            self._chk(rmse_hist, (n_iter, b), "rmse_hist", f64)
+        rc = self.lib.hn_step_f64(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), src.shape[0], b,
+                                  int(n_iter), _ptr(res_hist), _ptr(wf_hist), _ptr(st_hist), _ptr(rmse_hist), self._stream())
+        _lib.check(rc, self.ctx, "hn_step_f64")
+
     def unet(self, in6: torch.Tensor, states_in: torch.Tensor):
         b = in6.shape[0]
         self._chk(in6, (b, 6, self.n, self.n), "network input")

@@ -12,6 +12,8 @@ set_source_maps / set_multiple_sources / reset_source`` (:133-170), ``get_initia
 
 All per-iteration arithmetic runs in libhelmnet_hip.so: ``forward`` / ``n_steps`` hand the whole
 loop to ``hn_step`` (fused HIP kernels), ``get_residual`` to ``hn_residual``, ``f`` to ``hn_unet``.
+``forward64`` / ``n_steps64`` / ``deviation_from_float64`` (extension) run the same loop in float64 on ``hn_step_f64``: the reference's
+``solver.double()`` trajectory, to measure the other precision modes against.
 There is no CPU path: a solver left on the CPU raises as soon as it is asked to compute.
 """
 from __future__ import annotations
@@ -471,6 +473,104 @@ class IterativeSolver(nn.Module):
         res = residual.detach().float().clone().contiguous()
         st = self.f.get_states(flatten=True).float().contiguous().clone()
         return self._run(wf, res, st, k_sq.float().contiguous(), num_iterations, return_wavefields, return_states, residuals)
+
+    # ------------------------------------------------------------------ the loop in float64 ----
+    def _source64(self, source, batch: int) -> torch.Tensor:
+        n = int(self.hparams.domain_size)
+        if source is None:
+            return self.source.detach().double().contiguous()
+        if source.dtype != torch.float64 or source.dim() != 4 or tuple(source.shape[1:]) != (2, n, n) or source.shape[0] not in (1, batch):
+            raise ValueError(f"source must be a float64 [1 or {batch}, 2, {n}, {n}] tensor, got {source.dtype} {tuple(source.shape)}")
+        return source.detach().to(self.device).contiguous()
+
+    @staticmethod
+    def _no_grad64(what: str, *tensors):
+        for t in tensors:
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError(f"{what} runs without gradients: pass detached tensors (the differentiable path is forward())")
+
+    def _run64(self, wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals: str):
+        """``_run`` on hn_step_f64: wf / res / st (float64, owned by the caller of this helper) are updated in place; nothing held in f is touched."""
+        if residuals not in ("all", "norms", "last"):
+            raise ValueError("residuals must be 'all', 'norms' or 'last'")
+        eng = self.engine()
+        b, n, K = wf.shape[0], wf.shape[-1], int(num_iterations)
+        new = lambda *shape: torch.empty(shape, device=wf.device, dtype=torch.float64)  # noqa: E731
+        res_hist = new(K, b, 2, n, n) if residuals == "all" and K > 0 else None
+        wf_hist = new(K, b, 2, n, n) if return_wavefields and K > 0 else None
+        st_hist = new(K, b, 2, eng.state_len) if return_states and K > 0 else None
+        rmse = new(K, b) if K > 0 else None
+        if K > 0:
+            keep = self.f.to_engine_states(st)      # levels without state: zeros in, the caller's values back out (as _run does for the fp32 states)
+            eng.step64(wf, res, st, k_sq, src, K, res_hist, wf_hist, st_hist, rmse)
+            self.f.from_engine_states(keep, st, st_hist)
+        out = {
+            "wavefields": list(wf_hist.unbind(0)) if wf_hist is not None else [wf],
+            "residuals": list(res_hist.unbind(0)) if res_hist is not None else ([res] if residuals == "last" else []),
+            "states": list(st_hist.unbind(0)) if st_hist is not None else [],
+            "last_iteration": K - 1,
+            "residual_norms": rmse,
+        }
+        if residuals == "norms":
+            out["last_residual"] = res
+        return out
+
+    def _initials64(self, sos_maps, source):
+        """(wf = 0, residual, zero flat states, k_sq, source), all float64: get_initials on a float64 input (hybridnet.py:522-538) and cleared states."""
+        eng = self.engine()
+        sos = sos_maps.detach().to(self.device).double().contiguous()
+        src = self._source64(source, sos.shape[0])
+        k_sq = ((self.hparams.omega / sos) ** 2).contiguous()
+        wf = torch.zeros(sos.shape[0], 2, sos.shape[2], sos.shape[3], device=sos.device, dtype=torch.float64)
+        st = torch.zeros(sos.shape[0], 2, eng.state_len, device=sos.device, dtype=torch.float64)
+        return wf, eng.residual64(wf, k_sq, src, True, False)[0], st, k_sq, src
+
+    def forward64(self, sos_maps, num_iterations=None, return_wavefields=False, return_states=False, residuals: str = "all", source=None):
+        """``forward`` with the whole iteration in float64 on the GPU (hn_step_f64): the reference's ``solver.double()`` run, the trajectory the fp32 /
+        fp16 / bf16 modes are measured against.  Same keys as ``forward``, float64 tensors.  The weights are the solver's fp32 parameters up-cast;
+        ``source`` None uses ``self.source.double()``, a float64 [1 or B,2,n,n] map overrides it (a source map BUILT in float64 differs from the
+        up-cast fp32 one by ~1e-6).  No gradients; the (fp32) hidden states held in ``f`` are neither read nor written.  A reference, not a fast path."""
+        self._no_grad64("forward64", sos_maps, source)
+        if num_iterations is None:
+            num_iterations = self.hparams.max_iterations
+        wf, res, st, k_sq, src = self._initials64(sos_maps, source)
+        return self._run64(wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals)
+
+    def n_steps64(self, wavefield, k_sq, residual, states, num_iterations, return_wavefields=False, return_states=False,
+                  residuals: str = "all", source=None):
+        """``n_steps`` in float64, continuing from given tensors; the hidden states are passed in (flat [B,2,L]) instead of living in ``f`` and come back
+        as ``out["final_states"]``.  Inputs are up-cast if need be and not modified."""
+        self._no_grad64("n_steps64", wavefield, k_sq, residual, states, source)
+        self.engine()
+        wf, res, st, kq = (t.detach().to(self.device).double().clone().contiguous() for t in (wavefield, residual, states, k_sq))
+        out = self._run64(wf, res, st, kq, self._source64(source, wf.shape[0]), num_iterations, return_wavefields, return_states, residuals)
+        out["final_states"] = st
+        return out
+
+    def deviation_from_float64(self, sos_maps, num_iterations: int, checkpoints) -> dict:
+        """How far this solver's current precision mode is from the float64 trajectory on the caller's own maps: ``forward`` and ``forward64`` side by
+        side, compared at every iteration count in ``checkpoints``.  Returns ``iterations`` (the sorted checkpoints), ``linf`` [len(checkpoints), B]
+        (per-sample max |wavefield - float64 wavefield|), and the residual-norm traces ``rmse32`` / ``rmse64`` [num_iterations, B]."""
+        self._no_grad64("deviation_from_float64", sos_maps)
+        cps = sorted({int(c) for c in checkpoints} | {int(num_iterations)})
+        if cps[0] < 1 or cps[-1] > int(num_iterations):
+            raise ValueError(f"checkpoints must lie in [1, {int(num_iterations)}]")
+        with torch.no_grad():
+            wf64, res64, st64, k64, _ = self._initials64(sos_maps, None)
+            rows, r32, r64, done = {}, [], [], 0
+            for cp in cps:
+                if done == 0:
+                    o32 = self.forward(sos_maps, num_iterations=cp, residuals="norms")
+                    k32 = self.get_initials(sos_maps.float().contiguous())[0].contiguous()
+                else:
+                    o32 = self.n_steps(o32["wavefields"][0], k32, o32["last_residual"], cp - done, residuals="norms")
+                o64 = self.n_steps64(wf64, k64, res64, st64, cp - done, residuals="norms")
+                wf64, res64, st64, done = o64["wavefields"][0], o64["last_residual"], o64["final_states"], cp
+                r32.append(o32["residual_norms"])
+                r64.append(o64["residual_norms"])
+                rows[cp] = (o32["wavefields"][0].double() - wf64).abs().amax((1, 2, 3))
+        want = sorted({int(c) for c in checkpoints})
+        return {"iterations": torch.tensor(want), "linf": torch.stack([rows[c] for c in want]), "rmse32": torch.cat(r32), "rmse64": torch.cat(r64)}
 
     def solve_to_tolerance(self, sos_maps, tol: float, max_iterations: int = None, check_every: int = 50,
                            norm_reduce=None, verify: bool = False) -> dict:

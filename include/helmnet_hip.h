@@ -247,6 +247,23 @@ int hn_residual_f64(hn_ctx* ctx, const double* wf, const double* k_sq, const dou
 int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states_out, float* d_out,
             int batch, void* stream);
 
+/* ---- the solver loop in float64 (added within ABI v7: new entry points, nothing existing changes) ----
+ * hn_unet_f64: d[B,2,n,n] = HybridNet(in6[B,6,n,n]) in float64: the reference after solver.double() (architectures.py:439-465, 240-252).  Layout of
+ * hn_unet, every tensor double; no two tensors may overlap unless both are only read (HN_ERR_ARG).  Weights: the fp32 values of the last
+ * hn_load_weights up-cast exactly (what .double() does to the parameters); every activation kind is evaluated in double (erf gelu, softplus with
+ * threshold 20, celu with alpha 1, leakyrelu with the double 0.01).  The reference's layers one by one, fixed summation order: bit-reproducible.
+ * hn_step_f64: n_iter iterations of single_step (hybridnet.py:558-584) in float64,
+ *   d = HybridNet(cat[wf, 1e3*res, sigmas]);  wf = d/1e3 + wf;  res = L(wf) + k_sq*wf - src   (the residual of hn_residual_f64),
+ * arguments as hn_step, every tensor double, the sigma channels the fp32 table values up-cast; histories optional (NULL), rmse_hist[n_iter,B] from
+ * hn_residual_f64's fixed-order sums.  wf, res, states are updated in place; no tensor may overlap another unless both are only read (HN_ERR_ARG).
+ * Both: the up-cast weights, a float64 workspace (320 n^2 bytes per sample) and a second state buffer are built by the first call and grown by a
+ * larger batch, and freed by the next hn_load_weights / hn_set_domain / hn_destroy; such a first or growing call under stream capture returns
+ * HN_ERR_STATE before enqueuing anything (hn_step_f64 also where hn_residual_f64 would), later calls are plain launches on the caller's stream and
+ * capturable.  HN_ERR_STATE before hn_load_weights / hn_set_domain.  A reference to measure the fp32 / fp16 / bf16 modes against, not a fast path. */
+int hn_unet_f64(hn_ctx* ctx, const double* in6, const double* states_in, double* states_out, double* d_out, int batch, void* stream);
+int hn_step_f64(hn_ctx* ctx, double* wf, double* res, double* states, const double* k_sq, const double* src, int src_batch,
+                int batch, int n_iter, double* res_hist, double* wf_hist, double* st_hist, double* rmse_hist, void* stream);
+
 /* The UNet's sub-modules on their own -- what DoubleConv.forward (architectures.py:83-84), the 8x8 stride-2 convolution /
  * transposed convolution of an EncoderBlock / the decoder (:209-211, :375-382, as called in EncoderBlock.forward :252 and
  * HybridNet.forward :456) and OutConv.forward (:57-60) compute, for the channel shapes the UNet is made of.  Utility
