@@ -50,6 +50,7 @@ SYMBOLS = {
     "hn_rmse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_laplacian_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_residual_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "hn_gmres_cycle": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hn_unet": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_unet_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_step_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

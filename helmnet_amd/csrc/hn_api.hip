@@ -411,6 +411,7 @@ void hn_destroy(hn_ctx* ctx) {
     free_workspace(ctx);
     train_free(ctx);
     unet_f64_free(ctx);
+    krylov_free(ctx);
     spec_free(ctx->tab);
     (void)hipFree(ctx->wdev);
     (void)hipFree(ctx->fragdev);
@@ -536,6 +537,7 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     HN_HIP(ctx, hipDeviceSynchronize());
     clear_step_graphs(ctx);
     unet_f64_free(ctx);
+    krylov_free(ctx);
     if (n % 16 != 0) return fail(ctx, HN_ERR_ARG, "domain size %d must be divisible by 16", n);
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
     if (n != ctx->tab.n) free_workspace(ctx);

@@ -273,6 +273,31 @@ class Engine:
         _lib.check(self.lib.hn_rmse(self.ctx, _ptr(res), _ptr(out), b, self._stream()), self.ctx, "hn_rmse")
         return out
 
+    def gmres_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
+                    basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
+        """One restart cycle of GMRES(restart) on A u = L(u) + k_sq * u (hn_gmres_cycle), ``x`` updated in place, nothing synchronised.  Returns
+        (rmse [restart + 1, B], k_used [B] int32): row 0 the true residual RMSE of ``x`` at the start, row j the Givens estimate after j inner
+        iterations, ``k_used`` the inner iterations that entered each sample's update.  ``basis`` [B, restart + 1, 2 n^2] and ``hess``
+        [B, restart + 1, restart, 2] receive the Arnoldi vectors and the Hessenberg matrix; they are allocated when not given."""
+        b, restart = x.shape[0], int(restart)
+        for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError(f"gmres_cycle: {name} requires grad; the GMRES cycle is not differentiable")
+        self._chk(x, (b, 2, self.n, self.n), "x")
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
+        self._chk(rhs, (rhs.shape[0], 2, self.n, self.n), "rhs")
+        new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
+        basis = new(b, restart + 1, 2 * self.n * self.n) if basis is None else basis
+        hess = new(b, restart + 1, restart, 2) if hess is None else hess
+        self._chk(basis, (b, restart + 1, 2 * self.n * self.n), "basis")
+        self._chk(hess, (b, restart + 1, restart, 2), "hess")
+        rmse = new(restart + 1, b)
+        k_used = torch.empty(b, device=self.device, dtype=torch.int32)
+        rc = self.lib.hn_gmres_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), _ptr(basis), _ptr(hess),
+                                     _ptr(rmse), _ptr(k_used), self._stream())
+        _lib.check(rc, self.ctx, "hn_gmres_cycle")
+        return rmse, k_used
+
     # ---- the same operators in float64: the check the fp32 residual is measured against (hn_f64.hip) ----
     def laplacian64(self, wf: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]

@@ -50,8 +50,73 @@ def _back_substitute(R: np.ndarray, g: np.ndarray, k: int) -> np.ndarray:
     return y
 
 
+def drive_cycles(cycle, true_rmse, max_cycles: int, tol: float) -> dict:
+    """The host loop of ``gmres(backend="hip")``, free of torch and of the library so that it is tested on the CPU with a scripted cycle.
+
+    ``cycle()`` runs one restart cycle on the current iterate and returns ``(rmse [m + 1, B], k_used [B])`` as host arrays (the tables of
+    ``hn_gmres_cycle``: row 0 the true RMSE at the start, row j the estimate after j inner iterations); ``true_rmse()`` returns the true
+    residual RMSE [B] of the current iterate.  Per cycle the history gains rows 0 .. max(k_used), a sample's rows past its own ``k_used``
+    repeating the value it stopped at.  Once every sample's estimate at its ``k_used`` is below ``tol`` the true residual is evaluated
+    (the estimate comes from an fp32 Hessenberg matrix); it replaces the last history row, and the loop ends if it is below ``tol`` for
+    every sample -- else the next cycle starts from it.  Returns history (list of [B] float32 arrays), tables (the per-cycle tables as they
+    came), iterations (lock-step inner iterations: sum of max(k_used)), iterations_per_sample (int64 [B]: sum of k_used), cycles,
+    true_checks and converged."""
+    history, tables, its, per, converged, checks, cycles = [], [], 0, None, False, 0, 0
+    for _ in range(int(max_cycles)):
+        rm, ku = cycle()
+        rm, ku = np.asarray(rm, dtype=np.float32), np.asarray(ku, dtype=np.int64)
+        cycles += 1
+        tables.append(rm)
+        per = ku.copy() if per is None else per + ku
+        kmax = int(ku.max())
+        its += kmax
+        cols = np.arange(rm.shape[1])
+        for j in range(kmax + 1):
+            history.append(rm[np.minimum(j, ku), cols].copy())
+        if bool((rm[ku, cols] < tol).all()):
+            t = np.asarray(true_rmse(), dtype=np.float32)
+            checks += 1
+            history[-1] = t
+            if bool((t < tol).all()):
+                converged = True
+                break
+    return {"history": history, "tables": tables, "iterations": its, "iterations_per_sample": per if per is not None else np.zeros(0, np.int64),
+            "cycles": cycles, "true_checks": checks, "converged": converged}
+
+
+def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0):
+    """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own."""
+    for t in (sos_maps, x0):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError("gmres(backend='hip') runs without gradients: pass detached tensors")
+    eng = solver.engine()
+    sos_maps = sos_maps.float().contiguous()
+    k_sq, wf0 = solver.get_initials(sos_maps)
+    k_sq = k_sq.contiguous()
+    rhs = solver.source.detach().float().contiguous()
+    bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
+    dev = rhs.device
+    x = (wf0 if x0 is None else x0.detach().float()).contiguous().clone()
+    basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=dev)
+    hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
+
+    def cycle():
+        rmse, k_used = eng.gmres_cycle(x, k_sq, rhs, restart, tol, basis, hess)
+        both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
+        eng.check_async_errors()
+        return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
+
+    def true_rmse():
+        return eng.rmse(eng.residual(x, k_sq, rhs)).cpu().numpy()
+
+    out = drive_cycles(cycle, true_rmse, max_outer, tol)
+    return {"wavefield": x, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
+            "operator_applications": out["cycles"] * (restart + 1) + out["true_checks"], "converged": out["converged"],
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"]}
+
+
 def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
-          x0: Optional[torch.Tensor] = None):
+          x0: Optional[torch.Tensor] = None, backend: str = "torch"):
     """Solve (L + k_sq) u = source for every map of ``sos_maps`` [B, 1, N, N] (the reference's classical baseline:
     matlab/spectral_gmres_solver.m:86-115, MATLAB's ``gmres`` with restarts).
 
@@ -64,7 +129,15 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
     many basis vectors: the GMRES iterate of that step).
 
     Returns dict(wavefield [B,2,N,N], residual_norms: list of [B] RMSE (hybridnet.py:295-297 definition) at the start of every
-    cycle and after every inner iteration, iterations: inner iterations up to convergence, operator_applications: all of them)."""
+    cycle and after every inner iteration, iterations: inner iterations up to convergence, operator_applications: all of them).
+
+    ``backend="hip"``: the same method with a restart cycle as a handful of fused HIP launches per inner step (hn_gmres_cycle), the
+    Givens least-squares solve on the device and every sample stopping on its own; it adds ``iterations_per_sample`` (int64 [B]) and
+    ``cycle_tables`` (the per-cycle rmse tables)."""
+    if backend == "hip":
+        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0)
+    if backend != "torch":
+        raise ValueError(f"unknown GMRES backend {backend!r} (choose 'torch' or 'hip')")
     eng = solver.engine()
     sos_maps = sos_maps.float().contiguous()
     k_sq, wf0 = solver.get_initials(sos_maps)

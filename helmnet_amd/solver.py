@@ -605,6 +605,13 @@ class IterativeSolver(nn.Module):
             out["converged64"] = bool(float(worst64) < tol)
         return out
 
+    def gmres(self, sos_maps, restart: int = 20, max_cycles: int = 50, tol: float = 1e-4, x0=None) -> dict:
+        """The reference's classical baseline (matlab/spectral_gmres_solver.m:86-115) on this solver's operator and source: restarted GMRES with the
+        restart cycle fused on the device (``helmnet_amd.gmres.gmres(backend="hip")``), every map stopping on its own.  ``x0`` [B,2,n,n]: the
+        starting iterate, e.g. a learned solve's wavefield to be continued by Krylov iterations (default: zeros).  No gradients."""
+        from .gmres import gmres
+        return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip")
+
     def solve_many(self, sos_maps, tol: float, max_iterations: int = None, slots: int = 32, check_every: int = 25,
                    source_maps=None, diverge_rmse: float = None, keep_residuals: bool = False, norm_reduce=None) -> dict:
         """Extension: solve a stream of N maps to a tolerance, every map stopping on its own (continuous batching; the workload of the

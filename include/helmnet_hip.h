@@ -240,6 +240,30 @@ int hn_laplacian_f64(hn_ctx* ctx, const double* wf, double* out, int batch, void
 int hn_residual_f64(hn_ctx* ctx, const double* wf, const double* k_sq, const double* src, int src_batch,
                     double* res, double* rmse, int batch, void* stream);
 
+/* ---- restarted GMRES on the same operator (added within ABI v7: a new entry point, nothing existing changes) ----
+ * The reference's classical baseline is MATLAB's restarted gmres on the spectral PML operator (matlab/spectral_gmres_solver.m:86-115).
+ * hn_gmres_cycle: ONE restart cycle of GMRES(restart) on A u = L(u) + k_sq * u (hn_residual with a zero source), for `batch` independent samples in
+ * lock step: r = rhs - A x, v_0 = r / |r|; per inner step w = A v_k, two passes of classical Gram-Schmidt (H[:k+1, k] = h + h2), H[k+1, k] = |w|,
+ * v_{k+1} = w / |w|; progressive Givens rotations per sample (double precision on the fp32 H column) with the residual estimate |g[j+1]| / sqrt(2 n^2).
+ *   x        [B,2,n,n]  in: the iterate at the start of the cycle, out: the iterate after it (bit-for-bit untouched for a sample that starts below tol)
+ *   k_sq     [B,1,n,n]; rhs [rhs_batch,2,n,n], rhs_batch in {1, batch}
+ *   basis    [B, restart+1, 2*n*n]      caller-owned scratch; on return the orthonormal Arnoldi vectors of this cycle
+ *   hess     [B, restart+1, restart, 2] caller-owned; on return the (re, im) Hessenberg matrix BEFORE the rotations
+ *   rmse     [restart+1, B]             row 0: the TRUE residual RMSE of x at the start of the cycle (hybridnet.py:295-297 definition),
+ *                                       row j: the Givens estimate after j inner iterations (repeated after the sample has stopped)
+ *   k_used   [B] int32                  inner iterations whose basis vectors entered this sample's update (0 .. restart)
+ * Per-sample stop: a sample whose row 0 is below tol gets k_used = 0 and its x is not written; otherwise k_used is the first j whose estimate is below
+ * tol (restart if none is) and x += sum_{j < k_used} y_j v_j with the back-substituted y of exactly that truncation; the other samples' work goes on.
+ * A breakdown (|w| = 0) divides by a clamp (1e-30), not by zero.  All sums have a fixed order (per-block partial sums in a library workspace, summed
+ * in block order by their consumer; no float atomics): two calls on the same inputs give the same bits in every output, and a sample's results do
+ * not depend on what shares the batch with it.  Everything is enqueued on `stream` with no host synchronisation; besides the operator an inner step
+ * is five launches.  The workspace (partial sums, g, rotations, y, two dense fields) is sized from (batch, restart, n): a call that must create or
+ * grow it under stream capture returns HN_ERR_STATE with nothing enqueued; later calls are plain launches and capturable.  hn_set_domain and
+ * hn_destroy free it.  HN_ERR_ARG: restart outside [1, 64], batch < 1, rhs_batch not in {1, batch}, a NULL pointer, a field that is not 16-byte
+ * aligned, any two arguments overlapping, no domain set. */
+int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                   float* basis, float* hess, float* rmse, int32_t* k_used, void* stream);
+
 /* d[B,2,n,n] = HybridNet(in6[B,6,n,n]); the hidden states are read from `states_in` and the new
  * ones written to `states_out`, both in the reference's flat layout [B, 2, hn_state_len()]
  * (architectures.py:419-437).  states_in must not alias states_out.

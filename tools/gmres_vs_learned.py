@@ -28,9 +28,13 @@ def main():
     ap.add_argument("--restart", type=int, default=20)
     ap.add_argument("--budget", type=float, default=60.0, help="wall-clock seconds GMRES may spend")
     ap.add_argument("--floor", type=float, default=1e-3, help="GMRES stops early below this residual RMSE")
+    ap.add_argument("--backend", choices=("torch", "hip"), default="torch", help="GMRES backend (torch: the one the committed profiles were made with)")
     a = ap.parse_args()
+    from functools import partial
+
     from helmnet_amd import IterativeSolver
-    from helmnet_amd.gmres import gmres
+    from helmnet_amd.gmres import gmres as gmres_any
+    gmres = partial(gmres_any, backend=a.backend)
     from helmnet_amd.metrics import as_complex, difference_to_reference
     from helmnet_amd.phantoms import ring_sos_batch
     dev = "cuda:0"
@@ -39,7 +43,7 @@ def main():
     loc = [a.n - 62, a.n // 2]
     s.set_domain_size(a.n, source_location=loc)
     sos = torch.from_numpy(ring_sos_batch(a.n, a.batch, seed=11)).to(dev)
-    out = {"workload": f"{a.n}x{a.n} ring phantoms, batch {a.batch}, point source at {loc}", "restart": a.restart, "tolerances": []}   # "tolerances": the learned solver
+    out = {"workload": f"{a.n}x{a.n} ring phantoms, batch {a.batch}, point source at {loc}", "restart": a.restart, "gmres_backend": a.backend, "tolerances": []}   # "tolerances": the learned solver
     # warm both paths
     s.forward(sos, num_iterations=10)
     gmres(s, sos, restart=a.restart, max_outer=1, tol=1e-9)
