@@ -210,6 +210,12 @@ bool overlap(const double* a, const double* b, long count) { return a < b + coun
 
 }  // namespace
 
+int f64_reserve(hn_ctx* ctx, int batch, hipStream_t s) {
+    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    const int tiles_1d = (ctx->tab.n + kTile - 1) / kTile;
+    return f64_prepare(ctx, (long)batch * tiles_1d * tiles_1d, s);
+}
+
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s) {
     SpecTables& t = ctx->tab;
     if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");

@@ -210,6 +210,7 @@ struct AxisHost {
 };
 AxisHost spec_axis_host(int n, int pml, double sigma_max, double k);
 struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-squares problem, two dense fields for the operator
+struct RefineWs;  // GMRES refinement step (hn_krylov.hip): float64 copies of k_sq and rhs, the float64 residual, the fp32 scaled right-hand side and correction
 struct F64Unet;   // float64 solver loop (hn_unet_f64.hip): the up-cast weights, the activation workspace and the second flat-state buffer
 // First columns of the circulant spectral derivative operators in float64: D1[j][m] = g1[(j - m) mod n], D2[j][m] = g2[(j - m) mod n] with
 // g1[d] = (1/n) sum_p i k1_p exp(2 pi i p d / n), g2 likewise from k2.  g2 is real; g1 is real but for the Nyquist term i k1[n/2] (-1)^d / n.
@@ -228,6 +229,7 @@ struct hn_ctx {
     std::vector<float> raw_blob;   // the blob of the last hn_load_weights as it came (PyTorch layout): the float64 path up-casts it at its first call
     hn::F64Unet* f64 = nullptr;    // built / grown by the first hn_unet_f64 / hn_step_f64 that needs it; freed by hn_load_weights, hn_set_domain, hn_destroy
     hn::KrylovWs* kry = nullptr;   // built / grown by the first hn_gmres_cycle that needs it; freed by hn_set_domain, hn_destroy
+    hn::RefineWs* rfn = nullptr;   // built / grown by the first hn_gmres_refine_cycle that needs it; freed with kry (krylov_free)
     hn::DcLayer inc{}, sig[hn::kMaxDepth]{}, st[hn::kMaxDepth]{}, dec[hn::kMaxDepth + 1]{};   // (their pointers lead into wdev and fragdev)
     hn::K8Layer down[hn::kMaxDepth]{}, up[hn::kMaxDepth]{};
     float* fragdev = nullptr;   // every re-packing of the weights beyond wdev: the layers' fragments and what follows here
@@ -495,8 +497,10 @@ int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, cons
 // ---- float64 residual check (hn_f64.hip) ----
 // out = L(wf) [+ ksq * wf - src] in float64 (out nullable) and / or rmse[b] = sqrt(mean over (c, h, w) of out^2) (nullable)
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s);
+// the tables and the partial sums an rmse call of f64_apply with this batch needs, so that it has nothing left to build (HN_ERR_STATE under stream capture)
+int f64_reserve(hn_ctx* ctx, int batch, hipStream_t s);
 void unet_f64_free(hn_ctx* ctx);   // hn_unet_f64.hip (the caller has synchronised the device)
-void krylov_free(hn_ctx* ctx);     // hn_krylov.hip (the caller has synchronised the device)
+void krylov_free(hn_ctx* ctx);     // hn_krylov.hip: the cycle's and the refinement's workspaces (the caller has synchronised the device)
 void train_free(hn_ctx* ctx);   // hn_train.hip
 int stream_table_reserve(hn_ctx* ctx, int slots);   // hn_stream.hip: the verdict table holds at least `slots` records (growing it synchronises the device)
 void stream_table_free(hn_ctx* ctx);

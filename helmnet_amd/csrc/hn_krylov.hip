@@ -13,6 +13,9 @@
 // registers (one float4 per plane and thread) and streams the k + 1 basis pieces past it; the multiplication by i is the choice of plane.
 // Every sum has a fixed order: per-thread, a wavefront shuffle tree, the four wavefronts, then the blocks' partial sums in chunk order (in double) by
 // whoever consumes them -- no float atomics, nothing depends on the batch a sample shares (grid.y is the sample), two calls give the same bits.
+//
+// hn_gmres_refine_cycle (at the end of this file) wraps the same launches into one step of iterative refinement: the true residual (hn_f64.hip) and the
+// update in float64, the cycle in fp32 on the scaled correction equation A d = r / s.
 #include "hn_internal.h"
 
 namespace hn {
@@ -34,6 +37,19 @@ struct KrylovWs {
     double* R = nullptr;      // [B][restart][restart + 1][2]  column k of the triangular factor in rows 0 .. k
     float* y = nullptr;       // [B][restart][2]      the back-substituted coefficients of the truncation the sample stopped at
     int* stopped = nullptr;   // [B]
+};
+
+// what hn_gmres_refine_cycle needs beyond the cycle's workspace and the float64 operator's tables
+struct RefineWs {
+    int batch = 0, n = 0;
+    void* block = nullptr;    // one allocation; the pointers below lead into it
+    double* ksq64 = nullptr;  // [B][n^2]    k_sq up-cast
+    double* rhs64 = nullptr;  // [B][2 n^2]  rhs up-cast (the first rhs_batch samples)
+    double* res64 = nullptr;  // [B][2 n^2]  A x - b
+    float* rhs32 = nullptr;   // [B][2 n^2]  -res / s: the cycle's right-hand side
+    float* d32 = nullptr;     // [B][2 n^2]  the cycle's iterate: the correction
+    double* tol = nullptr;    // [B]  max(tol / s, inner_floor)
+    int* stop = nullptr;      // [B]  rmse64 < tol (or a residual of exactly zero)
 };
 
 namespace {
@@ -161,7 +177,11 @@ struct SmallArgs {
     float* hess; float* rmse; int32_t* k_used;
     int batch, restart, nchunk;
     double tol, inv_sqrt_npix;
+    // hn_gmres_refine_cycle only (both nullptr for hn_gmres_cycle): a tolerance per sample, written by k_refine_rhs, in place of `tol`; samples the float64
+    // residual test has stopped already, whatever their own row 0 says
+    const double* tol_dev; const int* pre_stopped;
 };
+__device__ __forceinline__ double sample_tol(const SmallArgs& a, int b) { return a.tol_dev != nullptr ? a.tol_dev[b] : a.tol; }
 
 // start of the cycle: beta, g = beta e_1, rmse row 0, the samples that start below the tolerance
 __global__ __launch_bounds__(64) void k_small_init(SmallArgs a) {
@@ -176,7 +196,7 @@ __global__ __launch_bounds__(64) void k_small_init(SmallArgs a) {
     g[1] = 0.0;
     const double est = (double)beta * a.inv_sqrt_npix;
     a.rmse[b] = (float)est;
-    a.stopped[b] = est < a.tol ? 1 : 0;
+    a.stopped[b] = (est < sample_tol(a, b) || (a.pre_stopped != nullptr && a.pre_stopped[b] != 0)) ? 1 : 0;
     a.k_used[b] = 0;
 }
 
@@ -247,7 +267,7 @@ __global__ __launch_bounds__(64) void k_small(SmallArgs a, int k) {
             row[b] = row[b - a.batch];   // the value the sample stopped at
         } else {
             row[b] = (float)est;
-            if (est < a.tol) back = k + 1;
+            if (est < sample_tol(a, b)) back = k + 1;
             else if (k == R - 1) back = R;
         }
     }
@@ -307,6 +327,14 @@ __global__ __launch_bounds__(256) void k_update(float* __restrict__ x, const flo
     *reinterpret_cast<float4*>(px + P) = xi;
 }
 
+void cycle_ws_free(hn_ctx* ctx) {
+    KrylovWs* ws = ctx->kry;
+    if (ws == nullptr) return;
+    (void)hipFree(ws->block);
+    delete ws;
+    ctx->kry = nullptr;
+}
+
 bool capturing(hipStream_t s) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
@@ -323,7 +351,7 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
         return fail(ctx, HN_ERR_STATE, "hn_gmres_cycle: the workspace (or a larger batch's / restart's) is built by the first call, which must not be under stream capture");
     const int cb = ws != nullptr && ws->n == n && ws->batch > batch ? ws->batch : batch;
     const int cr = ws != nullptr && ws->n == n && ws->restart > restart ? ws->restart : restart;
-    krylov_free(ctx);   // (hipFree waits for the launches that still use the old one)
+    cycle_ws_free(ctx);   // (hipFree waits for the launches that still use the old one)
     ws = new (std::nothrow) KrylovWs();
     if (!ws) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
     ctx->kry = ws;
@@ -337,7 +365,7 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
     if (e == hipSuccess) e = hipMemset(ws->block, 0, total);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        krylov_free(ctx);
+        cycle_ws_free(ctx);
         return fail(ctx, e == hipErrorOutOfMemory ? HN_ERR_NOMEM : HN_ERR_HIP, "hn_gmres_cycle: workspace of %zu bytes: %s", total, hipGetErrorString(e));
     }
     char* p = static_cast<char*>(ws->block);
@@ -352,14 +380,159 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
 
 struct Range { const void* p; size_t bytes; const char* name; };
 
-}  // namespace
+// first pair of overlapping ranges, or false
+bool overlapping(const Range* r, int count, const char** a_name, const char** b_name) {
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j) {
+            const char *a = static_cast<const char*>(r[i].p), *b = static_cast<const char*>(r[j].p);
+            if (a < b + r[j].bytes && b < a + r[i].bytes) { *a_name = r[i].name; *b_name = r[j].name; return true; }
+        }
+    return false;
+}
 
-void krylov_free(hn_ctx* ctx) {
-    KrylovWs* ws = ctx->kry;
+// The restart cycle's launches, the workspace prepared.  tol_dev / pre_stopped: see SmallArgs (nullptr: hn_gmres_cycle, whose bits they leave alone --
+// the comparison est < tol is the same one on the same doubles); x, rhs and the outputs may lie in a workspace of the library's.
+int launch_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol, const double* tol_dev,
+                 const int* pre_stopped, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
+    const KrylovWs& ws = *ctx->kry;
+    const long P = (long)ws.n * ws.n;
+    int rc;
+    // the partial-sum table is indexed with the CALL's restart and batch: a workspace sized for more holds it
+    const int nchunk = ws.nchunk;
+    const dim3 grid(nchunk, batch), blk(256);
+    SmallArgs a{ws.part, ws.npart, ws.scale, ws.g, ws.cs, ws.R, ws.y, ws.stopped, hess, rmse, k_used, batch, restart, nchunk,
+                tol, 1.0 / sqrt(2.0 * (double)P), tol_dev, pre_stopped};
+    // w = A x - rhs = -r
+    if ((rc = spec_apply(ctx, x, ws.w, k_sq, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
+    hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
+    hipLaunchKernelGGL(k_small_init, dim3(batch), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, -1.f, ws.vin, basis, P, 0, restart);
+    for (int k = 0; k < restart; ++k) {
+        if ((rc = spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s)) != HN_OK) return rc;
+        hipLaunchKernelGGL(k_dots, grid, blk, 0, s, ws.w, basis, ws.part, P, k, restart, nchunk);
+        hipLaunchKernelGGL(k_sub<0>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
+        hipLaunchKernelGGL(k_sub<1>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
+        hipLaunchKernelGGL(k_small, dim3(batch), dim3(64), 0, s, a, k);
+        hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, 1.f, ws.vin, basis, P, k + 1, restart);
+    }
+    hipLaunchKernelGGL(k_update, grid, blk, 0, s, x, basis, ws.y, k_used, P, restart);
+    HN_HIP(ctx, hipGetLastError());
+    return HN_OK;
+}
+
+// ---- iterative refinement around the cycle (hn_gmres_refine_cycle): r = b - A x and x += s d in float64, A d = r / s by the fp32 cycle above ----
+// The three kernels below stream: a thread owns four consecutive pixels of a plane, a block 1024 pixels of a sample, as the cycle's kernels do.  A float4
+// of fp32 stands against TWO double2 of float64, so that every access is 16 bytes on both sides (one double2 per float2 would halve the fp32 access).
+// None of them sums anything: the one sum of a refinement step, rmse64, is hn_residual_f64's own (k_helm_f64's per-tile sums, k_rmse_f64's fixed tree), launched
+// as hn_residual_f64 launches it, because the caller compares it bit for bit with that entry point's -- a block-order sum of the tile table by every
+// consumer block would be a second order of summation (and up to 4096 table reads per block).  s travels as rmse64[b], a device word.
+
+// float -> double, exactly: quad i of k_sq for i < nk4, then quad i - nk4 of rhs
+__global__ __launch_bounds__(256) void k_refine_upcast(const float* __restrict__ ksq, double* __restrict__ ksq64, long nk4, const float* __restrict__ rhs,
+                                                       double* __restrict__ rhs64, long nr4) {
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const float* src = ksq;
+    double* dst = ksq64;
+    if (i >= nk4) {
+        i -= nk4;
+        if (i >= nr4) return;
+        src = rhs;
+        dst = rhs64;
+    }
+    const float4 v = reinterpret_cast<const float4*>(src)[i];
+    reinterpret_cast<double2*>(dst)[2 * i] = make_double2((double)v.x, (double)v.y);
+    reinterpret_cast<double2*>(dst)[2 * i + 1] = make_double2((double)v.z, (double)v.w);
+}
+
+__device__ __forceinline__ float4 scaled_down(const double* p, double s) {   // fp32(-p / s): a true division, the value the caller can form itself
+    const double2 a = reinterpret_cast<const double2*>(p)[0], b = reinterpret_cast<const double2*>(p)[1];
+    return make_float4((float)(-a.x / s), (float)(-a.y / s), (float)(-b.x / s), (float)(-b.y / s));
+}
+
+// rhs32 = fp32(-res / s), d32 = 0, and per sample the inner tolerance and the float64 stop; s = max(rmse64, 1e-300)
+__global__ __launch_bounds__(256) void k_refine_rhs(const double* __restrict__ res, const double* __restrict__ rmse64, double tol, double inner_floor,
+                                                    float* __restrict__ rhs32, float* __restrict__ d32, double* __restrict__ tol_dev,
+                                                    int* __restrict__ stop, long P) {
+    const int b = blockIdx.y;
+    const double r = rmse64[b];
+    const double s = fmax(r, 1e-300);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        tol_dev[b] = fmax(tol / s, inner_floor);
+        stop[b] = (r < tol || r == 0.0) ? 1 : 0;   // a residual of exactly zero: nothing to correct, whatever the tolerance
+    }
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)b * 2 * P + off;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(rhs32 + at) = scaled_down(res + at, s);
+    *reinterpret_cast<float4*>(rhs32 + at + P) = scaled_down(res + at + P, s);
+    *reinterpret_cast<float4*>(d32 + at) = z;
+    *reinterpret_cast<float4*>(d32 + at + P) = z;
+}
+
+__device__ __forceinline__ void add_scaled(double* p, float4 d, double s) {
+    double2 a = reinterpret_cast<double2*>(p)[0], b = reinterpret_cast<double2*>(p)[1];
+    a.x += s * (double)d.x; a.y += s * (double)d.y; b.x += s * (double)d.z; b.y += s * (double)d.w;
+    reinterpret_cast<double2*>(p)[0] = a;
+    reinterpret_cast<double2*>(p)[1] = b;
+}
+
+// x += s * d in float64; a sample with k_used == 0 is not written
+__global__ __launch_bounds__(256) void k_refine_update(double* __restrict__ x, const float* __restrict__ d32, const double* __restrict__ rmse64,
+                                                       const int32_t* __restrict__ k_used, long P) {
+    const int b = blockIdx.y;
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (k_used[b] <= 0 || off >= P) return;
+    const double s = fmax(rmse64[b], 1e-300);
+    const long at = (long)b * 2 * P + off;
+    add_scaled(x + at, *reinterpret_cast<const float4*>(d32 + at), s);
+    add_scaled(x + at + P, *reinterpret_cast<const float4*>(d32 + at + P), s);
+}
+
+void refine_ws_free(hn_ctx* ctx) {
+    RefineWs* ws = ctx->rfn;
     if (ws == nullptr) return;
     (void)hipFree(ws->block);
     delete ws;
-    ctx->kry = nullptr;
+    ctx->rfn = nullptr;
+}
+
+// the refinement's own fields for `batch` samples on the current domain -- never built or grown under stream capture
+int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s) {
+    const int n = ctx->tab.n;
+    RefineWs* ws = ctx->rfn;
+    if (ws != nullptr && ws->n == n && batch <= ws->batch) return HN_OK;
+    if (capturing(s))
+        return fail(ctx, HN_ERR_STATE, "hn_gmres_refine_cycle: the workspace (or a larger batch's) is built by the first call, which must not be under stream capture");
+    refine_ws_free(ctx);   // (hipFree waits for the launches that still use the old one)
+    ws = new (std::nothrow) RefineWs();
+    if (!ws) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
+    ctx->rfn = ws;
+    const size_t P = (size_t)n * n, B = (size_t)batch;
+    const size_t sizes[] = {B * P * 8, B * 2 * P * 8, B * 2 * P * 8, B * 2 * P * 4, B * 2 * P * 4, B * 8, B * 4};
+    size_t total = 0;
+    for (size_t v : sizes) total += up256(v);
+    hipError_t e = hipMalloc(&ws->block, total);
+    if (e == hipSuccess) e = hipMemset(ws->block, 0, total);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        refine_ws_free(ctx);
+        return fail(ctx, e == hipErrorOutOfMemory ? HN_ERR_NOMEM : HN_ERR_HIP, "hn_gmres_refine_cycle: workspace of %zu bytes: %s", total, hipGetErrorString(e));
+    }
+    char* p = static_cast<char*>(ws->block);
+    int i = 0;
+    auto take = [&]() { char* q = p; p += up256(sizes[i++]); return q; };
+    ws->ksq64 = (double*)take(); ws->rhs64 = (double*)take(); ws->res64 = (double*)take(); ws->rhs32 = (float*)take(); ws->d32 = (float*)take();
+    ws->tol = (double*)take(); ws->stop = (int*)take();
+    ws->batch = batch; ws->n = n;
+    return HN_OK;
+}
+
+}  // namespace
+
+void krylov_free(hn_ctx* ctx) {
+    cycle_ws_free(ctx);
+    refine_ws_free(ctx);
 }
 
 }  // namespace hn
@@ -380,35 +553,50 @@ extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const fl
                        {hess, B * (R + 1) * R * 2 * 4, "hess"}, {rmse, (R + 1) * B * 4, "rmse"}, {k_used, B * 4, "k_used"}};
     for (int i = 0; i < 4; ++i)   // the fields are read and written as float4
         if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: %s is not 16-byte aligned", r[i].name);
-    for (int i = 0; i < 7; ++i)
-        for (int j = i + 1; j < 7; ++j) {
-            const char *a = static_cast<const char*>(r[i].p), *b = static_cast<const char*>(r[j].p);
-            if (a < b + r[j].bytes && b < a + r[i].bytes) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: %s overlaps %s", r[i].name, r[j].name);
-        }
+    const char *na, *nb;
+    if (overlapping(r, 7, &na, &nb)) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: %s overlaps %s", na, nb);
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
-    int rc = prepare(ctx, batch, restart, s);
+    const int rc = prepare(ctx, batch, restart, s);
     if (rc != HN_OK) return rc;
-    const KrylovWs& ws = *ctx->kry;
-    // the partial-sum table is indexed with the CALL's restart and batch: a workspace sized for more holds it
-    const int nchunk = ws.nchunk;
-    const dim3 grid(nchunk, batch), blk(256);
-    SmallArgs a{ws.part, ws.npart, ws.scale, ws.g, ws.cs, ws.R, ws.y, ws.stopped, hess, rmse, k_used, batch, restart, nchunk,
-                (double)tol, 1.0 / sqrt(2.0 * (double)P)};
-    // w = A x - rhs = -r
-    if ((rc = spec_apply(ctx, x, ws.w, k_sq, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
-    hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
-    hipLaunchKernelGGL(k_small_init, dim3(batch), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, -1.f, ws.vin, basis, P, 0, restart);
-    for (int k = 0; k < restart; ++k) {
-        if ((rc = spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s)) != HN_OK) return rc;
-        hipLaunchKernelGGL(k_dots, grid, blk, 0, s, ws.w, basis, ws.part, P, k, restart, nchunk);
-        hipLaunchKernelGGL(k_sub<0>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
-        hipLaunchKernelGGL(k_sub<1>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
-        hipLaunchKernelGGL(k_small, dim3(batch), dim3(64), 0, s, a, k);
-        hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, 1.f, ws.vin, basis, P, k + 1, restart);
-    }
-    hipLaunchKernelGGL(k_update, grid, blk, 0, s, x, basis, ws.y, k_used, P, restart);
+    return launch_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, basis, hess, rmse, k_used, s);
+}
+
+extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+                                     float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
+    const char* who = "hn_gmres_refine_cycle";
+    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || !rmse64) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain has not been called", who);
+    if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
+    if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);
+    if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: rhs batch %d must be 1 or equal to the batch %d", who, rhs_batch, batch);
+    if (!(tol >= 0.0)) return fail(ctx, HN_ERR_ARG, "%s: tol must be a number >= 0 (got %g)", who, tol);
+    if (!(inner_floor >= 0.f)) return fail(ctx, HN_ERR_ARG, "%s: inner_floor must be a number >= 0 (got %g)", who, (double)inner_floor);
+    const int n = ctx->tab.n;
+    const long P = (long)n * n;
+    const size_t B = (size_t)batch, R = (size_t)restart;
+    const Range r[] = {{x, B * 2 * P * 8, "x"}, {k_sq, B * P * 4, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, "rhs"}, {basis, B * (R + 1) * 2 * P * 4, "basis"},
+                       {hess, B * (R + 1) * R * 2 * 4, "hess"}, {rmse, (R + 1) * B * 4, "rmse"}, {k_used, B * 4, "k_used"}, {rmse64, B * 8, "rmse64"}};
+    for (int i = 0; i < 4; ++i)   // float4 on the fp32 fields, double2 on x
+        if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
+    if (reinterpret_cast<uintptr_t>(rmse64) % 8 != 0) return fail(ctx, HN_ERR_ARG, "%s: rmse64 is not 8-byte aligned", who);
+    const char *na, *nb;
+    if (overlapping(r, 8, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    // all three workspaces before the first launch: a call that has to build one under capture leaves nothing behind
+    int rc = prepare(ctx, batch, restart, s);
+    if (rc == HN_OK) rc = refine_prepare(ctx, batch, s);
+    if (rc == HN_OK) rc = f64_reserve(ctx, batch, s);
+    if (rc != HN_OK) return rc;
+    const RefineWs& ws = *ctx->rfn;
+    const long nk4 = (long)batch * P / 4, nr4 = (long)rhs_batch * 2 * P / 4;   // (n is a multiple of 16)
+    const dim3 grid(ctx->kry->nchunk, batch), blk(256);
+    hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + nr4 + 255) / 256)), blk, 0, s, k_sq, ws.ksq64, nk4, rhs, ws.rhs64, nr4);
+    if ((rc = f64_apply(ctx, x, ws.res64, ws.ksq64, ws.rhs64, rhs_batch, rmse64, batch, s)) != HN_OK) return rc;
+    hipLaunchKernelGGL(k_refine_rhs, grid, blk, 0, s, ws.res64, rmse64, tol, (double)inner_floor, ws.rhs32, ws.d32, ws.tol, ws.stop, P);
+    if ((rc = launch_cycle(ctx, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
+    hipLaunchKernelGGL(k_refine_update, grid, blk, 0, s, x, ws.d32, rmse64, k_used, P);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
 }

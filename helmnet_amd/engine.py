@@ -298,6 +298,32 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_gmres_cycle")
         return rmse, k_used
 
+    def gmres_refine_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float, inner_floor: float = 1e-6,
+                           basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
+        """One refinement step of restarted GMRES (hn_gmres_refine_cycle): the true residual of the float64 iterate ``x`` [B,2,n,n] in float64, one fp32
+        restart cycle on the scaled correction equation, ``x`` updated in place in float64; nothing synchronised.  ``k_sq`` and ``rhs`` are the fp32
+        problem.  Returns (rmse64 [B] float64: the true residual RMSE of ``x`` at the START of the call, rmse [restart + 1, B] and k_used [B] int32:
+        the inner cycle's tables, as ``gmres_cycle`` returns them).  A sample with rmse64 < tol is not written and has k_used 0."""
+        b, restart = x.shape[0], int(restart)
+        for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError(f"gmres_refine_cycle: {name} requires grad; the GMRES cycle is not differentiable")
+        self._chk(x, (b, 2, self.n, self.n), "x", torch.float64)
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
+        self._chk(rhs, (rhs.shape[0], 2, self.n, self.n), "rhs")
+        new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
+        basis = new(b, restart + 1, 2 * self.n * self.n) if basis is None else basis
+        hess = new(b, restart + 1, restart, 2) if hess is None else hess
+        self._chk(basis, (b, restart + 1, 2 * self.n * self.n), "basis")
+        self._chk(hess, (b, restart + 1, restart, 2), "hess")
+        rmse = new(restart + 1, b)
+        k_used = torch.empty(b, device=self.device, dtype=torch.int32)
+        rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
+        rc = self.lib.hn_gmres_refine_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor),
+                                            _ptr(basis), _ptr(hess), _ptr(rmse), _ptr(k_used), _ptr(rmse64), self._stream())
+        _lib.check(rc, self.ctx, "hn_gmres_refine_cycle")
+        return rmse64, rmse, k_used
+
     # ---- the same operators in float64: the check the fp32 residual is measured against (hn_f64.hip) ----
     def laplacian64(self, wf: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]

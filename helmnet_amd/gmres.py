@@ -84,6 +84,63 @@ def drive_cycles(cycle, true_rmse, max_cycles: int, tol: float) -> dict:
             "cycles": cycles, "true_checks": checks, "converged": converged}
 
 
+def drive_refinement(cycle, max_cycles: int, tol: float) -> dict:
+    """The host loop of ``gmres(backend="hip", refine=True)``, free of torch and of the library like ``drive_cycles``.
+
+    ``cycle()`` runs one refinement step on the current float64 iterate and returns ``(rmse64 [B], rmse [m + 1, B], k_used [B])`` as host arrays
+    (the outputs of ``hn_gmres_refine_cycle``: the TRUE float64 residual RMSE at the start of the step and the inner fp32 cycle's tables); they
+    are read once per cycle.  The loop ends with the first cycle whose ``rmse64`` is below ``tol`` for every sample: that cycle is the final true
+    check, it has updated nothing (its ``k_used`` is zero).  At most ``max_cycles`` calls are made, the checking one included.  Returns history
+    (list of [B] float64 arrays: the true RMSE at the start of every cycle, the last one that of the returned iterate when converged), tables
+    (the inner rmse tables as they came), iterations (lock-step inner iterations: sum of max(k_used)), iterations_per_sample (int64 [B]),
+    cycles and converged."""
+    history, tables, its, per, converged, cycles = [], [], 0, None, False, 0
+    for _ in range(int(max_cycles)):
+        r64, rm, ku = cycle()
+        r64, rm, ku = np.asarray(r64, dtype=np.float64), np.asarray(rm, dtype=np.float32), np.asarray(ku, dtype=np.int64)
+        cycles += 1
+        history.append(r64.copy())
+        tables.append(rm)
+        per = ku.copy() if per is None else per + ku
+        its += int(ku.max())
+        if bool((r64 < tol).all()):
+            converged = True
+            break
+    return {"history": history, "tables": tables, "iterations": its, "iterations_per_sample": per if per is not None else np.zeros(0, np.int64),
+            "cycles": cycles, "converged": converged}
+
+
+def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor):
+    """``gmres(backend="hip", refine=True)``: iterative refinement with the fp32 restart cycle as the inner solver (hn_gmres_refine_cycle).  The
+    iterate, its true residual and the update are float64; one host synchronisation per cycle."""
+    for t in (sos_maps, x0):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError("gmres(backend='hip') runs without gradients: pass detached tensors")
+    eng = solver.engine()
+    sos_maps = sos_maps.float().contiguous()
+    k_sq = solver.get_initials(sos_maps)[0].contiguous()
+    rhs = solver.source.detach().float().contiguous()
+    bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
+    dev = rhs.device
+    x = torch.zeros(bsz, 2, n, n, dtype=torch.float64, device=dev) if x0 is None else x0.detach().to(dev).double().contiguous().clone()
+    basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=dev)
+    hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
+
+    def cycle():
+        rmse64, rmse, k_used = eng.gmres_refine_cycle(x, k_sq, rhs, restart, tol, inner_floor, basis, hess)
+        both = torch.cat([rmse64, rmse.reshape(-1).double(), k_used.double()]).cpu().numpy()          # the one synchronisation of the cycle
+        eng.check_async_errors()
+        m = (restart + 1) * bsz
+        return both[:bsz], both[bsz: bsz + m].reshape(restart + 1, bsz), both[bsz + m:].astype(np.int64)
+
+    out = drive_refinement(cycle, max_outer, tol)
+    # converged: the last cycle checked the returned iterate and wrote nothing; else its last update is still unchecked
+    final = torch.from_numpy(out["history"][-1]).to(dev) if out["converged"] else eng.residual64(x, k_sq.double(), rhs.double(), False, True)[1]
+    return {"wavefield": x, "residual_norm64": final, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
+            "operator_applications": out["cycles"] * (restart + 1), "operator_applications64": out["cycles"], "converged": out["converged"],
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"]}
+
+
 def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0):
     """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own."""
     for t in (sos_maps, x0):
@@ -116,7 +173,7 @@ def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0):
 
 
 def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
-          x0: Optional[torch.Tensor] = None, backend: str = "torch"):
+          x0: Optional[torch.Tensor] = None, backend: str = "torch", refine: bool = False, inner_floor: float = 1e-6):
     """Solve (L + k_sq) u = source for every map of ``sos_maps`` [B, 1, N, N] (the reference's classical baseline:
     matlab/spectral_gmres_solver.m:86-115, MATLAB's ``gmres`` with restarts).
 
@@ -133,7 +190,18 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
 
     ``backend="hip"``: the same method with a restart cycle as a handful of fused HIP launches per inner step (hn_gmres_cycle), the
     Givens least-squares solve on the device and every sample stopping on its own; it adds ``iterations_per_sample`` (int64 [B]) and
-    ``cycle_tables`` (the per-cycle rmse tables)."""
+    ``cycle_tables`` (the per-cycle rmse tables).
+
+    ``backend="hip", refine=True``: GMRES to float64 accuracy at the fp32 cycle's speed -- classical iterative refinement with the fused fp32
+    cycle as the inner solver (hn_gmres_refine_cycle).  Per cycle the true residual of the float64 iterate is evaluated in float64
+    (hn_residual_f64's operator), the fp32 cycle solves the scaled correction equation A d = r / s from d = 0 to ``max(tol / s, inner_floor)``,
+    and x += s d in float64.  ``tol`` is then a float64 RMSE; ``wavefield`` comes back float64, ``residual_norms`` is the list of TRUE float64
+    RMSEs [B] at the start of every cycle, ``residual_norm64`` [B] that of the returned iterate, ``max_outer`` bounds the cycles, the
+    final checking one included; ``x0`` may be fp32 (a learned solve's wavefield) or float64."""
+    if refine and backend != "hip":
+        raise ValueError("refine=True needs backend='hip'")
+    if backend == "hip" and refine:
+        return _gmres_refine(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, float(inner_floor))
     if backend == "hip":
         return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0)
     if backend != "torch":

@@ -612,6 +612,29 @@ class IterativeSolver(nn.Module):
         from .gmres import gmres
         return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip")
 
+    def gmres64(self, sos_maps, restart: int = 20, max_cycles: int = 400, tol: float = 1e-10, x0=None) -> dict:
+        """GMRES to float64 accuracy on this solver's operator and source (the role MATLAB's double-precision ``gmres`` has in the reference,
+        matlab/spectral_gmres_solver.m:86-115: the ground truth the learned solver is measured against): iterative refinement with the fused fp32
+        restart cycle inside and the residual and the update in float64 (``helmnet_amd.gmres.gmres(backend="hip", refine=True)``).  ``tol`` is the
+        float64 residual RMSE to reach; ``x0`` [B,2,n,n], fp32 or float64: the starting iterate, e.g. the learned solver's wavefield to be polished
+        (default: zeros; it is not written).  Returns ``wavefield`` and ``residual_norms`` in float64.  No gradients."""
+        from .gmres import gmres
+        return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", refine=True)
+
+    def reference_error(self, wavefield, sos_maps, tol: float = 1e-10, restart: int = 20, max_cycles: int = 400) -> dict:
+        """How far ``wavefield`` [B,2,n,n] is from the solution of the discrete problem: ``gmres64`` started from it is the ground truth.  Returns per
+        sample ``linf`` (max |wavefield - reference| over both planes) and ``rms`` of the same difference, ``reference_rmse64`` (the float64
+        residual RMSE of the reference: how good the ground truth is; below ``tol`` when ``converged``), ``reference`` (the float64 wavefield),
+        ``converged`` and ``cycles``.  ``wavefield`` is not written."""
+        for t in (wavefield, sos_maps):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError("reference_error runs without gradients: pass detached tensors")
+        out = self.gmres64(sos_maps, restart=restart, max_cycles=max_cycles, tol=tol, x0=wavefield)
+        ref = out["wavefield"]
+        diff = wavefield.detach().to(ref.device).double() - ref
+        return {"linf": diff.abs().amax((1, 2, 3)), "rms": diff.pow(2).mean((1, 2, 3)).sqrt(), "reference_rmse64": out["residual_norm64"],
+                "reference": ref, "converged": out["converged"], "cycles": out["cycles"]}
+
     def solve_many(self, sos_maps, tol: float, max_iterations: int = None, slots: int = 32, check_every: int = 25,
                    source_maps=None, diverge_rmse: float = None, keep_residuals: bool = False, norm_reduce=None) -> dict:
         """Extension: solve a stream of N maps to a tolerance, every map stopping on its own (continuous batching; the workload of the

@@ -264,6 +264,37 @@ int hn_residual_f64(hn_ctx* ctx, const double* wf, const double* k_sq, const dou
 int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
                    float* basis, float* hess, float* rmse, int32_t* k_used, void* stream);
 
+/* ---- GMRES to float64 accuracy (added within ABI v7: a new entry point, nothing existing changes) ----
+ * One refinement step of restarted GMRES: the true residual and the update in float64, the restart cycle in fp32 (hn_gmres_cycle's kernels).
+ * Classical iterative refinement with GMRES(restart) as the inner solver: res = A x - b by the float64 operator (hn_residual_f64's), s = its RMSE,
+ * the fp32 cycle on the SCALED correction equation A d = -res / s from d = 0 (a right-hand side of RMSE 1, whatever the residual has shrunk to),
+ * x += s * d in float64.  The operator of both precisions is the same one: the fp32 tables' values.
+ *   x        [B,2,n,n] double  in/out: the iterate
+ *   k_sq     [B,1,n,n] float, rhs [rhs_batch,2,n,n] float, rhs_batch in {1, batch}: up-cast exactly, as hn_step_f64 treats fp32 tables
+ *   rmse64   [B] double        out: the TRUE float64 residual RMSE of x at the START of the call, bit for bit what hn_residual_f64 returns for
+ *                              (x, double(k_sq), double(rhs)): the same launches, the same fixed-order sum
+ *   basis, hess, rmse [restart+1,B], k_used [B]: as hn_gmres_cycle, for the fp32 cycle on the scaled correction equation, s = max(rmse64, 1e-300),
+ *                              rhs fp32(-res / s) (a true division), started from d = 0 with the tolerance max(tol / s, inner_floor) on ITS
+ *                              residual RMSE (rmse row 0 is about 1).  They equal, bit for bit, what hn_gmres_cycle returns for that right-hand
+ *                              side from x = 0 with a tolerance of the same value.
+ * then x += s * d in float64 (one rounding of the product and one of the sum per element).
+ * Per-sample stop: a sample whose rmse64 < tol gets k_used = 0 and its x is not written (bit for bit); its rmse column repeats row 0.  The call that
+ * finds every sample below tol is therefore the final true check and writes no x.  inner_floor bounds the accuracy asked of the fp32 cycle from below
+ * (its estimate carries no information below about 1e-6 of the right-hand side).
+ * Zero residual: s is the clamp, the scaled right-hand side is exactly zero, the sample counts as stopped for every tol and x is untouched; nothing
+ * divides by zero.
+ * No host synchronisation: everything is enqueued on `stream` -- one up-cast launch, the float64 operator with its RMSE, one launch that scales the
+ * residual down and writes the per-sample tolerance and stop words, the cycle's launches, one update launch.  All sums have a fixed order, no float
+ * atomics: two calls on equal inputs give equal bits in every output, and a sample's results do not depend on its batch mates.
+ * Workspace: the float64 copies of k_sq and rhs, one float64 residual field, the fp32 scaled right-hand side and correction, two words per sample,
+ * plus hn_gmres_cycle's workspace and hn_residual_f64's tables, sized from (batch, restart, n) and freed by hn_set_domain / hn_destroy.  A call that
+ * must create or grow any of them under stream capture returns HN_ERR_STATE with nothing enqueued; later calls are plain launches and capturable.
+ * HN_ERR_ARG: restart outside [1, 64], batch < 1, rhs_batch not in {1, batch}, a NULL pointer, x / k_sq / rhs / basis not 16-byte aligned, tol or
+ * inner_floor NaN or negative, any two arguments overlapping (x included).  HN_ERR_STATE before hn_set_domain. */
+int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart,
+                          double tol, float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64,
+                          void* stream);
+
 /* d[B,2,n,n] = HybridNet(in6[B,6,n,n]); the hidden states are read from `states_in` and the new
  * ones written to `states_out`, both in the reference's flat layout [B, 2, hn_state_len()]
  * (architectures.py:419-437).  states_in must not alias states_out.
