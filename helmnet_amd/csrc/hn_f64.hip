@@ -163,12 +163,49 @@ __global__ __launch_bounds__(256) void k_rmse_f64(const double* __restrict__ par
     if (threadIdx.x == 0) rmse[blockIdx.x] = sqrt(red[0] * inv_count);
 }
 
-// the first float64 call on a domain builds and uploads the tables; a larger batch grows the table of partial sums
-int f64_prepare(hn_ctx* ctx, long part_needed, hipStream_t s) {
-    SpecTables& t = ctx->tab;
-    if (t.f64_tab != nullptr && part_needed <= t.f64_part_cap) return HN_OK;
+}  // namespace
+
+bool stream_capturing(hipStream_t s) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+int DeviceBlock::alloc(hn_ctx* ctx, const char* who, const size_t* sizes, int count) {
+    free();
+    size_t total = 0;
+    for (int i = 0; i < count; ++i) { offs.push_back(total); total += (sizes[i] + 255) & ~(size_t)255; }
+    hipError_t e = hipMalloc((void**)&base, total);
+    if (e == hipSuccess) e = hipMemset(base, 0, total);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) return HN_OK;
+    free();
+    return fail(ctx, e == hipErrorOutOfMemory ? HN_ERR_NOMEM : HN_ERR_HIP, "%s: workspace of %zu bytes: %s", who, total, hipGetErrorString(e));
+}
+void DeviceBlock::free() {
+    (void)hipFree(base);
+    base = nullptr;
+    offs.clear();
+    taken = 0;
+}
+
+bool first_overlap(const MemRange* r, int count, const char** a_name, const char** b_name) {
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j) {
+            if (r[i].p == nullptr || r[j].p == nullptr || !(r[i].written || r[j].written)) continue;
+            const char *a = static_cast<const char*>(r[i].p), *b = static_cast<const char*>(r[j].p);
+            if (a < b + r[j].bytes && b < a + r[i].bytes) { *a_name = r[i].name; *b_name = r[j].name; return true; }
+        }
+    return false;
+}
+
+// the first float64 call on a domain builds and uploads the tables; a larger batch with an rmse grows the table of partial sums (one per tile and sample)
+int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s) {
+    SpecTables& t = ctx->tab;
+    if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    const int tiles_1d = (t.n + kTile - 1) / kTile;
+    const long part_needed = want_rmse ? (long)batch * tiles_1d * tiles_1d : 0;
+    if (t.f64_tab != nullptr && part_needed <= t.f64_part_cap) return HN_OK;
+    if (stream_capturing(s))
         return fail(ctx, HN_ERR_STATE, "the float64 tables of this domain (or a larger batch's partial sums) are built by the first call, which must not be under stream capture");
     if (t.f64_tab == nullptr) {
         const int n = t.n;
@@ -206,23 +243,16 @@ int f64_prepare(hn_ctx* ctx, long part_needed, hipStream_t s) {
     return HN_OK;
 }
 
-bool overlap(const double* a, const double* b, long count) { return a < b + count && b < a + count; }
-
-}  // namespace
-
-int f64_reserve(hn_ctx* ctx, int batch, hipStream_t s) {
-    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
-    const int tiles_1d = (ctx->tab.n + kTile - 1) / kTile;
-    return f64_prepare(ctx, (long)batch * tiles_1d * tiles_1d, s);
-}
-
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s) {
     SpecTables& t = ctx->tab;
     if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     const int n = t.n, tiles_1d = (n + kTile - 1) / kTile, tiles = tiles_1d * tiles_1d;
     const long plane = (long)n * n;
-    if (out != nullptr && overlap(wf, out, (long)batch * 2 * plane)) return fail(ctx, HN_ERR_ARG, "float64 residual: the wavefield must not alias the output");
-    if (int rc = f64_prepare(ctx, rmse != nullptr ? (long)batch * tiles : 0, s); rc != HN_OK) return rc;
+    const size_t bytes = (size_t)batch * 2 * plane * sizeof(double);
+    const MemRange r[] = {{wf, bytes, false, "wf"}, {out, bytes, true, "out"}};
+    const char *na, *nb;
+    if (first_overlap(r, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "float64 residual: the wavefield must not alias the output");
+    if (int rc = f64_reserve(ctx, batch, rmse != nullptr, s); rc != HN_OK) return rc;
     double* part = rmse != nullptr ? t.f64_part : nullptr;
     const dim3 grid(tiles_1d, tiles_1d, batch);
     const size_t lds = f64_lds_bytes(n);

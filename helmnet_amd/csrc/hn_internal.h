@@ -497,8 +497,24 @@ int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, cons
 // ---- float64 residual check (hn_f64.hip) ----
 // out = L(wf) [+ ksq * wf - src] in float64 (out nullable) and / or rmse[b] = sqrt(mean over (c, h, w) of out^2) (nullable)
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s);
-// the tables and the partial sums an rmse call of f64_apply with this batch needs, so that it has nothing left to build (HN_ERR_STATE under stream capture)
-int f64_reserve(hn_ctx* ctx, int batch, hipStream_t s);
+// the tables and, with want_rmse, the partial sums a call of f64_apply with this batch needs, so that it has nothing left to build (HN_ERR_STATE under
+// stream capture): an entry point that launches before it reaches f64_apply asks here first
+int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s);
+// ---- what the float64 and GMRES entry points share (defined in hn_f64.hip) ----
+bool stream_capturing(hipStream_t s);   // a non-null stream under capture: nothing may be built, grown or freed
+// One zeroed device allocation handed out as 256-byte-aligned pieces: alloc() with the pieces' byte sizes, then one take() per piece, in that order.
+struct DeviceBlock {
+    char* base = nullptr;
+    std::vector<size_t> offs;   // where each piece begins
+    size_t taken = 0;
+    // frees what it held; HN_ERR_NOMEM / HN_ERR_HIP with "<who>: workspace of <total> bytes: ..." and nothing allocated on failure; synchronises the device
+    int alloc(hn_ctx* ctx, const char* who, const size_t* sizes, int count);
+    void* take() { return base + offs[taken++]; }
+    void free();                // (hipFree waits for the launches that still use the block)
+};
+// The first pair of ranges (in index order) that overlap and of which at least one is written, as names for "<a> overlaps <b>"; NULL ranges are skipped.
+struct MemRange { const void* p; size_t bytes; bool written; const char* name; };
+bool first_overlap(const MemRange* r, int count, const char** a_name, const char** b_name);
 void unet_f64_free(hn_ctx* ctx);   // hn_unet_f64.hip (the caller has synchronised the device)
 void krylov_free(hn_ctx* ctx);     // hn_krylov.hip: the cycle's and the refinement's workspaces (the caller has synchronised the device)
 void train_free(hn_ctx* ctx);   // hn_train.hip

@@ -25,7 +25,7 @@ constexpr int kKryChunk = 1024;   // pixels per block: 256 threads x one float4 
 
 struct KrylovWs {
     int batch = 0, restart = 0, n = 0, nchunk = 0;
-    void* block = nullptr;    // one allocation; the pointers below lead into it
+    DeviceBlock block;        // one allocation; the pointers below lead into it
     float* vin = nullptr;     // [B][2 n^2]  v_k, densely strided: the operator's input
     float* w = nullptr;       // [B][2 n^2]  the operator's output, orthogonalised in place
     float* zero = nullptr;    // [2 n^2]     the zero source
@@ -42,7 +42,7 @@ struct KrylovWs {
 // what hn_gmres_refine_cycle needs beyond the cycle's workspace and the float64 operator's tables
 struct RefineWs {
     int batch = 0, n = 0;
-    void* block = nullptr;    // one allocation; the pointers below lead into it
+    DeviceBlock block;        // one allocation; the pointers below lead into it
     double* ksq64 = nullptr;  // [B][n^2]    k_sq up-cast
     double* rhs64 = nullptr;  // [B][2 n^2]  rhs up-cast (the first rhs_batch samples)
     double* res64 = nullptr;  // [B][2 n^2]  A x - b
@@ -328,30 +328,23 @@ __global__ __launch_bounds__(256) void k_update(float* __restrict__ x, const flo
 }
 
 void cycle_ws_free(hn_ctx* ctx) {
-    KrylovWs* ws = ctx->kry;
-    if (ws == nullptr) return;
-    (void)hipFree(ws->block);
-    delete ws;
+    if (ctx->kry == nullptr) return;
+    ctx->kry->block.free();
+    delete ctx->kry;
     ctx->kry = nullptr;
 }
-
-bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-
-size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // the workspace for (batch, restart) on the current domain: built by the first call, grown by a larger batch or restart -- never under stream capture
 int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
     const int n = ctx->tab.n;
     KrylovWs* ws = ctx->kry;
-    if (ws != nullptr && ws->n == n && batch <= ws->batch && restart <= ws->restart) return HN_OK;
-    if (capturing(s))
+    const bool same = ws != nullptr && ws->n == n;
+    if (same && batch <= ws->batch && restart <= ws->restart) return HN_OK;
+    if (stream_capturing(s))
         return fail(ctx, HN_ERR_STATE, "hn_gmres_cycle: the workspace (or a larger batch's / restart's) is built by the first call, which must not be under stream capture");
-    const int cb = ws != nullptr && ws->n == n && ws->batch > batch ? ws->batch : batch;
-    const int cr = ws != nullptr && ws->n == n && ws->restart > restart ? ws->restart : restart;
-    cycle_ws_free(ctx);   // (hipFree waits for the launches that still use the old one)
+    const int cb = same && ws->batch > batch ? ws->batch : batch;         // the larger of old and new, each on its own
+    const int cr = same && ws->restart > restart ? ws->restart : restart;
+    cycle_ws_free(ctx);
     ws = new (std::nothrow) KrylovWs();
     if (!ws) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
     ctx->kry = ws;
@@ -359,35 +352,13 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
     const size_t nchunk = (P + kKryChunk - 1) / kKryChunk;
     const size_t sizes[] = {B * 2 * P * 4, B * 2 * P * 4, 2 * P * 4, B * 2 * (R + 1) * nchunk * 2 * 4, B * nchunk * 4, B * 4,
                             B * (R + 1) * 2 * 8, B * R * 4 * 8, B * R * (R + 1) * 2 * 8, B * R * 2 * 4, B * 4};
-    size_t total = 0;
-    for (size_t v : sizes) total += up256(v);
-    hipError_t e = hipMalloc(&ws->block, total);
-    if (e == hipSuccess) e = hipMemset(ws->block, 0, total);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        cycle_ws_free(ctx);
-        return fail(ctx, e == hipErrorOutOfMemory ? HN_ERR_NOMEM : HN_ERR_HIP, "hn_gmres_cycle: workspace of %zu bytes: %s", total, hipGetErrorString(e));
-    }
-    char* p = static_cast<char*>(ws->block);
-    int i = 0;
-    auto take = [&]() { char* q = p; p += up256(sizes[i++]); return q; };
-    ws->vin = (float*)take(); ws->w = (float*)take(); ws->zero = (float*)take(); ws->part = (float*)take(); ws->npart = (float*)take();
-    ws->scale = (float*)take(); ws->g = (double*)take(); ws->cs = (double*)take(); ws->R = (double*)take(); ws->y = (float*)take();
-    ws->stopped = (int*)take();
+    DeviceBlock& k = ws->block;
+    if (const int rc = k.alloc(ctx, "hn_gmres_cycle", sizes, 11); rc != HN_OK) { cycle_ws_free(ctx); return rc; }
+    ws->vin = (float*)k.take(); ws->w = (float*)k.take(); ws->zero = (float*)k.take(); ws->part = (float*)k.take(); ws->npart = (float*)k.take();
+    ws->scale = (float*)k.take(); ws->g = (double*)k.take(); ws->cs = (double*)k.take(); ws->R = (double*)k.take(); ws->y = (float*)k.take();
+    ws->stopped = (int*)k.take();
     ws->batch = cb; ws->restart = cr; ws->n = n; ws->nchunk = (int)nchunk;
     return HN_OK;
-}
-
-struct Range { const void* p; size_t bytes; const char* name; };
-
-// first pair of overlapping ranges, or false
-bool overlapping(const Range* r, int count, const char** a_name, const char** b_name) {
-    for (int i = 0; i < count; ++i)
-        for (int j = i + 1; j < count; ++j) {
-            const char *a = static_cast<const char*>(r[i].p), *b = static_cast<const char*>(r[j].p);
-            if (a < b + r[j].bytes && b < a + r[i].bytes) { *a_name = r[i].name; *b_name = r[j].name; return true; }
-        }
-    return false;
 }
 
 // The restart cycle's launches, the workspace prepared.  tol_dev / pre_stopped: see SmallArgs (nullptr: hn_gmres_cycle, whose bits they leave alone --
@@ -490,10 +461,9 @@ __global__ __launch_bounds__(256) void k_refine_update(double* __restrict__ x, c
 }
 
 void refine_ws_free(hn_ctx* ctx) {
-    RefineWs* ws = ctx->rfn;
-    if (ws == nullptr) return;
-    (void)hipFree(ws->block);
-    delete ws;
+    if (ctx->rfn == nullptr) return;
+    ctx->rfn->block.free();
+    delete ctx->rfn;
     ctx->rfn = nullptr;
 }
 
@@ -502,29 +472,41 @@ int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s) {
     const int n = ctx->tab.n;
     RefineWs* ws = ctx->rfn;
     if (ws != nullptr && ws->n == n && batch <= ws->batch) return HN_OK;
-    if (capturing(s))
+    if (stream_capturing(s))
         return fail(ctx, HN_ERR_STATE, "hn_gmres_refine_cycle: the workspace (or a larger batch's) is built by the first call, which must not be under stream capture");
-    refine_ws_free(ctx);   // (hipFree waits for the launches that still use the old one)
+    refine_ws_free(ctx);
     ws = new (std::nothrow) RefineWs();
     if (!ws) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
     ctx->rfn = ws;
     const size_t P = (size_t)n * n, B = (size_t)batch;
     const size_t sizes[] = {B * P * 8, B * 2 * P * 8, B * 2 * P * 8, B * 2 * P * 4, B * 2 * P * 4, B * 8, B * 4};
-    size_t total = 0;
-    for (size_t v : sizes) total += up256(v);
-    hipError_t e = hipMalloc(&ws->block, total);
-    if (e == hipSuccess) e = hipMemset(ws->block, 0, total);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        refine_ws_free(ctx);
-        return fail(ctx, e == hipErrorOutOfMemory ? HN_ERR_NOMEM : HN_ERR_HIP, "hn_gmres_refine_cycle: workspace of %zu bytes: %s", total, hipGetErrorString(e));
-    }
-    char* p = static_cast<char*>(ws->block);
-    int i = 0;
-    auto take = [&]() { char* q = p; p += up256(sizes[i++]); return q; };
-    ws->ksq64 = (double*)take(); ws->rhs64 = (double*)take(); ws->res64 = (double*)take(); ws->rhs32 = (float*)take(); ws->d32 = (float*)take();
-    ws->tol = (double*)take(); ws->stop = (int*)take();
+    DeviceBlock& k = ws->block;
+    if (const int rc = k.alloc(ctx, "hn_gmres_refine_cycle", sizes, 7); rc != HN_OK) { refine_ws_free(ctx); return rc; }
+    ws->ksq64 = (double*)k.take(); ws->rhs64 = (double*)k.take(); ws->res64 = (double*)k.take(); ws->rhs32 = (float*)k.take(); ws->d32 = (float*)k.take();
+    ws->tol = (double*)k.take(); ws->stop = (int*)k.take();
     ws->batch = batch; ws->n = n;
+    return HN_OK;
+}
+
+// What hn_gmres_cycle (rmse64 NULL, x fp32) and hn_gmres_refine_cycle (x float64) refuse alike, under the entry point's name.  Any two arguments that
+// overlap are refused, read against read too (every range counts as written).  The two entry points report a missing domain with different codes, and
+// a caller may rely on either: a known wart.
+int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, const void* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart,
+                     const float* basis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64) {
+    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64)) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (ctx->tab.n == 0) return fail(ctx, refine ? HN_ERR_STATE : HN_ERR_ARG, "%s: hn_set_domain has not been called", who);
+    if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
+    if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);
+    if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: rhs batch %d must be 1 or equal to the batch %d", who, rhs_batch, batch);
+    const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
+    const MemRange r[] = {{x, B * 2 * P * (refine ? 8 : 4), true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
+                          {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"},
+                          {k_used, B * 4, true, "k_used"}, {rmse64, B * 8, true, "rmse64"}};
+    for (int i = 0; i < 4; ++i)   // the fields are read and written as float4 (x of the refinement: as double2)
+        if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
+    if (reinterpret_cast<uintptr_t>(rmse64) % 8 != 0) return fail(ctx, HN_ERR_ARG, "%s: rmse64 is not 8-byte aligned", who);
+    const char *na, *nb;
+    if (first_overlap(r, 8, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     return HN_OK;
 }
 
@@ -541,53 +523,28 @@ using namespace hn;
 
 extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
                               float* basis, float* hess, float* rmse, int32_t* k_used, void* stream) {
-    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: NULL argument");
-    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: hn_set_domain has not been called");
-    if (batch < 1) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: batch must be positive (got %d)", batch);
-    if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: restart %d outside [1, %d]", restart, kKryMaxRestart);
-    if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: rhs batch %d must be 1 or equal to the batch %d", rhs_batch, batch);
-    const int n = ctx->tab.n;
-    const long P = (long)n * n;
-    const size_t B = (size_t)batch, R = (size_t)restart;
-    const Range r[] = {{x, B * 2 * P * 4, "x"}, {k_sq, B * P * 4, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, "rhs"}, {basis, B * (R + 1) * 2 * P * 4, "basis"},
-                       {hess, B * (R + 1) * R * 2 * 4, "hess"}, {rmse, (R + 1) * B * 4, "rmse"}, {k_used, B * 4, "k_used"}};
-    for (int i = 0; i < 4; ++i)   // the fields are read and written as float4
-        if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: %s is not 16-byte aligned", r[i].name);
-    const char *na, *nb;
-    if (overlapping(r, 7, &na, &nb)) return fail(ctx, HN_ERR_ARG, "hn_gmres_cycle: %s overlaps %s", na, nb);
+    int rc = check_cycle_args(ctx, "hn_gmres_cycle", false, x, k_sq, rhs, rhs_batch, batch, restart, basis, hess, rmse, k_used, nullptr);
+    if (rc != HN_OK) return rc;
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
-    const int rc = prepare(ctx, batch, restart, s);
-    if (rc != HN_OK) return rc;
+    if ((rc = prepare(ctx, batch, restart, s)) != HN_OK) return rc;
     return launch_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, basis, hess, rmse, k_used, s);
 }
 
 extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
                                      float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
     const char* who = "hn_gmres_refine_cycle";
-    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || !rmse64) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
-    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain has not been called", who);
-    if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
-    if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);
-    if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: rhs batch %d must be 1 or equal to the batch %d", who, rhs_batch, batch);
+    int rc = check_cycle_args(ctx, who, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, hess, rmse, k_used, rmse64);
+    if (rc != HN_OK) return rc;
     if (!(tol >= 0.0)) return fail(ctx, HN_ERR_ARG, "%s: tol must be a number >= 0 (got %g)", who, tol);
     if (!(inner_floor >= 0.f)) return fail(ctx, HN_ERR_ARG, "%s: inner_floor must be a number >= 0 (got %g)", who, (double)inner_floor);
-    const int n = ctx->tab.n;
-    const long P = (long)n * n;
-    const size_t B = (size_t)batch, R = (size_t)restart;
-    const Range r[] = {{x, B * 2 * P * 8, "x"}, {k_sq, B * P * 4, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, "rhs"}, {basis, B * (R + 1) * 2 * P * 4, "basis"},
-                       {hess, B * (R + 1) * R * 2 * 4, "hess"}, {rmse, (R + 1) * B * 4, "rmse"}, {k_used, B * 4, "k_used"}, {rmse64, B * 8, "rmse64"}};
-    for (int i = 0; i < 4; ++i)   // float4 on the fp32 fields, double2 on x
-        if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
-    if (reinterpret_cast<uintptr_t>(rmse64) % 8 != 0) return fail(ctx, HN_ERR_ARG, "%s: rmse64 is not 8-byte aligned", who);
-    const char *na, *nb;
-    if (overlapping(r, 8, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    const long P = (long)ctx->tab.n * ctx->tab.n;
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     // all three workspaces before the first launch: a call that has to build one under capture leaves nothing behind
-    int rc = prepare(ctx, batch, restart, s);
+    rc = prepare(ctx, batch, restart, s);
     if (rc == HN_OK) rc = refine_prepare(ctx, batch, s);
-    if (rc == HN_OK) rc = f64_reserve(ctx, batch, s);
+    if (rc == HN_OK) rc = f64_reserve(ctx, batch, true, s);
     if (rc != HN_OK) return rc;
     const RefineWs& ws = *ctx->rfn;
     const long nk4 = (long)batch * P / 4, nr4 = (long)rhs_batch * 2 * P / 4;   // (n is a multiple of 16)

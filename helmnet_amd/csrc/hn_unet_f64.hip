@@ -29,11 +29,11 @@ struct F64Unet {
     F64Dc inc{}, sig[kMaxDepth]{}, st[kMaxDepth]{}, dec[kMaxDepth + 1]{};
     F64K8 down[kMaxDepth]{}, up[kMaxDepth]{};
     const double *outc_w = nullptr, *outc_b = nullptr;
-    // workspace for `cap` samples: per level x_d (later the upsampled u_d), out_d, y_d with 8 channels each; the assembled input and d of hn_step_f64
+    // workspace for `cap` samples (pieces of `block`): the assembled input and d of hn_step_f64; per level x_d (later the upsampled u_d), y_d and out_d
+    // (none at the bottleneck) with 8 channels each; the second flat state buffer, hn_step_f64 ping-pongs between it and the caller's
     int cap = 0;
-    double* ws = nullptr;
-    double *a[kMaxDepth + 1]{}, *o[kMaxDepth]{}, *y[kMaxDepth + 1]{}, *in6 = nullptr, *d = nullptr;
-    double* st_tmp = nullptr;     // second flat state buffer: hn_step_f64 ping-pongs between it and the caller's
+    DeviceBlock block;
+    double *a[kMaxDepth + 1]{}, *o[kMaxDepth]{}, *y[kMaxDepth + 1]{}, *in6 = nullptr, *d = nullptr, *st_tmp = nullptr;
 };
 
 namespace {
@@ -41,6 +41,7 @@ namespace {
 constexpr int kT = 16;              // output tile
 constexpr int kInW = kT + 4;        // input tile with halo 2
 constexpr int kMidW = kT + 2;       // mid tile with halo 1
+constexpr size_t kD = sizeof(double);   // (the overlap check and the workspace count bytes)
 
 struct View { const double* p; long sb, sc; };   // element (b, c, y, x) at p[b * sb + c * sc + y * W + x]
 struct OutView { double* p; long sb, sc; };
@@ -278,18 +279,6 @@ int launch_dc(hn_ctx* ctx, View a, View b, OutView out, const F64Dc& w, int H, i
     return HN_OK;
 }
 
-bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-
-// doubles of the workspace per sample: three 8-channel tensors per level (two at the bottleneck), the assembled input, d
-size_t ws_doubles(int n, int depth) {
-    size_t t = (size_t)(kInCh + 2) * n * n;
-    for (int d = 0; d <= depth; ++d) t += (size_t)(d < depth ? 3 : 2) * kFeat * (n >> d) * (n >> d);
-    return t;
-}
-
 int build(hn_ctx* ctx, int batch) {
     const int depth = ctx->depth, n = ctx->tab.n;
     if (ctx->f64 == nullptr) {
@@ -316,22 +305,21 @@ int build(hn_ctx* ctx, int batch) {
     }
     F64Unet* u = ctx->f64;
     if (batch > u->cap) {
-        (void)hipFree(u->ws);       // (waits for the launches that still use it)
-        (void)hipFree(u->st_tmp);
-        u->ws = u->st_tmp = nullptr;
         u->cap = 0;
-        HN_HIP(ctx, hipMalloc((void**)&u->ws, sizeof(double) * ws_doubles(n, depth) * batch));
-        HN_HIP(ctx, hipMalloc((void**)&u->st_tmp, sizeof(double) * (size_t)batch * kState * ctx->state_len));
-        double* p = u->ws;
-        auto take = [&](size_t per_sample) { double* q = p; p += per_sample * batch; return q; };
-        u->in6 = take((size_t)kInCh * n * n);
-        u->d = take((size_t)2 * n * n);
+        const size_t per = kD * batch;   // bytes per double of a sample
+        std::vector<size_t> sizes{per * kInCh * n * n, per * 2 * n * n};
+        for (int d = 0; d <= depth; ++d) sizes.insert(sizes.end(), d < depth ? 3 : 2, per * kFeat * (n >> d) * (n >> d));
+        sizes.push_back(per * kState * ctx->state_len);
+        if (const int rc = u->block.alloc(ctx, "float64 UNet", sizes.data(), (int)sizes.size()); rc != HN_OK) return rc;
+        auto take = [&]() { return static_cast<double*>(u->block.take()); };
+        u->in6 = take();
+        u->d = take();
         for (int d = 0; d <= depth; ++d) {
-            const size_t t = (size_t)kFeat * (n >> d) * (n >> d);
-            u->a[d] = take(t);
-            u->y[d] = take(t);
-            if (d < depth) u->o[d] = take(t);
+            u->a[d] = take();
+            u->y[d] = take();
+            if (d < depth) u->o[d] = take();
         }
+        u->st_tmp = take();
         u->cap = batch;
     }
     return HN_OK;
@@ -339,7 +327,7 @@ int build(hn_ctx* ctx, int batch) {
 // weights, workspace and state buffer for `batch` samples: built by the first call, grown by a larger batch -- never under stream capture
 int prepare(hn_ctx* ctx, int batch, hipStream_t s) {
     if (ctx->f64 != nullptr && batch <= ctx->f64->cap) return HN_OK;
-    if (capturing(s))
+    if (stream_capturing(s))
         return fail(ctx, HN_ERR_STATE, "the float64 weights and workspace (or a larger batch's) are built by the first call, which must not be under stream capture");
     const int rc = build(ctx, batch);
     if (rc != HN_OK) unet_f64_free(ctx);   // nothing half-built stays behind
@@ -376,17 +364,6 @@ int forward(hn_ctx* ctx, const double* in6, const double* st_in, double* st_out,
     return HN_OK;
 }
 
-struct Range { const double* p; size_t count; bool written; const char* name; };
-// range overlap between any two tensors of which at least one is written
-const char* first_clash(const Range* r, int count, const char** other) {
-    for (int i = 0; i < count; ++i)
-        for (int j = i + 1; j < count; ++j) {
-            if (r[i].p == nullptr || r[j].p == nullptr || !(r[i].written || r[j].written)) continue;
-            if (r[i].p < r[j].p + r[j].count && r[j].p < r[i].p + r[i].count) { *other = r[j].name; return r[i].name; }
-        }
-    return nullptr;
-}
-
 int check_f64_ready(hn_ctx* ctx, int batch) {
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "hn_load_weights has not been called");
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
@@ -402,8 +379,7 @@ void unet_f64_free(hn_ctx* ctx) {
     F64Unet* u = ctx->f64;
     if (u == nullptr) return;
     (void)hipFree(u->w);
-    (void)hipFree(u->ws);
-    (void)hipFree(u->st_tmp);
+    u->block.free();
     delete u;
     ctx->f64 = nullptr;
 }
@@ -418,11 +394,11 @@ int hn_unet_f64(hn_ctx* ctx, const double* in6, const double* states_in, double*
     if (!ctx || !in6 || !states_in || !states_out || !d_out) return fail(ctx, HN_ERR_ARG, "hn_unet_f64: NULL argument");
     int rc = check_f64_ready(ctx, batch);
     if (rc != HN_OK) return rc;
-    const size_t plane = (size_t)ctx->tab.n * ctx->tab.n, sl = (size_t)batch * kState * ctx->state_len;
-    const Range r[] = {{in6, batch * kInCh * plane, false, "in6"}, {states_in, sl, false, "states_in"}, {states_out, sl, true, "states_out"},
-                       {d_out, batch * 2 * plane, true, "d_out"}};
-    const char* other = nullptr;
-    if (const char* who = first_clash(r, 4, &other)) return fail(ctx, HN_ERR_ARG, "hn_unet_f64: %s overlaps %s", who, other);
+    const size_t plane = kD * ctx->tab.n * ctx->tab.n, sl = kD * batch * kState * ctx->state_len;   // bytes
+    const MemRange r[] = {{in6, batch * kInCh * plane, false, "in6"}, {states_in, sl, false, "states_in"}, {states_out, sl, true, "states_out"},
+                          {d_out, batch * 2 * plane, true, "d_out"}};
+    const char *who, *other;
+    if (first_overlap(r, 4, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_unet_f64: %s overlaps %s", who, other);
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     if ((rc = prepare(ctx, batch, s)) != HN_OK) return rc;
@@ -439,20 +415,19 @@ int hn_step_f64(hn_ctx* ctx, double* wf, double* res, double* states, const doub
     const int n = ctx->tab.n;
     const size_t plane = (size_t)n * n, L = (size_t)ctx->state_len;
     const size_t fc = (size_t)batch * 2 * plane, sc = (size_t)batch * kState * L;
-    const Range r[] = {{wf, fc, true, "wf"}, {res, fc, true, "res"}, {states, sc, true, "states"}, {k_sq, batch * plane, false, "k_sq"},
-                       {src, (size_t)src_batch * 2 * plane, false, "src"}, {res_hist, n_iter * fc, true, "res_hist"}, {wf_hist, n_iter * fc, true, "wf_hist"},
-                       {st_hist, n_iter * sc, true, "st_hist"}, {rmse_hist, (size_t)n_iter * batch, true, "rmse_hist"}};
-    const char* other = nullptr;
-    if (const char* who = first_clash(r, 9, &other)) return fail(ctx, HN_ERR_ARG, "hn_step_f64: %s overlaps %s", who, other);
+    const MemRange r[] = {{wf, kD * fc, true, "wf"}, {res, kD * fc, true, "res"}, {states, kD * sc, true, "states"}, {k_sq, kD * batch * plane, false, "k_sq"},
+                          {src, kD * src_batch * 2 * plane, false, "src"}, {res_hist, kD * n_iter * fc, true, "res_hist"},
+                          {wf_hist, kD * n_iter * fc, true, "wf_hist"}, {st_hist, kD * n_iter * sc, true, "st_hist"},
+                          {rmse_hist, kD * n_iter * batch, true, "rmse_hist"}};
+    const char *who, *other;
+    if (first_overlap(r, 9, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_step_f64: %s overlaps %s", who, other);
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     if ((rc = prepare(ctx, batch, s)) != HN_OK) return rc;
     if (n_iter == 0) return HN_OK;
-    // f64_apply builds the domain's float64 tables and grows its partial sums (one per 32 x 32 tile, hn_f64.hip) at its first call and refuses that under
-    // capture -- by then this call would have enqueued a UNet: refuse here, before anything is enqueued
-    const long tiles = (long)((n + 31) / 32) * ((n + 31) / 32);
-    if (capturing(s) && (ctx->tab.f64_tab == nullptr || (rmse_hist != nullptr && ctx->tab.f64_part_cap < batch * tiles)))
-        return fail(ctx, HN_ERR_STATE, "the float64 tables of this domain are built by the first call, which must not be under stream capture");
+    // f64_apply builds the domain's float64 tables and grows its partial sums at its first call and refuses that under capture -- by then this call
+    // would have enqueued a UNet: build (or be refused) here, before anything is enqueued
+    if ((rc = f64_reserve(ctx, batch, rmse_hist != nullptr, s)) != HN_OK) return rc;
     F64Unet& u = *ctx->f64;
     for (int it = 0; it < n_iter; ++it) {
         const double* st_in = (it & 1) ? u.st_tmp : states;   // the hidden states ping-pong between the caller's buffer and the library's

@@ -128,6 +128,13 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _require_no_grad(what: str, *tensors):
+    """The one refusal of every entry that computes without autograd (the float64 loop and residual, GMRES, solve_many)."""
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError(f"{what} runs without gradients: pass detached tensors (the differentiable path is forward())")
+
+
 class Engine:
     """One library context bound to one HIP device."""
 
@@ -273,26 +280,29 @@ class Engine:
         _lib.check(self.lib.hn_rmse(self.ctx, _ptr(res), _ptr(out), b, self._stream()), self.ctx, "hn_rmse")
         return out
 
+    def _gmres_buffers(self, what: str, x, x_dtype, k_sq, rhs, restart: int, basis, hess):
+        """What gmres_cycle and gmres_refine_cycle share: the grad refusal, the shape checks, ``basis`` / ``hess`` (allocated when not given) and the
+        fresh ``rmse`` [restart + 1, B] and ``k_used`` [B] int32 tables."""
+        b, p2 = x.shape[0], 2 * self.n * self.n
+        for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError(f"{what}: {name} requires grad; the GMRES cycle is not differentiable")
+        self._chk(x, (b, 2, self.n, self.n), "x", x_dtype)
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
+        self._chk(rhs, (rhs.shape[0], 2, self.n, self.n), "rhs")
+        new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
+        basis = self._chk(new(b, restart + 1, p2) if basis is None else basis, (b, restart + 1, p2), "basis")
+        hess = self._chk(new(b, restart + 1, restart, 2) if hess is None else hess, (b, restart + 1, restart, 2), "hess")
+        return b, basis, hess, new(restart + 1, b), torch.empty(b, device=self.device, dtype=torch.int32)
+
     def gmres_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
                     basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
         """One restart cycle of GMRES(restart) on A u = L(u) + k_sq * u (hn_gmres_cycle), ``x`` updated in place, nothing synchronised.  Returns
         (rmse [restart + 1, B], k_used [B] int32): row 0 the true residual RMSE of ``x`` at the start, row j the Givens estimate after j inner
         iterations, ``k_used`` the inner iterations that entered each sample's update.  ``basis`` [B, restart + 1, 2 n^2] and ``hess``
         [B, restart + 1, restart, 2] receive the Arnoldi vectors and the Hessenberg matrix; they are allocated when not given."""
-        b, restart = x.shape[0], int(restart)
-        for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError(f"gmres_cycle: {name} requires grad; the GMRES cycle is not differentiable")
-        self._chk(x, (b, 2, self.n, self.n), "x")
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(rhs, (rhs.shape[0], 2, self.n, self.n), "rhs")
-        new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
-        basis = new(b, restart + 1, 2 * self.n * self.n) if basis is None else basis
-        hess = new(b, restart + 1, restart, 2) if hess is None else hess
-        self._chk(basis, (b, restart + 1, 2 * self.n * self.n), "basis")
-        self._chk(hess, (b, restart + 1, restart, 2), "hess")
-        rmse = new(restart + 1, b)
-        k_used = torch.empty(b, device=self.device, dtype=torch.int32)
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("gmres_cycle", x, torch.float32, k_sq, rhs, restart, basis, hess)
         rc = self.lib.hn_gmres_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), _ptr(basis), _ptr(hess),
                                      _ptr(rmse), _ptr(k_used), self._stream())
         _lib.check(rc, self.ctx, "hn_gmres_cycle")
@@ -304,20 +314,8 @@ class Engine:
         restart cycle on the scaled correction equation, ``x`` updated in place in float64; nothing synchronised.  ``k_sq`` and ``rhs`` are the fp32
         problem.  Returns (rmse64 [B] float64: the true residual RMSE of ``x`` at the START of the call, rmse [restart + 1, B] and k_used [B] int32:
         the inner cycle's tables, as ``gmres_cycle`` returns them).  A sample with rmse64 < tol is not written and has k_used 0."""
-        b, restart = x.shape[0], int(restart)
-        for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError(f"gmres_refine_cycle: {name} requires grad; the GMRES cycle is not differentiable")
-        self._chk(x, (b, 2, self.n, self.n), "x", torch.float64)
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(rhs, (rhs.shape[0], 2, self.n, self.n), "rhs")
-        new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
-        basis = new(b, restart + 1, 2 * self.n * self.n) if basis is None else basis
-        hess = new(b, restart + 1, restart, 2) if hess is None else hess
-        self._chk(basis, (b, restart + 1, 2 * self.n * self.n), "basis")
-        self._chk(hess, (b, restart + 1, restart, 2), "hess")
-        rmse = new(restart + 1, b)
-        k_used = torch.empty(b, device=self.device, dtype=torch.int32)
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("gmres_refine_cycle", x, torch.float64, k_sq, rhs, restart, basis, hess)
         rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
         rc = self.lib.hn_gmres_refine_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor),
                                             _ptr(basis), _ptr(hess), _ptr(rmse), _ptr(k_used), _ptr(rmse64), self._stream())
@@ -358,23 +356,7 @@ class Engine:
 
     def step64(self, wf, res, states, k_sq, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
         """n_iter solver iterations in float64; wf, res, states updated in place (``step`` with every tensor float64)."""
-        b, f64 = wf.shape[0], torch.float64
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield", f64)
-        self._chk(res, (b, 2, self.n, self.n), "residual", f64)
-        self._chk(states, (b, 2, self.state_len), "hidden state", f64)
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq", f64)
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source", f64)
-        if res_hist is not None:
-            self._chk(res_hist, (n_iter, b, 2, self.n, self.n), "res_hist", f64)
-        if wf_hist is not None:
-            self._chk(wf_hist, (n_iter, b, 2, self.n, self.n), "wf_hist", f64)
-        if st_hist is not None:
-            self._chk(st_hist, (n_iter, b, 2, self.state_len), "st_hist", f64)
-        if rmse_hist is not None:
-            self._chk(rmse_hist, (n_iter, b), "rmse_hist", f64)
-        rc = self.lib.hn_step_f64(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), src.shape[0], b,
-                                  int(n_iter), _ptr(res_hist), _ptr(wf_hist), _ptr(st_hist), _ptr(rmse_hist), self._stream())
-        _lib.check(rc, self.ctx, "hn_step_f64")
+        self._step(self.lib.hn_step_f64, "hn_step_f64", torch.float64, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
 
     def unet(self, in6: torch.Tensor, states_in: torch.Tensor):
         b = in6.shape[0]
@@ -434,25 +416,29 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_out_conv")
         return out
 
+    def _step(self, entry, name: str, dtype, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist):
+        """``step`` / ``step64``: the checks and the one library call, for tensors of ``dtype``."""
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, self.n, self.n), "wavefield", dtype)
+        self._chk(res, (b, 2, self.n, self.n), "residual", dtype)
+        self._chk(states, (b, 2, self.state_len), "hidden state", dtype)
+        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq", dtype)
+        self._chk(src, (src.shape[0], 2, self.n, self.n), "source", dtype)
+        if res_hist is not None:
+            self._chk(res_hist, (n_iter, b, 2, self.n, self.n), "res_hist", dtype)
+        if wf_hist is not None:
+            self._chk(wf_hist, (n_iter, b, 2, self.n, self.n), "wf_hist", dtype)
+        if st_hist is not None:
+            self._chk(st_hist, (n_iter, b, 2, self.state_len), "st_hist", dtype)
+        if rmse_hist is not None:
+            self._chk(rmse_hist, (n_iter, b), "rmse_hist", dtype)
+        rc = entry(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), src.shape[0], b,
+                   int(n_iter), _ptr(res_hist), _ptr(wf_hist), _ptr(st_hist), _ptr(rmse_hist), self._stream())
+        _lib.check(rc, self.ctx, name)
+
     def step(self, wf, res, states, k_sq, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
         """n_iter solver iterations; wf, res, states updated in place."""
-        b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield")
-        self._chk(res, (b, 2, self.n, self.n), "residual")
-        self._chk(states, (b, 2, self.state_len), "hidden state")
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source")
-        if res_hist is not None:
-            self._chk(res_hist, (n_iter, b, 2, self.n, self.n), "res_hist")
-        if wf_hist is not None:
-            self._chk(wf_hist, (n_iter, b, 2, self.n, self.n), "wf_hist")
-        if st_hist is not None:
-            self._chk(st_hist, (n_iter, b, 2, self.state_len), "st_hist")
-        if rmse_hist is not None:
-            self._chk(rmse_hist, (n_iter, b), "rmse_hist")
-        rc = self.lib.hn_step(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), src.shape[0], b,
-                              int(n_iter), _ptr(res_hist), _ptr(wf_hist), _ptr(st_hist), _ptr(rmse_hist), self._stream())
-        _lib.check(rc, self.ctx, "hn_step")
+        self._step(self.lib.hn_step, "hn_step", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
 
     # ---- training step (hn_train_grad / hn_adam_step; SURVEY.md 8 f4) -------------------------------------------------
     def train_reserve(self, batch: int, n_unroll: int):

@@ -15,6 +15,8 @@ from typing import Optional
 import numpy as np
 import torch
 
+from .engine import _require_no_grad
+
 
 def _hessenberg_least_squares(H: np.ndarray, beta: np.ndarray):
     """Progressive Givens QR of the [B, m + 1, m] Hessenberg matrices (complex128, on the host: a few kilobytes once per restart
@@ -110,21 +112,25 @@ def drive_refinement(cycle, max_cycles: int, tol: float) -> dict:
             "cycles": cycles, "converged": converged}
 
 
+def _hip_setup(solver, sos_maps, restart, x0, dtype):
+    """What both HIP drivers start from: (engine, k_sq, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess)."""
+    _require_no_grad("gmres(backend='hip')", sos_maps, x0)
+    eng = solver.engine()
+    sos_maps = sos_maps.float().contiguous()
+    k_sq, wf0 = solver.get_initials(sos_maps)
+    rhs = solver.source.detach().float().contiguous()
+    bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
+    x = (wf0 if x0 is None else x0.detach()).to(rhs.device, dtype).contiguous().clone()
+    basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=rhs.device)
+    hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=rhs.device)
+    return eng, k_sq.contiguous(), rhs, x, basis, hess
+
+
 def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor):
     """``gmres(backend="hip", refine=True)``: iterative refinement with the fp32 restart cycle as the inner solver (hn_gmres_refine_cycle).  The
     iterate, its true residual and the update are float64; one host synchronisation per cycle."""
-    for t in (sos_maps, x0):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise RuntimeError("gmres(backend='hip') runs without gradients: pass detached tensors")
-    eng = solver.engine()
-    sos_maps = sos_maps.float().contiguous()
-    k_sq = solver.get_initials(sos_maps)[0].contiguous()
-    rhs = solver.source.detach().float().contiguous()
-    bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
-    dev = rhs.device
-    x = torch.zeros(bsz, 2, n, n, dtype=torch.float64, device=dev) if x0 is None else x0.detach().to(dev).double().contiguous().clone()
-    basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=dev)
-    hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
+    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float64)
+    bsz, dev = x.shape[0], x.device
 
     def cycle():
         rmse64, rmse, k_used = eng.gmres_refine_cycle(x, k_sq, rhs, restart, tol, inner_floor, basis, hess)
@@ -143,19 +149,8 @@ def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor):
 
 def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0):
     """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own."""
-    for t in (sos_maps, x0):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise RuntimeError("gmres(backend='hip') runs without gradients: pass detached tensors")
-    eng = solver.engine()
-    sos_maps = sos_maps.float().contiguous()
-    k_sq, wf0 = solver.get_initials(sos_maps)
-    k_sq = k_sq.contiguous()
-    rhs = solver.source.detach().float().contiguous()
-    bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
-    dev = rhs.device
-    x = (wf0 if x0 is None else x0.detach().float()).contiguous().clone()
-    basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=dev)
-    hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
+    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32)
+    bsz, dev = x.shape[0], x.device
 
     def cycle():
         rmse, k_used = eng.gmres_cycle(x, k_sq, rhs, restart, tol, basis, hess)

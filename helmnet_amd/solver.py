@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .checkpoint import AttributeDict, read_lightning_checkpoint
-from .engine import Engine
+from .engine import Engine, _require_no_grad
 from .laplacian import FastLaplacianWithPML
 from .source import SourceModule
 from .unet import HybridNet
@@ -355,9 +355,7 @@ class IterativeSolver(nn.Module):
         return self._residual64(wavefield, k_sq, True, False)[0]
 
     def _residual64(self, wavefield, k_sq, want_res: bool, want_rmse: bool):
-        for t in (wavefield, k_sq):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError("the float64 residual check runs without gradients: pass detached tensors")
+        _require_no_grad("the float64 residual check", wavefield, k_sq)
         return self.engine().residual64(wavefield.double().contiguous(), k_sq.double().contiguous(), self.source.detach().double().contiguous(),
                                         want_res, want_rmse)
 
@@ -367,9 +365,7 @@ class IterativeSolver(nn.Module):
         ``evaluator_error`` = RMSE of (fp32 residual - float64 residual), the floor below which an fp32 residual norm carries no information."""
         if (sos_maps is None) == (k_sq is None):
             raise ValueError("pass exactly one of sos_maps and k_sq")
-        for t in (wavefield, sos_maps, k_sq):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError("verify runs without gradients: pass detached tensors")
+        _require_no_grad("verify", wavefield, sos_maps, k_sq)
         if k_sq is None:
             k_sq = self.get_initials(sos_maps.float().contiguous())[0]
         eng = self.engine()
@@ -401,14 +397,15 @@ class IterativeSolver(nn.Module):
         return (wf, res) if get_residual else wf
 
     # ------------------------------------------------------------------ loops ------------
-    def _run(self, wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals: str):
+    def _loop(self, wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals: str):
+        """K iterations on wf / res / st, updated in place -- Engine.step for fp32 tensors, Engine.step64 for float64 ones -- with the histories asked
+        for, in wf's dtype; the result dictionary of ``forward``."""
         eng = self.engine()
         b, n, K = wf.shape[0], wf.shape[-1], int(num_iterations)
-        dev = wf.device
 
         def hist(shape, what):
             try:
-                return torch.empty(shape, device=dev, dtype=torch.float32)
+                return torch.empty(shape, device=wf.device, dtype=wf.dtype)
             except RuntimeError as e:  # out of memory
                 raise RuntimeError(
                     f"cannot keep {what} for {K} iterations ({shape}); pass residuals='norms' or 'last' "
@@ -418,12 +415,12 @@ class IterativeSolver(nn.Module):
         res_hist = hist((K, b, 2, n, n), "every residual") if residuals == "all" and K > 0 else None
         wf_hist = hist((K, b, 2, n, n), "every wavefield") if return_wavefields and K > 0 else None
         st_hist = hist((K, b, 2, eng.state_len), "every hidden state") if return_states and K > 0 else None
-        rmse = torch.empty((K, b), device=dev, dtype=torch.float32) if K > 0 else None
+        rmse = torch.empty((K, b), device=wf.device, dtype=wf.dtype) if K > 0 else None
         if K > 0:
             keep = self.f.to_engine_states(st)      # levels without state: zeros in, the caller's values back out
-            eng.step(wf, res, st, k_sq, self._src(), K, res_hist, wf_hist, st_hist, rmse)
+            step = eng.step64 if wf.dtype == torch.float64 else eng.step
+            step(wf, res, st, k_sq, src, K, res_hist, wf_hist, st_hist, rmse)
             self.f.from_engine_states(keep, st, st_hist)
-        self.f.adopt_states(st)
         out = {
             "wavefields": list(wf_hist.unbind(0)) if wf_hist is not None else [wf],
             "residuals": list(res_hist.unbind(0)) if res_hist is not None else ([res] if residuals == "last" else []),
@@ -432,8 +429,12 @@ class IterativeSolver(nn.Module):
             "residual_norms": rmse,  # [K, B] per-sample RMSE (extension; the reference derives it afterwards)
         }
         if residuals == "norms":
-            out["residuals"] = []
             out["last_residual"] = res
+        return out
+
+    def _run(self, wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals: str):
+        out = self._loop(wf, res, st, k_sq, self._src(), num_iterations, return_wavefields, return_states, residuals)
+        self.f.adopt_states(st)
         return out
 
     def forward(self, sos_maps, return_wavefields=False, return_states=False, num_iterations=None,
@@ -483,37 +484,11 @@ class IterativeSolver(nn.Module):
             raise ValueError(f"source must be a float64 [1 or {batch}, 2, {n}, {n}] tensor, got {source.dtype} {tuple(source.shape)}")
         return source.detach().to(self.device).contiguous()
 
-    @staticmethod
-    def _no_grad64(what: str, *tensors):
-        for t in tensors:
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError(f"{what} runs without gradients: pass detached tensors (the differentiable path is forward())")
-
     def _run64(self, wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals: str):
         """``_run`` on hn_step_f64: wf / res / st (float64, owned by the caller of this helper) are updated in place; nothing held in f is touched."""
         if residuals not in ("all", "norms", "last"):
             raise ValueError("residuals must be 'all', 'norms' or 'last'")
-        eng = self.engine()
-        b, n, K = wf.shape[0], wf.shape[-1], int(num_iterations)
-        new = lambda *shape: torch.empty(shape, device=wf.device, dtype=torch.float64)  # noqa: E731
-        res_hist = new(K, b, 2, n, n) if residuals == "all" and K > 0 else None
-        wf_hist = new(K, b, 2, n, n) if return_wavefields and K > 0 else None
-        st_hist = new(K, b, 2, eng.state_len) if return_states and K > 0 else None
-        rmse = new(K, b) if K > 0 else None
-        if K > 0:
-            keep = self.f.to_engine_states(st)      # levels without state: zeros in, the caller's values back out (as _run does for the fp32 states)
-            eng.step64(wf, res, st, k_sq, src, K, res_hist, wf_hist, st_hist, rmse)
-            self.f.from_engine_states(keep, st, st_hist)
-        out = {
-            "wavefields": list(wf_hist.unbind(0)) if wf_hist is not None else [wf],
-            "residuals": list(res_hist.unbind(0)) if res_hist is not None else ([res] if residuals == "last" else []),
-            "states": list(st_hist.unbind(0)) if st_hist is not None else [],
-            "last_iteration": K - 1,
-            "residual_norms": rmse,
-        }
-        if residuals == "norms":
-            out["last_residual"] = res
-        return out
+        return self._loop(wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals)
 
     def _initials64(self, sos_maps, source):
         """(wf = 0, residual, zero flat states, k_sq, source), all float64: get_initials on a float64 input (hybridnet.py:522-538) and cleared states."""
@@ -530,7 +505,7 @@ class IterativeSolver(nn.Module):
         fp16 / bf16 modes are measured against.  Same keys as ``forward``, float64 tensors.  The weights are the solver's fp32 parameters up-cast;
         ``source`` None uses ``self.source.double()``, a float64 [1 or B,2,n,n] map overrides it (a source map BUILT in float64 differs from the
         up-cast fp32 one by ~1e-6).  No gradients; the (fp32) hidden states held in ``f`` are neither read nor written.  A reference, not a fast path."""
-        self._no_grad64("forward64", sos_maps, source)
+        _require_no_grad("forward64", sos_maps, source)
         if num_iterations is None:
             num_iterations = self.hparams.max_iterations
         wf, res, st, k_sq, src = self._initials64(sos_maps, source)
@@ -540,7 +515,7 @@ class IterativeSolver(nn.Module):
                   residuals: str = "all", source=None):
         """``n_steps`` in float64, continuing from given tensors; the hidden states are passed in (flat [B,2,L]) instead of living in ``f`` and come back
         as ``out["final_states"]``.  Inputs are up-cast if need be and not modified."""
-        self._no_grad64("n_steps64", wavefield, k_sq, residual, states, source)
+        _require_no_grad("n_steps64", wavefield, k_sq, residual, states, source)
         self.engine()
         wf, res, st, kq = (t.detach().to(self.device).double().clone().contiguous() for t in (wavefield, residual, states, k_sq))
         out = self._run64(wf, res, st, kq, self._source64(source, wf.shape[0]), num_iterations, return_wavefields, return_states, residuals)
@@ -551,7 +526,7 @@ class IterativeSolver(nn.Module):
         """How far this solver's current precision mode is from the float64 trajectory on the caller's own maps: ``forward`` and ``forward64`` side by
         side, compared at every iteration count in ``checkpoints``.  Returns ``iterations`` (the sorted checkpoints), ``linf`` [len(checkpoints), B]
         (per-sample max |wavefield - float64 wavefield|), and the residual-norm traces ``rmse32`` / ``rmse64`` [num_iterations, B]."""
-        self._no_grad64("deviation_from_float64", sos_maps)
+        _require_no_grad("deviation_from_float64", sos_maps)
         cps = sorted({int(c) for c in checkpoints} | {int(num_iterations)})
         if cps[0] < 1 or cps[-1] > int(num_iterations):
             raise ValueError(f"checkpoints must lie in [1, {int(num_iterations)}]")
@@ -626,9 +601,7 @@ class IterativeSolver(nn.Module):
         sample ``linf`` (max |wavefield - reference| over both planes) and ``rms`` of the same difference, ``reference_rmse64`` (the float64
         residual RMSE of the reference: how good the ground truth is; below ``tol`` when ``converged``), ``reference`` (the float64 wavefield),
         ``converged`` and ``cycles``.  ``wavefield`` is not written."""
-        for t in (wavefield, sos_maps):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError("reference_error runs without gradients: pass detached tensors")
+        _require_no_grad("reference_error", wavefield, sos_maps)
         out = self.gmres64(sos_maps, restart=restart, max_cycles=max_cycles, tol=tol, x0=wavefield)
         ref = out["wavefield"]
         diff = wavefield.detach().to(ref.device).double() - ref
@@ -662,9 +635,7 @@ class IterativeSolver(nn.Module):
         from .stream_schedule import StreamScheduler
         if max_iterations is None:
             max_iterations = self.hparams.max_iterations
-        for t in (sos_maps, source_maps):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError("solve_many runs without gradients: pass detached tensors (the differentiable path is forward())")
+        _require_no_grad("solve_many", sos_maps, source_maps)
         if not (float(tol) == float(tol)):
             raise ValueError("tol is NaN")
         with torch.no_grad():

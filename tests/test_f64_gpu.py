@@ -149,6 +149,8 @@ def test_argument_and_state_errors(eng):
     assert lib.hn_residual_f64(eng.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), 1, None, None, 1, stream) == -1      # both NULL
     assert lib.hn_residual_f64(eng.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), 1, _ptr(wf), _ptr(rmse), 1, stream) == -1   # wf aliases res
     assert lib.hn_laplacian_f64(eng.ctx, _ptr(wf), _ptr(wf), 1, stream) == -1
+    both = torch.zeros(2 * wf.numel(), device=DEV, dtype=torch.float64)
+    assert lib.hn_laplacian_f64(eng.ctx, _ptr(both[: wf.numel()]), _ptr(both[wf.numel() // 2:]), 1, stream) == -1   # out overlaps half of wf
     assert lib.hn_residual_f64(eng.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), 2, _ptr(out), None, 1, stream) == -1   # src_batch neither 1 nor B
     assert lib.hn_residual_f64(eng.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), 1, _ptr(out), _ptr(rmse), 1, stream) == 0
     with pytest.raises(ValueError):

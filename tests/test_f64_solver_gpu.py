@@ -244,6 +244,9 @@ def test_step_argument_and_state_errors(eng, weights):
     assert call(res_hist=hist, wf_=hist[1]) == -1                      # wf is a slot of the residual history
     assert call(sb=3) == -1                                            # src_batch neither 1 nor B
     assert lib.hn_unet_f64(eng.ctx, _ptr(both), _ptr(st), _ptr(st), _ptr(wf), b, stream) == -1       # states_in is states_out
+    assert "states_in overlaps states_out" in lib.hn_last_error(eng.ctx).decode()
+    in6 = torch.zeros(b, 6, n, n, device=DEV, dtype=torch.float64)
+    assert lib.hn_unet_f64(eng.ctx, _ptr(in6), _ptr(in6.view(-1)[: st.numel()]), _ptr(torch.empty_like(st)), _ptr(torch.empty_like(wf)), b, stream) == 0   # read against read
     assert call() == 0
     with pytest.raises(TypeError):
         eng.step64(wf.float(), res, st, k_sq, src, 1)
@@ -294,6 +297,71 @@ def test_step_is_capturable_once_its_buffers_exist(eng, weights):
     assert torch.equal(wf, want_wf) and torch.equal(res, want_res) and torch.equal(st, want_st)
     assert torch.equal(wf_hist[-1], want_wf) and _rel(wf_hist[0], c["wf"][0]) <= BAR_STEP
     assert float(((rmse.cpu() - torch.stack(c["rmse"][:3])).abs() / torch.stack(c["rmse"][:3])).max()) <= BAR_STEP
+
+
+def _first_sample(c):
+    """The batch-1 problem that is sample 0 of a step_case with one source."""
+    return {k: c[k][:1].contiguous() for k in ("wf0", "res0", "st0", "k_sq", "src")}
+
+
+def _same_run(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a[:3], b[:3])) and all(torch.equal(a[3][k], b[3][k]) for k in a[3])
+
+
+# n = 16: one (partial) 32 x 32 tile of the residual per sample; 48: four, three of them partial
+@pytest.mark.parametrize("n", [16, 48])
+def test_step_workspace_grown_then_reused_by_a_smaller_batch(eng, weights, n):
+    """Batch 1, 2, 1 on one context: the workspace, the second state buffer and the partial sums are built for one sample, grown for two, and the
+    batch-1 call in buffers sized for two gives the bits of the call that built them -- as does a rebuild after hn_set_domain has freed everything."""
+    c2 = step_case(weights, n, 2, 1)
+    c1 = _first_sample(c2)
+    eng.set_domain(16, PML, SIGMA_MAX, K)
+    eng.set_domain(n, PML, SIGMA_MAX, K)                               # a fresh domain: no float64 weights, workspace or tables yet
+    first = _run_step(eng, c1, 1, n_iter=2)
+    big = _run_step(eng, c2, 2, n_iter=2)
+    last = _run_step(eng, c1, 1, n_iter=2)
+    assert bool(torch.isfinite(first[3]["rmse_hist"]).all()) and _same_run(first, last)
+    assert all(torch.equal(x[:1], y) for x, y in zip(big[:3], first[:3])) and torch.equal(big[3]["rmse_hist"][:, :1], first[3]["rmse_hist"])
+    eng.set_domain(16, PML, SIGMA_MAX, K)
+    eng.set_domain(n, PML, SIGMA_MAX, K)                               # frees and rebuilds
+    assert _same_run(first, _run_step(eng, c1, 1, n_iter=2))
+
+
+def test_captured_step_needs_the_partial_sums_only_with_an_rmse_history(eng, weights):
+    """The float64 weights, a workspace for two samples and the float64 tables exist, the partial sums are sized for ONE sample: a captured batch-2
+    call without an RMSE history has nothing to build and replays to the eager bits, one with an RMSE history is refused before it enqueues anything."""
+    n, b = 48, 2
+    c2 = step_case(weights, n, b, 1)
+    eng.set_domain(16, PML, SIGMA_MAX, K)
+    eng.set_domain(n, PML, SIGMA_MAX, K)
+    _run_step(eng, _first_sample(c2), 1, n_iter=1)                     # eager, batch 1, with an RMSE history: partial sums for one sample
+    want_wf, want_res, want_st, _ = _run_step(eng, c2, b, n_iter=3, hist=False)   # eager, batch 2, no RMSE: grows the workspace, not the partial sums
+    k_sq, src = c2["k_sq"].to(DEV), c2["src"].to(DEV)
+    wf, res, st = c2["wf0"].to(DEV).clone(), c2["res0"].to(DEV).clone(), c2["st0"].to(DEV).clone()
+    rmse = torch.full((3, b), -7.0, device=DEV, dtype=torch.float64)
+    probe = torch.zeros(4, device=DEV)
+
+    def call(rmse_hist):
+        return eng.lib.hn_step_f64(eng.ctx, _ptr(wf), _ptr(res), _ptr(st), _ptr(k_sq), _ptr(src), 1, b, 3, None, None, None, _ptr(rmse_hist), eng._stream())
+
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            probe.add_(1.0)
+            rc = call(rmse)
+        assert rc == -2 and "capture" in eng.lib.hn_last_error(eng.ctx).decode()
+        graph.replay()                                                 # the capture ended in order and holds nothing of the library's
+        torch.cuda.synchronize()
+        assert probe.tolist() == [1.0] * 4 and torch.equal(wf, c2["wf0"].to(DEV)) and bool((rmse == -7.0).all())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            rc = call(None)
+        assert rc == 0
+        graph.replay()
+        torch.cuda.synchronize()
+    assert torch.equal(wf, want_wf) and torch.equal(res, want_res) and torch.equal(st, want_st)
 
 
 # ---------------------------------------------------------------------------------------------- 4: the reference's own float64 trajectory

@@ -247,6 +247,39 @@ def test_determinism_and_batch_independence(n):
     assert torch.equal(a["rmse"][:, 1], solo["rmse"][:, 0])
 
 
+def _fresh_engine(key):
+    from helmnet_amd.engine import Engine
+    eng = Engine(torch.device(DEV))
+    eng.set_domain(16, *key[1:])
+    eng.set_domain(*key)                           # a fresh domain: no GMRES workspace yet
+    return eng
+
+
+def test_workspace_grown_then_reused_by_a_smaller_call():
+    """Small, large, small again on one context: the workspace is built for (1, 3), grown to (3, 6), then to (3, 9) -- the batch shrinks, the restart
+    grows: each keeps its own maximum -- and a (1, 3) call in a workspace sized for more gives the bits of the (1, 3) call that built it.
+    n = 48: three 1024-pixel chunks per sample, the last one partial, so the strides of the partial-sum table matter."""
+    n = 48
+    s, k_sq, rhs = _problem(n, 3)
+    eng, other = _fresh_engine(s.engine().domain_key), _fresh_engine(s.engine().domain_key)
+    one, two = k_sq[:1].contiguous(), k_sq[:2].contiguous()
+    first = _cycle(eng, one, rhs, 3, 0.0)
+    big = _cycle(eng, k_sq, rhs, 6, 0.0)
+    mid = _cycle(eng, two, rhs, 9, 0.0)
+    last = _cycle(eng, one, rhs, 3, 0.0)
+    assert first["k_used"].tolist() == [3] and big["k_used"].tolist() == [6] * 3 and mid["k_used"].tolist() == [9] * 2
+    for key in ("x", "basis", "hess", "rmse", "k_used"):
+        assert torch.equal(first[key], last[key]), key
+    solo = _cycle(other, one, rhs, 6, 0.0)         # a context that has only ever seen this call
+    for key in ("x", "basis", "hess", "k_used"):
+        assert torch.equal(big[key][0], solo[key][0]), key
+    assert torch.equal(big["rmse"][:, 0], solo["rmse"][:, 0])
+    for e in (eng, other):
+        torch.cuda.synchronize()
+        e.check_async_errors()
+        e.close()
+
+
 # ---------------------------------------------------------------------------------------------- 5
 def test_per_sample_stop_sample_below_tol_is_untouched():
     from helmnet_amd.gmres import gmres
@@ -351,6 +384,7 @@ def test_argument_refusals():
     err = lambda: eng.lib.hn_last_error(eng.ctx).decode()  # noqa: E731
     assert _raw(eng, x, k_sq, rhs, 1, 3, 4, 0.0, x, hess, rmse, k_used) == -1 and "overlaps" in err()
     assert _raw(eng, x, k_sq, rhs, 1, 3, 4, 0.0, x.data_ptr() + 16, hess, rmse, k_used) == -1 and "overlaps" in err()
+    assert _raw(eng, x, k_sq, k_sq, 1, 3, 4, 0.0, basis, hess, rmse, k_used) == -1 and "k_sq overlaps rhs" in err()      # read against read
     assert _raw(eng, x, k_sq, rhs, 1, 3, 0, 0.0, basis, hess, rmse, k_used) == -1 and "restart" in err()
     assert _raw(eng, x, k_sq, rhs, 1, 3, 65, 0.0, basis, hess, rmse, k_used) == -1 and "restart" in err()
     assert _raw(eng, x, k_sq, rhs, 2, 3, 4, 0.0, basis, hess, rmse, k_used) == -1 and "rhs batch" in err()

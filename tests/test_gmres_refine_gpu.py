@@ -220,6 +220,38 @@ def test_reproducible_and_broadcast_source_equals_explicit_copies(n):
         assert torch.equal(a[key][1], solo[key][0]), key
 
 
+def _fresh_engine(key):
+    from helmnet_amd.engine import Engine
+    eng = Engine(torch.device(DEV))
+    eng.set_domain(16, *key[1:])
+    eng.set_domain(*key)                           # a fresh domain: no workspace, no float64 tables yet
+    return eng
+
+
+def test_workspaces_grown_then_reused_by_a_smaller_call():
+    """Small, large, small again on one context (the cycle's workspace, the refinement's and the float64 partial sums all grow on the way): a
+    (1, 3) call in workspaces sized for (3, 9) gives the bits of the (1, 3) call that built them.  n = 48: three chunks per sample, the last partial."""
+    n = 48
+    s, _, k_sq, rhs = _problem(n, 3)
+    eng, other = _fresh_engine(s.engine().domain_key), _fresh_engine(s.engine().domain_key)
+    one, two = k_sq[:1].contiguous(), k_sq[:2].contiguous()
+    first = _refine(eng, one, rhs, 3, 0.0, 0.0)
+    big = _refine(eng, k_sq, rhs, 6, 0.0, 0.0)
+    mid = _refine(eng, two, rhs, 9, 0.0, 0.0)
+    last = _refine(eng, one, rhs, 3, 0.0, 0.0)
+    assert first["k_used"].tolist() == [3] and big["k_used"].tolist() == [6] * 3 and mid["k_used"].tolist() == [9] * 2
+    for key in _KEYS:
+        assert torch.equal(first[key], last[key]), key
+    solo = _refine(other, one, rhs, 6, 0.0, 0.0)   # a context that has only ever seen this call
+    for key in ("x", "basis", "hess", "k_used", "rmse64"):
+        assert torch.equal(big[key][0], solo[key][0]), key
+    assert torch.equal(big["rmse"][:, 0], solo["rmse"][:, 0])
+    for e in (eng, other):
+        torch.cuda.synchronize()
+        e.check_async_errors()
+        e.close()
+
+
 # ---------------------------------------------------------------------------------------------- 5
 @pytest.mark.parametrize("tol", [0.0, 1e-12])
 def test_zero_right_hand_side_with_zero_iterate(tol):
@@ -256,6 +288,7 @@ def test_argument_refusals():
     assert _raw(eng, x, k_sq, rhs, 1, 3, 65, 0.0, 0.0, basis, hess, rmse, k_used, rmse64) == -1 and "restart" in err()
     assert _raw(eng, x, k_sq, rhs, 2, 3, 4, 0.0, 0.0, basis, hess, rmse, k_used, rmse64) == -1 and "rhs batch" in err()
     assert _raw(eng, x, k_sq, rhs, 1, 3, 4, 0.0, 0.0, x, hess, rmse, k_used, rmse64) == -1 and "overlaps" in err()
+    assert _raw(eng, x, k_sq, k_sq, 1, 3, 4, 0.0, 0.0, basis, hess, rmse, k_used, rmse64) == -1 and "k_sq overlaps rhs" in err()   # read against read
     assert _raw(eng, x, k_sq, rhs, 1, 3, 4, 0.0, 0.0, basis, hess, rmse, k_used, x.data_ptr() + 64) == -1 and "overlaps" in err()
     assert _raw(eng, x.data_ptr() + 8, k_sq, rhs, 1, 2, 4, 0.0, 0.0, basis, hess, rmse, k_used, rmse64) == -1 and "aligned" in err()
     assert _raw(eng, x, k_sq, rhs, 1, 3, 4, float("nan"), 0.0, basis, hess, rmse, k_used, rmse64) == -1 and "tol" in err()
