@@ -458,6 +458,7 @@ int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int feature
     HN_HIP(ctx, hipDeviceSynchronize());  // nothing may still read the old weights
     clear_step_graphs(ctx);
     unet_f64_free(ctx);
+    precond_free(ctx);
     ctx->raw_blob.assign(blob, blob + L.total);
     (void)hipFree(ctx->wdev);
     ctx->wdev = nullptr;

@@ -211,6 +211,7 @@ struct AxisHost {
 AxisHost spec_axis_host(int n, int pml, double sigma_max, double k);
 struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-squares problem, two dense fields for the operator
 struct RefineWs;  // GMRES refinement step (hn_krylov.hip): float64 copies of k_sq and rhs, the float64 residual, the fp32 scaled right-hand side and correction
+struct PrecondWs; // flexible GMRES cycle (hn_krylov.hip): the learned preconditioner's source, wavefield, residual and hidden states
 struct F64Unet;   // float64 solver loop (hn_unet_f64.hip): the up-cast weights, the activation workspace and the second flat-state buffer
 // First columns of the circulant spectral derivative operators in float64: D1[j][m] = g1[(j - m) mod n], D2[j][m] = g2[(j - m) mod n] with
 // g1[d] = (1/n) sum_p i k1_p exp(2 pi i p d / n), g2 likewise from k2.  g2 is real; g1 is real but for the Nyquist term i k1[n/2] (-1)^d / n.
@@ -230,6 +231,7 @@ struct hn_ctx {
     hn::F64Unet* f64 = nullptr;    // built / grown by the first hn_unet_f64 / hn_step_f64 that needs it; freed by hn_load_weights, hn_set_domain, hn_destroy
     hn::KrylovWs* kry = nullptr;   // built / grown by the first hn_gmres_cycle that needs it; freed by hn_set_domain, hn_destroy
     hn::RefineWs* rfn = nullptr;   // built / grown by the first hn_gmres_refine_cycle that needs it; freed with kry (krylov_free)
+    hn::PrecondWs* pcw = nullptr;  // built / grown by the first hn_fgmres_cycle with precond_iters > 0; freed with kry and by hn_load_weights (precond_free)
     hn::DcLayer inc{}, sig[hn::kMaxDepth]{}, st[hn::kMaxDepth]{}, dec[hn::kMaxDepth + 1]{};   // (their pointers lead into wdev and fragdev)
     hn::K8Layer down[hn::kMaxDepth]{}, up[hn::kMaxDepth]{};
     float* fragdev = nullptr;   // every re-packing of the weights beyond wdev: the layers' fragments and what follows here
@@ -517,6 +519,7 @@ struct MemRange { const void* p; size_t bytes; bool written; const char* name; }
 bool first_overlap(const MemRange* r, int count, const char** a_name, const char** b_name);
 void unet_f64_free(hn_ctx* ctx);   // hn_unet_f64.hip (the caller has synchronised the device)
 void krylov_free(hn_ctx* ctx);     // hn_krylov.hip: the cycle's and the refinement's workspaces (the caller has synchronised the device)
+void precond_free(hn_ctx* ctx);    // hn_krylov.hip: the learned preconditioner's workspace alone (its hidden states follow the network's depth)
 void train_free(hn_ctx* ctx);   // hn_train.hip
 int stream_table_reserve(hn_ctx* ctx, int slots);   // hn_stream.hip: the verdict table holds at least `slots` records (growing it synchronises the device)
 void stream_table_free(hn_ctx* ctx);

@@ -16,6 +16,11 @@
 //
 // hn_gmres_refine_cycle (at the end of this file) wraps the same launches into one step of iterative refinement: the true residual (hn_f64.hip) and the
 // update in float64, the cycle in fp32 on the scaled correction equation A d = r / s.
+//
+// hn_fgmres_cycle / hn_fgmres_refine_cycle are the same launches as a FLEXIBLE cycle (Saad 1993), right-preconditioned by the learned iteration: per inner
+// step z_k = M(v_k) -- precond_iters iterations of hn_step on A z = alpha v_k from rest, z_k = wf / alpha --, w = A z_k, the orthogonalisation and the small
+// problem on V as before, the update x += sum y_j z_j over the caller's zbasis.  The preconditioner is a parameter of launch_cycle (Precond); without one
+// (zbasis nullptr) not one launch or argument of hn_gmres_cycle differs.  Three streaming kernels (k_seed, k_take, k_take_copy) move the vectors; none sums.
 #include "hn_internal.h"
 
 namespace hn {
@@ -50,6 +55,17 @@ struct RefineWs {
     float* d32 = nullptr;     // [B][2 n^2]  the cycle's iterate: the correction
     double* tol = nullptr;    // [B]  max(tol / s, inner_floor)
     int* stop = nullptr;      // [B]  rmse64 < tol (or a residual of exactly zero)
+};
+
+// what the learned preconditioner of hn_fgmres_cycle works on: one hn_step problem of `batch` samples
+struct PrecondWs {
+    int batch = 0, n = 0;
+    int64_t state_len = 0;
+    DeviceBlock block;        // one allocation; the pointers below lead into it
+    float* src = nullptr;     // [B][2 n^2]  alpha v_k
+    float* wf = nullptr;      // [B][2 n^2]  the learned iterate, from zero
+    float* res = nullptr;     // [B][2 n^2]  its residual, from 0 - src
+    float* states = nullptr;  // [B][2][state_len]  the hidden states, from zero
 };
 
 namespace {
@@ -301,14 +317,15 @@ __global__ __launch_bounds__(64) void k_small(SmallArgs a, int k) {
     if (lane == 0) { a.stopped[b] = 1; a.k_used[b] = m; }
 }
 
-// x += sum_{j < k_used} y_j v_j; a sample with k_used == 0 is not written
+// x += sum_{j < k_used} y_j v_j; a sample with k_used == 0 is not written.  `slots`: vectors per sample of `basis` (restart + 1; restart for the z_j of
+// the flexible cycle)
 __global__ __launch_bounds__(256) void k_update(float* __restrict__ x, const float* __restrict__ basis, const float* __restrict__ y,
-                                                const int32_t* __restrict__ k_used, long P, int restart) {
+                                                const int32_t* __restrict__ k_used, long P, int restart, int slots) {
     const int b = blockIdx.y;
     const int m = k_used[b];
     const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
     if (m <= 0 || off >= P) return;
-    const float* V = basis + (long)b * (restart + 1) * 2 * P;
+    const float* V = basis + (long)b * slots * 2 * P;
     const float* py = y + (long)b * restart * 2;
     float4 ar = make_float4(0.f, 0.f, 0.f, 0.f), ai = ar;
 #pragma unroll 2
@@ -325,6 +342,91 @@ __global__ __launch_bounds__(256) void k_update(float* __restrict__ x, const flo
     xi.x += ai.x; xi.y += ai.y; xi.z += ai.z; xi.w += ai.w;
     *reinterpret_cast<float4*>(px) = xr;
     *reinterpret_cast<float4*>(px + P) = xi;
+}
+
+// ---- the flexible cycle's vector traffic: a thread owns four consecutive pixels of both planes, a block 1024 pixels of a sample; nothing sums ----
+__device__ __forceinline__ float4 mul4(float4 v, float a) { return make_float4(a * v.x, a * v.y, a * v.z, a * v.w); }
+__device__ __forceinline__ float4 zero_minus4(float4 v) { return make_float4(0.f - v.x, 0.f - v.y, 0.f - v.z, 0.f - v.w); }
+__device__ __forceinline__ float4 div4(float4 v, float a) { return make_float4(v.x / a, v.y / a, v.z / a, v.w / a); }
+
+// the learned solve of A z = alpha v from rest: src = alpha v (one multiply), res = 0 - src, wf = 0; v is the dense operator input
+__global__ __launch_bounds__(256) void k_seed(const float* __restrict__ vin, float alpha, float* __restrict__ src, float* __restrict__ res,
+                                              float* __restrict__ wf, long P) {
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)blockIdx.y * 2 * P + off;
+    const float4 sr = mul4(*reinterpret_cast<const float4*>(vin + at), alpha), si = mul4(*reinterpret_cast<const float4*>(vin + at + P), alpha);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(src + at) = sr; *reinterpret_cast<float4*>(src + at + P) = si;
+    *reinterpret_cast<float4*>(res + at) = zero_minus4(sr); *reinterpret_cast<float4*>(res + at + P) = zero_minus4(si);
+    *reinterpret_cast<float4*>(wf + at) = z; *reinterpret_cast<float4*>(wf + at + P) = z;
+}
+
+// z = wf / alpha (a true division) into slot `slot` of the caller's zbasis [B][restart][2 P] and into the dense operator input
+__global__ __launch_bounds__(256) void k_take(const float* __restrict__ wf, float alpha, float* __restrict__ vin, float* __restrict__ zbasis, long P,
+                                              int slot, int restart) {
+    const int b = blockIdx.y;
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)b * 2 * P + off;
+    const float4 zr = div4(*reinterpret_cast<const float4*>(wf + at), alpha), zi = div4(*reinterpret_cast<const float4*>(wf + at + P), alpha);
+    float* pz = zbasis + ((long)b * restart + slot) * 2 * P + off;
+    *reinterpret_cast<float4*>(vin + at) = zr; *reinterpret_cast<float4*>(vin + at + P) = zi;
+    *reinterpret_cast<float4*>(pz) = zr; *reinterpret_cast<float4*>(pz + P) = zi;
+}
+
+// no preconditioner (precond_iters 0): z = v, copied exactly; the operator input holds it already
+__global__ __launch_bounds__(256) void k_take_copy(const float* __restrict__ vin, float* __restrict__ zbasis, long P, int slot, int restart) {
+    const int b = blockIdx.y;
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const float* pv = vin + (long)b * 2 * P + off;
+    float* pz = zbasis + ((long)b * restart + slot) * 2 * P + off;
+    *reinterpret_cast<float4*>(pz) = *reinterpret_cast<const float4*>(pv);
+    *reinterpret_cast<float4*>(pz + P) = *reinterpret_cast<const float4*>(pv + P);
+}
+
+// The preconditioner of a flexible cycle as launch_cycle takes it; zbasis nullptr: none, the cycle is plain GMRES
+struct Precond {
+    float* zbasis = nullptr;   // [B][restart][2 n^2], the caller's
+    int iters = 0;             // hn_step iterations per inner step; 0: z = v
+    float alpha = 1.f;         // the learned solve sees alpha v
+    const char* who = "";      // the entry point, for what hn_step reports from inside the cycle
+};
+
+// what hn_step reported, under the name of the entry point that called it
+int step_named(hn_ctx* ctx, const char* who, int rc) {
+    if (rc == HN_OK) return rc;
+    const std::string msg = ctx->err;
+    return fail(ctx, rc, "%s: hn_step: %s", who, msg.c_str());
+}
+
+void precond_ws_free(hn_ctx* ctx) {
+    if (ctx->pcw == nullptr) return;
+    ctx->pcw->block.free();
+    delete ctx->pcw;
+    ctx->pcw = nullptr;
+}
+
+// the learned preconditioner's problem for `batch` samples on the current domain and network -- the caller has refused stream capture
+int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, int batch, hipStream_t s) {
+    const int n = ctx->tab.n;
+    PrecondWs* ws = ctx->pcw;
+    if (ws == nullptr || ws->n != n || ws->state_len != ctx->state_len || batch > ws->batch) {
+        precond_ws_free(ctx);
+        ws = new (std::nothrow) PrecondWs();
+        if (!ws) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
+        ctx->pcw = ws;
+        const size_t F = (size_t)batch * 2 * n * n * 4;
+        const size_t sizes[] = {F, F, F, (size_t)batch * kState * (size_t)ctx->state_len * 4};
+        DeviceBlock& k = ws->block;
+        if (const int rc = k.alloc(ctx, who, sizes, 4); rc != HN_OK) { precond_ws_free(ctx); return rc; }
+        ws->src = (float*)k.take(); ws->wf = (float*)k.take(); ws->res = (float*)k.take(); ws->states = (float*)k.take();
+        ws->batch = batch; ws->n = n; ws->state_len = ctx->state_len;
+    }
+    // hn_step's own refusals (a domain the network's depth does not divide) and its workspace now, with nothing enqueued: the call of the cycle with
+    // zero iterations, which launches nothing
+    return step_named(ctx, who, hn_step(ctx, ws->wf, ws->res, ws->states, k_sq, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
 }
 
 void cycle_ws_free(hn_ctx* ctx) {
@@ -362,9 +464,10 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
 }
 
 // The restart cycle's launches, the workspace prepared.  tol_dev / pre_stopped: see SmallArgs (nullptr: hn_gmres_cycle, whose bits they leave alone --
-// the comparison est < tol is the same one on the same doubles); x, rhs and the outputs may lie in a workspace of the library's.
+// the comparison est < tol is the same one on the same doubles); x, rhs and the outputs may lie in a workspace of the library's.  pc: the flexible
+// cycle's preconditioner (its workspace prepared when pc.iters > 0); the operator input then holds z_k while A is applied and v_{k+1} after k_scale.
 int launch_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol, const double* tol_dev,
-                 const int* pre_stopped, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
+                 const int* pre_stopped, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
     const KrylovWs& ws = *ctx->kry;
     const long P = (long)ws.n * ws.n;
     int rc;
@@ -379,6 +482,16 @@ int launch_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int
     hipLaunchKernelGGL(k_small_init, dim3(batch), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, -1.f, ws.vin, basis, P, 0, restart);
     for (int k = 0; k < restart; ++k) {
+        if (pc.zbasis != nullptr && pc.iters > 0) {
+            const PrecondWs& p = *ctx->pcw;
+            hipLaunchKernelGGL(k_seed, grid, blk, 0, s, ws.vin, pc.alpha, p.src, p.res, p.wf, P);
+            if ((rc = zero_async(ctx, p.states, sizeof(float) * (size_t)batch * kState * (size_t)p.state_len, s)) != HN_OK) return rc;
+            rc = hn_step(ctx, p.wf, p.res, p.states, k_sq, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s);
+            if (rc != HN_OK) return step_named(ctx, pc.who, rc);
+            hipLaunchKernelGGL(k_take, grid, blk, 0, s, p.wf, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
+        } else if (pc.zbasis != nullptr) {
+            hipLaunchKernelGGL(k_take_copy, grid, blk, 0, s, ws.vin, pc.zbasis, P, k, restart);
+        }
         if ((rc = spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s)) != HN_OK) return rc;
         hipLaunchKernelGGL(k_dots, grid, blk, 0, s, ws.w, basis, ws.part, P, k, restart, nchunk);
         hipLaunchKernelGGL(k_sub<0>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
@@ -386,7 +499,8 @@ int launch_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int
         hipLaunchKernelGGL(k_small, dim3(batch), dim3(64), 0, s, a, k);
         hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, 1.f, ws.vin, basis, P, k + 1, restart);
     }
-    hipLaunchKernelGGL(k_update, grid, blk, 0, s, x, basis, ws.y, k_used, P, restart);
+    if (pc.zbasis != nullptr) hipLaunchKernelGGL(k_update, grid, blk, 0, s, x, pc.zbasis, ws.y, k_used, P, restart, restart);
+    else hipLaunchKernelGGL(k_update, grid, blk, 0, s, x, basis, ws.y, k_used, P, restart, restart + 1);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
 }
@@ -488,61 +602,56 @@ int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s) {
     return HN_OK;
 }
 
-// What hn_gmres_cycle (rmse64 NULL, x fp32) and hn_gmres_refine_cycle (x float64) refuse alike, under the entry point's name.  Any two arguments that
-// overlap are refused, read against read too (every range counts as written).  The two entry points report a missing domain with different codes, and
-// a caller may rely on either: a known wart.
-int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, const void* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart,
-                     const float* basis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64) {
-    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64)) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
-    if (ctx->tab.n == 0) return fail(ctx, refine ? HN_ERR_STATE : HN_ERR_ARG, "%s: hn_set_domain has not been called", who);
+// What the four cycle entry points refuse alike, under the entry point's name: x fp32 and rmse64 NULL for the plain cycles, x float64 for the refinements;
+// zbasis NULL for the two without a preconditioner, required for the flexible ones.  Any two arguments that overlap are refused, read against read too
+// (every range counts as written).  hn_gmres_cycle reports a missing domain with HN_ERR_ARG, the other three with HN_ERR_STATE, and a caller may rely on
+// either: a known wart.
+int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, const void* x, const float* k_sq, const float* rhs, int rhs_batch, int batch,
+                     int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64) {
+    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64) || (flexible && !zbasis))
+        return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (ctx->tab.n == 0) return fail(ctx, refine || flexible ? HN_ERR_STATE : HN_ERR_ARG, "%s: hn_set_domain has not been called", who);
     if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
     if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);
     if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: rhs batch %d must be 1 or equal to the batch %d", who, rhs_batch, batch);
     const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
     const MemRange r[] = {{x, B * 2 * P * (refine ? 8 : 4), true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
-                          {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"},
-                          {k_used, B * 4, true, "k_used"}, {rmse64, B * 8, true, "rmse64"}};
-    for (int i = 0; i < 4; ++i)   // the fields are read and written as float4 (x of the refinement: as double2)
+                          {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
+                          {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"},
+                          {rmse64, B * 8, true, "rmse64"}};
+    for (int i = 0; i < 5; ++i)   // the fields are read and written as float4 (x of the refinement: as double2); a NULL zbasis is aligned
         if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
     if (reinterpret_cast<uintptr_t>(rmse64) % 8 != 0) return fail(ctx, HN_ERR_ARG, "%s: rmse64 is not 8-byte aligned", who);
     const char *na, *nb;
-    if (first_overlap(r, 8, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    if (first_overlap(r, 9, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     return HN_OK;
 }
 
-}  // namespace
-
-void krylov_free(hn_ctx* ctx) {
-    cycle_ws_free(ctx);
-    refine_ws_free(ctx);
+// What the two flexible entry points refuse beyond check_cycle_args, and the preconditioner's workspace: nothing is enqueued before this has passed.
+// Not capturable: hn_step's first call on a new stream probes its side stream and synchronises.
+int check_precond(hn_ctx* ctx, const char* who, int precond_iters, float precond_scale, const float* k_sq, int batch, hipStream_t s) {
+    if (precond_iters < 0) return fail(ctx, HN_ERR_ARG, "%s: precond_iters must be >= 0 (got %d)", who, precond_iters);
+    if (!(precond_scale > 0.f) || !(precond_scale <= 3.402823466e38f))
+        return fail(ctx, HN_ERR_ARG, "%s: precond_scale must be finite and > 0 (got %g)", who, (double)precond_scale);
+    if (stream_capturing(s)) return fail(ctx, HN_ERR_STATE, "%s: not capturable (the preconditioner calls hn_step, whose first call on a stream synchronises)", who);
+    if (precond_iters == 0) return HN_OK;
+    if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "%s: hn_load_weights has not been called (precond_iters %d needs the network)", who, precond_iters);
+    return precond_prepare(ctx, who, k_sq, batch, s);
 }
 
-}  // namespace hn
-
-using namespace hn;
-
-extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
-                              float* basis, float* hess, float* rmse, int32_t* k_used, void* stream) {
-    int rc = check_cycle_args(ctx, "hn_gmres_cycle", false, x, k_sq, rhs, rhs_batch, batch, restart, basis, hess, rmse, k_used, nullptr);
-    if (rc != HN_OK) return rc;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = prepare(ctx, batch, restart, s)) != HN_OK) return rc;
-    return launch_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, basis, hess, rmse, k_used, s);
+// hn_gmres_cycle and hn_fgmres_cycle, the arguments checked
+int run_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol, const Precond& pc, float* basis,
+              float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
+    if (const int rc = prepare(ctx, batch, restart, s); rc != HN_OK) return rc;
+    return launch_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, pc, basis, hess, rmse, k_used, s);
 }
 
-extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
-                                     float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
-    const char* who = "hn_gmres_refine_cycle";
-    int rc = check_cycle_args(ctx, who, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, hess, rmse, k_used, rmse64);
-    if (rc != HN_OK) return rc;
-    if (!(tol >= 0.0)) return fail(ctx, HN_ERR_ARG, "%s: tol must be a number >= 0 (got %g)", who, tol);
-    if (!(inner_floor >= 0.f)) return fail(ctx, HN_ERR_ARG, "%s: inner_floor must be a number >= 0 (got %g)", who, (double)inner_floor);
+// hn_gmres_refine_cycle and hn_fgmres_refine_cycle, the arguments but tol and inner_floor checked
+int run_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+                     float inner_floor, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, hipStream_t s) {
     const long P = (long)ctx->tab.n * ctx->tab.n;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
     // all three workspaces before the first launch: a call that has to build one under capture leaves nothing behind
-    rc = prepare(ctx, batch, restart, s);
+    int rc = prepare(ctx, batch, restart, s);
     if (rc == HN_OK) rc = refine_prepare(ctx, batch, s);
     if (rc == HN_OK) rc = f64_reserve(ctx, batch, true, s);
     if (rc != HN_OK) return rc;
@@ -552,8 +661,72 @@ extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, 
     hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + nr4 + 255) / 256)), blk, 0, s, k_sq, ws.ksq64, nk4, rhs, ws.rhs64, nr4);
     if ((rc = f64_apply(ctx, x, ws.res64, ws.ksq64, ws.rhs64, rhs_batch, rmse64, batch, s)) != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_rhs, grid, blk, 0, s, ws.res64, rmse64, tol, (double)inner_floor, ws.rhs32, ws.d32, ws.tol, ws.stop, P);
-    if ((rc = launch_cycle(ctx, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
+    if ((rc = launch_cycle(ctx, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, pc, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_update, grid, blk, 0, s, x, ws.d32, rmse64, k_used, P);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
+}
+
+int check_refine_tols(hn_ctx* ctx, const char* who, double tol, float inner_floor) {
+    if (!(tol >= 0.0)) return fail(ctx, HN_ERR_ARG, "%s: tol must be a number >= 0 (got %g)", who, tol);
+    if (!(inner_floor >= 0.f)) return fail(ctx, HN_ERR_ARG, "%s: inner_floor must be a number >= 0 (got %g)", who, (double)inner_floor);
+    return HN_OK;
+}
+
+}  // namespace
+
+void krylov_free(hn_ctx* ctx) {
+    cycle_ws_free(ctx);
+    refine_ws_free(ctx);
+    precond_ws_free(ctx);
+}
+void precond_free(hn_ctx* ctx) { precond_ws_free(ctx); }
+
+}  // namespace hn
+
+using namespace hn;
+
+extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                              float* basis, float* hess, float* rmse, int32_t* k_used, void* stream) {
+    const int rc = check_cycle_args(ctx, "hn_gmres_cycle", false, false, x, k_sq, rhs, rhs_batch, batch, restart, basis, nullptr, hess, rmse, k_used, nullptr);
+    if (rc != HN_OK) return rc;
+    DeviceGuard guard(ctx);
+    return run_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{}, basis, hess, rmse, k_used, (hipStream_t)stream);
+}
+
+extern "C" int hn_fgmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                               int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
+                               void* stream) {
+    const char* who = "hn_fgmres_cycle";
+    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
+    if (rc != HN_OK) return rc;
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
+    return run_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse, k_used, s);
+}
+
+extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+                                     float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
+    const char* who = "hn_gmres_refine_cycle";
+    int rc = check_cycle_args(ctx, who, true, false, x, k_sq, rhs, rhs_batch, batch, restart, basis, nullptr, hess, rmse, k_used, rmse64);
+    if (rc == HN_OK) rc = check_refine_tols(ctx, who, tol, inner_floor);
+    if (rc != HN_OK) return rc;
+    DeviceGuard guard(ctx);
+    return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{}, basis, hess, rmse, k_used, rmse64,
+                            (hipStream_t)stream);
+}
+
+extern "C" int hn_fgmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+                                      float inner_floor, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse,
+                                      int32_t* k_used, double* rmse64, void* stream) {
+    const char* who = "hn_fgmres_refine_cycle";
+    int rc = check_cycle_args(ctx, who, true, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, rmse64);
+    if (rc == HN_OK) rc = check_refine_tols(ctx, who, tol, inner_floor);
+    if (rc != HN_OK) return rc;
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
+    return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{zbasis, precond_iters, precond_scale, who}, basis,
+                            hess, rmse, k_used, rmse64, s);
 }

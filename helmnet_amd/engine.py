@@ -281,8 +281,8 @@ class Engine:
         return out
 
     def _gmres_buffers(self, what: str, x, x_dtype, k_sq, rhs, restart: int, basis, hess):
-        """What gmres_cycle and gmres_refine_cycle share: the grad refusal, the shape checks, ``basis`` / ``hess`` (allocated when not given) and the
-        fresh ``rmse`` [restart + 1, B] and ``k_used`` [B] int32 tables."""
+        """What the four cycle methods share: the grad refusal, the shape checks, ``basis`` / ``hess`` (allocated when not given) and the fresh ``rmse``
+        [restart + 1, B] and ``k_used`` [B] int32 tables."""
         b, p2 = x.shape[0], 2 * self.n * self.n
         for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
             if isinstance(t, torch.Tensor) and t.requires_grad:
@@ -294,6 +294,11 @@ class Engine:
         basis = self._chk(new(b, restart + 1, p2) if basis is None else basis, (b, restart + 1, p2), "basis")
         hess = self._chk(new(b, restart + 1, restart, 2) if hess is None else hess, (b, restart + 1, restart, 2), "hess")
         return b, basis, hess, new(restart + 1, b), torch.empty(b, device=self.device, dtype=torch.int32)
+
+    def _zbasis(self, b: int, restart: int, zbasis):
+        """The flexible cycles' ``zbasis`` [B, restart, 2 n^2], allocated when not given."""
+        shape = (b, restart, 2 * self.n * self.n)
+        return self._chk(torch.empty(shape, device=self.device, dtype=torch.float32) if zbasis is None else zbasis, shape, "zbasis")
 
     def gmres_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
                     basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
@@ -320,6 +325,35 @@ class Engine:
         rc = self.lib.hn_gmres_refine_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor),
                                             _ptr(basis), _ptr(hess), _ptr(rmse), _ptr(k_used), _ptr(rmse64), self._stream())
         _lib.check(rc, self.ctx, "hn_gmres_refine_cycle")
+        return rmse64, rmse, k_used
+
+    def fgmres_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float, precond_iters: int, precond_scale: float,
+                     basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
+        """One FLEXIBLE restart cycle (hn_fgmres_cycle): ``gmres_cycle`` right-preconditioned by the learned iteration -- per inner step
+        ``precond_iters`` iterations of ``step`` on A z = precond_scale * v_k from rest, z_k = wf / precond_scale, w = A z_k, and the update over the
+        z_j.  Returns (rmse, k_used) as ``gmres_cycle``; ``zbasis`` [B, restart, 2 n^2] (allocated when not given) receives the z_j.
+        ``precond_iters`` 0: z = v, ``gmres_cycle`` bit for bit.  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_cycle", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        zbasis = self._zbasis(b, restart, zbasis)
+        rc = self.lib.hn_fgmres_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters),
+                                      float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used), self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_cycle")
+        return rmse, k_used
+
+    def fgmres_refine_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float, precond_iters: int,
+                            precond_scale: float, inner_floor: float = 1e-6, basis: Optional[torch.Tensor] = None,
+                            hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
+        """One refinement step with the flexible cycle inside (hn_fgmres_refine_cycle): ``gmres_refine_cycle`` with the learned preconditioner of
+        ``fgmres_cycle``.  Returns (rmse64, rmse, k_used) as ``gmres_refine_cycle``.  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_refine_cycle", x, torch.float64, k_sq, rhs, restart, basis, hess)
+        zbasis = self._zbasis(b, restart, zbasis)
+        rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
+        rc = self.lib.hn_fgmres_refine_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor),
+                                             int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse),
+                                             _ptr(k_used), _ptr(rmse64), self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_refine_cycle")
         return rmse64, rmse, k_used
 
     # ---- the same operators in float64: the check the fp32 residual is measured against (hn_f64.hip) ----

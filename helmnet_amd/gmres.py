@@ -112,6 +112,20 @@ def drive_refinement(cycle, max_cycles: int, tol: float) -> dict:
             "cycles": cycles, "converged": converged}
 
 
+def unet_evaluations(cycles: int, restart: int, precond_iterations: int) -> int:
+    """UNet evaluations a preconditioned solve of ``cycles`` cycles (a driver's count, a refinement's final checking cycle included) has enqueued:
+    every cycle runs all ``restart`` inner steps in lock step for the whole batch, whatever stopped on the way, each with ``precond_iterations``
+    iterations of the learned solver.  Zero without a preconditioner."""
+    return int(cycles) * int(restart) * int(precond_iterations)
+
+
+def default_precond_scale(source) -> float:
+    """alpha of ``precondition="learned"`` when none is given: the root-mean-square 2-norm of the source maps [S,2,n,n], ||src||_F / sqrt(S), in
+    float64 on the host -- the preconditioner's right-hand side alpha * v_k (|v_k| = 1) then has the magnitude the network was trained on."""
+    src = np.asarray(source.detach().double().cpu().numpy() if isinstance(source, torch.Tensor) else source, dtype=np.float64)
+    return float(np.sqrt((src ** 2).sum() / src.shape[0]))
+
+
 def _hip_setup(solver, sos_maps, restart, x0, dtype):
     """What both HIP drivers start from: (engine, k_sq, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess)."""
     _require_no_grad("gmres(backend='hip')", sos_maps, x0)
@@ -126,14 +140,19 @@ def _hip_setup(solver, sos_maps, restart, x0, dtype):
     return eng, k_sq.contiguous(), rhs, x, basis, hess
 
 
-def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor):
+def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor, precond=None):
     """``gmres(backend="hip", refine=True)``: iterative refinement with the fp32 restart cycle as the inner solver (hn_gmres_refine_cycle).  The
-    iterate, its true residual and the update are float64; one host synchronisation per cycle."""
+    iterate, its true residual and the update are float64; one host synchronisation per cycle.  ``precond`` (iterations, alpha): the flexible
+    cycle (hn_fgmres_refine_cycle)."""
     eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float64)
     bsz, dev = x.shape[0], x.device
+    zbasis = None if precond is None else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
 
     def cycle():
-        rmse64, rmse, k_used = eng.gmres_refine_cycle(x, k_sq, rhs, restart, tol, inner_floor, basis, hess)
+        if precond is None:
+            rmse64, rmse, k_used = eng.gmres_refine_cycle(x, k_sq, rhs, restart, tol, inner_floor, basis, hess)
+        else:
+            rmse64, rmse, k_used = eng.fgmres_refine_cycle(x, k_sq, rhs, restart, tol, precond[0], precond[1], inner_floor, basis, hess, zbasis)
         both = torch.cat([rmse64, rmse.reshape(-1).double(), k_used.double()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
         m = (restart + 1) * bsz
@@ -144,16 +163,22 @@ def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor):
     final = torch.from_numpy(out["history"][-1]).to(dev) if out["converged"] else eng.residual64(x, k_sq.double(), rhs.double(), False, True)[1]
     return {"wavefield": x, "residual_norm64": final, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
             "operator_applications": out["cycles"] * (restart + 1), "operator_applications64": out["cycles"], "converged": out["converged"],
-            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"]}
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"],
+            "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
 
 
-def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0):
-    """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own."""
+def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None):
+    """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own.
+    ``precond`` (iterations, alpha): the flexible cycle (hn_fgmres_cycle)."""
     eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32)
     bsz, dev = x.shape[0], x.device
+    zbasis = None if precond is None else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
 
     def cycle():
-        rmse, k_used = eng.gmres_cycle(x, k_sq, rhs, restart, tol, basis, hess)
+        if precond is None:
+            rmse, k_used = eng.gmres_cycle(x, k_sq, rhs, restart, tol, basis, hess)
+        else:
+            rmse, k_used = eng.fgmres_cycle(x, k_sq, rhs, restart, tol, precond[0], precond[1], basis, hess, zbasis)
         both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
@@ -164,11 +189,13 @@ def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0):
     out = drive_cycles(cycle, true_rmse, max_outer, tol)
     return {"wavefield": x, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
             "operator_applications": out["cycles"] * (restart + 1) + out["true_checks"], "converged": out["converged"],
-            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"]}
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"],
+            "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
 
 
 def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
-          x0: Optional[torch.Tensor] = None, backend: str = "torch", refine: bool = False, inner_floor: float = 1e-6):
+          x0: Optional[torch.Tensor] = None, backend: str = "torch", refine: bool = False, inner_floor: float = 1e-6,
+          precondition: Optional[str] = None, precond_iterations: int = 10, precond_scale: Optional[float] = None):
     """Solve (L + k_sq) u = source for every map of ``sos_maps`` [B, 1, N, N] (the reference's classical baseline:
     matlab/spectral_gmres_solver.m:86-115, MATLAB's ``gmres`` with restarts).
 
@@ -192,13 +219,29 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
     (hn_residual_f64's operator), the fp32 cycle solves the scaled correction equation A d = r / s from d = 0 to ``max(tol / s, inner_floor)``,
     and x += s d in float64.  ``tol`` is then a float64 RMSE; ``wavefield`` comes back float64, ``residual_norms`` is the list of TRUE float64
     RMSEs [B] at the start of every cycle, ``residual_norm64`` [B] that of the returned iterate, ``max_outer`` bounds the cycles, the
-    final checking one included; ``x0`` may be fp32 (a learned solve's wavefield) or float64."""
+    final checking one included; ``x0`` may be fp32 (a learned solve's wavefield) or float64.
+
+    ``backend="hip", precondition="learned"`` (with or without ``refine``): flexible GMRES with the learned solver as right preconditioner
+    (hn_fgmres_cycle / hn_fgmres_refine_cycle) -- per inner step ``precond_iterations`` iterations of the solver's network on A z = alpha v_k from
+    rest, z_k = wf / alpha.  ``precond_scale`` is alpha; None: ``default_precond_scale(solver.source)``.  The result gains ``unet_evaluations``
+    (cycles x restart x precond_iterations, all enqueued in lock step; 0 without a preconditioner).  ``precondition=None`` is the code path and the
+    bits of before."""
     if refine and backend != "hip":
         raise ValueError("refine=True needs backend='hip'")
+    if precondition not in (None, "learned"):
+        raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
+    if precondition is not None and backend != "hip":
+        raise ValueError("precondition='learned' needs backend='hip'")
+    precond = None
+    if precondition is not None:
+        if int(precond_iterations) < 0:
+            raise ValueError(f"precond_iterations must be >= 0 (got {precond_iterations})")
+        _require_no_grad("gmres(backend='hip')", sos_maps, x0)
+        precond = (int(precond_iterations), default_precond_scale(solver.source) if precond_scale is None else float(precond_scale))
     if backend == "hip" and refine:
-        return _gmres_refine(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, float(inner_floor))
+        return _gmres_refine(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, float(inner_floor), precond)
     if backend == "hip":
-        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0)
+        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, precond)
     if backend != "torch":
         raise ValueError(f"unknown GMRES backend {backend!r} (choose 'torch' or 'hip')")
     eng = solver.engine()

@@ -580,29 +580,38 @@ class IterativeSolver(nn.Module):
             out["converged64"] = bool(float(worst64) < tol)
         return out
 
-    def gmres(self, sos_maps, restart: int = 20, max_cycles: int = 50, tol: float = 1e-4, x0=None) -> dict:
+    def gmres(self, sos_maps, restart: int = 20, max_cycles: int = 50, tol: float = 1e-4, x0=None, precondition=None, precond_iterations: int = 10,
+              precond_scale=None) -> dict:
         """The reference's classical baseline (matlab/spectral_gmres_solver.m:86-115) on this solver's operator and source: restarted GMRES with the
         restart cycle fused on the device (``helmnet_amd.gmres.gmres(backend="hip")``), every map stopping on its own.  ``x0`` [B,2,n,n]: the
-        starting iterate, e.g. a learned solve's wavefield to be continued by Krylov iterations (default: zeros).  No gradients."""
+        starting iterate, e.g. a learned solve's wavefield to be continued by Krylov iterations (default: zeros).  ``precondition="learned"``:
+        flexible GMRES with this solver's network as right preconditioner, ``precond_iterations`` iterations per inner step on a right-hand side
+        scaled by ``precond_scale`` (None: the source's RMS 2-norm); see ``helmnet_amd.gmres.gmres``.  No gradients."""
         from .gmres import gmres
-        return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip")
+        return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", precondition=precondition,
+                     precond_iterations=precond_iterations, precond_scale=precond_scale)
 
-    def gmres64(self, sos_maps, restart: int = 20, max_cycles: int = 400, tol: float = 1e-10, x0=None) -> dict:
+    def gmres64(self, sos_maps, restart: int = 20, max_cycles: int = 400, tol: float = 1e-10, x0=None, precondition=None, precond_iterations: int = 10,
+                precond_scale=None) -> dict:
         """GMRES to float64 accuracy on this solver's operator and source (the role MATLAB's double-precision ``gmres`` has in the reference,
         matlab/spectral_gmres_solver.m:86-115: the ground truth the learned solver is measured against): iterative refinement with the fused fp32
         restart cycle inside and the residual and the update in float64 (``helmnet_amd.gmres.gmres(backend="hip", refine=True)``).  ``tol`` is the
         float64 residual RMSE to reach; ``x0`` [B,2,n,n], fp32 or float64: the starting iterate, e.g. the learned solver's wavefield to be polished
-        (default: zeros; it is not written).  Returns ``wavefield`` and ``residual_norms`` in float64.  No gradients."""
+        (default: zeros; it is not written).  Returns ``wavefield`` and ``residual_norms`` in float64.  ``precondition``, ``precond_iterations``,
+        ``precond_scale``: as ``gmres`` (the flexible cycle inside the refinement).  No gradients."""
         from .gmres import gmres
-        return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", refine=True)
+        return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", refine=True, precondition=precondition,
+                     precond_iterations=precond_iterations, precond_scale=precond_scale)
 
-    def reference_error(self, wavefield, sos_maps, tol: float = 1e-10, restart: int = 20, max_cycles: int = 400) -> dict:
+    def reference_error(self, wavefield, sos_maps, tol: float = 1e-10, restart: int = 20, max_cycles: int = 400, precondition=None,
+                        precond_iterations: int = 10, precond_scale=None) -> dict:
         """How far ``wavefield`` [B,2,n,n] is from the solution of the discrete problem: ``gmres64`` started from it is the ground truth.  Returns per
         sample ``linf`` (max |wavefield - reference| over both planes) and ``rms`` of the same difference, ``reference_rmse64`` (the float64
         residual RMSE of the reference: how good the ground truth is; below ``tol`` when ``converged``), ``reference`` (the float64 wavefield),
         ``converged`` and ``cycles``.  ``wavefield`` is not written."""
         _require_no_grad("reference_error", wavefield, sos_maps)
-        out = self.gmres64(sos_maps, restart=restart, max_cycles=max_cycles, tol=tol, x0=wavefield)
+        out = self.gmres64(sos_maps, restart=restart, max_cycles=max_cycles, tol=tol, x0=wavefield, precondition=precondition,
+                           precond_iterations=precond_iterations, precond_scale=precond_scale)
         ref = out["wavefield"]
         diff = wavefield.detach().to(ref.device).double() - ref
         return {"linf": diff.abs().amax((1, 2, 3)), "rms": diff.pow(2).mean((1, 2, 3)).sqrt(), "reference_rmse64": out["residual_norm64"],

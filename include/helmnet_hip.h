@@ -295,6 +295,38 @@ int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float
                           double tol, float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64,
                           void* stream);
 
+/* ---- flexible GMRES, preconditioned by the learned iteration (added within ABI v7: new entry points, nothing existing changes) ----
+ * hn_fgmres_cycle is hn_gmres_cycle as a FLEXIBLE restart cycle (FGMRES, Saad 1993) with the learned solver as a right preconditioner that may
+ * change from step to step and be nonlinear.  With m = precond_iters and alpha = precond_scale, inner step k computes z_k = M(v_k):
+ *   m >= 1: the learned solve of A z = alpha v_k from rest on a library workspace -- src = alpha * v_k (one fp32 multiply per element), wf = 0,
+ *           states = 0, res = 0 - src, then exactly the launches of hn_step(wf, res, states, k_sq, src, src_batch = batch, batch, n_iter = m, no
+ *           histories) on `stream` (the context's precision mode and options apply as to any hn_step), z_k = wf / alpha (a true division);
+ *   m == 0: z_k = v_k, copied exactly: x, basis, hess, rmse and k_used then equal hn_gmres_cycle's bit for bit and zbasis[:, j] == basis[:, j].
+ * w = A z_k is the operator hn_gmres_cycle applies (not the step's last residual); the two Gram-Schmidt passes, the Hessenberg column, the rotations,
+ * rmse, the per-sample stop and v_{k+1} = w / |w| are unchanged and work on `basis`; the update is x += sum_{j < k_used} y_j z_j.
+ *   zbasis   [B, restart, 2*n*n]  caller-owned scratch like basis; on return the z_j of this cycle
+ * Everything else as hn_gmres_cycle: a sample below tol at the start is untouched bit for bit, fixed-order sums, no float atomics, two calls on equal
+ * inputs on a context with equal options give equal bits.  In exact arithmetic the residual estimate is the true residual of the truncated iterate
+ * whatever M is (A Z_k = V_{k+1} H_k holds by construction).
+ * hn_fgmres_refine_cycle is hn_gmres_refine_cycle with this cycle inside: the up-cast, the float64 operator, the scaled right-hand side, the float64
+ * update, the per-sample tolerance and the stop words are the same launches in the same order, rmse64 is bit for bit hn_residual_f64's, and with m == 0
+ * every output equals hn_gmres_refine_cycle's bit for bit.
+ * Workspace: src, wf, res [B][2 n^2] and the hidden states [B][2][hn_state_len] beside hn_gmres_cycle's, built by the first call with m >= 1, grown by
+ * a larger batch, freed by hn_set_domain, hn_load_weights and hn_destroy.
+ * NOT capturable: under stream capture both return HN_ERR_STATE before enqueuing anything (hn_step's first call on a stream probes and synchronises).
+ * For the same reason the FIRST call with precond_iters >= 1 on a stream blocks the host once, inside the first inner step (behind the launches
+ * enqueued up to there), as a first hn_step on that stream would; later calls on it enqueue without a host synchronisation.  What hn_step reports
+ * from inside the cycle comes back under this entry point's name.
+ * HN_ERR_ARG: everything hn_gmres_cycle / hn_gmres_refine_cycle refuse, precond_iters < 0, precond_scale not finite or <= 0, zbasis NULL, not 16-byte
+ * aligned or overlapping any other argument, and what hn_step refuses (a domain the network's depth does not divide).  HN_ERR_STATE before
+ * hn_set_domain, and before hn_load_weights when precond_iters >= 1.  A refused call has enqueued nothing. */
+int hn_fgmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                    int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
+                    void* stream);
+int hn_fgmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart,
+                           double tol, float inner_floor, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
+                           float* rmse, int32_t* k_used, double* rmse64, void* stream);
+
 /* d[B,2,n,n] = HybridNet(in6[B,6,n,n]); the hidden states are read from `states_in` and the new
  * ones written to `states_out`, both in the reference's flat layout [B, 2, hn_state_len()]
  * (architectures.py:419-437).  states_in must not alias states_out.
