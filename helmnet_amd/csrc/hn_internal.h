@@ -184,7 +184,7 @@ struct SpecTables {
     float* k2 = nullptr;       // -(k1*k1) evaluated in fp32 like the reference
     float2* a = nullptr;       // PML first-derivative coefficient  (-gamma' / gamma^3)
     float2* b = nullptr;       // PML second-derivative coefficient (1 / gamma^2)
-    // prime-factor path (n = P * Q, P in {3, 5}, Q a power of two): Q-point twiddles and the derivative multipliers in
+    // prime-factor path (n = P * Q, P in {3, 5, 7}, Q a power of two): Q-point twiddles and the derivative multipliers in
     // the (k1, k2) order of the Good-Thomas output map; a / b above stay in natural order
     int pfa_p = 0, pfa_q = 0;
     float2* tw_q = nullptr;    // exp(-2 pi i m / Q)

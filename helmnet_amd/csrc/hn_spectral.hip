@@ -1043,7 +1043,7 @@ __global__ __launch_bounds__(256) void k_spec16_rows(const float* __restrict__ w
 __global__ void k_bump(int* counter) { atomicAdd(counter, 1); }
 
 // ------------------------------------------------------------------------------------------
-// Prime-factor (Good-Thomas) path for n = P * Q, P in {3, 5}, Q = 2^k: the 96^2 training size, 160, 192, 320, ...
+// Prime-factor (Good-Thomas) path for n = P * Q, P in {3, 5, 7}, Q = 2^k: the 96^2 training size, 112, 160, 192, 320, ...
 //   input map   n = (Q n1 + P n2) mod N        output map   k = (Q (Q^-1 mod P) k1 + P (P^-1 mod Q) k2) mod N
 //   X[k(k1, k2)] = sum_n1 W_P^(n1 k1) sum_n2 W_Q^(n2 k2) x[n(n1, n2)]          (no twiddles between the factors)
 // so a length-N transform is P interleaved Q-point transforms -- run in lock step by the in-LDS Stockham pass above
