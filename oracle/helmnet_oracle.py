@@ -250,6 +250,8 @@ def _keep(tape: Optional[dict], name: str, x: Tensor) -> Tensor:
             # evaluate the graph AT the given value (straight-through: the gradient passes unchanged).  The HIP path's
             # pre-activations differ from these by fp32 rounding; a PReLU input within rounding of zero then takes the other
             # branch, and a comparison of gradients would measure that coin flip instead of the kernels
+            if "__computed__" in tape:     # what the graph itself computed here, from the forced tensors upstream
+                tape["__computed__"][name] = x.detach()
             x = force[name].to(x.dtype).detach() + (x - x.detach())   # value: exactly the forced one; gradient: identity
         if x.requires_grad:
             x.retain_grad()
@@ -295,10 +297,12 @@ def unet_forward(x6: Tensor, states: List[Tensor], w: Dict[str, Tensor], depth: 
     skips, new_states = [], []
     for d in range(depth):
         if d >= state_depth:
-            out = double_conv(x, w, f"enc.{d}.conv_signal", act)
+            # (a tape records -- and forces -- these levels only on request: ``tape["__stateless__"] = True``)
+            tp = tape if tape is not None and tape.get("__stateless__") else None
+            out = _keep(tp, f"out{d}", double_conv(x, w, f"enc.{d}.conv_signal", act, tp))
             new_states.append(states[d])
             skips.append(out)
-            x = F.conv2d(out, w[f"enc.{d}.down.weight"], w[f"enc.{d}.down.bias"], stride=2, padding=3)
+            x = _keep(tp, f"x{d + 1}", F.conv2d(out, w[f"enc.{d}.down.weight"], w[f"enc.{d}.down.bias"], stride=2, padding=3))
             continue
         out = _keep(tape, f"out{d}", double_conv(torch.cat([x, states[d]], 1), w, f"enc.{d}.conv_signal", act, tape))
         new_states.append(double_conv(torch.cat([out, states[d]], 1), w, f"enc.{d}.conv_state", act, tape))

@@ -139,4 +139,20 @@ GPU_CONFIGS = {
     "d4_256_softplus": (4, 741, None, "softplus", 4, 256, 2), "d4_256_gelu": (4, 741, None, "gelu", 4, 256, 2),
     "d4_512_softplus": (4, 742, None, "softplus", 4, 512, 1), "d4_512_gelu": (4, 742, None, "gelu", 4, 512, 1),
     "d4_272_A": (4, 749, "A", "prelu", 4, 272, 3), "d4_512_A16": (4, 742, "A", "prelu", 4, 512, 1),
+    "d4_528_A": (4, 742, "A", "prelu", 4, 528, 1),      # 528 = 16 * 33: level 3 is 66 wide, the bottleneck 33 (odd and wider than 32)
 }
+
+# the training / reverse-mode configurations of tests/train_matrix.py (test_train_matrix_gpu.py, test_train_matrix_host.py): tag -> (depth,
+# seed, slope plan, activation, state_depth, n, batch); the input seed is 7000 + n (train_matrix.train_case).  Seeds picked so that
+# tape_check holds (tests/test_config_weights.py).  528 = 16 * 33: the only way to an odd level wider than 32 is an odd bottleneck
+TRAIN_CONFIGS = {
+    "d4_528": (4, 760, "A", "prelu", 4, 528, 1),
+    "d4_80_A": (4, 760, "A", "prelu", 4, 80, 2), "d4_80_B": (4, 760, "B", "prelu", 4, 80, 2),
+    "d1_80": (1, 760, "A", "prelu", 1, 80, 2), "d2_112": (2, 760, "B", "prelu", 2, 112, 1), "d3_144": (3, 760, "B", "prelu", 3, 144, 1),
+    "d5_96": (5, 760, "A", "prelu", 5, 96, 2), "d6_192": (6, 760, "B", "prelu", 6, 192, 1), "d6_64": (6, 781, "A", "prelu", 6, 64, 2),
+    "d5_160_sd2": (5, 760, "A", "prelu", 2, 160, 1), "d4_64_sd0": (4, 760, "B", "prelu", 0, 64, 2),
+    "d4_80_relu": (4, 760, None, "relu", 4, 80, 2), "d4_64_tanhshrink": (4, 769, None, "tanhshrink", 4, 64, 1),
+    "d4_64_gelu": (4, 760, None, "gelu", 4, 64, 2), "d5_96_tanh": (5, 760, None, "tanh", 5, 96, 2),
+    "d4_160_A": (4, 760, "A", "prelu", 4, 160, 1),      # level 0 at least 128 wide: the fused forward kernel is the strip kernel there
+}
+TRAIN_INPUT_SEED = 7000

@@ -81,6 +81,9 @@ ROUTES = {
     "d4_256_gelu": ({"inc", "deep"}, {"conv_signal2", "conv_signal3", "bottleneck"}, [("deep", 0)]),
     "d4_512_softplus": ({"inc", "conv_signal2", "deep"}, {"conv_signal3", "bottleneck"}, [("deep", 0)]),
     "d4_512_gelu": ({"inc", "conv_signal2", "deep"}, {"conv_signal3", "bottleneck"}, [("deep", 0)]),
+    # 528 = 16 * 33: no level is 32 or 64 wide, so neither deep kernel applies (deep_applies, deepx_levels): every level layer by layer down to a 33-wide
+    # bottleneck; level 0 (528 = 4 * 132 >= 256) still takes the paired hand-scheduled kernel
+    "d4_528_A": ({"inc_conv_signal0", "conv_signal1", "conv_signal2", "conv_signal3", "bottleneck"}, {"deep", "inc", "conv_signal0"}, [("dc_valu", 0)]),
 }
 
 

@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from config_weights import (GOLDEN_B, GOLDEN_CONFIGS, GOLDEN_INPUT_SEED, GOLDEN_N, GPU_CONFIGS, config_input, config_weights, slope_plan,
-                            tape_check)
+from config_weights import (GOLDEN_B, GOLDEN_CONFIGS, GOLDEN_INPUT_SEED, GOLDEN_N, GPU_CONFIGS, TRAIN_CONFIGS, TRAIN_INPUT_SEED, config_input,
+                            config_weights, slope_plan, tape_check)
 from helmnet_amd.engine import pack_weights, weight_shapes
 from oracle import helmnet_oracle as O
 
@@ -87,4 +87,17 @@ def test_gpu_configurations_use_every_slope_branch(tag):
     x = config_input(n, min(b, 2), depth, 9000 + n, wf_scale=1e-6)
     tape = {}
     O.unet_forward(torch.from_numpy(x["x6"]), O.unflatten_states(torch.from_numpy(x["states"]), n, depth), w, depth, act, state_depth=sd, tape=tape)
+    tape_check(tape)
+
+
+@pytest.mark.parametrize("tag", list(TRAIN_CONFIGS))
+def test_training_configurations_use_every_slope_branch(tag):
+    """The networks of tests/test_train_matrix_gpu.py at their own sizes and inputs (the levels without state included): >= 20 % negative
+    pre-activations in the first convolution of every DoubleConv, every layer's RMS within [0.1, 10]."""
+    depth, seed, plan, act, sd, n, b = TRAIN_CONFIGS[tag]
+    w = {k: torch.from_numpy(v) for k, v in config_weights(depth, seed, plan, act, sd, n=n).items()}
+    x = config_input(n, b, depth, TRAIN_INPUT_SEED + n)
+    tape = {"__stateless__": True}
+    O.unet_forward(torch.from_numpy(x["x6"]), O.unflatten_states(torch.from_numpy(x["states"]), n, depth), w, depth, act, state_depth=sd, tape=tape)
+    assert sum(k.endswith(".mid") for k in tape) == 2 * depth + 2 + sd
     tape_check(tape)

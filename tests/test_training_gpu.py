@@ -76,74 +76,22 @@ def _report(errs, bar):
     assert not bad, f"above {bar}: {bad}\nall: {errs}"
 
 
-PEEK_MIDS = {"sig_mid": "enc.{d}.conv_signal.mid", "st_mid": "enc.{d}.conv_state.mid", "dec_mid": "decode.{d}.mid"}
-PEEK_OUTS = {"x": "x{d}", "out": "out{d}", "u": "u{d}", "y": "y{d}"}
-
-
 def _one_step_case(solver_, weights, n, b, act, seed, force_mids):
     """One unrolled iteration on white-noise inputs: HIP (hn_train_grad + hn_train_peek) against the oracle's autograd, every
-    tape tensor, activation gradient, input gradient and parameter gradient.  ``force_mids``: the oracle's graph is evaluated AT
-    the HIP path's pre-activation tensors (they differ by fp32 rounding; without this a PReLU input within rounding of zero takes
+    tape tensor, activation gradient, input gradient and parameter gradient: leg (a) of tests/train_matrix.py (the harness this function
+    was, generalised over depth, activation, state_depth and weights) on the shipped depth-4 network.  ``force_mids``: the oracle's graph is
+    evaluated AT the HIP path's pre-activation tensors (they differ by fp32 rounding; without this a PReLU input within rounding of zero takes
     the other branch in one of the two and the gradient comparison measures that coin flip, not the kernels).  The oracle runs
     in float64: it is the truth both fp32 implementations approximate (PyTorch's own fp32 reductions of ~10^5 terms with both
-    signs, e.g. the PReLU-slope gradient, are themselves only good to ~3e-4)."""
+    signs, e.g. the PReLU-slope gradient, are themselves only good to ~3e-4).  The forward tape (1e-5 * max), the loss and the exact zeros are
+    asserted inside; the gradient errors are returned."""
+    import train_matrix as TM
     solver_.set_domain_size(n, source_location=[n // 3, n // 2])
     eng = solver_.engine()
     ti = teacher_inputs(n, b, seed=seed)
     wf, res, st, sos = (torch.from_numpy(ti[k]) for k in ("wf", "res", "states", "sos"))
-    st = 0.2 * st
-    k_sq = (1.0 / sos) ** 2
-    t = O.SpectralTables(n, 8, 2, 1.0, dtype=torch.float64)
-    src = O.point_source_map(n, [n // 3, n // 2], 10.0)
-    names = [k for k in weight_names(4) if k in weights]
-    blob = torch.from_numpy(pack_weights({k: v.detach() for k, v in weights.items()}, 4, act)).to(DEV)
-    out = eng.train_grad(blob, wf.to(DEV), res.to(DEV), st.to(DEV), k_sq.to(DEV).contiguous(), src.to(DEV).contiguous(), 1, 1e4, input_grads=True)
-    torch.cuda.synchronize()
-    mids = {"inc.mid": eng.train_peek("inc_mid", 0, b).cpu()}
-    for kind, pat in PEEK_MIDS.items():
-        for d in range(5):
-            if kind == "dec_mid" or d < 4:
-                mids[pat.format(d=d)] = eng.train_peek(kind, d, b).cpu()
-    tape = {"__force__": mids} if force_mids else {}
-    loss, w, gin, lists = _oracle_grads(weights, wf, res, st, k_sq, src, t, 1, act=act, tape=tape, dtype=torch.float64)
-    # forward tape, level by level
-    fwd = {}
-    if not force_mids:
-        fwd.update({k: rel(v, tape[k]) for k, v in mids.items()})
-    for kind, pat in PEEK_OUTS.items():
-        for d in range(5):
-            name = pat.format(d=d)
-            if name in tape:
-                fwd[f"{kind}{d}"] = rel(eng.train_peek(kind, d, b), tape[name])
-    fwd["wf1"] = rel(out["wavefields"][0], lists[0][0])
-    fwd["res1"] = rel(out["residuals"][0], lists[1][0])
-    fwd["st1"] = rel(out["states"][0], lists[2][0])
-    _report(fwd, 1e-5)
-    assert abs(float(out["loss"][0]) - float(loss)) <= 1e-5 * float(loss)
-    # activation gradients, then parameter gradients tensor by tensor
-    bwd = {}
-    for kind, pat in (("g_y", "y{d}"), ("g_u", "u{d}"), ("g_x", "x{d}"), ("g_out", "out{d}")):
-        for d in range(5):
-            name = pat.format(d=d)
-            if name in tape and tape[name].grad is not None:
-                bwd[f"{kind}{d}"] = rel(eng.train_peek(kind, d, b), tape[name].grad)
-    bwd["grad_wf"] = rel(out["grad_wf"], gin[0])
-    bwd["grad_res"] = rel(out["grad_res"], gin[1])
-    bwd["grad_states"] = rel(out["grad_states"], gin[2])
-    got = unpack_weights(out["grad"], 4)
-    gmax = max(float(w[k].grad.abs().max()) for k in names if w[k].grad is not None)
-    for k in names:
-        if w[k].grad is None:     # conv_state feeds only the NEXT iteration: no gradient after one unrolled iteration
-            assert ".conv_state." in k and float(np.abs(got[k]).max()) == 0.0, k
-        elif w[k].grad.numel() == 1:
-            # a PReLU slope: ONE number, the sum of ~10^5..10^6 products of both signs; measured against the scale of the whole
-            # gradient (against its own, possibly cancelled, value it is ill-conditioned in fp32 for either implementation)
-            bwd[k] = abs(float(got[k].reshape(-1)[0]) - float(w[k].grad)) / gmax
-        else:
-            bwd[k] = rel(torch.from_numpy(got[k]), w[k].grad)
-    if act != "prelu":
-        assert all(float(np.abs(got[k]).max()) == 0.0 for k in got if k.endswith("double_conv.1.weight"))
-    return bwd
+    case = TM.make_case(4, act, 4, n, b, {k: v.detach() for k, v in weights.items()}, wf, res, 0.2 * st, sos)
+    return TM.run_case(eng, case, force_mids, leg_b=False, fp32_bars=False)["a"][0]
 
 
 @pytest.mark.parametrize("n,b", [(96, 2), (64, 3), (256, 1), (48, 1), (80, 2), (112, 1)])
