@@ -190,6 +190,11 @@ struct SpecTables {
     float2* tw_q = nullptr;    // exp(-2 pi i m / Q)
     float* k1_pfa = nullptr;   // [P][Q]
     float* k2_pfa = nullptr;
+    // mixed path (hn_spectral_mixed.hip; n = P * Q, P any odd factor, HN_OPT_SPECTRAL_MIXED): tw_q as above; k1_pfa / k2_pfa in the order the
+    // kernel meets the spectrum (Good-Thomas output map, k2 bit-reversed); a / b in natural order
+    int mix_p = 0, mix_q = 0;
+    int* mix_slot = nullptr;   // [n]: where element i of a line sits in the [P][Q] layout (Good-Thomas input map)
+    float2* mix_wp = nullptr;  // exp(-2 pi i m / P), m in [0, P)
     // dense fallback (any other n): complex n x n operator, stored transposed
     float2* dense_t = nullptr; // dense_t[m*n + j] = M[j][m]
     float2* dense_adj_t = nullptr; // the same for the adjoint operator M^H (training, hn_train.hip)
@@ -253,6 +258,7 @@ struct hn_ctx {
                                // anyway (~100 us of launch calls per 560 us iteration) and the graph's node-to-node dependencies
                                // cost more than in-order stream launches
     int opt_pfa = 1;           // prime-factor FFT for n = 3 * 2^k, 5 * 2^k (0: dense operator, A/B; takes effect at hn_set_domain)
+    int opt_mixed = 0;         // HN_OPT_SPECTRAL_MIXED: FFT for n = P * 2^k with any odd P instead of the dense operator (takes effect at hn_set_domain)
     int opt_radix16 = 1;       // 256-point transforms as two register-resident radix-16 passes (0: the radix-4 Stockham kernels)
     int opt_cols_t = 1;        // 256-point column pass through an LDS transpose: 0 the r2 kernel (16-byte global accesses), 1: 16 columns per block, 2: 32
     bool cols_t_attr_set = false, cols512_attr_set = false;
@@ -496,6 +502,14 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
 // out = L^H(g) + ksq * g [+ add]: the adjoint (conjugate transpose) of the residual operator, i.e. the vector-Jacobian product
 // of hn_residual with respect to the wavefield (training).  `add` may alias `out`.
 int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
+// ---- spectral, runtime odd factor (hn_spectral_mixed.hip) ----
+// (P, Q) with n = P * Q, P odd in [3, 127], Q a power of two in [16, 512]: the sizes the mixed kernels take; false otherwise
+bool spec_mixed_factor(int n, int* P, int* Q);
+// the tables of ctx->tab for n = P * Q (tw_q, k1_pfa, k2_pfa, a, b, mix_slot, mix_wp) and the kernels' dynamic-LDS attribute
+int spec_mixed_build(hn_ctx* ctx, const AxisHost& ax, int P, int Q);
+int spec_mixed_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, long src_sb, int batch, bool resid,
+                     float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride);
+int spec_mixed_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
 // ---- float64 residual check (hn_f64.hip) ----
 // out = L(wf) [+ ksq * wf - src] in float64 (out nullable) and / or rmse[b] = sqrt(mean over (c, h, w) of out^2) (nullable)
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s);

@@ -1333,7 +1333,7 @@ int upload(hn_ctx* ctx, T** dst, const std::vector<T>& h) {
 
 void spec_free(SpecTables& t) {
     for (void* p : {(void*)t.tw, (void*)t.k1, (void*)t.k2, (void*)t.a, (void*)t.b, (void*)t.dense_t, (void*)t.dense_adj_t, (void*)t.sigmas, (void*)t.tw_q,
-                    (void*)t.k1_pfa, (void*)t.k2_pfa, (void*)t.f64_tab, (void*)t.f64_part}) (void)hipFree(p);
+                    (void*)t.k1_pfa, (void*)t.k2_pfa, (void*)t.mix_slot, (void*)t.mix_wp, (void*)t.f64_tab, (void*)t.f64_part}) (void)hipFree(p);
     t = SpecTables{};
 }
 
@@ -1453,6 +1453,9 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
         if ((rc = upload(ctx, &t.k2_pfa, k2p)) != HN_OK) return rc;
         if ((rc = upload(ctx, &t.a, fa)) != HN_OK) return rc;
         if ((rc = upload(ctx, &t.b, fb)) != HN_OK) return rc;
+    } else if (int mp = 0, mq = 0; ctx->opt_mixed && spec_mixed_factor(n, &mp, &mq)) {
+        // HN_OPT_SPECTRAL_MIXED: any other n = P * 2^k with P odd (hn_spectral_mixed.hip); with HN_OPT_SPECTRAL_PFA 0 that includes P = 3, 5, 7
+        if ((rc = spec_mixed_build(ctx, ax, mp, mq)) != HN_OK) return rc;
     } else {
         // M[j][m] = (1/n) sum_p (a_j * i*k_p + b_j * k2_p) exp(2 pi i p (j - m) / n), k2_p = -(k_p^2)
         std::vector<std::complex<double>> g1, g2;
@@ -1553,6 +1556,9 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
         }
 #undef HN_PFA
         if (rc != HN_OK) return rc;
+    } else if (t.mix_p != 0) {
+        const int rc = spec_mixed_apply(ctx, wf, out, ksq, src, src_sb, batch, resid, accum_sumsq, s, it_counter, sumsq_stride);
+        if (rc != HN_OK) return rc;
     } else {
         if (it_counter != nullptr) hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, s, it_counter);
         ProfScope ps(ctx, KID_SPEC_ROWS, s);
@@ -1588,6 +1594,9 @@ int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, cons
             default: return fail(ctx, HN_ERR_ARG, "internal: no prime-factor kernel for %d x %d", t.pfa_p, t.pfa_q);
         }
 #undef HN_PFA
+        if (rc != HN_OK) return rc;
+    } else if (t.mix_p != 0) {
+        const int rc = spec_mixed_adjoint(ctx, g, out, ksq, add, batch, s);
         if (rc != HN_OK) return rc;
     } else {
         if (add == out) return fail(ctx, HN_ERR_ARG, "spec_adjoint: the dense operator cannot accumulate in place");

@@ -38,6 +38,29 @@ def pml_profile(n: int, pml: int, sigma_max: float, k: float):
     return sigma, a, b
 
 
+def spectral_route(n: int, pfa: int = 1, mixed: int = 0):
+    """(name, P, Q) of the kernels hn_set_domain picks for an n x n domain under the options 'spectral_pfa' and 'spectral_mixed' -- the rule of
+    spec_build (hn_spectral.hip), whose outcome Engine.counter('spectral_route') reports as 1 .. 4.  n = P * Q, P odd, Q a power of two.
+        'pow2'          P == 1: the power-of-two kernels
+        'prime_factor'  P in (3, 5, 7), Q >= 16 (up to 512 for P = 3, 256 for 5 and 7) and spectral_pfa: k_spec_pfa<Q, P>
+        'mixed'         any other P in [3, 127] with Q in [16, 512] and spectral_mixed: k_spec_mixed (runtime P)
+        'dense'         everything else: the n x n operator
+    Every multiple of 16 in [16, 2048] that is neither 'pow2' nor 'prime_factor' has P in [9, 127] and Q in {16, 32, 64, 128}; no size was taken
+    out of the mixed rule after measurement (profiles/spectral_mixed_bench.txt)."""
+    n = int(n)
+    if n < 16 or n > 2048:
+        raise ValueError(f"domain size {n} outside [16, 2048]")
+    q = n & -n
+    p = n // q
+    if p == 1:
+        return "pow2", p, q
+    if pfa and p in (3, 5, 7) and 16 <= q <= (512 if p == 3 else 256):
+        return "prime_factor", p, q
+    if mixed and 3 <= p <= 127 and 16 <= q <= 512:
+        return "mixed", p, q
+    return "dense", p, q
+
+
 def _frozen(t: torch.Tensor) -> nn.Parameter:
     return nn.Parameter(t, requires_grad=False)
 

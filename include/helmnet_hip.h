@@ -73,7 +73,7 @@ enum hn_precision { HN_PREC_FP32 = 0, HN_PREC_BF16X3 = 1, HN_PREC_FP16 = 2, HN_P
 /* Tuning knobs (hn_set_option).  Bit-exact ones -- the same kernels and summation order, only launched differently: LANES,
  * SIDE_STREAM, SPECTRAL_COLS (same butterflies, other memory access).  The others select a different kernel for the same
  * fp32 arithmetic and agree to fp32 rounding, like two fp32 implementations of the reference do: DEEP (other summation order,
- * 2e-6 * max), SPECTRAL_PFA (FFT instead of the dense operator), SPECTRAL_RADIX16 (other butterfly order), DC_VALU. */
+ * 2e-6 * max), SPECTRAL_PFA and SPECTRAL_MIXED (FFT instead of the dense operator), SPECTRAL_RADIX16 (other butterfly order), DC_VALU. */
 enum hn_option {
     HN_OPT_LANES = 0,        /* 1..8 sub-batches pipelined on internal streams (default 1; [measured, r5] 2 loses 3 % at 256^2 x 32 and 2 % at
                               * 256^2 x 64 -- one chain of 64 maps is the faster form since the r5 level-0 kernels --, +1 % at batch 128) */
@@ -87,6 +87,11 @@ enum hn_option {
                               * by layer.  Its waits are bounded like HN_OPT_SIDE_SYNC's and report through hn_check_async_errors                   */
     HN_OPT_SPECTRAL_PFA = 4, /* 0/1: prime-factor FFT for n = 3 * 2^k, 5 * 2^k, 7 * 2^k instead of the dense n x n operator (default 1;
                               * read by the next hn_set_domain)                                                     */
+    HN_OPT_SPECTRAL_MIXED = 17, /* 0/1 (default 0): FFT for every other size n = P * 2^k, P odd >= 9 (2^k >= 16: all multiples of 16 that are neither a power
+                              * of two nor taken by HN_OPT_SPECTRAL_PFA; with HN_OPT_SPECTRAL_PFA 0 also P = 3, 5, 7) instead of the dense n x n operator:
+                              * P interleaved 2^k-point transforms in LDS and a direct P-point DFT across them (hn_spectral_mixed.hip).  Agrees with
+                              * the dense operator to fp32 rounding, not bit for bit; read by the next hn_set_domain.  HN_CNT_SPECTRAL_ROUTE tells
+                              * which route the current domain took                                                            */
     HN_OPT_SPECTRAL_RADIX16 = 5, /* 256-point lines: 0 the radix-4 kernels, 1 radix-16 columns + 8x4x8 rows (default), 2 radix-16 rows too */
     HN_OPT_DC_VALU = 6,      /* fp32 DoubleConvs of the largest level (W >= 256) on the packed vector FMA (every FMA useful, same peak as the
                               * fp32 MFMA, whose 3x3 packing fills 75 % of its slots): 0 none (matrix core); 1 inc and the decoder, 2 all three on the
@@ -154,8 +159,10 @@ enum hn_counter { HN_CNT_GRAPH_REPLAYS = 0, HN_CNT_EAGER_ITERATIONS = 1, HN_CNT_
                   HN_CNT_SIDE_CANDIDATE = 4,    /* candidate (0 .. 3) hn_step's side stream was last picked from; -1 before the first pick */
                   HN_CNT_TRAIN_FWD_EVENTS = 5,  /* times hn_train_grad recorded the registered forward event (hn_train_set_forward_event): a caller compares the
                                                  * counter before and after a call to know whether event and table are valid for it (not under capture) */
-                  HN_CNT_FLAG_SYNC_ITERATIONS = 6 };/* hn_step iterations whose side-stream hand-overs went through device words (HN_OPT_SIDE_SYNC): n_iter - 1 per
+                  HN_CNT_FLAG_SYNC_ITERATIONS = 6,  /* hn_step iterations whose side-stream hand-overs went through device words (HN_OPT_SIDE_SYNC): n_iter - 1 per
                                                  * eligible call, 0 with the option off, under stream capture, under counter collection, with several lanes */
+                  HN_CNT_SPECTRAL_ROUTE = 7 };  /* not a count: the kernels the current domain's spectral operator runs on.  0 no domain, 1 power of two,
+                                                 * 2 prime-factor (HN_OPT_SPECTRAL_PFA), 3 dense, 4 mixed (HN_OPT_SPECTRAL_MIXED) */
 
 #define HN_ABI_VERSION 7
 int hn_abi_version(void);
