@@ -684,9 +684,17 @@ int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states
     if (states_in == states_out) return fail(ctx, HN_ERR_ARG, "hn_unet: states_in must not alias states_out");
     int rc = check_ready(ctx, batch);
     if (rc != HN_OK) return rc;
+    const long plane = (long)ctx->tab.n * ctx->tab.n;
+    {
+        // the hidden-state kernels write states_out level by level while later kernels still read states_in: any overlap, not only equal pointers, is refused
+        const size_t sl = sizeof(float) * (size_t)batch * kState * ctx->state_len;
+        const MemRange r[] = {{in6, sizeof(float) * (size_t)batch * kInCh * plane, false, "in6"}, {states_in, sl, false, "states_in"},
+                              {states_out, sl, true, "states_out"}, {d_out, sizeof(float) * (size_t)batch * 2 * plane, true, "d_out"}};
+        const char *who, *other;
+        if (first_overlap(r, 4, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_unet: %s overlaps %s", who, other);
+    }
     DeviceGuard guard(ctx);
     if ((rc = hn_reserve(ctx, batch)) != HN_OK) return rc;
-    const long plane = (long)ctx->tab.n * ctx->tab.n;
     UnetCall c;
     c.wf = Src{in6, kInCh * plane, plane, 1.f};
     c.res = Src{in6 + 2 * plane, kInCh * plane, plane, 1.f};
@@ -982,13 +990,27 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
     int rc = check_ready(ctx, batch);
     if (rc != HN_OK) return rc;
+    const long plane = (long)ctx->tab.n * ctx->tab.n;
+    const long L = ctx->state_len;
+    {
+        // No tensor may overlap another unless both are only read.  ONE tolerated form: res_hist == res / wf_hist == wf, the live buffer being slot 0 of
+        // its history (the copying form below runs; that slot and the live buffer are one piece of memory and end up holding the last iteration's value).
+        // Any other overlap of a live buffer with its history -- a view of slot j > 0, a shifted view -- would be overwritten while later iterations still
+        // need it, in the zero-copy and in the copying form alike: refused before anything is enqueued.
+        const size_t fc = sizeof(float) * (size_t)batch * 2 * plane, sc = sizeof(float) * (size_t)batch * kState * L, it = (size_t)n_iter;
+        const MemRange r[] = {{wf_hist != nullptr && wf_hist == wf ? nullptr : wf, fc, true, "wf"}, {res_hist != nullptr && res_hist == res ? nullptr : res, fc, true, "res"},
+                              {states, sc, true, "states"}, {k_sq, sizeof(float) * (size_t)batch * plane, false, "k_sq"},
+                              {src, sizeof(float) * (size_t)src_batch * 2 * plane, false, "src"}, {res_hist, it * fc, true, "res_hist"},
+                              {wf_hist, it * fc, true, "wf_hist"}, {st_hist, it * sc, true, "st_hist"},
+                              {rmse_hist, sizeof(float) * it * batch, true, "rmse_hist"}};
+        const char *who, *other;
+        if (first_overlap(r, 9, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_step: %s overlaps %s", who, other);
+    }
     DeviceGuard guard(ctx);
     if ((rc = hn_reserve(ctx, batch)) != HN_OK) return rc;
     if (n_iter == 0) return HN_OK;
     if ((rc = check_async(ctx, "hn_step (an earlier call)")) != HN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const long plane = (long)ctx->tab.n * ctx->tab.n;
-    const long L = ctx->state_len;
     int ns = ctx->opt_lanes;
     if (batch < 2 * ns) ns = 1;                       // tiny batches: not worth splitting
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;

@@ -17,6 +17,22 @@
  *   - every entry point selects the context's device for its own duration and restores the caller's.
  *   - all tensor arguments are DEVICE pointers to contiguous fp32, NCHW, owned by the caller,
  *     who guarantees their lifetime until `stream` has been synchronised.
+ *   - alignment and overlap.  ALIGNMENT: a tensor argument needs the alignment of its element type and no more -- 4 bytes for fp32 and int32, 8 for
+ *     the doubles of the _f64 family, 1 for hn_adam_step's mask -- so a view carved out of a larger allocation (a replay buffer, a history, a flat
+ *     workspace) is a valid argument.  This holds for hn_laplacian, hn_residual, hn_residual_vjp, hn_rmse, hn_unet, hn_step, hn_double_conv, hn_conv8x8,
+ *     hn_out_conv, hn_get_sigmas, hn_laplacian_f64, hn_residual_f64, hn_unet_f64, hn_step_f64, hn_train_grad, hn_step_vjp, hn_adam_step, hn_train_peek,
+ *     hn_stream_verdict and hn_rows_gather / hn_rows_scatter (which copy with 16-byte accesses where pointers and rows allow it and element by element
+ *     otherwise).  The exceptions name their requirement and refuse otherwise with HN_ERR_ARG: 16 bytes for the fields of hn_gmres_cycle, hn_fgmres_cycle
+ *     and their _refine_ forms, and for hn_stream_swap.  Alignment can cost speed, never results beyond fp32 rounding: where wf, res or the hidden states
+ *     of hn_step / hn_unet are not 16-byte aligned, the kernels that stage them with 16-byte LDS-direct loads stand down -- the level-0 DoubleConvs
+ *     (HN_OPT_DC_VALU 3 / 4, and with them the paired launch of HN_OPT_DC_PAIR) run on hn_dcv.hip, which agrees to fp32 rounding (4e-6 * max), and the
+ *     hidden-state DoubleConvs (HN_OPT_STATE_KERNEL) on the general kernel, bit-identical; every other kernel, the spectral operator included, is the
+ *     same for every alignment and gives the same bits.
+ *     OVERLAP: no tensor a call WRITES may overlap any other tensor of that call; tensors that are only read may share memory.  Checked, with
+ *     HN_ERR_ARG naming the two arguments and nothing enqueued, by hn_step (one tolerated form, see there), hn_unet, the _f64 family and the GMRES
+ *     family; hn_residual_vjp refuses g == out.  The other entry points (hn_laplacian, hn_residual, hn_rmse, the three sub-module calls, hn_train_grad,
+ *     hn_step_vjp, hn_adam_step, hn_rows_*, hn_stream_swap beyond its own slot rules) do not check: an output that overlaps an input or another
+ *     output there gives undefined values (never an access outside the caller's tensors).
  *   - all work is enqueued asynchronously on the caller's `stream` (a hipStream_t passed as
  *     void*; NULL = the default stream).  A ctx is bound to one device and is NOT thread-safe.
  *     ONE exception, "side streams": hn_step and hn_train_grad run part of their work on library streams beside the caller's, and HIP
@@ -336,7 +352,9 @@ int hn_fgmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const floa
 
 /* d[B,2,n,n] = HybridNet(in6[B,6,n,n]); the hidden states are read from `states_in` and the new
  * ones written to `states_out`, both in the reference's flat layout [B, 2, hn_state_len()]
- * (architectures.py:419-437).  states_in must not alias states_out.
+ * (architectures.py:419-437).  states_out and d_out must not overlap each other, states_in or in6 -- states_out is written level by level while
+ * later kernels still read states_in, so a partial overlap is as wrong as equal pointers: HN_ERR_ARG "hn_unet: <a> overlaps <b>", nothing enqueued.
+ * Any 4-byte-aligned pointers (see "alignment and overlap" above for what a pointer off a 16-byte boundary costs).
  * Replaces HybridNet.forward + EncoderBlock.forward (architectures.py:439-465, 240-252). */
 int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states_out, float* d_out,
             int batch, void* stream);
@@ -388,8 +406,15 @@ int hn_out_conv(hn_ctx* ctx, const float* x, const float* weights_host, float* o
  *     rmse_hist [n_iter, B]           per-sample residual RMSE after every iteration
  * Histories cost no copies (v7): the residual / wavefield of iteration `it` is WRITTEN into slot `it` of res_hist / wf_hist by the kernels
  * that compute it and read there by iteration it + 1 -- the reference keeps every residual for free too (it appends tensors, :676-697);
- * wf and res receive the last slot with one device-to-device copy per call.  Requires the slots not to alias wf / res; with captured
- * iterations (HN_EXP_GRAPH), several lanes or HN_OPT_HIST_COPY 1 the r1 - r6 form (in place + one copy per iteration and history) runs. */
+ * wf and res receive the last slot with one device-to-device copy per call.  With captured iterations (HN_EXP_GRAPH), several lanes or
+ * HN_OPT_HIST_COPY 1 the r1 - r6 form (in place + one copy per iteration and history) runs.
+ * Overlap: no tensor of the call that is written (wf, res, states and the four histories) may overlap any other; k_sq and src, which are only read,
+ * may share memory.  HN_ERR_ARG "hn_step: <a> overlaps <b>" with nothing enqueued, in every form of the loop (zero-copy, HN_OPT_HIST_COPY 1, lanes,
+ * captured iterations).  In particular wf / res may not be a view INTO their own history -- slot j > 0, or a view shifted against the slots: a later
+ * iteration would overwrite it while the history still needs it, whichever form runs.  ONE form is tolerated: res_hist == res and / or wf_hist == wf
+ * (equal pointers: the live buffer IS slot 0).  The copying form then runs; slots 1 .. n_iter - 1, wf, res and states are bit for bit those of a call
+ * on separate buffers, and slot 0, being the live buffer, ends up holding the last iteration's value.
+ * Alignment: any 4-byte-aligned pointers (see "alignment and overlap" above). */
 int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* src,
             int src_batch, int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist,
             float* rmse_hist, void* stream);
