@@ -200,13 +200,14 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Library tuning knobs (enum hn_option of include/helmnet_hip.h): 'lanes' 1..8, 'side_stream' 0..3, 'deep' 0/1, 'spectral_pfa' 0/1,
-        'spectral_radix16' 0..2, 'dc_valu' 0..4, 'spectral_cols' 0..2, 'train_fused', 'train_overlap'; laboratory knobs (HN_EXP_*): 'graph' 0, 1 or an even
+        'spectral_radix16' 0..2, 'dc_valu' 0..4, 'spectral_cols' 0..3, 'train_fused', 'train_overlap'; laboratory knobs (HN_EXP_*): 'graph' 0, 1 or an even
         number <= 64 of iterations per graph, 'train_lanes' 1/2 (hn_train_grad: the halves of the batch as two chains of launches on two streams).
         'spectral_pfa' and 'spectral_mixed' 0/1 (FFT for every other size P * 2^k, P odd; default 0) are read when the spectral tables are built:
         changing one re-builds them; counter('spectral_route') tells which kernels the domain runs on (1 power of two, 2 prime-factor, 3 dense,
         4 mixed).
-        'spectral_cols' is bit-exact: for a fixed 'spectral_radix16' its three column kernels give the same bits (with 'spectral_radix16' 0 it is not
-        read).  'spectral_radix16' and 'spectral_pfa' select other kernels for the same fp32 arithmetic: results agree to fp32 rounding (every
+        'spectral_cols' 0..2 is bit-exact: for a fixed 'spectral_radix16' these three column kernels give the same bits (with 'spectral_radix16' 0 it
+        is not read); 3 is another factorisation (fp32 rounding).  'spectral_plain' (laboratory knob) 1: the 256- / 512-point kernels on plain C++
+        complex helpers, bit-identical to 0.  'spectral_radix16' and 'spectral_pfa' select other kernels for the same fp32 arithmetic: results agree to fp32 rounding (every
         combination is within 1e-6 of the operator's scale of the float64 oracle, the dense operator within 7e-6), not bit for bit.  Neither makes a
         sample's result depend on what shares its batch (tests/test_spectral_gpu.py)."""
         if name not in _lib.HN_OPTION:

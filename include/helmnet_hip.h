@@ -144,7 +144,9 @@ enum hn_option {
                               * host, at hn_load_weights / hn_set_domain) and the hand-scheduled input layer (HN_OPT_DC_VALU 3 / 4) convolves four
                               * channels, adding the map in the tiles near the border (it is zero elsewhere).  Agrees with 0 to fp32 rounding  */
     HN_OPT_SPECTRAL_COLS = 7, /* 256-point column pass: 0 the r2 kernel (16-byte global accesses), 1 (default) / 2: coalesced float4 row
-                              * segments transposed through LDS, 16 / 32 columns per workgroup                      */
+                              * segments transposed through LDS, 16 / 32 columns per workgroup; 0, 1 and 2 give the same bits.  3: the staging
+                              * of 1 around the row pass's 8 x 4 x 8 transform, 32 threads per column (k_spec8_cols_t: four wavefronts per
+                              * SIMD instead of two): another factorisation, equal to the others within fp32 rounding, not bit for bit    */
     HN_OPT_TRAIN_FUSED = 10, /* hn_train_grad: sum of 1 (forward pass: an 8-channel DoubleConv is ONE launch of the fused matrix-core kernels of
                               * the inference path, which also store the pre-activation mid tensor to the tape; same tape within fp32
                               * rounding), 2 (backward pass: both backward-data convolutions of a big level's DoubleConv as one tiled
@@ -166,8 +168,12 @@ enum hn_option {
      * and are not part of the supported surface (DESIGN_NOTEBOOK.md has the measurements) ---- */
     HN_EXP_GRAPH = 100,      /* 0: launch every kernel (default; measured 4 % faster); 1: replay one captured iteration per HIP graph
                               * launch; even n <= 64: n iterations per graph.  Bit-identical                              */
-    HN_EXP_TRAIN_LANES = 101 /* hn_train_grad: 1 (default) the whole batch as one chain of launches; 2: the two halves of the batch as
+    HN_EXP_TRAIN_LANES = 101, /* hn_train_grad: 1 (default) the whole batch as one chain of launches; 2: the two halves of the batch as
                               * two chains on two streams.  Same gradient up to the order of the final sum over the halves; measured equal to 1 */
+    HN_EXP_SPECTRAL_PLAIN = 102 /* 0 (default): the 256-point 8x4x8 row pass, the 256-point transposed column pass and both 512-point passes multiply and
+                              * rotate complex numbers with the swap and the sign in the operand modifiers of the packed instructions, and take the
+                              * residual flags at compile time; 1: the same kernels on plain C++ helpers with run-time flags, as before.  Bit-identical
+                              * (same products, same fused multiply-adds); for the bit-identity test and in-process A/B runs                 */
 };
 /* Diagnostics counters (hn_get_counter). */
 enum hn_counter { HN_CNT_GRAPH_REPLAYS = 0, HN_CNT_EAGER_ITERATIONS = 1, HN_CNT_GRAPHS_CAPTURED = 2,
