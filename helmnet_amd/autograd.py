@@ -12,6 +12,10 @@ Functions supply the backward passes:
 The weight blob the kernels read is assembled from the network's parameters with torch ops (``weight_blob``), so the blob gradient
 lands on each ``nn.Parameter`` and the zero padding of levels without state gets none.  No double backward: a backward pass
 recorded with ``create_graph=True`` raises.
+
+Forward mode (``torch.autograd.forward_ad``): each Function also has a ``jvp``.  ``Laplacian.jvp`` is L of the tangent, ``Residual.jvp``
+L(wf') + k_sq wf' + k_sq' wf - src', ``Solve.jvp`` hn_step_jvp over the same tape (segments re-run with hn_step when c > 1).  The weights
+are constants of the linearisation: a tangent on the weight blob raises NotImplementedError.
 """
 from __future__ import annotations
 
@@ -81,6 +85,10 @@ class Laplacian(torch.autograd.Function):
         zero = torch.zeros(g.shape[0], 1, g.shape[2], g.shape[3], device=g.device, dtype=torch.float32)
         return None, eng.residual_vjp(g, zero)
 
+    @staticmethod
+    def jvp(ctx, _eng, t_x):
+        return ctx.eng.laplacian(t_x.float().contiguous())
+
 
 class Residual(torch.autograd.Function):
     @staticmethod
@@ -88,6 +96,7 @@ class Residual(torch.autograd.Function):
         wf, k_sq, src = wf.detach().contiguous(), k_sq.detach().contiguous(), src.detach().contiguous()
         ctx.eng, ctx.src_batch = eng, src.shape[0]
         ctx.save_for_backward(wf, k_sq)
+        ctx.save_for_forward(wf, k_sq)
         return eng.residual(wf, k_sq, src)
 
     @staticmethod
@@ -101,6 +110,18 @@ class Residual(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             g_s = -g if ctx.src_batch == g.shape[0] else -g.sum(0, keepdim=True)
         return None, g_wf, g_k, g_s
+
+    @staticmethod
+    def jvp(ctx, _eng, t_wf, t_k, t_s):
+        wf, k_sq = ctx.saved_tensors
+        s_tilde = (t_s.float() - t_k.float() * wf).contiguous()   # [B, 2, n, n]: the residual of the tangent with this source is the whole tangent
+        return ctx.eng.residual(t_wf.float().contiguous(), k_sq, s_tilde)
+
+
+def rmse_tangent(t_res: torch.Tensor, res: torch.Tensor, rmse: torch.Tensor) -> torch.Tensor:
+    """Tangent of rmse = sqrt(mean_{c,h,w} res^2): <res, t_res> / (numel * rmse), per leading index (the transpose of ``rmse_cotangent``)."""
+    numel = res.shape[-3] * res.shape[-2] * res.shape[-1]
+    return (res * t_res).sum((-3, -2, -1)) / (numel * rmse)
 
 
 class SolveSpec:
@@ -165,8 +186,10 @@ class Solve(torch.autograd.Function):
         # everything backward reads goes through save_for_backward: a tape tensor that is also an output (or shares its storage) and is
         # modified in place by the caller makes backward raise instead of linearising around the modified values
         ctx.spec, ctx.src_batch, ctx.n_ck = spec, srcd.shape[0], len(ck)
-        ctx.save_for_backward(wf0.detach().float().contiguous(), res0.detach().float().contiguous(), st_in, ksq, blobd, rmse, srcd,
-                              *(tape if tape is not None else ()), *(t for trip in ck for t in trip))
+        saved = (wf0.detach().float().contiguous(), res0.detach().float().contiguous(), st_in, ksq, blobd, rmse, srcd,
+                 *(tape if tape is not None else ()), *(t for trip in ck for t in trip))
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
         ctx.set_materialize_grads(False)
         return outs[0], outs[1], outs[2], rmse
 
@@ -236,3 +259,55 @@ class Solve(torch.autograd.Function):
                 g_st_T[:, :, a:e] = ident[:, :, a:e]
         return (None, g_wf_T if need[1] else None, g_res_T if need[2] else None, g_st_T if need[3] else None, g_k, g_s, g_w)
 
+    @staticmethod
+    def jvp(ctx, _spec, t_wf0, t_res0, t_st0, t_k, t_s, t_blob):
+        """Tangents of the four outputs: hn_step_jvp over the tape the forward kept, or (c > 1) over each segment re-run from its checkpoint."""
+        if t_blob is not None:
+            raise NotImplementedError("helmnet_amd: forward mode has no weight tangents: the weights are constants of the linearisation "
+                                      "(hn_step_jvp); take weight derivatives in reverse mode")
+        spec, eng = ctx.spec, ctx.spec.eng
+        K, c = spec.K, spec.c
+        saved = ctx.saved_tensors
+        wf0, res0, st0, ksq, _blob, rmse, _srcd = saved[:7]
+        tape = saved[7:10] if c == 1 else None
+        ck = [saved[7 + 3 * j: 10 + 3 * j] for j in range(ctx.n_ck)]
+        b, n, L = wf0.shape[0], eng.n, eng.state_len
+        dev = wf0.device
+        new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
+        own = lambda t, like: torch.zeros_like(like) if t is None else t.detach().float().clone().contiguous()  # noqa: E731
+        t_wf, t_res, t_st = own(t_wf0, wf0), own(t_res0, res0), own(t_st0, st0)
+        ident = t_st.clone() if spec.stateless else None   # levels without state pass their slot through unchanged: so does its tangent
+        for a, e in spec.stateless:
+            t_st[:, :, a:e] = 0
+        t_k = None if t_k is None else t_k.detach().float().contiguous()
+        t_s = None if t_s is None else t_s.detach().float().contiguous()
+        t_wf_h = new(K, b, 2, n, n) if spec.keep_wf else None
+        t_st_h = new(K, b, 2, L) if spec.keep_st else None
+        t_res_h = new(K, b, 2, n, n) if spec.keep_res else None
+        t_rmse = new(K, b)
+        segs = [(0, K)] if c == 1 else [(s0, min(s0 + c, K)) for s0 in range(0, K, c)]
+        for j, (s0, s1) in enumerate(segs):
+            if c == 1:
+                wf_t, res_t, st_t = tape
+                start = (wf0, res0, st0)
+            else:   # re-run the segment from its checkpoint: hn_step is deterministic, so this is the forward's tape bit for bit
+                start = ck[j]
+                m = s1 - s0
+                wf_t, res_t, st_t = new(m, b, 2, n, n), new(m, b, 2, n, n), new(m, b, 2, L)
+                wf, res, st = (t.clone() for t in start)
+                eng.step(wf, res, st, ksq, _srcd, m, res_t, wf_t, st_t, new(m, b))
+            if spec.stateless:   # the kernels saw zeros in the stateless slots
+                st_t = st_t.clone()
+                for a, e in spec.stateless:
+                    st_t[..., a:e] = 0
+            seg = lambda h: None if h is None else h[s0:s1]  # noqa: E731
+            t_res_seg = seg(t_res_h) if spec.keep_res else new(s1 - s0, b, 2, n, n)   # every iteration's residual tangent feeds the rmse tangent
+            eng.step_jvp(start[0], start[1], start[2], ksq, ctx.src_batch, wf_t, res_t, st_t, t_wf, t_res, t_st, t_k, t_s,
+                         seg(t_wf_h), t_res_seg, seg(t_st_h))
+            t_rmse[s0:s1] = rmse_tangent(t_res_seg, res_t, rmse[s0:s1])
+        out_wf = t_wf_h if spec.keep_wf else t_wf[None]
+        out_res = t_res_h if spec.keep_res else t_res[None]
+        out_st = t_st_h if spec.keep_st else t_st[None]
+        for a, e in spec.stateless:
+            out_st[..., a:e] = ident[:, :, a:e]
+        return out_wf, out_res, out_st, t_rmse

@@ -420,6 +420,7 @@ void hn_destroy(hn_ctx* ctx) {
     free_workspace(ctx);
     train_free(ctx);
     unet_f64_free(ctx);
+    jvp_free(ctx);
     krylov_free(ctx);
     spec_free(ctx->tab);
     (void)hipFree(ctx->wdev);
@@ -467,6 +468,7 @@ int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int feature
     HN_HIP(ctx, hipDeviceSynchronize());  // nothing may still read the old weights
     clear_step_graphs(ctx);
     unet_f64_free(ctx);
+    jvp_free(ctx);
     precond_free(ctx);
     ctx->raw_blob.assign(blob, blob + L.total);
     (void)hipFree(ctx->wdev);
@@ -547,6 +549,7 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     HN_HIP(ctx, hipDeviceSynchronize());
     clear_step_graphs(ctx);
     unet_f64_free(ctx);
+    jvp_free(ctx);
     krylov_free(ctx);
     if (n % 16 != 0) return fail(ctx, HN_ERR_ARG, "domain size %d must be divisible by 16", n);
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");

@@ -217,6 +217,7 @@ AxisHost spec_axis_host(int n, int pml, double sigma_max, double k);
 struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-squares problem, two dense fields for the operator
 struct RefineWs;  // GMRES refinement step (hn_krylov.hip): float64 copies of k_sq and rhs, the float64 residual, the fp32 scaled right-hand side and correction
 struct PrecondWs; // flexible GMRES cycle (hn_krylov.hip): the learned preconditioner's source, wavefield, residual and hidden states
+struct JvpWs;     // forward-mode loop (hn_jvp.hip): the fp32 blob on the device, the packed-dual activation workspace, the second tangent-state buffer and the tangent source
 struct F64Unet;   // float64 solver loop (hn_unet_f64.hip): the up-cast weights, the activation workspace and the second flat-state buffer
 // First columns of the circulant spectral derivative operators in float64: D1[j][m] = g1[(j - m) mod n], D2[j][m] = g2[(j - m) mod n] with
 // g1[d] = (1/n) sum_p i k1_p exp(2 pi i p d / n), g2 likewise from k2.  g2 is real; g1 is real but for the Nyquist term i k1[n/2] (-1)^d / n.
@@ -234,6 +235,7 @@ struct hn_ctx {
     float* wdev = nullptr;  // all re-packed weights
     std::vector<float> raw_blob;   // the blob of the last hn_load_weights as it came (PyTorch layout): the float64 path up-casts it at its first call
     hn::F64Unet* f64 = nullptr;    // built / grown by the first hn_unet_f64 / hn_step_f64 that needs it; freed by hn_load_weights, hn_set_domain, hn_destroy
+    hn::JvpWs* jvp = nullptr;      // built / grown by the first hn_step_jvp that needs it; freed by hn_load_weights, hn_set_domain, hn_destroy
     hn::KrylovWs* kry = nullptr;   // built / grown by the first hn_gmres_cycle that needs it; freed by hn_set_domain, hn_destroy
     hn::RefineWs* rfn = nullptr;   // built / grown by the first hn_gmres_refine_cycle that needs it; freed with kry (krylov_free)
     hn::PrecondWs* pcw = nullptr;  // built / grown by the first hn_fgmres_cycle with precond_iters > 0; freed with kry and by hn_load_weights (precond_free)
@@ -533,6 +535,7 @@ struct DeviceBlock {
 struct MemRange { const void* p; size_t bytes; bool written; const char* name; };
 bool first_overlap(const MemRange* r, int count, const char** a_name, const char** b_name);
 void unet_f64_free(hn_ctx* ctx);   // hn_unet_f64.hip (the caller has synchronised the device)
+void jvp_free(hn_ctx* ctx);        // hn_jvp.hip (the caller has synchronised the device)
 void krylov_free(hn_ctx* ctx);     // hn_krylov.hip: the cycle's and the refinement's workspaces (the caller has synchronised the device)
 void precond_free(hn_ctx* ctx);    // hn_krylov.hip: the learned preconditioner's workspace alone (its hidden states follow the network's depth)
 void train_free(hn_ctx* ctx);   // hn_train.hip

@@ -537,6 +537,29 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_step_vjp")
         return out
 
+    def step_jvp(self, wf0, res0, states0, k_sq, src_batch: int, wf_hist, res_hist, st_hist, t_wf, t_res, t_states, t_k_sq=None, t_src=None,
+                 t_wf_hist=None, t_res_hist=None, t_st_hist=None) -> dict:
+        """hn_step_jvp: forward mode of ``n_iter = wf_hist.shape[0]`` solver iterations, the histories of ``step`` being the tape.  ``t_wf`` /
+        ``t_res`` / ``t_states`` hold the tangents of (wf0, res0, states0) and are updated IN PLACE to those of the last iteration's outputs
+        (the same three tensors are returned); ``t_k_sq`` [B,1,n,n] and ``t_src`` [src_batch,2,n,n] are the
+        directions on k_sq and the source (None = zero); the optional histories receive the tangents after every iteration."""
+        b, T = wf0.shape[0], int(wf_hist.shape[0])
+        for t, shape, name in ((wf0, (b, 2, self.n, self.n), "wavefield"), (res0, (b, 2, self.n, self.n), "residual"),
+                               (states0, (b, 2, self.state_len), "hidden state"), (k_sq, (b, 1, self.n, self.n), "k_sq"),
+                               (wf_hist, (T, b, 2, self.n, self.n), "wf_hist"), (res_hist, (T, b, 2, self.n, self.n), "res_hist"),
+                               (st_hist, (T, b, 2, self.state_len), "st_hist"), (t_wf, wf0.shape, "t_wf"), (t_res, res0.shape, "t_res"),
+                               (t_states, states0.shape, "t_states")):
+            self._chk(t, shape, name)
+        for t, shape, name in ((t_k_sq, k_sq.shape, "t_k_sq"), (t_src, (int(src_batch), 2, self.n, self.n), "t_src"),
+                               (t_wf_hist, wf_hist.shape, "t_wf_hist"), (t_res_hist, res_hist.shape, "t_res_hist"), (t_st_hist, st_hist.shape, "t_st_hist")):
+            if t is not None:
+                self._chk(t, shape, name)
+        rc = self.lib.hn_step_jvp(self.ctx, _ptr(wf0), _ptr(res0), _ptr(states0), _ptr(k_sq), int(src_batch), b, T, _ptr(wf_hist), _ptr(res_hist),
+                                  _ptr(st_hist), _ptr(t_wf), _ptr(t_res), _ptr(t_states), _ptr(t_k_sq), _ptr(t_src), _ptr(t_wf_hist), _ptr(t_res_hist),
+                                  _ptr(t_st_hist), self._stream())
+        _lib.check(rc, self.ctx, "hn_step_jvp")
+        return {"t_wf": t_wf, "t_res": t_res, "t_states": t_states}
+
     def adam_step(self, weights, grad, exp_avg, exp_avg_sq, step: int, lr: float, betas=(0.9, 0.95), eps: float = 1e-8,
                   weight_decay: float = 0.0, clip_value: float = 0.0, trainable: Optional[torch.Tensor] = None):
         """clip_grad_value_ + torch.optim.Adam step (hybridnet.py:172-176, 250-258) on caller-owned flat device tensors, in place."""

@@ -14,6 +14,8 @@ All per-iteration arithmetic runs in libhelmnet_hip.so: ``forward`` / ``n_steps`
 loop to ``hn_step`` (fused HIP kernels), ``get_residual`` to ``hn_residual``, ``f`` to ``hn_unet``.
 ``forward64`` / ``n_steps64`` / ``deviation_from_float64`` (extension) run the same loop in float64 on ``hn_step_f64``: the reference's
 ``solver.double()`` trajectory, to measure the other precision modes against.
+``jvp`` / ``linearize`` (extension) are the solver's forward mode on ``hn_step_jvp``: directional derivatives with respect to the sound-speed
+map and the source, O(chunk) memory.
 There is no CPU path: a solver left on the CPU raises as soon as it is asked to compute.
 """
 from __future__ import annotations
@@ -28,6 +30,64 @@ from .engine import Engine, _require_no_grad
 from .laplacian import FastLaplacianWithPML
 from .source import SourceModule
 from .unet import HybridNet
+
+
+def jvp_initial_tangents(omega: float, sos: torch.Tensor, d_sos: Optional[torch.Tensor], d_source: Optional[torch.Tensor]):
+    """Tangents of ``get_initials`` and of the first residual along (d_sos, d_source): k_sq = (omega / sos)^2 gives
+    k_sq' = -2 omega^2 sos' / sos^3; the wavefield starts at zero, so wf0' = 0 and res0' = L(0) + k_sq' . 0 - src' = -src'.
+    Returns (t_k_sq or None, t_wf0, t_res0) with t_wf0 / t_res0 [B, 2, n, n]."""
+    b, n = sos.shape[0], sos.shape[-1]
+    t_k = None if d_sos is None else (-2.0 * omega ** 2 * d_sos / sos ** 3).contiguous()
+    t_wf = torch.zeros(b, 2, n, n, device=sos.device, dtype=sos.dtype)
+    t_res = t_wf.clone() if d_source is None else (-d_source).expand(b, 2, n, n).contiguous()
+    return t_k, t_wf, t_res
+
+
+def jvp_chunks(eng, wf, res, st, k_sq, src, t_wf, t_res, t_st, t_k, t_src, num_iterations: int, chunk: int):
+    """Primal and tangent interleaved, ``chunk`` iterations at a time: ``eng.step`` into a chunk-slot history, then ``eng.step_jvp`` over it with
+    the (wf, res, states) in front of the chunk as its linearisation start.  Every tensor but k_sq / src / t_k / t_src is updated in place;
+    memory is O(chunk) whatever ``num_iterations`` is.  Returns the per-sample RMSE of the last iteration, [B]."""
+    K, c = int(num_iterations), max(1, min(int(chunk), int(num_iterations)))
+    b = wf.shape[0]
+    new = lambda *shape: torch.empty(shape, device=wf.device, dtype=torch.float32)  # noqa: E731
+    wf_h, res_h, st_h, rmse = new(c, *wf.shape), new(c, *res.shape), new(c, *st.shape), new(c, b)
+    last = None
+    for s0 in range(0, K, c):
+        m = min(c, K - s0)
+        start = (wf.clone(), res.clone(), st.clone())
+        eng.step(wf, res, st, k_sq, src, m, res_h[:m], wf_h[:m], st_h[:m], rmse[:m])
+        eng.step_jvp(start[0], start[1], start[2], k_sq, src.shape[0], wf_h[:m], res_h[:m], st_h[:m], t_wf, t_res, t_st, t_k, t_src)
+        last = rmse[m - 1].clone()
+    return last
+
+
+class Linearization:
+    """``IterativeSolver.linearize``: a solve with its whole trajectory kept, to push any number of directions through."""
+
+    def __init__(self, eng, omega: float, sos, k_sq, src, start, tape, rmse):
+        self._eng, self._omega, self._sos, self._k_sq, self._src, self._start, self._tape = eng, omega, sos, k_sq, src, start, tape
+        self.wavefield, self.residual, self.rmse = tape[0][-1], tape[1][-1], rmse
+
+    def jvp(self, d_sos=None, d_source=None) -> dict:
+        """Tangents of the final wavefield, residual and RMSE along (d_sos [B,1,n,n], d_source shaped like the source); None = zero."""
+        from .autograd import rmse_tangent
+        d_sos, d_source = _jvp_directions(self._sos, self._src, d_sos, d_source)
+        t_k, t_wf, t_res = jvp_initial_tangents(self._omega, self._sos, d_sos, d_source)
+        t_st = torch.zeros_like(self._start[2])
+        self._eng.step_jvp(*self._start, self._k_sq, self._src.shape[0], *self._tape, t_wf, t_res, t_st, t_k, d_source)
+        return {"d_wavefield": t_wf, "d_residual": t_res, "d_rmse": rmse_tangent(t_res, self.residual, self.rmse)}
+
+
+def _jvp_directions(sos, src, d_sos, d_source):
+    if d_sos is not None:
+        if tuple(d_sos.shape) != tuple(sos.shape):
+            raise ValueError(f"d_sos has shape {tuple(d_sos.shape)}, expected {tuple(sos.shape)}")
+        d_sos = d_sos.detach().to(sos.device).float().contiguous()
+    if d_source is not None:
+        if tuple(d_source.shape) != tuple(src.shape):
+            raise ValueError(f"d_source has shape {tuple(d_source.shape)}, expected the source's {tuple(src.shape)}")
+        d_source = d_source.detach().to(sos.device).float().contiguous()
+    return d_sos, d_source
 
 
 class IterativeSolver(nn.Module):
@@ -474,6 +534,50 @@ class IterativeSolver(nn.Module):
         res = residual.detach().float().clone().contiguous()
         st = self.f.get_states(flatten=True).float().contiguous().clone()
         return self._run(wf, res, st, k_sq.float().contiguous(), num_iterations, return_wavefields, return_states, residuals)
+
+    # ------------------------------------------------------------------ forward mode ----
+    def _jvp_setup(self, sos_maps):
+        """(engine, sos, k_sq, source, wf0 = 0, res0, zero flat states) of a solve from cleared states; the states held in f are not touched."""
+        eng = self.engine()
+        self._check_grad_precision(eng)
+        sos = sos_maps.detach().to(self.device).float().contiguous()
+        k_sq, wf = self.get_initials(sos)
+        k_sq, src = k_sq.contiguous(), self._src()
+        res = eng.residual(wf, k_sq, src)
+        st = torch.zeros(sos.shape[0], 2, eng.state_len, device=sos.device, dtype=torch.float32)
+        return eng, sos, k_sq, src, wf, res, st
+
+    def jvp(self, sos_maps, d_sos=None, d_source=None, num_iterations=None, chunk: int = 25) -> dict:
+        """Extension: the solve of ``forward`` together with its directional derivative along (``d_sos`` [B,1,n,n], ``d_source`` shaped like
+        the source map; None = zero), in forward mode (hn_step_jvp).  Primal and tangent run interleaved, ``chunk`` iterations at a time, so
+        memory is O(chunk) whatever the iteration count.  Returns wavefield, residual, rmse [B] and d_wavefield, d_residual, d_rmse.  The
+        weights are constants; several directions at once: repeat the batch.  The hidden states held in ``f`` are neither read nor written."""
+        from .autograd import rmse_tangent
+        _require_no_grad("jvp", sos_maps, d_sos, d_source)
+        K = int(self.hparams.max_iterations if num_iterations is None else num_iterations)
+        if K < 1 or int(chunk) < 1:
+            raise ValueError("jvp needs num_iterations >= 1 and chunk >= 1")
+        eng, sos, k_sq, src, wf, res, st = self._jvp_setup(sos_maps)
+        d_sos, d_source = _jvp_directions(sos, src, d_sos, d_source)
+        t_k, t_wf, t_res = jvp_initial_tangents(float(self.hparams.omega), sos, d_sos, d_source)
+        t_st = torch.zeros_like(st)
+        rmse = jvp_chunks(eng, wf, res, st, k_sq, src, t_wf, t_res, t_st, t_k, d_source, K, chunk)
+        return {"wavefield": wf, "residual": res, "rmse": rmse, "d_wavefield": t_wf, "d_residual": t_res, "d_rmse": rmse_tangent(t_res, res, rmse)}
+
+    def linearize(self, sos_maps, num_iterations=None) -> Linearization:
+        """Extension: solve once keeping the whole trajectory (O(num_iterations) memory) and return an object with ``.wavefield``,
+        ``.residual`` and ``.jvp(d_sos=None, d_source=None)``, callable repeatedly: one column of the Jacobian per call."""
+        _require_no_grad("linearize", sos_maps)
+        K = int(self.hparams.max_iterations if num_iterations is None else num_iterations)
+        if K < 1:
+            raise ValueError("linearize needs num_iterations >= 1")
+        eng, sos, k_sq, src, wf, res, st = self._jvp_setup(sos_maps)
+        start = (wf.clone(), res.clone(), st.clone())
+        new = lambda *shape: torch.empty(shape, device=sos.device, dtype=torch.float32)  # noqa: E731
+        tape = (new(K, *wf.shape), new(K, *res.shape), new(K, *st.shape))
+        rmse = new(K, sos.shape[0])
+        eng.step(wf, res, st, k_sq, src, K, tape[1], tape[0], tape[2], rmse)
+        return Linearization(eng, float(self.hparams.omega), sos, k_sq, src, start, tape, rmse[K - 1])
 
     # ------------------------------------------------------------------ the loop in float64 ----
     def _source64(self, source, batch: int) -> torch.Tensor:

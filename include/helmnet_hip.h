@@ -20,7 +20,7 @@
  *   - alignment and overlap.  ALIGNMENT: a tensor argument needs the alignment of its element type and no more -- 4 bytes for fp32 and int32, 8 for
  *     the doubles of the _f64 family, 1 for hn_adam_step's mask -- so a view carved out of a larger allocation (a replay buffer, a history, a flat
  *     workspace) is a valid argument.  This holds for hn_laplacian, hn_residual, hn_residual_vjp, hn_rmse, hn_unet, hn_step, hn_double_conv, hn_conv8x8,
- *     hn_out_conv, hn_get_sigmas, hn_laplacian_f64, hn_residual_f64, hn_unet_f64, hn_step_f64, hn_train_grad, hn_step_vjp, hn_adam_step, hn_train_peek,
+ *     hn_out_conv, hn_get_sigmas, hn_laplacian_f64, hn_residual_f64, hn_unet_f64, hn_step_f64, hn_train_grad, hn_step_vjp, hn_step_jvp, hn_adam_step, hn_train_peek,
  *     hn_stream_verdict and hn_rows_gather / hn_rows_scatter (which copy with 16-byte accesses where pointers and rows allow it and element by element
  *     otherwise).  The exceptions name their requirement and refuse otherwise with HN_ERR_ARG: 16 bytes for the fields of hn_gmres_cycle, hn_fgmres_cycle
  *     and their _refine_ forms, and for hn_stream_swap.  Alignment can cost speed, never results beyond fp32 rounding: where wf, res or the hidden states
@@ -29,7 +29,7 @@
  *     hidden-state DoubleConvs (HN_OPT_STATE_KERNEL) on the general kernel, bit-identical; every other kernel, the spectral operator included, is the
  *     same for every alignment and gives the same bits.
  *     OVERLAP: no tensor a call WRITES may overlap any other tensor of that call; tensors that are only read may share memory.  Checked, with
- *     HN_ERR_ARG naming the two arguments and nothing enqueued, by hn_step (one tolerated form, see there), hn_unet, the _f64 family and the GMRES
+ *     HN_ERR_ARG naming the two arguments and nothing enqueued, by hn_step (one tolerated form, see there), hn_unet, hn_step_jvp, the _f64 family and the GMRES
  *     family; hn_residual_vjp refuses g == out.  The other entry points (hn_laplacian, hn_residual, hn_rmse, the three sub-module calls, hn_train_grad,
  *     hn_step_vjp, hn_adam_step, hn_rows_*, hn_stream_swap beyond its own slot rules) do not check: an output that overlaps an input or another
  *     output there gives undefined values (never an access outside the caller's tensors).
@@ -485,6 +485,35 @@ int hn_step_vjp(hn_ctx* ctx, const float* weights, const float* wf0, const float
                 int batch, int n_iter, const float* wf_hist, const float* res_hist, const float* st_hist, const float* g_wf_hist,
                 const float* g_res_hist, const float* g_st_hist, const float* g_wf_T, const float* g_res_T, const float* g_st_T, float* g_wf0,
                 float* g_res0, float* g_st0, float* g_k_sq, float* g_src, float* g_weights, int flags, void* stream);
+
+/* ---- forward mode of the solver loop (added within ABI v7: a new entry point, nothing existing changes, so HN_ABI_VERSION stays 7) ----
+ * hn_step_jvp: the Jacobian-vector product of n_iter iterations of hn_step, i.e. what torch.autograd.forward_ad computes when a dual tensor runs
+ * through the reference's solver.  Iteration t maps (wf, res, st)_{t-1} -> (wf, res, st)_t as in hn_step_vjp: index -1 is (wf0, res0, states0) and
+ * index t is slot t of the histories hn_step wrote from them (all three required: they are the tape, the linearisation point of every iteration).
+ * The UNet's primal activations are recomputed from the slot in front of each iteration beside the tangents (packed duals: a float2 (primal,
+ * tangent) per activation, one packed FMA per tap, hn_jvp.hip) and discarded: only tangents leave an iteration, memory does not grow with n_iter.
+ *     d' = J_net [wf', 1e3 res', 0, 0; st'];  wf' = d' / 1e3 + wf';  res' = L(wf') + k_sq * wf' + k_sq' * wf_t - src'
+ * In / out (device, in place): t_wf / t_res [B,2,n,n], t_states [B,2,L]: the tangents of (wf0, res0, states0) on entry, of the last iteration's
+ * outputs on return.  In (NULL = zero): t_k_sq [B,1,n,n], t_src [src_batch,2,n,n], the same direction at every iteration.  Out (optional, NULL =
+ * skip): t_wf_hist / t_res_hist [n_iter,B,2,n,n], t_st_hist [n_iter,B,2,L], the tangents after every iteration.  The source map itself is not read,
+ * only its batch (1 or B).
+ * It linearises the network of the last hn_load_weights; there are NO weight tangents (the weights are constants of the linearisation).  fp32 UNet
+ * arithmetic only (HN_ERR_UNSUPPORTED in the 16-bit modes, as hn_step_vjp).  Levels without state (zero-padded weights, see hn_train_grad) get a
+ * zero state tangent out of the kernels: their slots pass through the solver unchanged, so their tangent is the caller's identity.
+ * Alignment: any 4-byte-aligned pointers, like hn_step (the dual kernels use scalar accesses to the caller's tensors).
+ * Overlap: t_wf, t_res, t_states and the three tangent histories are written; a written tensor may overlap no other tensor of the call, tensors that
+ * are only read may share memory.  An overlap returns HN_ERR_ARG "hn_step_jvp: <a> overlaps <b>" with nothing enqueued.
+ * Other refusals: HN_ERR_ARG for a NULL required pointer, n_iter < 1, batch < 1, src_batch not in {1, batch}; HN_ERR_STATE before hn_load_weights or
+ * hn_set_domain.
+ * Workspace: the dual activations, a second tangent-state buffer and the tangent source s~ = src' - k_sq' * wf_t, built by the first call and grown
+ * by a larger batch; hn_load_weights, hn_set_domain and hn_destroy free it.  Such a first or growing call under stream capture returns HN_ERR_STATE
+ * before enqueuing anything; later calls are plain launches on the caller's stream (no side stream, no device words, no atomics) and can be captured.
+ * Determinism: two calls on equal inputs give equal bits; a sample's tangents do not depend on its batch mates; n_iter = a + b in one call equals two
+ * calls of a and b bit for bit (the second fed the first's t_* and the tape's slot a - 1 as its (wf0, res0, states0)); t_res of every iteration
+ * equals, bit for bit, hn_residual(t_wf, k_sq, s~) with s~ composed by the caller (one rounded product, one rounded difference). */
+int hn_step_jvp(hn_ctx* ctx, const float* wf0, const float* res0, const float* states0, const float* k_sq, int src_batch, int batch, int n_iter,
+                const float* wf_hist, const float* res_hist, const float* st_hist, float* t_wf, float* t_res, float* t_states, const float* t_k_sq,
+                const float* t_src, float* t_wf_hist, float* t_res_hist, float* t_st_hist, void* stream);
 
 /* ABI v5.  `event` (a hipEvent_t, or NULL to clear): every later hn_train_grad on this context records it on the caller's stream BEHIND THE FORWARD SWEEP, i.e. when
  * wf_hist / res_hist / st_hist are complete and before the backward pass starts.  The reference's training_step decides from the residual of one
