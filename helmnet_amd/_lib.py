@@ -41,6 +41,7 @@ SYMBOLS = {
     "hn_weight_count": (c_size_t, [c_int, c_int, c_int]),
     "hn_load_weights": (c_int, [c_void_p, POINTER(c_float), c_size_t, c_int, c_int, c_int, c_int]),
     "hn_set_domain": (c_int, [c_void_p, c_int, c_int, c_float, c_float]),
+    "hn_set_domain_rect": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float]),
     "hn_get_sigmas": (c_int, [c_void_p, c_void_p, c_void_p]),
     "hn_state_len": (c_int64, [c_void_p]),
     "hn_reserve": (c_int, [c_void_p, c_int]),

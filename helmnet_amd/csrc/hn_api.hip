@@ -105,20 +105,6 @@ int with_temp_weights(hn_ctx* ctx, size_t n_floats, hipStream_t s, Fill fill, Go
     return rc;
 }
 
-void free_workspace(hn_ctx* c) {
-    for (int d = 0; d <= kMaxDepth; ++d) {
-        (void)hipFree(c->buf_a[d]); c->buf_a[d] = nullptr;
-        (void)hipFree(c->buf_y[d]); c->buf_y[d] = nullptr;
-        if (d < kMaxDepth) { (void)hipFree(c->buf_o[d]); c->buf_o[d] = nullptr; }
-    }
-    (void)hipFree(c->st_tmp); c->st_tmp = nullptr;
-    (void)hipFree(c->pair_flags); c->pair_flags = nullptr; c->pair_flags_cap = 0;
-    (void)hipFree(c->pair_done); c->pair_done = nullptr;
-    (void)hipFree(c->dx_flags); c->dx_flags = nullptr;
-    (void)hipFree(c->dx_done); c->dx_done = nullptr;
-    c->cap_batch = 0;
-}
-
 int check_ready(hn_ctx* ctx, int batch) {
     if (!ctx) return HN_ERR_ARG;
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "hn_load_weights has not been called");
@@ -144,6 +130,25 @@ __global__ void k_rmse_finalize(float* __restrict__ v, int count, float inv_n) {
 }
 
 }  // namespace
+
+void free_workspace(hn_ctx* c) {
+    for (int d = 0; d <= kMaxDepth; ++d) {
+        (void)hipFree(c->buf_a[d]); c->buf_a[d] = nullptr;
+        (void)hipFree(c->buf_y[d]); c->buf_y[d] = nullptr;
+        if (d < kMaxDepth) { (void)hipFree(c->buf_o[d]); c->buf_o[d] = nullptr; }
+    }
+    (void)hipFree(c->st_tmp); c->st_tmp = nullptr;
+    (void)hipFree(c->pair_flags); c->pair_flags = nullptr; c->pair_flags_cap = 0;
+    (void)hipFree(c->pair_done); c->pair_done = nullptr;
+    (void)hipFree(c->dx_flags); c->dx_flags = nullptr;
+    (void)hipFree(c->dx_done); c->dx_done = nullptr;
+    c->cap_batch = 0;
+}
+
+void launch_rmse_finalize(float* v, int count, float inv_n, hipStream_t s) {
+    hipLaunchKernelGGL(k_rmse_finalize, dim3((count + 255) / 256), dim3(256), 0, s, v, count, inv_n);
+}
+
 // Zero `bytes` (a multiple of 4) at p on stream s with a kernel of this library instead of hipMemsetAsync.  [seen, r5, tools/graph_null_stream_probe.py] a
 // hipMemsetAsync on the legacy default stream -- from anyone in the process -- between the capture of a graph that holds memset nodes and its replay leaves the
 // replay's memsets zeroing something else (a captured training step then adds its weight gradients onto garbage): a captured hn_train_grad holds no memset
@@ -405,7 +410,7 @@ int64_t hn_get_counter(const hn_ctx* ctx, int counter) {
         case HN_CNT_TRAIN_FWD_EVENTS: return ctx->train_fwd_events;
         case HN_CNT_FLAG_SYNC_ITERATIONS: return ctx->flag_sync_iterations;
         case HN_CNT_SIDE_CANDIDATE: return ctx->picks[0].known.empty() ? -1 : ctx->picks[0].last_chosen;
-        case HN_CNT_SPECTRAL_ROUTE: return ctx->tab.n == 0 ? 0 : ctx->tab.pow2 ? 1 : ctx->tab.pfa_p != 0 ? 2 : ctx->tab.mix_p != 0 ? 4 : 3;
+        case HN_CNT_SPECTRAL_ROUTE: return ctx->rect != nullptr ? 5 : ctx->tab.n == 0 ? 0 : ctx->tab.pow2 ? 1 : ctx->tab.pfa_p != 0 ? 2 : ctx->tab.mix_p != 0 ? 4 : 3;
         default: return -1;
     }
 }
@@ -423,6 +428,7 @@ void hn_destroy(hn_ctx* ctx) {
     jvp_free(ctx);
     krylov_free(ctx);
     spec_free(ctx->tab);
+    spec_rect_free(ctx);
     (void)hipFree(ctx->wdev);
     (void)hipFree(ctx->fragdev);
     for (int j = 0; j < ctx->n_streams; ++j) {
@@ -536,6 +542,7 @@ int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int feature
     if (ctx->have_weights && ctx->depth != depth) free_workspace(ctx);
     ctx->depth = depth;
     ctx->have_weights = true;
+    if (ctx->rect) rect_state_layout(ctx);
     if (ctx->tab.n) {  // state layout depends on depth
         ctx->state_len = 0;
         for (int d = 0; d < depth; ++d) { ctx->state_off[d] = ctx->state_len; ctx->state_len += (int64_t)(ctx->tab.n >> d) * (ctx->tab.n >> d); }
@@ -554,6 +561,7 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     if (n % 16 != 0) return fail(ctx, HN_ERR_ARG, "domain size %d must be divisible by 16", n);
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
     if (n != ctx->tab.n) free_workspace(ctx);
+    spec_rect_free(ctx);   // (a rectangular domain's tab.n is 0: its workspace has just gone)
     int rc = spec_build(ctx, n, pml, (double)sigma_max, (double)k);
     if (rc != HN_OK) return rc;
     const int depth = ctx->have_weights ? ctx->depth : 4;
@@ -562,8 +570,39 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     return build_inc_sigma_map(ctx);
 }
 
+// h == w is hn_set_domain itself; otherwise the per-axis tables of hn_spectral_rect.hip, and tab stays empty
+int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, float k) {
+    if (!ctx) return HN_ERR_ARG;
+    if (h == w) return hn_set_domain(ctx, h, pml, sigma_max, k);
+    const int m = ctx->have_weights && ctx->depth > 4 ? 1 << ctx->depth : 16;
+    for (const int len : {h, w}) {
+        if (len % m != 0) return fail(ctx, HN_ERR_ARG, "domain size %d x %d: %d must be divisible by %d", h, w, len, m);
+        if (len < 16 || len > 2048) return fail(ctx, HN_ERR_ARG, "domain size %d x %d: %d outside [16, 2048]", h, w, len);
+        if (pml < 1 || 2 * pml > len) return fail(ctx, HN_ERR_ARG, "PML size %d does not fit domain %d x %d", pml, h, w);
+    }
+    if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
+    DeviceGuard guard(ctx);
+    HN_HIP(ctx, hipDeviceSynchronize());
+    clear_step_graphs(ctx);
+    unet_f64_free(ctx);
+    jvp_free(ctx);
+    krylov_free(ctx);
+    free_workspace(ctx);
+    spec_free(ctx->tab);
+    int rc = build_inc_sigma_map(ctx);   // (no n x n domain: frees the map)
+    if (rc != HN_OK) return rc;
+    if ((rc = spec_rect_build(ctx, h, w, pml, (double)sigma_max, (double)k)) != HN_OK) return rc;
+    rect_state_layout(ctx);
+    return HN_OK;
+}
+
 int hn_get_sigmas(hn_ctx* ctx, float* out, void* stream) {
     if (!ctx || !out) return fail(ctx, HN_ERR_ARG, "hn_get_sigmas: NULL argument");
+    if (ctx->rect) {
+        DeviceGuard guard(ctx);
+        HN_HIP(ctx, hipMemcpyAsync(out, ctx->rect->sigmas, sizeof(float) * 2 * ctx->rect->h * ctx->rect->w, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return HN_OK;
+    }
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     DeviceGuard guard(ctx);
     HN_HIP(ctx, hipMemcpyAsync(out, ctx->tab.sigmas, sizeof(float) * 2 * ctx->tab.n * ctx->tab.n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -573,6 +612,10 @@ int hn_get_sigmas(hn_ctx* ctx, float* out, void* stream) {
 int64_t hn_state_len(const hn_ctx* ctx) { return ctx ? ctx->state_len : 0; }
 
 int hn_reserve(hn_ctx* ctx, int max_batch) {
+    if (ctx && ctx->rect) {
+        DeviceGuard guard(ctx);
+        return rect_reserve(ctx, max_batch, nullptr);
+    }
     int rc = check_ready(ctx, max_batch);
     if (rc != HN_OK) return rc;
     if (max_batch <= ctx->cap_batch) return HN_OK;
@@ -653,6 +696,7 @@ int hn_laplacian(hn_ctx* ctx, const float* wf, float* out, int batch, void* stre
     if (!ctx || !wf || !out) return fail(ctx, HN_ERR_ARG, "hn_laplacian: NULL argument");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     DeviceGuard guard(ctx);
+    if (ctx->rect) return spec_rect_apply(ctx, wf, out, nullptr, nullptr, 1, batch, nullptr, (hipStream_t)stream);
     return spec_apply(ctx, wf, out, nullptr, nullptr, 1, batch, nullptr, (hipStream_t)stream);
 }
 
@@ -662,11 +706,13 @@ int hn_residual(hn_ctx* ctx, const float* wf, const float* k_sq, const float* sr
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
     DeviceGuard guard(ctx);
+    if (ctx->rect) return spec_rect_apply(ctx, wf, res, k_sq, src, src_batch, batch, nullptr, (hipStream_t)stream);
     return spec_apply(ctx, wf, res, k_sq, src, src_batch, batch, nullptr, (hipStream_t)stream);
 }
 
 int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, int batch, void* stream) {
     if (!ctx || !g || !k_sq || !out) return fail(ctx, HN_ERR_ARG, "hn_residual_vjp: NULL argument");
+    if (ctx->rect) return rect_unsupported(ctx, "hn_residual_vjp");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     DeviceGuard guard(ctx);
     return spec_adjoint(ctx, g, out, k_sq, nullptr, batch, (hipStream_t)stream);
@@ -674,11 +720,11 @@ int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, 
 
 int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream) {
     if (!ctx || !res || !rmse) return fail(ctx, HN_ERR_ARG, "hn_rmse: NULL argument");
-    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    if (ctx->tab.n == 0 && !ctx->rect) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
-    const long per = 2L * ctx->tab.n * ctx->tab.n;
+    const long per = ctx->rect ? 2L * ctx->rect->h * ctx->rect->w : 2L * ctx->tab.n * ctx->tab.n;
     if (int rcz = zero_async(ctx, rmse, sizeof(float) * batch, s); rcz != HN_OK) return rcz;
     hipLaunchKernelGGL(k_sumsq, dim3(32, batch), dim3(256), 0, s, res, rmse, per);
     hipLaunchKernelGGL(k_rmse_finalize, dim3((batch + 255) / 256), dim3(256), 0, s, rmse, batch, 1.0f / (float)per);
@@ -689,6 +735,10 @@ int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream)
 int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states_out, float* d_out, int batch, void* stream) {
     if (!ctx || !in6 || !states_in || !states_out || !d_out) return fail(ctx, HN_ERR_ARG, "hn_unet: NULL argument");
     if (states_in == states_out) return fail(ctx, HN_ERR_ARG, "hn_unet: states_in must not alias states_out");
+    if (ctx->rect) {
+        DeviceGuard guard(ctx);
+        return rect_unet(ctx, in6, states_in, states_out, d_out, batch, (hipStream_t)stream);
+    }
     int rc = check_ready(ctx, batch);
     if (rc != HN_OK) return rc;
     const long plane = (long)ctx->tab.n * ctx->tab.n;
@@ -995,6 +1045,10 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
     if (n_iter < 0) return fail(ctx, HN_ERR_ARG, "n_iter must be >= 0");
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
+    if (ctx->rect) {
+        DeviceGuard guard(ctx);
+        return rect_step(ctx, wf, res, states, k_sq, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, (hipStream_t)stream);
+    }
     int rc = check_ready(ctx, batch);
     if (rc != HN_OK) return rc;
     const long plane = (long)ctx->tab.n * ctx->tab.n;

@@ -271,6 +271,7 @@ extern "C" {
 
 int hn_laplacian_f64(hn_ctx* ctx, const double* wf, double* out, int batch, void* stream) {
     if (!ctx || !wf || !out) return hn::fail(ctx, HN_ERR_ARG, "hn_laplacian_f64: NULL argument");
+    if (ctx->rect) return hn::rect_unsupported(ctx, "hn_laplacian_f64");
     if (batch <= 0) return hn::fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     hn::DeviceGuard guard(ctx);
     return hn::f64_apply(ctx, wf, out, nullptr, nullptr, 1, nullptr, batch, (hipStream_t)stream);
@@ -279,6 +280,7 @@ int hn_laplacian_f64(hn_ctx* ctx, const double* wf, double* out, int batch, void
 int hn_residual_f64(hn_ctx* ctx, const double* wf, const double* k_sq, const double* src, int src_batch, double* res, double* rmse, int batch,
                     void* stream) {
     if (!ctx || !wf || !k_sq || !src) return hn::fail(ctx, HN_ERR_ARG, "hn_residual_f64: NULL argument");
+    if (ctx->rect) return hn::rect_unsupported(ctx, "hn_residual_f64");
     if (!res && !rmse) return hn::fail(ctx, HN_ERR_ARG, "hn_residual_f64: res and rmse are both NULL");
     if (batch <= 0) return hn::fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     if (src_batch != 1 && src_batch != batch)

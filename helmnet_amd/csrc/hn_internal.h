@@ -214,6 +214,20 @@ struct AxisHost {
     std::vector<float2> fa, fb;
 };
 AxisHost spec_axis_host(int n, int pml, double sigma_max, double k);
+// A rectangular h x w domain (hn_set_domain_rect with h != w): one factorisation len = P * Q and one set of tables per axis (hn_spectral_rect.hip).
+// While it exists ctx->tab is empty (tab.n == 0): whatever is built for n x n cannot run on it by accident.
+struct RectAxis {
+    int len = 0, P = 0, Q = 0;   // P odd in [1, 127], Q = 2^k in [16, 2048]
+    float2 *tw_q = nullptr, *wp = nullptr;   // exp(-2 pi i m / Q), exp(-2 pi i m / P)
+    float *k1m = nullptr, *k2m = nullptr;    // [P][Q]: k and -k^2 in the order the kernel meets the spectrum (Good-Thomas output map, k2 bit-reversed)
+    float2 *a = nullptr, *b = nullptr;       // PML coefficients, natural order
+    int* slot = nullptr;                     // [len]: where element i of a line sits in the [P][Q] layout
+};
+struct RectDomain {
+    int h = 0, w = 0;
+    RectAxis cols, rows;       // cols: lines of length h (the y axis); rows: lines of length w (the x axis)
+    float* sigmas = nullptr;   // [2, h, w]
+};
 struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-squares problem, two dense fields for the operator
 struct RefineWs;  // GMRES refinement step (hn_krylov.hip): float64 copies of k_sq and rhs, the float64 residual, the fp32 scaled right-hand side and correction
 struct PrecondWs; // flexible GMRES cycle (hn_krylov.hip): the learned preconditioner's source, wavefield, residual and hidden states
@@ -311,6 +325,7 @@ struct hn_ctx {
     const float* outc_b = nullptr;  // [2]
     // domain
     hn::SpecTables tab;
+    hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty
     int64_t state_len = 0;
     int64_t state_off[hn::kMaxDepth]{};
     // workspace
@@ -513,6 +528,15 @@ int spec_mixed_build(hn_ctx* ctx, const AxisHost& ax, int P, int Q);
 int spec_mixed_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, long src_sb, int batch, bool resid,
                      float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride);
 int spec_mixed_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
+// ---- spectral, rectangular domain (hn_spectral_rect.hip) ----
+// (P, Q) with len = P * Q, P odd in [1, 127], Q a power of two in [16, 2048]: every multiple of 16 in [16, 2048]; false otherwise
+bool spec_rect_factor(int len, int* P, int* Q);
+int spec_rect_build(hn_ctx* ctx, int h, int w, int pml, double sigma_max, double k);   // ctx->rect: both axes' tables, the sigma maps, the kernels' LDS attribute
+void spec_rect_free(hn_ctx* ctx);
+int spec_rect_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch, int batch, float* accum_sumsq,
+                    hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);   // as spec_apply
+// HN_ERR_UNSUPPORTED "<who>: not implemented on a rectangular domain ..." (every entry point that reads the domain and has no rectangular path)
+int rect_unsupported(hn_ctx* ctx, const char* who);
 // ---- float64 residual check (hn_f64.hip) ----
 // out = L(wf) [+ ksq * wf - src] in float64 (out nullable) and / or rmse[b] = sqrt(mean over (c, h, w) of out^2) (nullable)
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s);
@@ -644,6 +668,20 @@ struct UnetCall {
     bool defer_join = false;              // leave the side stream unjoined: the next call on this lane (or side_join) waits for it
 };
 int unet_forward(hn_ctx* ctx, const UnetCall& c);
+// ---- the same on a rectangular domain (hn_unet_rect.hip): one stream, layer by layer; side_lane, after_down0 and defer_join are not used ----
+int unet_forward_rect(hn_ctx* ctx, const UnetCall& c);
+void rect_state_layout(hn_ctx* ctx);   // state_len / state_off of ctx->rect for the loaded depth
+int rect_reserve(hn_ctx* ctx, int max_batch, hipStream_t s);   // hn_reserve; s (nullable): HN_ERR_STATE when it would build or grow under capture of s
+int rect_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states_out, float* d_out, int batch, hipStream_t s);
+int rect_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* src, int src_batch, int batch, int n_iter, float* res_hist,
+              float* wf_hist, float* st_hist, float* rmse_hist, hipStream_t s);
+void free_workspace(hn_ctx* ctx);   // (hn_api.hip)
+void launch_rmse_finalize(float* v, int count, float inv_n, hipStream_t s);   // (hn_api.hip) v[i] = sqrt(v[i] * inv_n): sums of squares -> RMSE rows
+// the direct fp32 kernels of hn_unet.hip (k_double_conv, k_down8x8, k_up8x8: any H, W) for a driver in another file; fin as launch_dc8's
+void launch_dc_direct(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s);
+void launch_state_direct(const StateLevel& v, int batch, hipStream_t s);
+void launch_down_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s);
+void launch_up_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s);
 // make stream s wait for the hidden-state kernels of the previous unet_forward with defer_join on this lane
 int side_join(hn_ctx* ctx, hn_ctx::SideLane* side_lane, hipStream_t s);
 bool side_flags_apply(hn_ctx* ctx, hipStream_t s);

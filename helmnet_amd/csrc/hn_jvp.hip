@@ -422,6 +422,7 @@ int hn_step_jvp(hn_ctx* ctx, const float* wf0, const float* res0, const float* s
                 const float* t_src, float* t_wf_hist, float* t_res_hist, float* t_st_hist, void* stream) {
     if (!ctx || !wf0 || !res0 || !states0 || !k_sq || !wf_hist || !res_hist || !st_hist || !t_wf || !t_res || !t_states)
         return fail(ctx, HN_ERR_ARG, "hn_step_jvp: NULL argument (the inputs, the three histories and the three tangents are required)");
+    if (ctx->rect) return rect_unsupported(ctx, "hn_step_jvp");
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "hn_load_weights has not been called");
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (n_iter < 1) return fail(ctx, HN_ERR_ARG, "hn_step_jvp: n_iter must be >= 1 (got %d)", n_iter);

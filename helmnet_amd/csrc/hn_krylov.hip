@@ -610,6 +610,7 @@ int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, c
                      int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64) {
     if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64) || (flexible && !zbasis))
         return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (ctx->rect) return rect_unsupported(ctx, who);
     if (ctx->tab.n == 0) return fail(ctx, refine || flexible ? HN_ERR_STATE : HN_ERR_ARG, "%s: hn_set_domain has not been called", who);
     if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
     if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);

@@ -179,6 +179,7 @@ int hn_stream_swap(hn_ctx* ctx, float* wf, float* res, float* states, float* k_s
                    float* out_wf, float* out_res, void* stream) {
     const char* who = "hn_stream_swap";
     if (!ctx) return HN_ERR_ARG;
+    if (ctx->rect) return rect_unsupported(ctx, who);
     if (ctx->tab.n == 0 || ctx->state_len == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain / hn_load_weights have not been called", who);
     if (!wf || !res || !states || !k_sq || !src || (count > 0 && !ops)) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (batch < 1 || count < 0 || n_maps < 0) return fail(ctx, HN_ERR_ARG, "%s: batch %d, count %d, n_maps %lld", who, batch, count, (long long)n_maps);

@@ -1763,6 +1763,7 @@ int train_reserve(hn_ctx* ctx, hn_ctx::TrainWs& W, int batch, int n_unroll, int 
 
 int train_ready(hn_ctx* ctx, int batch, int n_unroll) {
     if (!ctx) return HN_ERR_ARG;
+    if (ctx->rect) return rect_unsupported(ctx, "hn_train_reserve / hn_train_grad / hn_step_vjp");
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "hn_load_weights has not been called (it defines depth and activation)");
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0 || n_unroll <= 0) return fail(ctx, HN_ERR_ARG, "batch and n_unroll must be positive (got %d, %d)", batch, n_unroll);

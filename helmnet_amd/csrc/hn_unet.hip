@@ -731,4 +731,30 @@ int module_out_conv(hn_ctx* ctx, const float* x, const float* w_io, const float*
     return HN_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The same direct kernels for a driver in another file (hn_unet_rect.hip): HN_PREC_FP32_VALU's layers, and conv_state where the streaming kernel
+// does not apply.  Any H, W.
+// ------------------------------------------------------------------------------------------
+void launch_dc_direct(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s) {
+    const DcEpi noepi{nullptr, nullptr, nullptr, nullptr};
+    switch (kind) {
+        case DcKind::Inc: launch_dc<2, 2, 2, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s); break;
+        case DcKind::Signal: launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s); break;
+        case DcKind::Bottleneck: launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s); break;
+        case DcKind::Decoder:
+            if (fin == nullptr) launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s);
+            else launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(a, b, c, out, w, DcEpi{ctx->outc_w, ctx->outc_b, fin->d_out, fin->wf_out, fin->wf_in}, H, W, batch, s);
+            break;
+    }
+}
+void launch_state_direct(const StateLevel& v, int batch, hipStream_t s) {
+    launch_dc<kFeat, kState, 0, kState, kState, 0>(v.a, v.b, Src{nullptr, 0, 0, 1.f}, v.out, v.w, DcEpi{nullptr, nullptr, nullptr, nullptr}, v.H, v.W, batch, s);
+}
+void launch_down_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s) {
+    hipLaunchKernelGGL(k_down8x8, dim3(cdiv(Win / 2, DownCfg::TW), cdiv(Hin / 2, DownCfg::TH), batch), dim3(DownCfg::NT), 0, s, in, out, w, Hin, Win);
+}
+void launch_up_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s) {
+    hipLaunchKernelGGL(k_up8x8, dim3(cdiv(Win, UpCfg::TW), cdiv(Hin, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s, in, out, w, Hin, Win);
+}
+
 }  // namespace hn

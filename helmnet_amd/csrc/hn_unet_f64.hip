@@ -365,6 +365,7 @@ int forward(hn_ctx* ctx, const double* in6, const double* st_in, double* st_out,
 }
 
 int check_f64_ready(hn_ctx* ctx, int batch) {
+    if (ctx->rect) return rect_unsupported(ctx, "hn_unet_f64 / hn_step_f64");
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "hn_load_weights has not been called");
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);

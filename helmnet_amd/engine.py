@@ -152,7 +152,8 @@ class Engine:
             torch.cuda.current_stream()  # make sure torch initialised HIP on this device first
             _lib.check(self.lib.hn_create(ctypes.byref(ctx), self.device.index), None, "hn_create")
         self.ctx = ctx
-        self.n = 0
+        self.n = 0                # side of a square domain; 0 without a domain and on a rectangular one
+        self.hw = (0, 0)          # (rows, columns) of the domain
         self.depth = 0
         self.weights_key = None
         self.domain_key = None
@@ -182,7 +183,19 @@ class Engine:
     def set_domain(self, n: int, pml: int, sigma_max: float, k: float):
         _lib.check(self.lib.hn_set_domain(self.ctx, int(n), int(pml), float(sigma_max), float(k)), self.ctx, "hn_set_domain")
         self.n = int(n)
+        self.hw = (int(n), int(n))
         self.domain_key = (int(n), int(pml), float(sigma_max), float(k))
+
+    def set_domain_rect(self, h: int, w: int, pml: int, sigma_max: float, k: float):
+        """An h x w domain (hn_set_domain_rect): h rows by w columns, tensors [B, C, h, w].  h == w is ``set_domain(h, ...)`` itself.  On h != w the
+        operators, ``unet`` and ``step`` work in the 'fp32' and 'valu' precision modes; every other method that reads the domain raises
+        NotImplementedError naming the rectangular domain.  ``domain_key`` carries both sizes: ((h, w), pml, sigma_max, k)."""
+        if int(h) == int(w):
+            return self.set_domain(h, pml, sigma_max, k)
+        _lib.check(self.lib.hn_set_domain_rect(self.ctx, int(h), int(w), int(pml), float(sigma_max), float(k)), self.ctx, "hn_set_domain_rect")
+        self.n = 0
+        self.hw = (int(h), int(w))
+        self.domain_key = ((int(h), int(w)), int(pml), float(sigma_max), float(k))
 
     def set_unet_precision(self, mode: str):
         """Arithmetic of the UNet convolutions for this context: 'fp32' (default), 'bf16x3', 'fp16', 'bf16x2', 'valu'."""
@@ -204,7 +217,7 @@ class Engine:
         number <= 64 of iterations per graph, 'train_lanes' 1/2 (hn_train_grad: the halves of the batch as two chains of launches on two streams).
         'spectral_pfa' and 'spectral_mixed' 0/1 (FFT for every other size P * 2^k, P odd; default 0) are read when the spectral tables are built:
         changing one re-builds them; counter('spectral_route') tells which kernels the domain runs on (1 power of two, 2 prime-factor, 3 dense,
-        4 mixed).
+        4 mixed, 5 rectangular).
         'spectral_cols' 0..2 is bit-exact: for a fixed 'spectral_radix16' these three column kernels give the same bits (with 'spectral_radix16' 0 it
         is not read); 3 is another factorisation (fp32 rounding).  'spectral_plain' (laboratory knob) 1: the 256- / 512-point kernels on plain C++
         complex helpers, bit-identical to 0.  'spectral_radix16' and 'spectral_pfa' select other kernels for the same fp32 arithmetic: results agree to fp32 rounding (every
@@ -213,7 +226,7 @@ class Engine:
         if name not in _lib.HN_OPTION:
             raise ValueError(f"unknown option {name!r} (choose from {sorted(_lib.HN_OPTION)})")
         _lib.check(self.lib.hn_set_option(self.ctx, _lib.HN_OPTION[name], int(value)), self.ctx, "hn_set_option")
-        if name in ("spectral_pfa", "spectral_mixed") and self.domain_key is not None:
+        if name in ("spectral_pfa", "spectral_mixed") and self.domain_key is not None and self.n:   # (a rectangular domain reads neither)
             self.set_domain(*self.domain_key)
 
     def counter(self, name: str) -> int:
@@ -250,22 +263,22 @@ class Engine:
 
     # ---- operators ---------------------------------------------------------------------
     def sigmas(self) -> torch.Tensor:
-        out = torch.empty(2, self.n, self.n, device=self.device, dtype=torch.float32)
+        out = torch.empty(2, *self.hw, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.hn_get_sigmas(self.ctx, _ptr(out), self._stream()), self.ctx, "hn_get_sigmas")
         return out
 
     def laplacian(self, wf: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield")
+        self._chk(wf, (b, 2, *self.hw), "wavefield")
         out = torch.empty_like(wf)
         _lib.check(self.lib.hn_laplacian(self.ctx, _ptr(wf), _ptr(out), b, self._stream()), self.ctx, "hn_laplacian")
         return out
 
     def residual(self, wf: torch.Tensor, k_sq: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield")
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source")
+        self._chk(wf, (b, 2, *self.hw), "wavefield")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk(src, (src.shape[0], 2, *self.hw), "source")
         out = torch.empty_like(wf)
         rc = self.lib.hn_residual(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), src.shape[0], _ptr(out), b, self._stream())
         _lib.check(rc, self.ctx, "hn_residual")
@@ -274,15 +287,15 @@ class Engine:
     def residual_vjp(self, g: torch.Tensor, k_sq: torch.Tensor) -> torch.Tensor:
         """J^T g of ``residual`` with respect to the wavefield: L^H(g) + k_sq * g."""
         b = g.shape[0]
-        self._chk(g, (b, 2, self.n, self.n), "cotangent")
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
+        self._chk(g, (b, 2, *self.hw), "cotangent")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
         out = torch.empty_like(g)
         _lib.check(self.lib.hn_residual_vjp(self.ctx, _ptr(g), _ptr(k_sq), _ptr(out), b, self._stream()), self.ctx, "hn_residual_vjp")
         return out
 
     def rmse(self, res: torch.Tensor) -> torch.Tensor:
         b = res.shape[0]
-        self._chk(res, (b, 2, self.n, self.n), "residual")
+        self._chk(res, (b, 2, *self.hw), "residual")
         out = torch.empty(b, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.hn_rmse(self.ctx, _ptr(res), _ptr(out), b, self._stream()), self.ctx, "hn_rmse")
         return out
@@ -290,13 +303,13 @@ class Engine:
     def _gmres_buffers(self, what: str, x, x_dtype, k_sq, rhs, restart: int, basis, hess):
         """What the four cycle methods share: the grad refusal, the shape checks, ``basis`` / ``hess`` (allocated when not given) and the fresh ``rmse``
         [restart + 1, B] and ``k_used`` [B] int32 tables."""
-        b, p2 = x.shape[0], 2 * self.n * self.n
+        b, p2 = x.shape[0], 2 * self.hw[0] * self.hw[1]
         for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
             if isinstance(t, torch.Tensor) and t.requires_grad:
                 raise RuntimeError(f"{what}: {name} requires grad; the GMRES cycle is not differentiable")
-        self._chk(x, (b, 2, self.n, self.n), "x", x_dtype)
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(rhs, (rhs.shape[0], 2, self.n, self.n), "rhs")
+        self._chk(x, (b, 2, *self.hw), "x", x_dtype)
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk(rhs, (rhs.shape[0], 2, *self.hw), "rhs")
         new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
         basis = self._chk(new(b, restart + 1, p2) if basis is None else basis, (b, restart + 1, p2), "basis")
         hess = self._chk(new(b, restart + 1, restart, 2) if hess is None else hess, (b, restart + 1, restart, 2), "hess")
@@ -304,7 +317,7 @@ class Engine:
 
     def _zbasis(self, b: int, restart: int, zbasis):
         """The flexible cycles' ``zbasis`` [B, restart, 2 n^2], allocated when not given."""
-        shape = (b, restart, 2 * self.n * self.n)
+        shape = (b, restart, 2 * self.hw[0] * self.hw[1])
         return self._chk(torch.empty(shape, device=self.device, dtype=torch.float32) if zbasis is None else zbasis, shape, "zbasis")
 
     def gmres_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
@@ -366,7 +379,7 @@ class Engine:
     # ---- the same operators in float64: the check the fp32 residual is measured against (hn_f64.hip) ----
     def laplacian64(self, wf: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield", torch.float64)
+        self._chk(wf, (b, 2, *self.hw), "wavefield", torch.float64)
         out = torch.empty_like(wf)
         _lib.check(self.lib.hn_laplacian_f64(self.ctx, _ptr(wf), _ptr(out), b, self._stream()), self.ctx, "hn_laplacian_f64")
         return out
@@ -374,9 +387,9 @@ class Engine:
     def residual64(self, wf: torch.Tensor, k_sq: torch.Tensor, src: torch.Tensor, want_res: bool = True, want_rmse: bool = True):
         """(res [B,2,n,n] or None, rmse [B] or None), both float64; the RMSE is summed in a fixed order (bit-reproducible)."""
         b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield", torch.float64)
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq", torch.float64)
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source", torch.float64)
+        self._chk(wf, (b, 2, *self.hw), "wavefield", torch.float64)
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq", torch.float64)
+        self._chk(src, (src.shape[0], 2, *self.hw), "source", torch.float64)
         res = torch.empty_like(wf) if want_res else None
         rmse = torch.empty(b, device=self.device, dtype=torch.float64) if want_rmse else None
         rc = self.lib.hn_residual_f64(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), src.shape[0], _ptr(res), _ptr(rmse), b, self._stream())
@@ -387,9 +400,9 @@ class Engine:
     def unet64(self, in6: torch.Tensor, states_in: torch.Tensor):
         """(d [B,2,n,n], states_out [B,2,L]) = HybridNet(in6, states_in) in float64, the weights of the last load_weights up-cast."""
         b = in6.shape[0]
-        self._chk(in6, (b, 6, self.n, self.n), "network input", torch.float64)
+        self._chk(in6, (b, 6, *self.hw), "network input", torch.float64)
         self._chk(states_in, (b, 2, self.state_len), "hidden state", torch.float64)
-        d = torch.empty(b, 2, self.n, self.n, device=self.device, dtype=torch.float64)
+        d = torch.empty(b, 2, *self.hw, device=self.device, dtype=torch.float64)
         states_out = torch.empty_like(states_in)
         rc = self.lib.hn_unet_f64(self.ctx, _ptr(in6), _ptr(states_in), _ptr(states_out), _ptr(d), b, self._stream())
         _lib.check(rc, self.ctx, "hn_unet_f64")
@@ -401,9 +414,9 @@ class Engine:
 
     def unet(self, in6: torch.Tensor, states_in: torch.Tensor):
         b = in6.shape[0]
-        self._chk(in6, (b, 6, self.n, self.n), "network input")
+        self._chk(in6, (b, 6, *self.hw), "network input")
         self._chk(states_in, (b, 2, self.state_len), "hidden state")
-        d = torch.empty(b, 2, self.n, self.n, device=self.device, dtype=torch.float32)
+        d = torch.empty(b, 2, *self.hw, device=self.device, dtype=torch.float32)
         states_out = torch.empty_like(states_in)
         rc = self.lib.hn_unet(self.ctx, _ptr(in6), _ptr(states_in), _ptr(states_out), _ptr(d), b, self._stream())
         _lib.check(rc, self.ctx, "hn_unet")
@@ -460,15 +473,15 @@ class Engine:
     def _step(self, entry, name: str, dtype, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist):
         """``step`` / ``step64``: the checks and the one library call, for tensors of ``dtype``."""
         b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield", dtype)
-        self._chk(res, (b, 2, self.n, self.n), "residual", dtype)
+        self._chk(wf, (b, 2, *self.hw), "wavefield", dtype)
+        self._chk(res, (b, 2, *self.hw), "residual", dtype)
         self._chk(states, (b, 2, self.state_len), "hidden state", dtype)
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq", dtype)
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source", dtype)
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq", dtype)
+        self._chk(src, (src.shape[0], 2, *self.hw), "source", dtype)
         if res_hist is not None:
-            self._chk(res_hist, (n_iter, b, 2, self.n, self.n), "res_hist", dtype)
+            self._chk(res_hist, (n_iter, b, 2, *self.hw), "res_hist", dtype)
         if wf_hist is not None:
-            self._chk(wf_hist, (n_iter, b, 2, self.n, self.n), "wf_hist", dtype)
+            self._chk(wf_hist, (n_iter, b, 2, *self.hw), "wf_hist", dtype)
         if st_hist is not None:
             self._chk(st_hist, (n_iter, b, 2, self.state_len), "st_hist", dtype)
         if rmse_hist is not None:
@@ -492,14 +505,14 @@ class Engine:
         ``n_steps(..., True, True)`` as stacked tensors, and with ``input_grads`` the gradients of the three inputs."""
         b, n_w = wf.shape[0], int(self.lib.hn_weight_count(8, self.depth, 2))
         self._chk(weights, (n_w,), "weights")
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield")
-        self._chk(res, (b, 2, self.n, self.n), "residual")
+        self._chk(wf, (b, 2, *self.hw), "wavefield")
+        self._chk(res, (b, 2, *self.hw), "residual")
         self._chk(states, (b, 2, self.state_len), "hidden state")
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk(src, (src.shape[0], 2, *self.hw), "source")
         T = int(n_unroll)
         new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
-        out = {"wavefields": new(T, b, 2, self.n, self.n), "residuals": new(T, b, 2, self.n, self.n), "states": new(T, b, 2, self.state_len),
+        out = {"wavefields": new(T, b, 2, *self.hw), "residuals": new(T, b, 2, *self.hw), "states": new(T, b, 2, self.state_len),
                "loss": new(1), "grad": grad if grad is not None else new(n_w)}
         self._chk(out["grad"], (n_w,), "grad")
         g_in = [new(*wf.shape), new(*res.shape), new(*states.shape)] if input_grads else [None, None, None]
@@ -519,14 +532,14 @@ class Engine:
         b, T = wf0.shape[0], int(wf_hist.shape[0])
         n_w = int(self.lib.hn_weight_count(8, self.depth, 2))
         self._chk(weights, (n_w,), "weights")
-        for t, shape, name in ((wf0, (b, 2, self.n, self.n), "wavefield"), (res0, (b, 2, self.n, self.n), "residual"),
-                               (states0, (b, 2, self.state_len), "hidden state"), (k_sq, (b, 1, self.n, self.n), "k_sq"),
-                               (wf_hist, (T, b, 2, self.n, self.n), "wf_hist"), (res_hist, (T, b, 2, self.n, self.n), "res_hist"),
+        for t, shape, name in ((wf0, (b, 2, *self.hw), "wavefield"), (res0, (b, 2, *self.hw), "residual"),
+                               (states0, (b, 2, self.state_len), "hidden state"), (k_sq, (b, 1, *self.hw), "k_sq"),
+                               (wf_hist, (T, b, 2, *self.hw), "wf_hist"), (res_hist, (T, b, 2, *self.hw), "res_hist"),
                                (st_hist, (T, b, 2, self.state_len), "st_hist")):
             self._chk(t, shape, name)
         for t, shape, name in ((g_wf_hist, wf_hist.shape, "g_wf_hist"), (g_res_hist, res_hist.shape, "g_res_hist"), (g_st_hist, st_hist.shape, "g_st_hist"),
                                (g_wf_T, wf0.shape, "g_wf_T"), (g_res_T, res0.shape, "g_res_T"), (g_st_T, states0.shape, "g_st_T"),
-                               (g_k_sq, k_sq.shape, "g_k_sq"), (g_src, (int(src_batch), 2, self.n, self.n), "g_src"), (g_weights, (n_w,), "g_weights")):
+                               (g_k_sq, k_sq.shape, "g_k_sq"), (g_src, (int(src_batch), 2, *self.hw), "g_src"), (g_weights, (n_w,), "g_weights")):
             if t is not None:
                 self._chk(t, shape, name)
         out = {"grad_wf": torch.empty_like(wf0), "grad_res": torch.empty_like(res0), "grad_states": torch.empty_like(states0)}
@@ -544,13 +557,13 @@ class Engine:
         (the same three tensors are returned); ``t_k_sq`` [B,1,n,n] and ``t_src`` [src_batch,2,n,n] are the
         directions on k_sq and the source (None = zero); the optional histories receive the tangents after every iteration."""
         b, T = wf0.shape[0], int(wf_hist.shape[0])
-        for t, shape, name in ((wf0, (b, 2, self.n, self.n), "wavefield"), (res0, (b, 2, self.n, self.n), "residual"),
-                               (states0, (b, 2, self.state_len), "hidden state"), (k_sq, (b, 1, self.n, self.n), "k_sq"),
-                               (wf_hist, (T, b, 2, self.n, self.n), "wf_hist"), (res_hist, (T, b, 2, self.n, self.n), "res_hist"),
+        for t, shape, name in ((wf0, (b, 2, *self.hw), "wavefield"), (res0, (b, 2, *self.hw), "residual"),
+                               (states0, (b, 2, self.state_len), "hidden state"), (k_sq, (b, 1, *self.hw), "k_sq"),
+                               (wf_hist, (T, b, 2, *self.hw), "wf_hist"), (res_hist, (T, b, 2, *self.hw), "res_hist"),
                                (st_hist, (T, b, 2, self.state_len), "st_hist"), (t_wf, wf0.shape, "t_wf"), (t_res, res0.shape, "t_res"),
                                (t_states, states0.shape, "t_states")):
             self._chk(t, shape, name)
-        for t, shape, name in ((t_k_sq, k_sq.shape, "t_k_sq"), (t_src, (int(src_batch), 2, self.n, self.n), "t_src"),
+        for t, shape, name in ((t_k_sq, k_sq.shape, "t_k_sq"), (t_src, (int(src_batch), 2, *self.hw), "t_src"),
                                (t_wf_hist, wf_hist.shape, "t_wf_hist"), (t_res_hist, res_hist.shape, "t_res_hist"), (t_st_hist, st_hist.shape, "t_st_hist")):
             if t is not None:
                 self._chk(t, shape, name)
@@ -631,18 +644,18 @@ class Engine:
         refill_map), -1 = none -- host integers, they travel in the kernel arguments.  ``sos_in`` [n_maps,1,n,n] / ``src_in`` [n_maps,2,n,n]
         feed refills (``src_in`` only when ``src`` has one row per slot), ``out_wf`` / ``out_res`` [n_maps,2,n,n] receive retired slots."""
         b = wf.shape[0]
-        self._chk(wf, (b, 2, self.n, self.n), "wavefield")
-        self._chk(res, (b, 2, self.n, self.n), "residual")
+        self._chk(wf, (b, 2, *self.hw), "wavefield")
+        self._chk(res, (b, 2, *self.hw), "residual")
         self._chk(states, (b, 2, self.state_len), "hidden state")
-        self._chk(k_sq, (b, 1, self.n, self.n), "k_sq")
-        self._chk(src, (src.shape[0], 2, self.n, self.n), "source")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk(src, (src.shape[0], 2, *self.hw), "source")
         n_maps = {int(t.shape[0]) for t in (sos_in, src_in, out_wf, out_res) if t is not None}
         if len(n_maps) > 1:
             raise ValueError(f"sos_in / src_in / out_wf / out_res disagree on the number of maps: {sorted(n_maps)}")
         n_maps = n_maps.pop() if n_maps else 0
         for t, ch, name in ((sos_in, 1, "sos_in"), (src_in, 2, "src_in"), (out_wf, 2, "out_wf"), (out_res, 2, "out_res")):
             if t is not None:
-                self._chk(t, (n_maps, ch, self.n, self.n), name)
+                self._chk(t, (n_maps, ch, *self.hw), name)
         ops = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1, 4))
         rc = self.lib.hn_stream_swap(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), int(src.shape[0]), b, int(ops.shape[0]),
                                      ops.ctypes.data_as(ctypes.c_void_p), _ptr(sos_in), _ptr(src_in), n_maps, float(omega), _ptr(out_wf), _ptr(out_res),

@@ -2,7 +2,9 @@
 
 Mirrors ``FastLaplacianWithPML`` (reference helmnet/spectral.py:246-363): same constructor,
 same attribute names and tensor layouts (``kx, ky, kx_sq, ky_sq, ax, bx, ay, by`` as
-``[1, N, N, 2]`` (re, im) fp32 parameters, ``sigma_x, sigma_y`` as ``[N, N]``), same
+``[1, N, N, 2]`` (re, im) fp32 parameters, ``sigma_x, sigma_y`` as ``[N, N]``; with a pair ``(H, W)`` as
+``domain_size`` -- an extension, the reference assumes a square -- ``[1, H, W, 2]`` and ``[H, W]``, the x tables from the
+1-D tables of length W, the y tables from those of length H), same
 ``forward(x[B, N, N, 2])`` and ``sigmas()``.  The tables are built exactly as the reference does
 (float64 numpy, then cast); the arithmetic of ``forward`` runs in libhelmnet_hip.so
 (``hn_laplacian``), which builds its own copy of the constants in C++ -- the GPU tests check
@@ -61,6 +63,33 @@ def spectral_route(n: int, pfa: int = 1, mixed: int = 0):
     return "dense", p, q
 
 
+def domain_hw(domain_size):
+    """(rows, columns) of a domain size given as an int (n x n) or a pair (H, W)."""
+    if isinstance(domain_size, (tuple, list)):
+        if len(domain_size) != 2:
+            raise ValueError(f"a rectangular domain size is a pair (H, W), got {domain_size!r}")
+        return int(domain_size[0]), int(domain_size[1])
+    return int(domain_size), int(domain_size)
+
+
+def spectral_route_rect(h: int, w: int):
+    """('rectangular', (P_h, Q_h), (P_w, Q_w)): the factorisation hn_set_domain_rect uses for an h x w domain with h != w -- the rule of
+    spec_rect_factor (hn_spectral_rect.hip), reported by Engine.counter('spectral_route') as 5.  Each axis on its own: len = P * Q with Q the
+    largest power of two dividing it, which for every multiple of 16 in [16, 2048] gives P odd in [1, 127] and Q in [16, 2048]; every such
+    length runs by FFT (P = 1: a plain power-of-two transform) and neither option 'spectral_pfa' nor 'spectral_mixed' is read.  h == w is
+    hn_set_domain itself: see ``spectral_route``."""
+    h, w = int(h), int(w)
+    if h == w:
+        raise ValueError(f"{h} x {w} is a square domain: hn_set_domain_rect delegates it to hn_set_domain (spectral_route)")
+    out = []
+    for n in (h, w):
+        if n < 16 or n > 2048 or n % 16:
+            raise ValueError(f"domain size {h} x {w}: {n} is not a multiple of 16 in [16, 2048]")
+        q = n & -n
+        out.append((n // q, q))
+    return "rectangular", out[0], out[1]
+
+
 def _frozen(t: torch.Tensor) -> nn.Parameter:
     return nn.Parameter(t, requires_grad=False)
 
@@ -73,27 +102,28 @@ class FastLaplacianWithPML(nn.Module):
 
     def init_variables(self, PMLsize, domain_size, sigma_max, k):
         self.PMLsize, self.domain_size, self.sigma_max, self.k = PMLsize, domain_size, sigma_max, k
-        n = domain_size
-        sigma, a, b = pml_profile(n, PMLsize, sigma_max, k)
-        k32 = torch.from_numpy(k_grid(n)).float()          # cast before squaring, as the reference does
-        kx = k32.view(1, 1, n, 1).expand(1, n, n, 1)       # varies along the LAST axis ("x" = W)
-        ky = k32.view(1, n, 1, 1).expand(1, n, n, 1)
-        zero = torch.zeros(1, n, n, 1)
+        h, w = domain_hw(domain_size)                      # one set of 1-D tables per axis, each normalised by its own length
+        sigma_h, a_h, b_h = pml_profile(h, PMLsize, sigma_max, k)
+        sigma_w, a_w, b_w = pml_profile(w, PMLsize, sigma_max, k)
+        kh32 = torch.from_numpy(k_grid(h)).float()         # cast before squaring, as the reference does
+        kw32 = torch.from_numpy(k_grid(w)).float()
+        kx = kw32.view(1, 1, w, 1).expand(1, h, w, 1)      # varies along the LAST axis ("x" = W)
+        ky = kh32.view(1, h, 1, 1).expand(1, h, w, 1)
+        zero = torch.zeros(1, h, w, 1)
         self.kx = _frozen(torch.cat([zero, kx], -1).contiguous())            # i*kx
         self.ky = _frozen(torch.cat([zero, ky], -1).contiguous())
         self.kx_sq = _frozen(torch.cat([-kx.pow(2), zero], -1).contiguous())  # -kx^2
         self.ky_sq = _frozen(torch.cat([-ky.pow(2), zero], -1).contiguous())
 
         def pair(c, along_x):
-            t = torch.from_numpy(np.stack([c.real, c.imag], -1)).float()     # [n, 2]
-            t = t.view(1, 1, n, 2).expand(1, n, n, 2) if along_x else t.view(1, n, 1, 2).expand(1, n, n, 2)
+            t = torch.from_numpy(np.stack([c.real, c.imag], -1)).float()     # [len, 2]
+            t = t.view(1, 1, w, 2).expand(1, h, w, 2) if along_x else t.view(1, h, 1, 2).expand(1, h, w, 2)
             return _frozen(t.contiguous())
 
-        self.ax, self.bx = pair(a, True), pair(b, True)
-        self.ay, self.by = pair(a, False), pair(b, False)
-        s = torch.from_numpy(sigma).float()
-        self.sigma_x = _frozen(s.view(1, n).expand(n, n).contiguous())
-        self.sigma_y = _frozen(s.view(n, 1).expand(n, n).contiguous())
+        self.ax, self.bx = pair(a_w, True), pair(b_w, True)
+        self.ay, self.by = pair(a_h, False), pair(b_h, False)
+        self.sigma_x = _frozen(torch.from_numpy(sigma_w).float().view(1, w).expand(h, w).contiguous())
+        self.sigma_y = _frozen(torch.from_numpy(sigma_h).float().view(h, 1).expand(h, w).contiguous())
 
     def sigmas(self):
         return self.sigma_x, self.sigma_y
@@ -104,11 +134,14 @@ class FastLaplacianWithPML(nn.Module):
 
     def _get_engine(self, device):
         from .engine import Engine
-        key = (int(self.domain_size), int(self.PMLsize), float(self.sigma_max), float(self.k))
+        h, w = domain_hw(self.domain_size)
+        tail = (int(self.PMLsize), float(self.sigma_max), float(self.k))
         if self._engine is None or self._engine.device != torch.device(device):
             self._engine = Engine(device)
-        if self._engine.domain_key != key:
-            self._engine.set_domain(*key)
+        if h == w and self._engine.domain_key != (h,) + tail:
+            self._engine.set_domain(h, *tail)
+        elif h != w and self._engine.domain_key != ((h, w),) + tail:
+            self._engine.set_domain_rect(h, w, *tail)
         return self._engine
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

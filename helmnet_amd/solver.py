@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from .checkpoint import AttributeDict, read_lightning_checkpoint
 from .engine import Engine, _require_no_grad
-from .laplacian import FastLaplacianWithPML
+from .laplacian import FastLaplacianWithPML, domain_hw
 from .source import SourceModule
 from .unet import HybridNet
 
@@ -197,15 +197,33 @@ class IterativeSolver(nn.Module):
             dev = torch.device("cuda", torch.cuda.current_device())
         if self._engine is None or self._engine.device != dev:
             self._engine = Engine(dev)
-        key = (int(self.hparams.domain_size), int(self.hparams.PMLsize), float(self.hparams.sigma_max), float(self.hparams.k))
+        rect = self._rect()
+        tail = (int(self.hparams.PMLsize), float(self.hparams.sigma_max), float(self.hparams.k))
+        key = ((rect,) if rect else (int(self.hparams.domain_size),)) + tail
         if self._engine.domain_key != key:
-            self._engine.set_domain(*key)
+            if rect:
+                self._engine.set_domain_rect(*rect, *tail)
+            else:
+                self._engine.set_domain(*key)
         if self._unet_precision is not None and self._engine.unet_precision != self._unet_precision:
             self._engine.set_unet_precision(self._unet_precision)
         self.f.bind(self._engine)
         self.Lap.bind(self._engine)
         self.f.sync_weights(self._engine)
         return self._engine
+
+    # ------------------------------------------------------------------ rectangular domains ---------
+    def _rect(self):
+        """(H, W) when the domain is rectangular (``set_domain_size((H, W))`` with H != W), else None."""
+        ds = self.hparams.domain_size
+        return (int(ds[0]), int(ds[1])) if isinstance(ds, (tuple, list)) else None
+
+    def _require_square(self, what: str):
+        """The one refusal of everything the rectangular path does not cover: the library has no kernels for it on H x W (hn_set_domain_rect)."""
+        rect = self._rect()
+        if rect:
+            raise NotImplementedError(f"{what} is not implemented on a rectangular domain ({rect[0]} x {rect[1]}): the rectangular path covers forward, "
+                                      "n_steps, single_step, get_residual, apply_laplacian and solve_to_tolerance without gradients in fp32")
 
     # ------------------------------------------------------------------ autograd ---------
     def differentiable(self, on: bool = True):
@@ -220,12 +238,13 @@ class IterativeSolver(nn.Module):
         grad -- or differentiable(True) was called."""
         if not torch.is_grad_enabled():
             return False
-        if self._differentiable:
-            return True
         ts = [t for t in tensors if isinstance(t, torch.Tensor)] + [self.source]
         if states:
             ts += [enc.state for enc in self.f.enc if enc.state is not None]
-        return any(t.requires_grad for t in ts)
+        wanted = self._differentiable or any(t.requires_grad for t in ts)
+        if wanted:
+            self._require_square("the autograd path")
+        return wanted
 
     def _check_grad_precision(self, eng: Engine):
         if eng.unet_precision not in ("fp32", "valu"):
@@ -273,12 +292,21 @@ class IterativeSolver(nn.Module):
         from . import _lib
         if mode not in _lib.HN_PRECISION:
             raise ValueError(f"unknown UNet precision {mode!r} (choose from {sorted(_lib.HN_PRECISION)})")
+        if mode not in ("fp32", "valu"):
+            self._require_square(f"the 16-bit UNet precision {mode!r}")
         self._unet_precision = mode
         if self._engine is not None:
             self._engine.set_unet_precision(mode)
 
     # ------------------------------------------------------------------ setup ------------
     def set_domain_size(self, domain_size, source_location=None, source_map=None):
+        """hybridnet.py:92-108.  ``domain_size``: an int as in the reference, or (extension) a pair (H, W) of rows and columns with
+        ``source_location=[row, col]`` or ``source_map=[S, 2, H, W]``; a pair with H == W is the int."""
+        if isinstance(domain_size, (tuple, list)):
+            h, w = domain_hw(domain_size)
+            domain_size = h if h == w else (h, w)
+            if h != w and self._unet_precision not in (None, "fp32", "valu"):
+                raise NotImplementedError(f"the 16-bit UNet precision {self._unet_precision!r} is not implemented on a rectangular domain ({h} x {w})")
         self.hparams.domain_size = domain_size
         self.f.domain_size = self.hparams.domain_size
         self.set_laplacian()
@@ -311,9 +339,10 @@ class IterativeSolver(nn.Module):
     def setup_source(self, location=None):
         n = self.hparams.domain_size
         if location is None:
+            h, w = domain_hw(n)
             location = self.hparams.source_location
-            if not (0 <= location[0] < n and 0 <= location[1] < n):
-                location = [n // 2, n // 2]  # placeholder; a source map / location is set right after
+            if not (0 <= location[0] < h and 0 <= location[1] < w):
+                location = [h // 2, w // 2]  # placeholder; a source map / location is set right after
         self.source_module = SourceModule(
             image_size=n,
             omega=self.hparams.omega,
@@ -362,6 +391,7 @@ class IterativeSolver(nn.Module):
     def get_random_source_loc(self):
         """hybridnet.py:178-190: a random source location on a circle of radius L - PMLsize - 2 around the domain centre."""
         import numpy as np
+        self._require_square("get_random_source_loc")
         theta = 2 * np.pi * np.random.rand()
         L = self.hparams.domain_size // 2
         dL = L - self.hparams.PMLsize - 2
@@ -387,6 +417,7 @@ class IterativeSolver(nn.Module):
     def trainer(self, **kwargs):
         """The training half of the reference class (replay buffer, training_step, Adam + ReduceLROnPlateau) for this solver."""
         from .training import Trainer
+        self._require_square("trainer()")
         return Trainer(self, **kwargs)
 
     def get_initials(self, sos_maps: torch.Tensor):
@@ -416,6 +447,7 @@ class IterativeSolver(nn.Module):
 
     def _residual64(self, wavefield, k_sq, want_res: bool, want_rmse: bool):
         _require_no_grad("the float64 residual check", wavefield, k_sq)
+        self._require_square("the float64 residual check")
         return self.engine().residual64(wavefield.double().contiguous(), k_sq.double().contiguous(), self.source.detach().double().contiguous(),
                                         want_res, want_rmse)
 
@@ -423,6 +455,7 @@ class IterativeSolver(nn.Module):
         """How far the fp32 residual norm of ``wavefield`` can be trusted.  Pass exactly one of ``sos_maps`` / ``k_sq`` (the fp32 problem the solver ran).
         Returns per sample: ``residual_norm64`` (float64 RMSE of the float64 residual), ``residual_norm32`` (what hn_residual + hn_rmse give) and
         ``evaluator_error`` = RMSE of (fp32 residual - float64 residual), the floor below which an fp32 residual norm carries no information."""
+        self._require_square("verify")
         if (sos_maps is None) == (k_sq is None):
             raise ValueError("pass exactly one of sos_maps and k_sq")
         _require_no_grad("verify", wavefield, sos_maps, k_sq)
@@ -461,7 +494,7 @@ class IterativeSolver(nn.Module):
         """K iterations on wf / res / st, updated in place -- Engine.step for fp32 tensors, Engine.step64 for float64 ones -- with the histories asked
         for, in wf's dtype; the result dictionary of ``forward``."""
         eng = self.engine()
-        b, n, K = wf.shape[0], wf.shape[-1], int(num_iterations)
+        b, hw, K = wf.shape[0], tuple(wf.shape[-2:]), int(num_iterations)
 
         def hist(shape, what):
             try:
@@ -472,8 +505,8 @@ class IterativeSolver(nn.Module):
                     "to IterativeSolver.forward, or fewer iterations"
                 ) from e
 
-        res_hist = hist((K, b, 2, n, n), "every residual") if residuals == "all" and K > 0 else None
-        wf_hist = hist((K, b, 2, n, n), "every wavefield") if return_wavefields and K > 0 else None
+        res_hist = hist((K, b, 2) + hw, "every residual") if residuals == "all" and K > 0 else None
+        wf_hist = hist((K, b, 2) + hw, "every wavefield") if return_wavefields and K > 0 else None
         st_hist = hist((K, b, 2, eng.state_len), "every hidden state") if return_states and K > 0 else None
         rmse = torch.empty((K, b), device=wf.device, dtype=wf.dtype) if K > 0 else None
         if K > 0:
@@ -538,6 +571,7 @@ class IterativeSolver(nn.Module):
     # ------------------------------------------------------------------ forward mode ----
     def _jvp_setup(self, sos_maps):
         """(engine, sos, k_sq, source, wf0 = 0, res0, zero flat states) of a solve from cleared states; the states held in f are not touched."""
+        self._require_square("the forward-AD path (jvp / linearize)")
         eng = self.engine()
         self._check_grad_precision(eng)
         sos = sos_maps.detach().to(self.device).float().contiguous()
@@ -581,6 +615,7 @@ class IterativeSolver(nn.Module):
 
     # ------------------------------------------------------------------ the loop in float64 ----
     def _source64(self, source, batch: int) -> torch.Tensor:
+        self._require_square("the float64 loop (forward64 / n_steps64 / deviation_from_float64)")
         n = int(self.hparams.domain_size)
         if source is None:
             return self.source.detach().double().contiguous()
@@ -596,6 +631,7 @@ class IterativeSolver(nn.Module):
 
     def _initials64(self, sos_maps, source):
         """(wf = 0, residual, zero flat states, k_sq, source), all float64: get_initials on a float64 input (hybridnet.py:522-538) and cleared states."""
+        self._require_square("the float64 loop (forward64 / n_steps64 / deviation_from_float64)")
         eng = self.engine()
         sos = sos_maps.detach().to(self.device).double().contiguous()
         src = self._source64(source, sos.shape[0])
@@ -620,6 +656,7 @@ class IterativeSolver(nn.Module):
         """``n_steps`` in float64, continuing from given tensors; the hidden states are passed in (flat [B,2,L]) instead of living in ``f`` and come back
         as ``out["final_states"]``.  Inputs are up-cast if need be and not modified."""
         _require_no_grad("n_steps64", wavefield, k_sq, residual, states, source)
+        self._require_square("the float64 loop (forward64 / n_steps64 / deviation_from_float64)")
         self.engine()
         wf, res, st, kq = (t.detach().to(self.device).double().clone().contiguous() for t in (wavefield, residual, states, k_sq))
         out = self._run64(wf, res, st, kq, self._source64(source, wf.shape[0]), num_iterations, return_wavefields, return_states, residuals)
@@ -631,6 +668,7 @@ class IterativeSolver(nn.Module):
         side, compared at every iteration count in ``checkpoints``.  Returns ``iterations`` (the sorted checkpoints), ``linf`` [len(checkpoints), B]
         (per-sample max |wavefield - float64 wavefield|), and the residual-norm traces ``rmse32`` / ``rmse64`` [num_iterations, B]."""
         _require_no_grad("deviation_from_float64", sos_maps)
+        self._require_square("deviation_from_float64")
         cps = sorted({int(c) for c in checkpoints} | {int(num_iterations)})
         if cps[0] < 1 or cps[-1] > int(num_iterations):
             raise ValueError(f"checkpoints must lie in [1, {int(num_iterations)}]")
@@ -661,6 +699,8 @@ class IterativeSolver(nn.Module):
         ``verify()`` for the final wavefield and ``converged64``: the worst float64 residual norm is below ``tol``."""
         if max_iterations is None:
             max_iterations = self.hparams.max_iterations
+        if verify:
+            self._require_square("solve_to_tolerance(verify=True)")
         sos_maps = sos_maps.float().contiguous()
         k_sq, wf = self.get_initials(sos_maps)
         self.f.clear_states(wf)
@@ -692,6 +732,7 @@ class IterativeSolver(nn.Module):
         flexible GMRES with this solver's network as right preconditioner, ``precond_iterations`` iterations per inner step on a right-hand side
         scaled by ``precond_scale`` (None: the source's RMS 2-norm); see ``helmnet_amd.gmres.gmres``.  No gradients."""
         from .gmres import gmres
+        self._require_square("gmres")
         return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", precondition=precondition,
                      precond_iterations=precond_iterations, precond_scale=precond_scale)
 
@@ -704,6 +745,7 @@ class IterativeSolver(nn.Module):
         (default: zeros; it is not written).  Returns ``wavefield`` and ``residual_norms`` in float64.  ``precondition``, ``precond_iterations``,
         ``precond_scale``: as ``gmres`` (the flexible cycle inside the refinement).  No gradients."""
         from .gmres import gmres
+        self._require_square("gmres64")
         return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", refine=True, precondition=precondition,
                      precond_iterations=precond_iterations, precond_scale=precond_scale)
 
@@ -714,6 +756,7 @@ class IterativeSolver(nn.Module):
         residual RMSE of the reference: how good the ground truth is; below ``tol`` when ``converged``), ``reference`` (the float64 wavefield),
         ``converged`` and ``cycles``.  ``wavefield`` is not written."""
         _require_no_grad("reference_error", wavefield, sos_maps)
+        self._require_square("reference_error")
         out = self.gmres64(sos_maps, restart=restart, max_cycles=max_cycles, tol=tol, x0=wavefield, precondition=precondition,
                            precond_iterations=precond_iterations, precond_scale=precond_scale)
         ref = out["wavefield"]
@@ -749,6 +792,7 @@ class IterativeSolver(nn.Module):
         if max_iterations is None:
             max_iterations = self.hparams.max_iterations
         _require_no_grad("solve_many", sos_maps, source_maps)
+        self._require_square("solve_many")
         if not (float(tol) == float(tol)):
             raise ValueError("tol is NaN")
         with torch.no_grad():

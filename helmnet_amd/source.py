@@ -31,12 +31,12 @@ class SourceModule(nn.Module):
 
     def make_abs_spatial_map(self, smooth: bool = True):
         """source_module.py:41-79: |ifft2(ifftshift(fftshift(fft2(delta)) [* blackman^2]))|."""
-        m = torch.zeros((self.L, self.L))
+        h, w = (int(self.L[0]), int(self.L[1])) if isinstance(self.L, (tuple, list)) else (self.L, self.L)   # image_size: an int or a pair (H, W)
+        m = torch.zeros((h, w))
         m[self.location[0], self.location[1]] = self.amplitude
         f = torch.fft.fftshift(torch.fft.fft2(m))
         if smooth:
-            w = torch.blackman_window(self.L)
-            f = f * torch.outer(w, w)
+            f = f * torch.outer(torch.blackman_window(h), torch.blackman_window(w))
         self._abs_spatial_map = torch.abs(torch.fft.ifft2(torch.fft.ifftshift(f))).to(self._dummy_for_device.device)
 
     def set_new_location(self, location):
@@ -49,7 +49,7 @@ class SourceModule(nn.Module):
         return self.location
 
     def spatial_map(self, t: float) -> torch.Tensor:
-        """source_module.py:94-116 -> [1, L, L, 2]."""
+        """source_module.py:94-116 -> [1, L, L, 2] ([1, H, W, 2] for an image size (H, W))."""
         ang = float(self.omega * t + self.phase)
         a = self._abs_spatial_map
         return torch.stack([a * math.cos(ang), a * math.sin(ang)], dim=2).unsqueeze(0)

@@ -102,7 +102,8 @@ class EncoderBlock(nn.Module):
         return self.state
 
     def clear_state(self, x):
-        self.state = torch.zeros([x.shape[0], 2, self.domain_size, self.domain_size], device=x.device)
+        h, w = self.domain_size if isinstance(self.domain_size, (tuple, list)) else (self.domain_size, self.domain_size)
+        self.state = torch.zeros([x.shape[0], 2, h, w], device=x.device)
 
     def forward(self, x):
         """architectures.py:240-252 on the library's standalone entry points (hn_double_conv, hn_conv8x8)."""
@@ -145,12 +146,20 @@ class HybridNet(nn.Module):
 
     # ---- state bookkeeping (architectures.py:390-437) -----------------------------------
     def init_by_size(self):
-        self.states_dimension = [self.domain_size // 2 ** x for x in range(self.depth)]
-        self.total_state_length = sum(x ** 2 for x in self.states_dimension)
+        """``domain_size`` an int: architectures.py:390-404.  A pair (H, W): ``states_dimension`` holds pairs (H // 2^d, W // 2^d) and the
+        flat state is sum_d (H >> d)(W >> d) long, level 0 first, each level row-major."""
+        if isinstance(self.domain_size, (tuple, list)):
+            h, w = int(self.domain_size[0]), int(self.domain_size[1])
+            self.states_dimension = [(h // 2 ** x, w // 2 ** x) for x in range(self.depth)]
+            areas = [a * b for a, b in self.states_dimension]
+        else:
+            self.states_dimension = [self.domain_size // 2 ** x for x in range(self.depth)]
+            areas = [x ** 2 for x in self.states_dimension]
+        self.total_state_length = sum(areas)
         self.state_boundaries, o = [], 0
-        for s in self.states_dimension:
-            self.state_boundaries.append([o, o + s * s])
-            o += s * s
+        for s in areas:
+            self.state_boundaries.append([o, o + s])
+            o += s
 
     def get_states(self, flatten=False):
         h = [enc.get_state() for enc in self.enc]
@@ -200,7 +209,8 @@ class HybridNet(nn.Module):
     def unflatten_state(self, h_flatten):
         h, shp = [], h_flatten.shape
         for (a, b), size in zip(self.state_boundaries, self.states_dimension):
-            h.append(h_flatten[:, :, a:b].reshape(shp[0], shp[1], size, size))
+            rows, cols = size if isinstance(size, tuple) else (size, size)
+            h.append(h_flatten[:, :, a:b].reshape(shp[0], shp[1], rows, cols))
         return h
 
     # ---- engine plumbing -----------------------------------------------------------------
@@ -230,7 +240,10 @@ class HybridNet(nn.Module):
             if not self._owns_engine and self._engine is not None:
                 raise RuntimeError(f"input on {device} but the solver's engine lives on {self._engine.device}")
             self._engine = Engine(device)
-        if self._owns_engine and self._engine.n != self.domain_size:
+        if self._owns_engine and isinstance(self.domain_size, (tuple, list)):
+            if self._engine.hw != tuple(self.domain_size):
+                self._engine.set_domain_rect(self.domain_size[0], self.domain_size[1], 1, 0.0, 1.0)
+        elif self._owns_engine and self._engine.n != self.domain_size:
             # standalone use: the spectral tables are not needed, but the library wants a domain
             self._engine.set_domain(self.domain_size, 1, 0.0, 1.0)
         if self._owns_engine and self._unet_precision is not None and self._engine.unet_precision != self._unet_precision:

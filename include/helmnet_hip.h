@@ -184,7 +184,8 @@ enum hn_counter { HN_CNT_GRAPH_REPLAYS = 0, HN_CNT_EAGER_ITERATIONS = 1, HN_CNT_
                   HN_CNT_FLAG_SYNC_ITERATIONS = 6,  /* hn_step iterations whose side-stream hand-overs went through device words (HN_OPT_SIDE_SYNC): n_iter - 1 per
                                                  * eligible call, 0 with the option off, under stream capture, under counter collection, with several lanes */
                   HN_CNT_SPECTRAL_ROUTE = 7 };  /* not a count: the kernels the current domain's spectral operator runs on.  0 no domain, 1 power of two,
-                                                 * 2 prime-factor (HN_OPT_SPECTRAL_PFA), 3 dense, 4 mixed (HN_OPT_SPECTRAL_MIXED) */
+                                                 * 2 prime-factor (HN_OPT_SPECTRAL_PFA), 3 dense, 4 mixed (HN_OPT_SPECTRAL_MIXED),
+                                                 * 5 rectangular (hn_set_domain_rect with h != w) */
 
 #define HN_ABI_VERSION 7
 int hn_abi_version(void);
@@ -227,6 +228,28 @@ int hn_check_async_errors(hn_ctx* ctx);
  * FourierDerivative k-grid (spectral.py:126-146), IterativeSolver.set_laplacian
  * (hybridnet.py:110-131).  n must be divisible by 2^depth (16 for the shipped net). */
 int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k);
+
+/* ---- rectangular domains (added within ABI v7: a new entry point, nothing existing changes, so HN_ABI_VERSION stays 7) ----
+ * hn_set_domain_rect: an h x w domain, h rows (the y axis, the first spatial index) by w columns (the x axis, the last index); tensors are
+ * [B, C, h, w], contiguous.  The tables are the reference's formulas taken per axis (spectral.py:126-146, 298-363), each axis normalised by its own
+ * length: sigma_x[i, j] = sigma_w[j], sigma_y[i, j] = sigma_h[i]; kx, ax, bx vary along the last axis (length w), ky, ay, by along the first (length h).
+ * h and w must each satisfy what hn_set_domain asks of n: a multiple of 2^depth (16 for the shipped net) in [16, 2048] with 1 <= pml <= len / 2
+ * (HN_ERR_ARG otherwise).  h == w IS hn_set_domain(ctx, h, ...): same routes, same tables, same bits from every entry point.
+ * On a rectangular domain (h != w):
+ *   - hn_state_len returns sum_d (h >> d) * (w >> d); the flat state is [B, 2, that], level 0 first, each level row-major; hn_get_sigmas writes [2, h, w];
+ *     hn_get_counter(HN_CNT_SPECTRAL_ROUTE) returns 5;
+ *   - hn_reserve, hn_get_sigmas, hn_laplacian, hn_residual, hn_rmse, hn_unet and hn_step work with the contracts they have on a square (hn_step: all four
+ *     histories and rmse_hist, the overlap check, 4-byte-aligned pointers, n_iter in one call = the same iterations in several calls bit for bit) in
+ *     HN_PREC_FP32 and HN_PREC_FP32_VALU.  The spectral residual runs by FFT on every legal length (each axis factored on its own as P * 2^k, P odd <= 127);
+ *     the UNet runs layer by layer on the caller's stream, the histories are copied.  The workspace is sized from (h, w, batch), built by the first
+ *     call or hn_reserve and freed by the next domain or weight load: a call that builds or grows it under stream capture returns HN_ERR_STATE with
+ *     nothing enqueued; later calls are plain launches and capturable;
+ *   - every other entry point that reads the domain returns HN_ERR_UNSUPPORTED, its message naming the rectangular domain, with nothing enqueued:
+ *     hn_residual_vjp, the _f64 family, the GMRES family, hn_train_reserve / hn_train_grad, hn_step_vjp, hn_step_jvp, hn_stream_swap; so do hn_unet and
+ *     hn_step in a 16-bit precision mode and hn_step with HN_OPT_LANES > 1.  HN_EXP_GRAPH, HN_OPT_SIDE_STREAM, HN_OPT_DEEP and HN_OPT_DC_PAIR have no
+ *     effect.  Shape-free calls are unchanged (hn_stream_verdict, hn_adam_step, hn_rows_*, hn_double_conv, hn_conv8x8, hn_out_conv).
+ * A later hn_set_domain or hn_set_domain_rect replaces the domain and frees what the previous one built. */
+int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, float k);
 
 /* Copy the sigma maps [2, n, n] (sigma_x, sigma_y) to `out` (device). hybridnet.py:126-131. */
 int hn_get_sigmas(hn_ctx* ctx, float* out, void* stream);
