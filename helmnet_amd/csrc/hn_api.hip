@@ -108,11 +108,32 @@ int with_temp_weights(hn_ctx* ctx, size_t n_floats, hipStream_t s, Fill fill, Go
 int check_ready(hn_ctx* ctx, int batch) {
     if (!ctx) return HN_ERR_ARG;
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "hn_load_weights has not been called");
-    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    const int h = ctx->geo.h, w = ctx->geo.w, m = 1 << ctx->depth;
+    if (h == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
-    if (ctx->tab.n % (1 << ctx->depth) != 0)
-        return fail(ctx, HN_ERR_ARG, "domain size %d is not divisible by 2^depth = %d", ctx->tab.n, 1 << ctx->depth);
+    if (h % m == 0 && w % m == 0) return HN_OK;
+    if (ctx->rect) return fail(ctx, HN_ERR_ARG, "domain size %d x %d is not divisible by 2^depth = %d", h, w, m);
+    return fail(ctx, HN_ERR_ARG, "domain size %d is not divisible by 2^depth = %d", h, m);
+}
+// ... and, for the entry points that run the UNet, its precision mode: a rectangular domain has the two fp32 modes only
+int check_ready_unet(hn_ctx* ctx, const char* who, int batch) {
+    if (const int rc = check_ready(ctx, batch); rc != HN_OK) return rc;
+    if (ctx->rect && ctx->precision != HN_PREC_FP32 && ctx->precision != HN_PREC_FP32_VALU) return rect_unsupported(ctx, who);
     return HN_OK;
+}
+
+// The domain as the entry points see it (ctx->geo), from whichever tables the context holds now -- none: no domain -- and the layout of the flat hidden
+// state that follows from it: level d's (h >> d) x (w >> d) plane at state_off[d] (depth 4 until weights are loaded)
+void set_geometry(hn_ctx* ctx) {
+    ctx->geo = {};
+    if (ctx->rect) ctx->geo = {ctx->rect->h, ctx->rect->w, ctx->rect->sigmas};
+    else if (ctx->tab.n) ctx->geo = {ctx->tab.n, ctx->tab.n, ctx->tab.sigmas};
+    const int depth = ctx->have_weights ? ctx->depth : 4;
+    ctx->state_len = 0;
+    for (int d = 0; d < depth; ++d) {
+        ctx->state_off[d] = ctx->state_len;
+        ctx->state_len += (int64_t)(ctx->geo.h >> d) * (ctx->geo.w >> d);
+    }
 }
 
 __global__ void k_sumsq(const float* __restrict__ x, float* __restrict__ out, long per_sample) {
@@ -129,8 +150,6 @@ __global__ void k_rmse_finalize(float* __restrict__ v, int count, float inv_n) {
     if (i < count) v[i] = sqrtf(v[i] * inv_n);
 }
 
-}  // namespace
-
 void free_workspace(hn_ctx* c) {
     for (int d = 0; d <= kMaxDepth; ++d) {
         (void)hipFree(c->buf_a[d]); c->buf_a[d] = nullptr;
@@ -145,9 +164,43 @@ void free_workspace(hn_ctx* c) {
     c->cap_batch = 0;
 }
 
-void launch_rmse_finalize(float* v, int count, float inv_n, hipStream_t s) {
-    hipLaunchKernelGGL(k_rmse_finalize, dim3((count + 255) / 256), dim3(256), 0, s, v, count, inv_n);
+// hn_reserve.  s (nullable): the stream of the entry point that asks; a workspace that has to be built or grown while s is capturing is refused
+int reserve_workspace(hn_ctx* ctx, int max_batch, hipStream_t s) {
+    int rc = check_ready(ctx, max_batch);
+    if (rc != HN_OK) return rc;
+    if (max_batch <= ctx->cap_batch) return HN_OK;
+    if (stream_capturing(s))
+        return fail(ctx, HN_ERR_STATE, "the workspace must be built or grown (batch %d) outside stream capture: call hn_reserve first", max_batch);
+    HN_HIP(ctx, hipDeviceSynchronize());  // nothing may still be using the old workspace
+    clear_step_graphs(ctx);
+    free_workspace(ctx);
+    const int h = ctx->geo.h, w = ctx->geo.w, depth = ctx->depth;
+    for (int d = 0; d <= depth; ++d) {
+        const size_t bytes = sizeof(float) * (size_t)max_batch * kFeat * (h >> d) * (w >> d);
+        HN_HIP(ctx, hipMalloc((void**)&ctx->buf_a[d], bytes));
+        if (d < depth) HN_HIP(ctx, hipMalloc((void**)&ctx->buf_o[d], bytes));
+        if (d > 0) HN_HIP(ctx, hipMalloc((void**)&ctx->buf_y[d], bytes));
+    }
+    HN_HIP(ctx, hipMalloc((void**)&ctx->st_tmp, sizeof(float) * (size_t)max_batch * kState * ctx->state_len));
+    if (!ctx->it_counter) HN_HIP(ctx, hipMalloc((void**)&ctx->it_counter, 8 * sizeof(int)));   // (here: a first hn_step under capture is then nothing but launches)
+    // The device words of what a square domain alone runs (their gates compare against tab.n: never read on a rectangle)
+    ctx->pair_flags_cap = (long)((w + 63) / 64) * ((h + 15) / 16) * max_batch;   // one flag word per level-0 tile (k_dc_asm_pair); epochs start at 1
+    HN_HIP(ctx, hipMalloc((void**)&ctx->pair_flags, sizeof(unsigned) * (size_t)ctx->pair_flags_cap));
+    HN_HIP(ctx, hipMemset(ctx->pair_flags, 0, sizeof(unsigned) * (size_t)ctx->pair_flags_cap));
+    HN_HIP(ctx, hipMalloc((void**)&ctx->pair_done, sizeof(unsigned) * kCounterStride * (size_t)max_batch));          // (zero: the first launch's epoch is 1)
+    HN_HIP(ctx, hipMemset(ctx->pair_done, 0, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
+    // hn_deepx.hip: 64 epoch words and one counter per sample slot (zero: the first launch's epoch is 1)
+    HN_HIP(ctx, hipMalloc((void**)&ctx->dx_flags, sizeof(unsigned) * 64 * (size_t)max_batch));
+    HN_HIP(ctx, hipMemset(ctx->dx_flags, 0, sizeof(unsigned) * 64 * (size_t)max_batch));
+    HN_HIP(ctx, hipMalloc((void**)&ctx->dx_done, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
+    HN_HIP(ctx, hipMemset(ctx->dx_done, 0, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
+    if ((rc = ensure_sync_words(ctx)) != HN_OK) return rc;
+    if ((rc = stream_table_reserve(ctx, max_batch)) != HN_OK) return rc;
+    ctx->cap_batch = max_batch;
+    return HN_OK;
 }
+
+}  // namespace
 
 // Zero `bytes` (a multiple of 4) at p on stream s with a kernel of this library instead of hipMemsetAsync.  [seen, r5, tools/graph_null_stream_probe.py] a
 // hipMemsetAsync on the legacy default stream -- from anyone in the process -- between the capture of a graph that holds memset nodes and its replay leaves the
@@ -542,11 +595,7 @@ int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int feature
     if (ctx->have_weights && ctx->depth != depth) free_workspace(ctx);
     ctx->depth = depth;
     ctx->have_weights = true;
-    if (ctx->rect) rect_state_layout(ctx);
-    if (ctx->tab.n) {  // state layout depends on depth
-        ctx->state_len = 0;
-        for (int d = 0; d < depth; ++d) { ctx->state_off[d] = ctx->state_len; ctx->state_len += (int64_t)(ctx->tab.n >> d) * (ctx->tab.n >> d); }
-    }
+    set_geometry(ctx);   // (the state layout depends on depth)
     return build_inc_sigma_map(ctx);
 }
 
@@ -562,11 +611,9 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
     if (n != ctx->tab.n) free_workspace(ctx);
     spec_rect_free(ctx);   // (a rectangular domain's tab.n is 0: its workspace has just gone)
-    int rc = spec_build(ctx, n, pml, (double)sigma_max, (double)k);
+    const int rc = spec_build(ctx, n, pml, (double)sigma_max, (double)k);
+    set_geometry(ctx);   // (also after a failure: whatever tables spec_build has left)
     if (rc != HN_OK) return rc;
-    const int depth = ctx->have_weights ? ctx->depth : 4;
-    ctx->state_len = 0;
-    for (int d = 0; d < depth; ++d) { ctx->state_off[d] = ctx->state_len; ctx->state_len += (int64_t)(n >> d) * (n >> d); }
     return build_inc_sigma_map(ctx);
 }
 
@@ -590,61 +637,24 @@ int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, floa
     free_workspace(ctx);
     spec_free(ctx->tab);
     int rc = build_inc_sigma_map(ctx);   // (no n x n domain: frees the map)
-    if (rc != HN_OK) return rc;
-    if ((rc = spec_rect_build(ctx, h, w, pml, (double)sigma_max, (double)k)) != HN_OK) return rc;
-    rect_state_layout(ctx);
-    return HN_OK;
+    if (rc == HN_OK) rc = spec_rect_build(ctx, h, w, pml, (double)sigma_max, (double)k);
+    set_geometry(ctx);   // (also after a failure: whatever is left)
+    return rc;
 }
 
 int hn_get_sigmas(hn_ctx* ctx, float* out, void* stream) {
     if (!ctx || !out) return fail(ctx, HN_ERR_ARG, "hn_get_sigmas: NULL argument");
-    if (ctx->rect) {
-        DeviceGuard guard(ctx);
-        HN_HIP(ctx, hipMemcpyAsync(out, ctx->rect->sigmas, sizeof(float) * 2 * ctx->rect->h * ctx->rect->w, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        return HN_OK;
-    }
-    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    if (ctx->geo.h == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     DeviceGuard guard(ctx);
-    HN_HIP(ctx, hipMemcpyAsync(out, ctx->tab.sigmas, sizeof(float) * 2 * ctx->tab.n * ctx->tab.n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HN_HIP(ctx, hipMemcpyAsync(out, ctx->geo.sigmas, sizeof(float) * 2 * ctx->geo.plane(), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return HN_OK;
 }
 
 int64_t hn_state_len(const hn_ctx* ctx) { return ctx ? ctx->state_len : 0; }
 
 int hn_reserve(hn_ctx* ctx, int max_batch) {
-    if (ctx && ctx->rect) {
-        DeviceGuard guard(ctx);
-        return rect_reserve(ctx, max_batch, nullptr);
-    }
-    int rc = check_ready(ctx, max_batch);
-    if (rc != HN_OK) return rc;
-    if (max_batch <= ctx->cap_batch) return HN_OK;
     DeviceGuard guard(ctx);
-    HN_HIP(ctx, hipDeviceSynchronize());  // nothing may still be using the old workspace
-    clear_step_graphs(ctx);
-    free_workspace(ctx);
-    const int n = ctx->tab.n, depth = ctx->depth;
-    for (int d = 0; d <= depth; ++d) {
-        const size_t bytes = sizeof(float) * (size_t)max_batch * kFeat * (n >> d) * (n >> d);
-        HN_HIP(ctx, hipMalloc((void**)&ctx->buf_a[d], bytes));
-        if (d < depth) HN_HIP(ctx, hipMalloc((void**)&ctx->buf_o[d], bytes));
-        if (d > 0) HN_HIP(ctx, hipMalloc((void**)&ctx->buf_y[d], bytes));
-    }
-    HN_HIP(ctx, hipMalloc((void**)&ctx->st_tmp, sizeof(float) * (size_t)max_batch * kState * ctx->state_len));
-    ctx->pair_flags_cap = (long)((n + 63) / 64) * ((n + 15) / 16) * max_batch;   // one flag word per level-0 tile (k_dc_asm_pair); epochs start at 1
-    HN_HIP(ctx, hipMalloc((void**)&ctx->pair_flags, sizeof(unsigned) * (size_t)ctx->pair_flags_cap));
-    HN_HIP(ctx, hipMemset(ctx->pair_flags, 0, sizeof(unsigned) * (size_t)ctx->pair_flags_cap));
-    HN_HIP(ctx, hipMalloc((void**)&ctx->pair_done, sizeof(unsigned) * kCounterStride * (size_t)max_batch));          // (zero: the first launch's epoch is 1)
-    HN_HIP(ctx, hipMemset(ctx->pair_done, 0, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
-    // hn_deepx.hip: 64 epoch words and one counter per sample slot (zero: the first launch's epoch is 1)
-    HN_HIP(ctx, hipMalloc((void**)&ctx->dx_flags, sizeof(unsigned) * 64 * (size_t)max_batch));
-    HN_HIP(ctx, hipMemset(ctx->dx_flags, 0, sizeof(unsigned) * 64 * (size_t)max_batch));
-    HN_HIP(ctx, hipMalloc((void**)&ctx->dx_done, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
-    HN_HIP(ctx, hipMemset(ctx->dx_done, 0, sizeof(unsigned) * kCounterStride * (size_t)max_batch));
-    if (int rc_sync = ensure_sync_words(ctx); rc_sync != HN_OK) return rc_sync;
-    if (int rc_tab = stream_table_reserve(ctx, max_batch); rc_tab != HN_OK) return rc_tab;
-    ctx->cap_batch = max_batch;
-    return HN_OK;
+    return reserve_workspace(ctx, max_batch, nullptr);
 }
 
 int hn_profile_enable(hn_ctx* ctx, uint64_t kernel_mask) {
@@ -696,7 +706,6 @@ int hn_laplacian(hn_ctx* ctx, const float* wf, float* out, int batch, void* stre
     if (!ctx || !wf || !out) return fail(ctx, HN_ERR_ARG, "hn_laplacian: NULL argument");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     DeviceGuard guard(ctx);
-    if (ctx->rect) return spec_rect_apply(ctx, wf, out, nullptr, nullptr, 1, batch, nullptr, (hipStream_t)stream);
     return spec_apply(ctx, wf, out, nullptr, nullptr, 1, batch, nullptr, (hipStream_t)stream);
 }
 
@@ -706,7 +715,6 @@ int hn_residual(hn_ctx* ctx, const float* wf, const float* k_sq, const float* sr
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
     DeviceGuard guard(ctx);
-    if (ctx->rect) return spec_rect_apply(ctx, wf, res, k_sq, src, src_batch, batch, nullptr, (hipStream_t)stream);
     return spec_apply(ctx, wf, res, k_sq, src, src_batch, batch, nullptr, (hipStream_t)stream);
 }
 
@@ -720,11 +728,11 @@ int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, 
 
 int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream) {
     if (!ctx || !res || !rmse) return fail(ctx, HN_ERR_ARG, "hn_rmse: NULL argument");
-    if (ctx->tab.n == 0 && !ctx->rect) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    if (ctx->geo.h == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
-    const long per = ctx->rect ? 2L * ctx->rect->h * ctx->rect->w : 2L * ctx->tab.n * ctx->tab.n;
+    const long per = 2 * ctx->geo.plane();
     if (int rcz = zero_async(ctx, rmse, sizeof(float) * batch, s); rcz != HN_OK) return rcz;
     hipLaunchKernelGGL(k_sumsq, dim3(32, batch), dim3(256), 0, s, res, rmse, per);
     hipLaunchKernelGGL(k_rmse_finalize, dim3((batch + 255) / 256), dim3(256), 0, s, rmse, batch, 1.0f / (float)per);
@@ -735,13 +743,9 @@ int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream)
 int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states_out, float* d_out, int batch, void* stream) {
     if (!ctx || !in6 || !states_in || !states_out || !d_out) return fail(ctx, HN_ERR_ARG, "hn_unet: NULL argument");
     if (states_in == states_out) return fail(ctx, HN_ERR_ARG, "hn_unet: states_in must not alias states_out");
-    if (ctx->rect) {
-        DeviceGuard guard(ctx);
-        return rect_unet(ctx, in6, states_in, states_out, d_out, batch, (hipStream_t)stream);
-    }
-    int rc = check_ready(ctx, batch);
+    int rc = check_ready_unet(ctx, "hn_unet", batch);
     if (rc != HN_OK) return rc;
-    const long plane = (long)ctx->tab.n * ctx->tab.n;
+    const long plane = ctx->geo.plane();
     {
         // the hidden-state kernels write states_out level by level while later kernels still read states_in: any overlap, not only equal pointers, is refused
         const size_t sl = sizeof(float) * (size_t)batch * kState * ctx->state_len;
@@ -751,7 +755,7 @@ int hn_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states
         if (first_overlap(r, 4, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_unet: %s overlaps %s", who, other);
     }
     DeviceGuard guard(ctx);
-    if ((rc = hn_reserve(ctx, batch)) != HN_OK) return rc;
+    if ((rc = reserve_workspace(ctx, batch, (hipStream_t)stream)) != HN_OK) return rc;
     UnetCall c;
     c.wf = Src{in6, kInCh * plane, plane, 1.f};
     c.res = Src{in6 + 2 * plane, kInCh * plane, plane, 1.f};
@@ -811,6 +815,7 @@ struct StepArgs {
     const float *k_sq, *src;
     int src_batch, batch;
     float* rmse_hist;   // base of the [n_iter, batch] table (rows are selected on the device through it_counter)
+    bool side_stream;   // the hidden-state kernels may leave the main chain for the lane's side stream (hn_step's route)
 };
 
 __global__ void k_probe_spin(long ticks) {
@@ -919,7 +924,6 @@ int ensure_step_resources(hn_ctx* ctx, int ns, bool want_side, hipStream_t calle
         if ((rc = side_stream_for(ctx, 4, ctx->sub_stream, 1, may_sync, &ctx->sub_stream[1])) != HN_OK) return rc;
     }
     if (!ctx->ev_fork) HN_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    if (!ctx->it_counter) HN_HIP(ctx, hipMalloc((void**)&ctx->it_counter, 8 * sizeof(int)));
     if (want_side) {
         for (int j = 0; j < ns; ++j) {
             auto& sl = ctx->side[j];
@@ -948,7 +952,7 @@ int ensure_step_resources(hn_ctx* ctx, int ns, bool want_side, hipStream_t calle
 struct IterIo { const float* wf_in; float* wf_out; const float* res_in; float* res_out; };
 int one_iteration(hn_ctx* ctx, const StepArgs& a, int parity, int b0, int nb, int lane, hipStream_t sj, hipEvent_t stagger, bool defer_join = false,
                   const IterIo* io = nullptr) {
-    const long plane = (long)ctx->tab.n * ctx->tab.n, L = ctx->state_len;
+    const long plane = ctx->geo.plane(), L = ctx->state_len;
     const size_t fo = (size_t)b0 * 2 * plane;
     float* wf_j = (io ? io->wf_out : a.wf) + fo;
     float* res_j = (io ? io->res_out : a.res) + fo;
@@ -959,11 +963,11 @@ int one_iteration(hn_ctx* ctx, const StepArgs& a, int parity, int b0, int nb, in
     UnetCall c;
     c.wf = Src{wf_in, 2 * plane, plane, 1.f};
     c.res = Src{res_in, 2 * plane, plane, 1e3f};     // 1e3 * residual (hybridnet.py:566)
-    c.sig = Src{ctx->tab.sigmas, 0, plane, 1.f};     // sigmas.repeat(B) without the copy
+    c.sig = Src{ctx->geo.sigmas, 0, plane, 1.f};     // sigmas.repeat(B) without the copy
     c.states_in = parity ? st_tmp : st_user; c.states_out = parity ? st_user : st_tmp;
     c.wf_in = wf_in; c.wf_out = wf_j;
     c.batch = nb; c.stream = sj; c.ws_off = b0;
-    c.after_down0 = stagger; c.side_lane = ctx->opt_side_stream ? &ctx->side[lane] : nullptr; c.defer_join = defer_join;
+    c.after_down0 = stagger; c.side_lane = a.side_stream ? &ctx->side[lane] : nullptr; c.defer_join = defer_join;
     int rc = unet_forward(ctx, c);
     if (rc != HN_OK) return rc;
     const float* src_j = a.src_batch == 1 ? a.src : a.src + (size_t)b0 * 2 * plane;
@@ -1045,13 +1049,18 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
     if (n_iter < 0) return fail(ctx, HN_ERR_ARG, "n_iter must be >= 0");
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
-    if (ctx->rect) {
-        DeviceGuard guard(ctx);
-        return rect_step(ctx, wf, res, states, k_sq, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, (hipStream_t)stream);
-    }
-    int rc = check_ready(ctx, batch);
+    int rc = check_ready_unet(ctx, "hn_step", batch);
     if (rc != HN_OK) return rc;
-    const long plane = (long)ctx->tab.n * ctx->tab.n;
+    // The route.  A rectangular domain takes the plainest one whatever the options say: one lane, every kernel launched on the caller's stream (no side
+    // stream, so no flag sync; no captured iterations) and the copying form of the histories.  The same launches whatever n_iter is, so n_iter in one call
+    // equals the same iterations in several calls bit for bit.
+    const bool rect = ctx->rect != nullptr;
+    if (rect && ctx->opt_lanes > 1)
+        return fail(ctx, HN_ERR_UNSUPPORTED, "hn_step: HN_OPT_LANES %d is not implemented on a rectangular domain (one lane only)", ctx->opt_lanes);
+    const bool use_side = !rect && ctx->opt_side_stream != 0;
+    const int opt_graph = rect ? 0 : ctx->opt_graph;
+    const bool hist_copy = rect || ctx->opt_hist_copy != 0;
+    const long plane = ctx->geo.plane();
     const long L = ctx->state_len;
     {
         // No tensor may overlap another unless both are only read.  ONE tolerated form: res_hist == res / wf_hist == wf, the live buffer being slot 0 of
@@ -1068,20 +1077,20 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
         if (first_overlap(r, 9, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_step: %s overlaps %s", who, other);
     }
     DeviceGuard guard(ctx);
-    if ((rc = hn_reserve(ctx, batch)) != HN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = reserve_workspace(ctx, batch, s)) != HN_OK) return rc;
     if (n_iter == 0) return HN_OK;
     if ((rc = check_async(ctx, "hn_step (an earlier call)")) != HN_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
     int ns = ctx->opt_lanes;
     if (batch < 2 * ns) ns = 1;                       // tiny batches: not worth splitting
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cap_status);
-    if ((rc = ensure_step_resources(ctx, ns, ctx->opt_side_stream != 0, s, cap_status == hipStreamCaptureStatusNone)) != HN_OK) return rc;
+    if ((rc = ensure_step_resources(ctx, ns, use_side, s, cap_status == hipStreamCaptureStatusNone)) != HN_OK) return rc;
     if (rmse_hist) {
         if ((rc = zero_async(ctx, rmse_hist, sizeof(float) * (size_t)n_iter * batch, s)) != HN_OK) return rc;
         if ((rc = zero_async(ctx, ctx->it_counter, 8 * sizeof(int), s)) != HN_OK) return rc;
     }
-    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist};
+    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist, use_side};
     const size_t fb_all = sizeof(float) * (size_t)batch * 2 * plane, sb_all = sizeof(float) * (size_t)batch * kState * L;
     if (ns == 1) {
         // One lane: an iteration is a fixed kernel sequence over fixed buffers (the hidden states ping-pong between the
@@ -1093,15 +1102,15 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         const bool caller_capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
         hn_ctx::StepGraph* g = nullptr;
-        const int per_graph = ctx->opt_graph > 1 ? ctx->opt_graph : 1;
+        const int per_graph = opt_graph > 1 ? opt_graph : 1;
         const bool hist = res_hist || wf_hist || st_hist;
-        if (ctx->opt_graph && n_iter >= 4 * per_graph && !caller_capturing && !(per_graph > 1 && (hist || ctx->prof_mask))) g = step_graph(ctx, a);
+        if (opt_graph && n_iter >= 4 * per_graph && !caller_capturing && !(per_graph > 1 && (hist || ctx->prof_mask))) g = step_graph(ctx, a);
         // flag sync (hn_internal.h: sync_flags): between the iterations of this call the side stream is released and joined through device words instead
         // of event packets.  Its gate kernel spins from the moment the side stream is free, so the side stream first waits for the caller's stream to get
         // here (one event per CALL), and the last iteration joins with an event as before (the caller's stream must own the final states).
-        const bool flag_sync = g == nullptr && n_iter > 1 && !st_hist && side_flags_apply(ctx, s);
+        const bool flag_sync = g == nullptr && n_iter > 1 && !st_hist && use_side && side_flags_apply(ctx, s);
         // histories without copies: every iteration launched kernel by kernel (no graph) and the slots not aliasing the caller's own buffers
-        const bool zero_copy = g == nullptr && ctx->opt_hist_copy == 0 && (res_hist == nullptr || res_hist != res) && (wf_hist == nullptr || wf_hist != wf);
+        const bool zero_copy = g == nullptr && !hist_copy && (res_hist == nullptr || res_hist != res) && (wf_hist == nullptr || wf_hist != wf);
         if (flag_sync) {
             HN_HIP(ctx, hipEventRecord(ctx->ev_fork, s));
             HN_HIP(ctx, hipStreamWaitEvent(ctx->side[0].stream, ctx->ev_fork, 0));
@@ -1126,7 +1135,7 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
             } else {
                 // the new hidden states are first needed by the next iteration's conv_signal_0: the side-stream join moves there,
                 // unless something reads them right away (a state history) or this is the last iteration
-                const bool defer = (ctx->opt_defer_join || flag_sync) && ctx->opt_side_stream && !st_hist && it + 1 < n_iter && g == nullptr;
+                const bool defer = (ctx->opt_defer_join || flag_sync) && use_side && !st_hist && it + 1 < n_iter && g == nullptr;
                 // zero-copy histories (kernel-by-kernel launches only: a captured iteration has its buffers baked in): iteration `it` reads slot it - 1
                 // (the caller's wf / res for it = 0) and writes slot it; the caller's buffers receive the last slot once, behind the loop
                 const size_t slot = (size_t)batch * 2 * plane;
@@ -1190,13 +1199,12 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
 }
 
 // Laboratory accessor (tools/deepx_check.py; not part of the ABI of include/helmnet_hip.h): the workspace tensor kind (0 x_d / upsampled, 1 skip out_d,
-// 2 decoder output y_d) of level d, [reserved batch][8][n_d][n_d] floats.
+// 2 decoder output y_d) of level d, [reserved batch][8][h >> d][w >> d] floats.
 int hn_debug_workspace(hn_ctx* ctx, int which, int level, float** ptr, long* floats) {
     if (!ctx || !ptr || !floats || level < 0 || level > kMaxDepth) return HN_ERR_ARG;
     float* p = which == 0 ? ctx->buf_a[level] : which == 1 ? (level < kMaxDepth ? ctx->buf_o[level] : nullptr) : ctx->buf_y[level];
-    const long m = ctx->tab.n >> level;
     *ptr = p;
-    *floats = p ? (long)ctx->cap_batch * kFeat * m * m : 0;
+    *floats = p ? (long)ctx->cap_batch * kFeat * (ctx->geo.h >> level) * (ctx->geo.w >> level) : 0;
     return HN_OK;
 }
 

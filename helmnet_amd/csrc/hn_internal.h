@@ -326,6 +326,13 @@ struct hn_ctx {
     // domain
     hn::SpecTables tab;
     hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty
+    // what either kind of domain is to the entry points and to unet_forward: rows, columns and the device's [2, h, w] sigma maps (they belong to tab or
+    // to rect).  Set by hn_set_domain / hn_set_domain_rect, cleared (h == 0) when the domain goes.
+    struct Geometry {
+        int h = 0, w = 0;
+        const float* sigmas = nullptr;
+        long plane() const { return (long)h * w; }
+    } geo;
     int64_t state_len = 0;
     int64_t state_off[hn::kMaxDepth]{};
     // workspace
@@ -514,7 +521,7 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k);
 void spec_free(SpecTables& t);
 // out = L(wf) [+ ksq*wf - src]; `accum_sumsq` (nullable) receives sum over (c,h,w) of out^2 per sample, in row
 // `*it_counter - 1` of a [.., sumsq_stride] table when `it_counter` is given (the column pass increments it: one
-// captured iteration can then be replayed for every row of the RMSE history), else in row 0.
+// captured iteration can then be replayed for every row of the RMSE history), else in row 0.  On a rectangular domain: spec_rect_apply.
 int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch,
                int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
 // out = L^H(g) + ksq * g [+ add]: the adjoint (conjugate transpose) of the residual operator, i.e. the vector-Jacobian product
@@ -667,21 +674,8 @@ struct UnetCall {
     hn_ctx::SideLane* side_lane = nullptr;   // non-null: the hidden-state kernels may leave the main chain for this lane's side stream
     bool defer_join = false;              // leave the side stream unjoined: the next call on this lane (or side_join) waits for it
 };
+// On the h x w domain of ctx->geo.  A rectangular one (the caller leaves side_lane and after_down0 null): one stream, layer by layer.
 int unet_forward(hn_ctx* ctx, const UnetCall& c);
-// ---- the same on a rectangular domain (hn_unet_rect.hip): one stream, layer by layer; side_lane, after_down0 and defer_join are not used ----
-int unet_forward_rect(hn_ctx* ctx, const UnetCall& c);
-void rect_state_layout(hn_ctx* ctx);   // state_len / state_off of ctx->rect for the loaded depth
-int rect_reserve(hn_ctx* ctx, int max_batch, hipStream_t s);   // hn_reserve; s (nullable): HN_ERR_STATE when it would build or grow under capture of s
-int rect_unet(hn_ctx* ctx, const float* in6, const float* states_in, float* states_out, float* d_out, int batch, hipStream_t s);
-int rect_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* src, int src_batch, int batch, int n_iter, float* res_hist,
-              float* wf_hist, float* st_hist, float* rmse_hist, hipStream_t s);
-void free_workspace(hn_ctx* ctx);   // (hn_api.hip)
-void launch_rmse_finalize(float* v, int count, float inv_n, hipStream_t s);   // (hn_api.hip) v[i] = sqrt(v[i] * inv_n): sums of squares -> RMSE rows
-// the direct fp32 kernels of hn_unet.hip (k_double_conv, k_down8x8, k_up8x8: any H, W) for a driver in another file; fin as launch_dc8's
-void launch_dc_direct(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s);
-void launch_state_direct(const StateLevel& v, int batch, hipStream_t s);
-void launch_down_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s);
-void launch_up_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s);
 // make stream s wait for the hidden-state kernels of the previous unet_forward with defer_join on this lane
 int side_join(hn_ctx* ctx, hn_ctx::SideLane* side_lane, hipStream_t s);
 bool side_flags_apply(hn_ctx* ctx, hipStream_t s);

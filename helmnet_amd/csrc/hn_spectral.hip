@@ -2151,6 +2151,7 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
 
 int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch,
                int batch, float* accum_sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
+    if (ctx->rect) return spec_rect_apply(ctx, wf, out, ksq, src, src_batch, batch, accum_sumsq, s, it_counter, sumsq_stride);
     const SpecTables& t = ctx->tab;
     if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return HN_OK;

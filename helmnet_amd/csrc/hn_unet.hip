@@ -437,7 +437,9 @@ __global__ void k_sync_gate(const unsigned* flag, unsigned epoch, int* err) {
 }  // namespace
 
 int unet_forward(hn_ctx* ctx, const UnetCall& c) {
-    const int n = ctx->tab.n, depth = ctx->depth, batch = c.batch, ws_off = c.ws_off;
+    // H x W: the domain, square or not.  What exists for n x n alone (the merged level-0 launch, the deep-level kernels, the input layer's sigma map) asks
+    // its own gate, and those compare against tab.n, which is 0 on a rectangle: there every layer is launched on its own, on c.stream
+    const int H = ctx->geo.h, W = ctx->geo.w, depth = ctx->depth, batch = c.batch, ws_off = c.ws_off;
     const hipStream_t s = c.stream;
     hn_ctx::SideLane* const side_lane = c.side_lane;
     const long L = ctx->state_len;
@@ -445,43 +447,43 @@ int unet_forward(hn_ctx* ctx, const UnetCall& c) {
     const DcEpi noepi{nullptr, nullptr, nullptr, nullptr};
     const bool mfma = ctx->precision != HN_PREC_FP32_VALU;
     hipStream_t side = side_lane ? side_lane->stream : nullptr;
-    auto plane = [&](int d) { const long m = n >> d; return m * m; };
+    auto plane = [&](int d) { return (long)(H >> d) * (W >> d); };
     // ws_off: first sample slot of the workspace this call may use (sub-batches on parallel streams)
     auto feat = [&](float* p, int d) { return Dst{p + (long)ws_off * kFeat * plane(d), kFeat * plane(d), plane(d)}; };
     auto featsrc = [&](const float* p, int d) { return Src{p + (long)ws_off * kFeat * plane(d), kFeat * plane(d), plane(d), 1.f}; };
     auto st_old = [&](int d) { return Src{c.states_in + ctx->state_off[d], 2 * L, L, 1.f}; };
     // state = conv_state(cat[out, state_old]) of level d                  (architectures.py:248)
     auto state_level = [&](int d) {
-        return StateLevel{featsrc(ctx->buf_o[d], d), st_old(d), Dst{c.states_out + ctx->state_off[d], 2 * L, L}, ctx->st[d].w, n >> d, n >> d};
+        return StateLevel{featsrc(ctx->buf_o[d], d), st_old(d), Dst{c.states_out + ctx->state_off[d], 2 * L, L}, ctx->st[d].w, H >> d, W >> d};
     };
     // One DoubleConv of level d: the matrix-core / vector-pipe launchers (launch_dc8) or, in HN_PREC_FP32_VALU, the direct kernel above.
     // fin (decode_0 only): + outc 1x1 (architectures.py:463) and wf <- d/1e3 + wf (hybridnet.py:570)
     auto dc = [&](DcKind kind, int d, Src a, Src b, Src c3, Dst out, const FinalEpi* fin) {
         const DcLayer& l = kind == DcKind::Inc ? ctx->inc : kind == DcKind::Signal ? ctx->sig[d] : ctx->dec[d];
-        const int m = n >> d;
-        if (mfma) return launch_dc8(ctx, kind, a, b, c3, out, l, fin, m, m, batch, s);
+        const int h = H >> d, w = W >> d;
+        if (mfma) return launch_dc8(ctx, kind, a, b, c3, out, l, fin, h, w, batch, s);
         switch (kind) {
-            case DcKind::Inc: launch_dc<2, 2, 2, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s); break;
-            case DcKind::Signal: launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s); break;
-            case DcKind::Bottleneck: launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s); break;
+            case DcKind::Inc: launch_dc<2, 2, 2, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, h, w, batch, s); break;
+            case DcKind::Signal: launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, h, w, batch, s); break;
+            case DcKind::Bottleneck: launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, h, w, batch, s); break;
             case DcKind::Decoder:
-                if (fin == nullptr) launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, m, m, batch, s);
-                else launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(a, b, c3, out, l.w, DcEpi{ctx->outc_w, ctx->outc_b, fin->d_out, fin->wf_out, fin->wf_in}, m, m, batch, s);
+                if (fin == nullptr) launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(a, b, c3, out, l.w, noepi, h, w, batch, s);
+                else launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(a, b, c3, out, l.w, DcEpi{ctx->outc_w, ctx->outc_b, fin->d_out, fin->wf_out, fin->wf_in}, h, w, batch, s);
                 break;
         }
     };
     // x_{d+1} = down(out_d) / u_d = up[d](y_{d+1}): the matrix-core kernels or the direct ones above
     auto down = [&](int d) {
-        const int m = n >> d;
-        if (mfma) launch_down(ctx, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].f, m, m, batch, s);
-        else hipLaunchKernelGGL(k_down8x8, dim3(cdiv(m / 2, DownCfg::TW), cdiv(m / 2, DownCfg::TH), batch), dim3(DownCfg::NT), 0, s,
-                                featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].w, m, m);
+        const int h = H >> d, w = W >> d;
+        if (mfma) launch_down(ctx, featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].f, h, w, batch, s);
+        else hipLaunchKernelGGL(k_down8x8, dim3(cdiv(w / 2, DownCfg::TW), cdiv(h / 2, DownCfg::TH), batch), dim3(DownCfg::NT), 0, s,
+                                featsrc(ctx->buf_o[d], d), feat(ctx->buf_a[d + 1], d + 1), ctx->down[d].w, h, w);
     };
     auto up = [&](int d, const SyncHook& hook) {
-        const int m = n >> d;
-        if (mfma) launch_up(ctx, featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].f, m / 2, m / 2, batch, s, false, hook);
-        else hipLaunchKernelGGL(k_up8x8, dim3(cdiv(m / 2, UpCfg::TW), cdiv(m / 2, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s,
-                                featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].w, m / 2, m / 2);
+        const int h = H >> (d + 1), w = W >> (d + 1);   // (the input's)
+        if (mfma) launch_up(ctx, featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].f, h, w, batch, s, false, hook);
+        else hipLaunchKernelGGL(k_up8x8, dim3(cdiv(w, UpCfg::TW), cdiv(h, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s,
+                                featsrc(ctx->buf_y[d + 1], d + 1), feat(ctx->buf_a[d], d), ctx->up[d].w, h, w);
     };
     // one level's conv_state on stream st: the streaming kernel (hn_cs.hip) where it applies, else the general kernel
     auto conv_state = [&](const StateLevel& v, hipStream_t st) {
@@ -495,14 +497,14 @@ int unet_forward(hn_ctx* ctx, const UnetCall& c) {
     const bool not_capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
     (void)hipGetLastError();
     const bool eager = not_capturing && ws_off == 0 && ctx->opt_lanes == 1 && side_lane != nullptr;   // hn_step's single lane, launched kernel by kernel (flag sync below)
-    const bool pair = mfma && dc_asm_pair_applies(ctx, c.wf, c.res, c.sig, featsrc(ctx->buf_a[0], 0), st_old(0), n, n, batch, ws_off);
+    const bool pair = mfma && dc_asm_pair_applies(ctx, c.wf, c.res, c.sig, featsrc(ctx->buf_a[0], 0), st_old(0), H, W, batch, ws_off);
     if (pair) {
         if (side_lane != nullptr) {   // (deferred join: conv_signal_0 reads the new states)
             int rc = side_join(ctx, side_lane, s);
             if (rc != HN_OK) return rc;
         }
         ProfScope ps(ctx, KID_INC_SIG0, s);
-        HN_REP(KID_INC_SIG0) launch_dc_asm_pair(ctx, c.wf, c.res, c.sig, feat(ctx->buf_a[0], 0), featsrc(ctx->buf_a[0], 0), st_old(0), feat(ctx->buf_o[0], 0), n, n, batch, ws_off, !not_capturing, s);
+        HN_REP(KID_INC_SIG0) launch_dc_asm_pair(ctx, c.wf, c.res, c.sig, feat(ctx->buf_a[0], 0), featsrc(ctx->buf_a[0], 0), st_old(0), feat(ctx->buf_o[0], 0), H, W, batch, ws_off, !not_capturing, s);
     } else {
         // inc: DoubleConv(6 -> 8 -> 8) on [wf, 1e3*res, sigmas]  (architectures.py:442, hybridnet.py:566)
         ProfScope ps(ctx, KID_INC, s);
@@ -729,32 +731,6 @@ int module_out_conv(hn_ctx* ctx, const float* x, const float* w_io, const float*
     hipLaunchKernelGGL(k_out_conv, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w_io, b, out, plane, total);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// The same direct kernels for a driver in another file (hn_unet_rect.hip): HN_PREC_FP32_VALU's layers, and conv_state where the streaming kernel
-// does not apply.  Any H, W.
-// ------------------------------------------------------------------------------------------
-void launch_dc_direct(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcW& w, const FinalEpi* fin, int H, int W, int batch, hipStream_t s) {
-    const DcEpi noepi{nullptr, nullptr, nullptr, nullptr};
-    switch (kind) {
-        case DcKind::Inc: launch_dc<2, 2, 2, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s); break;
-        case DcKind::Signal: launch_dc<kFeat, kState, 0, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s); break;
-        case DcKind::Bottleneck: launch_dc<kFeat, 0, 0, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s); break;
-        case DcKind::Decoder:
-            if (fin == nullptr) launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 0>(a, b, c, out, w, noepi, H, W, batch, s);
-            else launch_dc<kFeat, kFeat, 0, kFeat, kFeat, 1>(a, b, c, out, w, DcEpi{ctx->outc_w, ctx->outc_b, fin->d_out, fin->wf_out, fin->wf_in}, H, W, batch, s);
-            break;
-    }
-}
-void launch_state_direct(const StateLevel& v, int batch, hipStream_t s) {
-    launch_dc<kFeat, kState, 0, kState, kState, 0>(v.a, v.b, Src{nullptr, 0, 0, 1.f}, v.out, v.w, DcEpi{nullptr, nullptr, nullptr, nullptr}, v.H, v.W, batch, s);
-}
-void launch_down_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s) {
-    hipLaunchKernelGGL(k_down8x8, dim3(cdiv(Win / 2, DownCfg::TW), cdiv(Hin / 2, DownCfg::TH), batch), dim3(DownCfg::NT), 0, s, in, out, w, Hin, Win);
-}
-void launch_up_direct(Src in, Dst out, const K8W& w, int Hin, int Win, int batch, hipStream_t s) {
-    hipLaunchKernelGGL(k_up8x8, dim3(cdiv(Win, UpCfg::TW), cdiv(Hin, UpCfg::TH), batch), dim3(UpCfg::NT), 0, s, in, out, w, Hin, Win);
 }
 
 }  // namespace hn

@@ -41,7 +41,13 @@ OPERATOR_SHAPES = [(16, 32), (32, 16), (48, 80), (80, 48), (144, 64), (64, 272),
 TRANSPOSE_SHAPES = [(48, 80), (144, 64)]
 SQUARE_SIZES = [96, 256]
 # (16, 512): the kernels of W >= 256 on a very short H (level 3 is 2 x 64 on the streaming conv_state kernel, the bottleneck 1 x 32)
-STEP_SHAPES = [(32, 80, 2), (80, 32, 2), (16, 48, 1), (64, 256, 1), (256, 64, 1), (48, 272, 1), (16, 512, 1)]
+# (256, 512): H >> 3 = 32 and W >> 3 = 64, the sizes at which the deep-level kernels take a square; W >= 256: the hand-scheduled level-0 kernels
+STEP_SHAPES = [(32, 80, 2), (80, 32, 2), (16, 48, 1), (64, 256, 1), (256, 64, 1), (48, 272, 1), (16, 512, 1), (256, 512, 1)]
+ROUTE_SHAPES = [(32, 80, 2), (256, 512, 1)]
+# options that select something a square domain alone has (captured iterations, the side stream and its device words, the deep-level kernels, zero-copy
+# histories, the merged level-0 launch, the input layer's sigma map), each away from its default
+SQUARE_ONLY_OPTIONS = [("graph", 1, 0), ("side_stream", 0, 1), ("side_stream", 2, 1), ("side_stream", 3, 1), ("deep", 0, 2), ("hist_copy", 1, 0),
+                       ("dc_pair", 0, 1), ("side_sync", 0, 1), ("inc_sigma_map", 0, 1)]      # (name, value, default)
 LOOP_SHAPES = [(96, 160, 2), (160, 96, 1)]
 # batch 384 at (144, 64): columns 144 long, 64 of them -> 64 * 384 / 16 = 1536 blocks >= 512: 16 lines per block; rows 64 long, 144 of them: 16 too
 BATCH_SHAPES = [(32, 80, 3), (144, 64, 3), (144, 64, 384)]
@@ -447,6 +453,43 @@ def test_second_call_can_be_captured_and_replayed(blob):
             torch.cuda.synchronize()
         assert torch.equal(wf, eager["wf"]) and torch.equal(res, eager["res"]) and torch.equal(st, eager["st"])
         assert torch.allclose(rmse, eager["rmse"], rtol=1e-5, atol=0)
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("h,w,b", ROUTE_SHAPES)
+def test_square_only_options_do_not_move_a_rectangle_off_its_route(blob, h, w, b):
+    """A rectangle runs one lane, launched kernel by kernel on the caller's stream, with copied histories, whatever the options of the square path say:
+    the same bits, no captured iteration, no flag-synchronised one, no stream probe, and every iteration counted as launched one by one.
+    The RMSE rows keep this file's rtol 1e-5 (one atomicAdd per block: two runs of one route need not give the same bits there); they are also the
+    RMSE of the residual history, which is compared exactly."""
+    n_iter = 8
+    still = ("graph_replays", "graphs_captured", "flag_sync_iterations", "stream_probes")
+    e = _engine(h, w, blob)
+    try:
+        p = _problem(h, w, b, 29 + w)
+
+        def counted_run():
+            before = {k: e.counter(k) for k in still + ("eager_iterations",)}
+            out = _run(e, p, n_iter, hist=True)
+            e.check_async_errors()
+            moved = {k: e.counter(k) - v for k, v in before.items()}
+            assert moved.pop("eager_iterations") == n_iter
+            assert not any(moved.values()), moved
+            return out
+
+        base = counted_run()
+        for k in base:
+            assert not bool(torch.isnan(base[k]).any()), k
+        for name, value, default in SQUARE_ONLY_OPTIONS:
+            e.set_option(name, value)
+            got = counted_run()
+            e.set_option(name, default)
+            for k in base:
+                if k == "rmse":
+                    assert torch.allclose(got[k], base[k], rtol=1e-5, atol=0), (name, value)
+                else:
+                    assert torch.equal(got[k], base[k]), (name, value, k)
     finally:
         e.close()
 
