@@ -340,7 +340,7 @@ int hn_create(hn_ctx** out, int device_id) {
     }
     const struct { const char* env; int opt; } knobs[] = {{"HN_STREAMS", HN_OPT_LANES}, {"HN_SIDE_STREAM", HN_OPT_SIDE_STREAM},
                                                             {"HN_GRAPH", HN_EXP_GRAPH}, {"HN_DEEP", HN_OPT_DEEP},
-                                                            {"HN_TRAIN_LANES", HN_EXP_TRAIN_LANES}, {"HN_TRAIN_FUSED", HN_OPT_TRAIN_FUSED}, {"HN_TRAIN_OVERLAP", HN_OPT_TRAIN_OVERLAP}, {"HN_DC_VALU", HN_OPT_DC_VALU}, {"HN_DC_PAIR", HN_OPT_DC_PAIR}, {"HN_SIDE_SYNC", HN_OPT_SIDE_SYNC}, {"HN_STATE_KERNEL", HN_OPT_STATE_KERNEL}, {"HN_HIST_COPY", HN_OPT_HIST_COPY}, {"HN_INC_SIGMA_MAP", HN_OPT_INC_SIGMA_MAP}, {"HN_SPECTRAL_MIXED", HN_OPT_SPECTRAL_MIXED}, {"HN_SPECTRAL_PLAIN", HN_EXP_SPECTRAL_PLAIN}};
+                                                            {"HN_TRAIN_LANES", HN_EXP_TRAIN_LANES}, {"HN_TRAIN_FUSED", HN_OPT_TRAIN_FUSED}, {"HN_TRAIN_OVERLAP", HN_OPT_TRAIN_OVERLAP}, {"HN_DC_VALU", HN_OPT_DC_VALU}, {"HN_DC_PAIR", HN_OPT_DC_PAIR}, {"HN_SIDE_SYNC", HN_OPT_SIDE_SYNC}, {"HN_STATE_KERNEL", HN_OPT_STATE_KERNEL}, {"HN_HIST_COPY", HN_OPT_HIST_COPY}, {"HN_INC_SIGMA_MAP", HN_OPT_INC_SIGMA_MAP}, {"HN_SPECTRAL_MIXED", HN_OPT_SPECTRAL_MIXED}, {"HN_F64_FFT", HN_OPT_F64_FFT}, {"HN_SPECTRAL_PLAIN", HN_EXP_SPECTRAL_PLAIN}};
     // Counter collection (rocprofv3 --pmc, rocprof -i / ROCP_METRICS) runs ONE kernel at a time across all queues, in an order of the tool's choosing: a kernel that
     // waits for a word another queue's kernel stores may then be the one that runs -- the bounded wait gives up after 2 s and hn_step fails [seen, r5].  Under such
     // a tool the hand-overs stay event packets unless HN_SIDE_SYNC says otherwise (the merged level-0 launch is ONE kernel and is not affected).
@@ -398,6 +398,10 @@ int hn_set_option(hn_ctx* ctx, int option, int value) {
         case HN_OPT_SPECTRAL_MIXED:
             if (value < 0 || value > 1) return fail(ctx, HN_ERR_ARG, "HN_OPT_SPECTRAL_MIXED must be 0 or 1 (got %d)", value);
             ctx->opt_mixed = value;
+            break;
+        case HN_OPT_F64_FFT:
+            if (value < 0 || value > 1) return fail(ctx, HN_ERR_ARG, "HN_OPT_F64_FFT must be 0 or 1 (got %d)", value);
+            ctx->opt_f64_fft = value;
             break;
         case HN_OPT_DC_VALU:
             if (value < 0 || value > 4) return fail(ctx, HN_ERR_ARG, "HN_OPT_DC_VALU must be 0 .. 4 (got %d)", value);
@@ -464,6 +468,7 @@ int64_t hn_get_counter(const hn_ctx* ctx, int counter) {
         case HN_CNT_FLAG_SYNC_ITERATIONS: return ctx->flag_sync_iterations;
         case HN_CNT_SIDE_CANDIDATE: return ctx->picks[0].known.empty() ? -1 : ctx->picks[0].last_chosen;
         case HN_CNT_SPECTRAL_ROUTE: return ctx->rect != nullptr ? 5 : ctx->tab.n == 0 ? 0 : ctx->tab.pow2 ? 1 : ctx->tab.pfa_p != 0 ? 2 : ctx->tab.mix_p != 0 ? 4 : 3;
+        case HN_CNT_F64_ROUTE: return ctx->f64_route;
         default: return -1;
     }
 }
@@ -480,6 +485,7 @@ void hn_destroy(hn_ctx* ctx) {
     unet_f64_free(ctx);
     jvp_free(ctx);
     krylov_free(ctx);
+    f64_fft_free(ctx);
     spec_free(ctx->tab);
     spec_rect_free(ctx);
     (void)hipFree(ctx->wdev);
@@ -607,6 +613,8 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     unet_f64_free(ctx);
     jvp_free(ctx);
     krylov_free(ctx);
+    f64_fft_free(ctx);
+    ctx->f64_route = 0;
     if (n % 16 != 0) return fail(ctx, HN_ERR_ARG, "domain size %d must be divisible by 16", n);
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
     if (n != ctx->tab.n) free_workspace(ctx);
@@ -634,6 +642,8 @@ int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, floa
     unet_f64_free(ctx);
     jvp_free(ctx);
     krylov_free(ctx);
+    f64_fft_free(ctx);
+    ctx->f64_route = 0;
     free_workspace(ctx);
     spec_free(ctx->tab);
     int rc = build_inc_sigma_map(ctx);   // (no n x n domain: frees the map)

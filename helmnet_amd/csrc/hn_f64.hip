@@ -3,7 +3,7 @@
 //   L(u) = ax . D1x u + bx . D2x u + ay . D1y u + by . D2y u        (spectral.py:31-79 under .double())
 //   res  = L(u) + k_sq . u - src                                    (hybridnet.py:544-556)
 //
-// ONE code path for every legal n.  D1 = F^-1 diag(i k) F and D2 = F^-1 diag(-k^2) F are circulant, D[j][m] = g[(j - m) mod n], so an axis'
+// ONE dense code path for every legal n (the default; HN_OPT_F64_FFT 1 routes f64_reserve / f64_apply to the line transforms of hn_f64_fft.hip instead).  D1 = F^-1 diag(i k) F and D2 = F^-1 diag(-k^2) F are circulant, D[j][m] = g[(j - m) mod n], so an axis'
 // operator is its first column: g2 real, g1 real but for the Nyquist term (the reference keeps k = -pi there, which makes Im g1[d] = k1[n/2] (-1)^d / n).
 // The kernel keeps Re g1, Im g1 and g2 in LDS (24 n bytes) and reads matrix elements from there; only the wavefield is streamed.  The values are the
 // reference's: the fp32 wavenumber grid with its fp32 square and the fp32-rounded PML coefficients, carried and applied in float64.
@@ -199,9 +199,10 @@ bool first_overlap(const MemRange* r, int count, const char** a_name, const char
 }
 
 // the first float64 call on a domain builds and uploads the tables; a larger batch with an rmse grows the table of partial sums (one per tile and sample)
-int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s) {
+int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s, bool want_out) {
     SpecTables& t = ctx->tab;
     if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    if (ctx->opt_f64_fft) return f64_fft_reserve(ctx, batch, want_rmse, want_out, s);   // (its tables live beside the dense ones: flipping back finds them)
     const int tiles_1d = (t.n + kTile - 1) / kTile;
     const long part_needed = want_rmse ? (long)batch * tiles_1d * tiles_1d : 0;
     if (t.f64_tab != nullptr && part_needed <= t.f64_part_cap) return HN_OK;
@@ -252,7 +253,15 @@ int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, con
     const MemRange r[] = {{wf, bytes, false, "wf"}, {out, bytes, true, "out"}};
     const char *na, *nb;
     if (first_overlap(r, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "float64 residual: the wavefield must not alias the output");
-    if (int rc = f64_reserve(ctx, batch, rmse != nullptr, s); rc != HN_OK) return rc;
+    if (int rc = f64_reserve(ctx, batch, rmse != nullptr, s, out != nullptr); rc != HN_OK) return rc;
+    if (ctx->opt_f64_fft) {
+        double* lines = nullptr;   // one partial sum per line: k_rmse_f64 adds a sample's n of them
+        if (int rc = f64_fft_launch(ctx, wf, out, ksq, src, src_batch == 1 ? 0L : 2 * plane, rmse != nullptr, batch, s, &lines); rc != HN_OK) return rc;
+        if (rmse != nullptr) hipLaunchKernelGGL(k_rmse_f64, dim3(batch), dim3(256), 0, s, lines, n, 1.0 / (2.0 * (double)plane), rmse);
+        HN_HIP(ctx, hipGetLastError());
+        ctx->f64_route = 2;
+        return HN_OK;
+    }
     double* part = rmse != nullptr ? t.f64_part : nullptr;
     const dim3 grid(tiles_1d, tiles_1d, batch);
     const size_t lds = f64_lds_bytes(n);
@@ -262,6 +271,7 @@ int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, con
         hipLaunchKernelGGL(k_helm_f64<false>, grid, dim3(256), lds, s, wf, out, ksq, src, 0L, t.f64_tab, n, part);
     if (rmse != nullptr) hipLaunchKernelGGL(k_rmse_f64, dim3(batch), dim3(256), 0, s, part, tiles, 1.0 / (2.0 * (double)plane), rmse);
     HN_HIP(ctx, hipGetLastError());
+    ctx->f64_route = 1;
     return HN_OK;
 }
 

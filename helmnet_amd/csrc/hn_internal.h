@@ -232,6 +232,7 @@ struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-
 struct RefineWs;  // GMRES refinement step (hn_krylov.hip): float64 copies of k_sq and rhs, the float64 residual, the fp32 scaled right-hand side and correction
 struct PrecondWs; // flexible GMRES cycle (hn_krylov.hip): the learned preconditioner's source, wavefield, residual and hidden states
 struct JvpWs;     // forward-mode loop (hn_jvp.hip): the fp32 blob on the device, the packed-dual activation workspace, the second tangent-state buffer and the tangent source
+struct F64Fft;    // float64 operator by FFT (hn_f64_fft.hip, HN_OPT_F64_FFT): the double tables, the per-line partial sums and the intermediate field of an rmse-only call
 struct F64Unet;   // float64 solver loop (hn_unet_f64.hip): the up-cast weights, the activation workspace and the second flat-state buffer
 // First columns of the circulant spectral derivative operators in float64: D1[j][m] = g1[(j - m) mod n], D2[j][m] = g2[(j - m) mod n] with
 // g1[d] = (1/n) sum_p i k1_p exp(2 pi i p d / n), g2 likewise from k2.  g2 is real; g1 is real but for the Nyquist term i k1[n/2] (-1)^d / n.
@@ -325,6 +326,9 @@ struct hn_ctx {
     const float* outc_b = nullptr;  // [2]
     // domain
     hn::SpecTables tab;
+    hn::F64Fft* f64fft = nullptr;     // built / grown by the first float64 call on the FFT route that needs it (beside tab.f64_tab, which stays); freed by hn_set_domain, hn_set_domain_rect, hn_destroy
+    int opt_f64_fft = 0;              // HN_OPT_F64_FFT: 0 the dense kernel k_helm_f64, 1 the two line passes of hn_f64_fft.hip; read by every float64 call
+    int f64_route = 0;                // HN_CNT_F64_ROUTE: 0 no float64 call on this domain yet, 1 the last one ran dense, 2 by FFT
     hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty
     // what either kind of domain is to the entry points and to unet_forward: rows, columns and the device's [2, h, w] sigma maps (they belong to tab or
     // to rect).  Set by hn_set_domain / hn_set_domain_rect, cleared (h == 0) when the domain goes.
@@ -549,7 +553,14 @@ int rect_unsupported(hn_ctx* ctx, const char* who);
 int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, int src_batch, double* rmse, int batch, hipStream_t s);
 // the tables and, with want_rmse, the partial sums a call of f64_apply with this batch needs, so that it has nothing left to build (HN_ERR_STATE under
 // stream capture): an entry point that launches before it reaches f64_apply asks here first
-int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s);
+// (want_out false: the call will pass out == NULL, for which the FFT route needs an intermediate field of its own)
+int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s, bool want_out = true);
+// ---- the same operator by FFT (hn_f64_fft.hip; HN_OPT_F64_FFT 1).  f64_reserve / f64_apply are the only callers ----
+int f64_fft_reserve(hn_ctx* ctx, int batch, bool want_rmse, bool want_out, hipStream_t s);
+// the two passes on `s` (everything reserved); *part = the [batch][n] per-line sums of squares if want_part, else NULL
+int f64_fft_launch(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, long src_sb, bool want_part, int batch, hipStream_t s,
+                   double** part);
+void f64_fft_free(hn_ctx* ctx);   // (the caller has synchronised the device)
 // ---- what the float64 and GMRES entry points share (defined in hn_f64.hip) ----
 bool stream_capturing(hipStream_t s);   // a non-null stream under capture: nothing may be built, grown or freed
 // One zeroed device allocation handed out as 256-byte-aligned pieces: alloc() with the pieces' byte sizes, then one take() per piece, in that order.

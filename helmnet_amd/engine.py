@@ -222,7 +222,11 @@ class Engine:
         is not read); 3 is another factorisation (fp32 rounding).  'spectral_plain' (laboratory knob) 1: the 256- / 512-point kernels on plain C++
         complex helpers, bit-identical to 0.  'spectral_radix16' and 'spectral_pfa' select other kernels for the same fp32 arithmetic: results agree to fp32 rounding (every
         combination is within 1e-6 of the operator's scale of the float64 oracle, the dense operator within 7e-6), not bit for bit.  Neither makes a
-        sample's result depend on what shares its batch (tests/test_spectral_gpu.py)."""
+        sample's result depend on what shares its batch (tests/test_spectral_gpu.py).
+        'f64_fft' 0/1 (default 0) picks the route of the float64 operator (laplacian64, residual64, step64, the refine cycles): 0 the dense kernel, 1 two
+        FFT line passes in double (laplacian.f64_route).  It is read by every float64 call, needs no table re-build and can be flipped between calls;
+        the routes agree to float64 rounding (2e-11 of the scale), not bit for bit; counter('f64_route') tells which one the last float64 call on the
+        domain took (0 none yet, 1 dense, 2 FFT)."""
         if name not in _lib.HN_OPTION:
             raise ValueError(f"unknown option {name!r} (choose from {sorted(_lib.HN_OPTION)})")
         _lib.check(self.lib.hn_set_option(self.ctx, _lib.HN_OPTION[name], int(value)), self.ctx, "hn_set_option")

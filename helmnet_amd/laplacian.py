@@ -63,6 +63,22 @@ def spectral_route(n: int, pfa: int = 1, mixed: int = 0):
     return "dense", p, q
 
 
+def f64_route(n: int, f64_fft: int = 0):
+    """The route of the float64 operator (hn_laplacian_f64, hn_residual_f64 and everything built on them) on an n x n domain under the option
+    'f64_fft', context-free like ``spectral_route``: ('dense',) for 0, the circulant kernel at every size; ('fft', P, Q) for 1, the line transforms
+    of hn_f64_fft.hip with n = P * Q, Q the largest power of two dividing n -- for every multiple of 16 in [16, 2048] P is odd in [1, 127] and Q
+    in [16, 2048], so no legal size falls back.  Engine.counter('f64_route') reports the route the last call took as 1 / 2."""
+    n, f64_fft = int(n), int(f64_fft)
+    if n < 16 or n > 2048 or n % 16:
+        raise ValueError(f"domain size {n} is not a multiple of 16 in [16, 2048]")
+    if f64_fft not in (0, 1):
+        raise ValueError(f"f64_fft must be 0 or 1 (got {f64_fft})")
+    if not f64_fft:
+        return ("dense",)
+    q = n & -n
+    return "fft", n // q, q
+
+
 def domain_hw(domain_size):
     """(rows, columns) of a domain size given as an int (n x n) or a pair (H, W)."""
     if isinstance(domain_size, (tuple, list)):

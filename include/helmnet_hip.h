@@ -108,6 +108,14 @@ enum hn_option {
                               * P interleaved 2^k-point transforms in LDS and a direct P-point DFT across them (hn_spectral_mixed.hip).  Agrees with
                               * the dense operator to fp32 rounding, not bit for bit; read by the next hn_set_domain.  HN_CNT_SPECTRAL_ROUTE tells
                               * which route the current domain took                                                            */
+    HN_OPT_F64_FFT = 18,     /* 0/1 (default 0; environment default HN_F64_FFT): the route of the float64 operator (hn_laplacian_f64, hn_residual_f64, hn_step_f64,
+                              * both refine cycles).  0: the dense circulant kernel (24 n^3 flops per sample).  1: two line passes by FFT in double
+                              * (hn_f64_fft.hip: n = P * 2^k, every legal size, a line in LDS), which agree with the dense kernel to float64 rounding
+                              * (<= 2e-11 * max), not bit for bit.  Read by every float64 call, so it can be flipped between calls on one domain: each route
+                              * keeps its own tables, built by its first call (not under stream capture), and flipping back gives the earlier bits.
+                              * HN_CNT_F64_ROUTE tells which route the last call took.  [measured, profiles/f64_fft_bench.txt] the FFT
+                              * route is faster at every measured size: 0.106 vs 0.311 ms at 256^2 x 32, 0.257 vs 1.100 at 512^2 x 16, 0.323 vs 2.360 at
+                              * 1024^2 x 4, 0.470 vs 5.551 at 2048^2; it stays opt-in until the default is decided on those numbers */
     HN_OPT_SPECTRAL_RADIX16 = 5, /* 256-point lines: 0 the radix-4 kernels, 1 radix-16 columns + 8x4x8 rows (default), 2 radix-16 rows too */
     HN_OPT_DC_VALU = 6,      /* fp32 DoubleConvs of the largest level (W >= 256) on the packed vector FMA (every FMA useful, same peak as the
                               * fp32 MFMA, whose 3x3 packing fills 75 % of its slots): 0 none (matrix core); 1 inc and the decoder, 2 all three on the
@@ -183,9 +191,11 @@ enum hn_counter { HN_CNT_GRAPH_REPLAYS = 0, HN_CNT_EAGER_ITERATIONS = 1, HN_CNT_
                                                  * counter before and after a call to know whether event and table are valid for it (not under capture) */
                   HN_CNT_FLAG_SYNC_ITERATIONS = 6,  /* hn_step iterations whose side-stream hand-overs went through device words (HN_OPT_SIDE_SYNC): n_iter - 1 per
                                                  * eligible call, 0 with the option off, under stream capture, under counter collection, with several lanes */
-                  HN_CNT_SPECTRAL_ROUTE = 7 };  /* not a count: the kernels the current domain's spectral operator runs on.  0 no domain, 1 power of two,
+                  HN_CNT_SPECTRAL_ROUTE = 7,    /* not a count: the kernels the current domain's spectral operator runs on.  0 no domain, 1 power of two,
                                                  * 2 prime-factor (HN_OPT_SPECTRAL_PFA), 3 dense, 4 mixed (HN_OPT_SPECTRAL_MIXED),
                                                  * 5 rectangular (hn_set_domain_rect with h != w) */
+                  HN_CNT_F64_ROUTE = 8 };       /* not a count: the route the last float64 call on this domain took (HN_OPT_F64_FFT).  0 none yet (reset by
+                                                 * hn_set_domain / hn_set_domain_rect), 1 dense, 2 FFT */
 
 #define HN_ABI_VERSION 7
 int hn_abi_version(void);
@@ -282,7 +292,10 @@ int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream)
 
 /* The same operator in float64, as an independent check of the fp32 residual: what the reference computes after solver.double()
  * (apply_laplacian / get_residual, hybridnet.py:540-556, on fast_laplacian_with_pml, spectral.py:31-79 run under .double(): the fp32 tables'
- * values, float64 arithmetic).  One code path for every legal domain size: dense circulant derivative operators on the f64 matrix instruction.
+ * values, float64 arithmetic).  Two routes, each for every legal domain size, chosen per call by HN_OPT_F64_FFT: 0 (default) dense circulant derivative
+ * operators on the f64 matrix instruction; 1 two line passes by FFT in double, one partial sum of squares per line (the rmse does not depend on the batch
+ * on either route).  The routes agree to float64 rounding, not bit for bit; each builds its own tables (and, for an rmse-only call on the FFT route, an
+ * intermediate field [B,2,n,n]) at its first call, under the capture rule below.
  * Shapes and layout as for hn_laplacian / hn_residual, all tensors doubles.  wf must not overlap out / res (HN_ERR_ARG).
  * hn_residual_f64: res[B,2,n,n] (may be NULL) and / or rmse[B] = sqrt(mean_{c,h,w} res^2) (may be NULL; not both, HN_ERR_ARG), the RMSE summed in a
  * fixed order (bit-reproducible).  The first call on a domain builds and uploads the float64 tables (freed by the next hn_set_domain / hn_destroy), and

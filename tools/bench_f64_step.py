@@ -1,7 +1,7 @@
-"""Time of one solver iteration in float64 (hn_step_f64: the layer-by-layer UNet of hn_unet_f64.hip + the dense float64 residual) next to the fp32
-hn_step on the same problem.
+"""Time of one solver iteration in float64 (hn_step_f64: the layer-by-layer UNet of hn_unet_f64.hip + the float64 residual on the route --f64-fft
+picks: 0 dense, 1 FFT) next to the fp32 hn_step on the same problem.
 
-    python tools/bench_f64_step.py [--iters 20] [--calls 7] [--sizes 96x8,256x4,512x1] [--out profiles/f64_step.txt]
+    python tools/bench_f64_step.py [--iters 20] [--calls 7] [--sizes 96x8,256x4,512x1] [--f64-fft 0] [--out profiles/f64_step.txt]
 
 Per size (n^2 x batch): median over --calls timed calls of --iters iterations each (device events on the caller's stream) after one warm-up call of each
 path, the two paths alternating call by call so that both see the same clocks.  Shipped weights, ring phantoms, the solver's point source.
@@ -25,18 +25,20 @@ def main():
     ap.add_argument("--calls", type=int, default=7)
     ap.add_argument("--sizes", default="96x8,256x4,512x1")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--f64-fft", type=int, default=0, choices=(0, 1), help="route of the float64 residual (option 'f64_fft')")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     solver = IterativeSolver.from_exported_weights()
     solver.freeze()
     solver.to(dev)
-    lines = [f"one solver iteration, median over {args.calls} calls of {args.iters} iterations (ms per iteration): hn_step_f64 vs hn_step (fp32)",
+    lines = [f"one solver iteration, median over {args.calls} calls of {args.iters} iterations (ms per iteration): hn_step_f64 (f64_fft {args.f64_fft}) vs hn_step (fp32)",
              "size        hn_step_f64      hn_step   ratio (f64 / fp32)   max|wf32 - wf64|"]
     for size in args.sizes.split(","):
         n, batch = (int(v) for v in size.split("x"))
         solver.set_domain_size(n, source_location=[n - n // 7, n // 2])
         sos = torch.from_numpy(ring_sos_batch(n, batch, seed=n)).to(dev)
         eng = solver.engine()
+        eng.set_option("f64_fft", args.f64_fft)
         k32, wf32 = solver.get_initials(sos)
         k32 = k32.contiguous()
         src32, src64 = solver._src(), solver.source.detach().double().contiguous()

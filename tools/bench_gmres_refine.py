@@ -2,11 +2,11 @@
 """Seconds per restart cycle of GMRES(20): the plain fp32 cycle (hn_gmres_cycle) next to the refined one (hn_gmres_refine_cycle: the same cycle plus
 one float64 operator application and three streaming launches), in one process with alternating runs.
 
-    python tools/bench_gmres_refine.py [--out FILE]
+    python tools/bench_gmres_refine.py [--f64-fft 0] [--out FILE]
 
 Shapes 256^2 x 4 and 256^2 x 32, as tools/bench_gmres.py.  Both run every inner step (tol = 0, inner_floor = 0) and are enqueued back to back, `--cycles`
 calls per timed window with one synchronisation at its end (no host read-back: the driver's one read per cycle is not part of either figure).  Also:
-the float64 operator alone (hn_residual_f64 with its RMSE).  Times are medians of `--rounds` alternating rounds; the shader clock is the median of the
+the float64 operator alone (hn_residual_f64 with its RMSE), on the route --f64-fft picks (option 'f64_fft': 0 dense, 1 FFT).  Times are medians of `--rounds` alternating rounds; the shader clock is the median of the
 board's hwmon readings while the timed windows run (bench.py's sampler), null where the board does not expose it."""
 import argparse
 import json
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--restart", type=int, default=20)
     ap.add_argument("--cycles", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--f64-fft", type=int, default=0, choices=(0, 1), help="route of the float64 operator (option 'f64_fft')")
     a = ap.parse_args()
     from bench import Hwmon
     from helmnet_amd import IterativeSolver
@@ -42,6 +43,7 @@ def main():
     s = IterativeSolver.from_exported_weights(); s.freeze(); s.to(dev)
     s.set_domain_size(n, source_location=[n - 62, n // 2])
     eng = s.engine()
+    eng.set_option("f64_fft", a.f64_fft)
     rows = []
     hw = Hwmon(torch.device(dev))
     with hw:
@@ -69,7 +71,7 @@ def main():
                          "plain_spread": [min(t["plain"]), max(t["plain"])], "refined_spread": [min(t["refined"]), max(t["refined"])],
                          "float64_operator_s": t_op, "extra_s": refined - plain})
     props = torch.cuda.get_device_properties(0)
-    out = {"device": props.name, "hwmon": hw.summary(), "cycles_per_window": a.cycles, "rounds": a.rounds, "rows": rows}
+    out = {"device": props.name, "hwmon": hw.summary(), "cycles_per_window": a.cycles, "rounds": a.rounds, "f64_fft": a.f64_fft, "rows": rows}
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
