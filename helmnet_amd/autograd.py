@@ -8,6 +8,8 @@ Functions supply the backward passes:
   * ``Residual``    L(wf) + k_sq wf - src;       backward w.r.t. wf (hn_residual_vjp), k_sq and src
   * ``Solve``       K iterations of hn_step;     backward hn_step_vjp, the forward's histories being the tape (every ``checkpoint_every``-th
                     state kept and the segments in between re-run with hn_step when c > 1: the same bits as c = 1)
+  * ``SolveImplicit``  the wavefield a linear solve converged to (IterativeSolver.solve_implicit); backward by the adjoint-state method: one solve
+                    of A^H lam = g (gmres_adjoint) and hn_adjoint_grad, nothing taped; no forward mode
 
 The weight blob the kernels read is assembled from the network's parameters with torch ops (``weight_blob``), so the blob gradient
 lands on each ``nn.Parameter`` and the zero padding of levels without state gets none.  No double backward: a backward pass
@@ -311,3 +313,43 @@ class Solve(torch.autograd.Function):
         for a, e in spec.stateless:
             out_st[..., a:e] = ident[:, :, a:e]
         return out_wf, out_res, out_st, t_rmse
+
+
+# ---- adjoint-state gradients of a converged linear solve (IterativeSolver.solve_implicit) ----
+def adjoint_state_grads(lam: torch.Tensor, u: torch.Tensor, sos: torch.Tensor, omega: float, g_k_sq: torch.Tensor = None):
+    """The chain rule of the adjoint-state method, in the tensors' own dtype (float64 on the host in the tests, fp32 on the device in
+    ``SolveImplicit``).  With A u = src, A u = L(u) + k_sq * u, k_sq = (omega / sos)^2, a real loss J and A^H lam = dJ/du (fields as two real planes
+    [B,2,n,n]): dJ = Re<lam, dsrc - dk_sq * u>, hence dJ/dsrc = lam, dJ/dk_sq = -Re(conj(lam) u) = -(lam_re u_re + lam_im u_im) and
+    dJ/dsos = dJ/dk_sq * (-2 omega^2 / sos^3).  ``g_k_sq`` [B,1,n,n]: dJ/dk_sq when the caller has it already (hn_adjoint_grad), else it is formed
+    here.  Returns (g_sos [B,1,n,n], g_k_sq); the per-sample source gradient is ``lam`` itself."""
+    if g_k_sq is None:
+        g_k_sq = -(lam * u).sum(1, keepdim=True)
+    return g_k_sq * (-2.0 * float(omega) ** 2 / sos ** 3), g_k_sq
+
+
+class SolveImplicit(torch.autograd.Function):
+    """(sos, src) -> the wavefield a forward solve converged to, whichever route converged it; backward is the adjoint-state method: one solve of
+    A^H lam = g (gmres_adjoint), hn_adjoint_grad and the chain rule -- O(1) memory, nothing of the forward solve is taped.  ``spec``: solver, the
+    converged wavefield, the adjoint solve's keyword arguments and ``info``, the dictionary the backward pass fills (cycles, rmse, converged)."""
+
+    @staticmethod
+    def forward(ctx, spec, sos, src):
+        ctx.spec, ctx.src_batch, ctx.adjoint_info = spec, src.shape[0], spec["info"]
+        ctx.save_for_backward(sos.detach())
+        return spec["wavefield"].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        _no_double_backward()
+        from .gmres import gmres_adjoint
+        spec = ctx.spec
+        (sos,) = ctx.saved_tensors
+        solver, u = spec["solver"], spec["wavefield"]
+        with torch.no_grad():
+            adj = gmres_adjoint(solver, sos, g.detach().float().contiguous(), **spec["adjoint_kwargs"])
+            lam = adj["wavefield"]
+            g_k_sq, g_src = solver.engine().adjoint_grad(lam, u, ctx.src_batch if ctx.needs_input_grad[2] else None)
+            g_sos = adjoint_state_grads(lam, u, sos, float(solver.hparams.omega), g_k_sq)[0] if ctx.needs_input_grad[1] else None
+        ctx.adjoint_info.update({"cycles": adj["cycles"], "rmse": adj["residual_norm"], "converged": adj["converged"], "iterations": adj["iterations"],
+                             "unet_evaluations": adj["unet_evaluations"]})
+        return None, g_sos, g_src

@@ -231,6 +231,7 @@ struct RectDomain {
 struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-squares problem, two dense fields for the operator
 struct RefineWs;  // GMRES refinement step (hn_krylov.hip): float64 copies of k_sq and rhs, the float64 residual, the fp32 scaled right-hand side and correction
 struct PrecondWs; // flexible GMRES cycle (hn_krylov.hip): the learned preconditioner's source, wavefield, residual and hidden states
+struct AdjointW;  // adjoint flexible cycle (hn_krylov.hip): the similarity weight W = gamma_y gamma_x and 1 / W of the domain as fp32 planes
 struct JvpWs;     // forward-mode loop (hn_jvp.hip): the fp32 blob on the device, the packed-dual activation workspace, the second tangent-state buffer and the tangent source
 struct F64Fft;    // float64 operator by FFT (hn_f64_fft.hip, HN_OPT_F64_FFT): the double tables, the per-line partial sums and the intermediate field of an rmse-only call
 struct F64Unet;   // float64 solver loop (hn_unet_f64.hip): the up-cast weights, the activation workspace and the second flat-state buffer
@@ -254,6 +255,7 @@ struct hn_ctx {
     hn::KrylovWs* kry = nullptr;   // built / grown by the first hn_gmres_cycle that needs it; freed by hn_set_domain, hn_destroy
     hn::RefineWs* rfn = nullptr;   // built / grown by the first hn_gmres_refine_cycle that needs it; freed with kry (krylov_free)
     hn::PrecondWs* pcw = nullptr;  // built / grown by the first hn_fgmres_cycle with precond_iters > 0; freed with kry and by hn_load_weights (precond_free)
+    hn::AdjointW* adjw = nullptr;  // built by the first hn_fgmres_adjoint_cycle with precond_iters > 0 on a domain; freed with kry (krylov_free)
     hn::DcLayer inc{}, sig[hn::kMaxDepth]{}, st[hn::kMaxDepth]{}, dec[hn::kMaxDepth + 1]{};   // (their pointers lead into wdev and fragdev)
     hn::K8Layer down[hn::kMaxDepth]{}, up[hn::kMaxDepth]{};
     float* fragdev = nullptr;   // every re-packing of the weights beyond wdev: the layers' fragments and what follows here

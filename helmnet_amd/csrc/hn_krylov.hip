@@ -21,6 +21,13 @@
 // step z_k = M(v_k) -- precond_iters iterations of hn_step on A z = alpha v_k from rest, z_k = wf / alpha --, w = A z_k, the orthogonalisation and the small
 // problem on V as before, the update x += sum y_j z_j over the caller's zbasis.  The preconditioner is a parameter of launch_cycle (Precond); without one
 // (zbasis nullptr) not one launch or argument of hn_gmres_cycle differs.  Three streaming kernels (k_seed, k_take, k_take_copy) move the vectors; none sums.
+//
+// hn_fgmres_adjoint_cycle is the flexible cycle on A^H (spec_adjoint): the operator is a parameter of launch_cycle (Op), and with Op::Forward not one launch
+// or argument of the four entry points above differs.  spec_adjoint has no source operand: the start residual is its output minus rhs (k_minus_rhs, which
+// also leaves the partial sums of |w|^2 that k_norm_part leaves for the forward operator).  The learned network approximates A^-1, not A^-H; the PML
+// operator is complex-symmetric up to the diagonal similarity W = gamma_y[i] gamma_x[j] (A^T ~ W A W^-1), so A^-H v ~ conj(W A^-1 (conj(v) / W)): the
+// preconditioner is the SAME hn_step problem between two streaming kernels (k_seed_adj, k_take_adj) that conjugate and scale by 1 / W and W.
+// hn_adjoint_grad (at the end) is the pointwise product that turns the adjoint solution into the gradients with respect to k_sq and the source.
 #include "hn_internal.h"
 
 namespace hn {
@@ -66,6 +73,15 @@ struct PrecondWs {
     float* wf = nullptr;      // [B][2 n^2]  the learned iterate, from zero
     float* res = nullptr;     // [B][2 n^2]  its residual, from 0 - src
     float* states = nullptr;  // [B][2][state_len]  the hidden states, from zero
+};
+
+// the similarity weight of the adjoint preconditioner on the current domain: gamma = 1 + i sigma / k per axis with sigma the fp32 table's value,
+// W[i][j] = gamma[i] gamma[j] and 1 / W formed in double, each rounded once to fp32
+struct AdjointW {
+    int n = 0;
+    DeviceBlock block;        // one allocation; the pointers below lead into it
+    float* w = nullptr;       // [2][n^2]  W, (re | im) planes
+    float* winv = nullptr;    // [2][n^2]  1 / W
 };
 
 namespace {
@@ -165,6 +181,29 @@ __global__ __launch_bounds__(256) void k_norm_part(const float* __restrict__ w, 
     const bool on = off < P;
     const float* pw = w + (long)b * 2 * P + off;
     const float4 wr = ld4(pw, on), wi = ld4(pw + P, on);
+    const float s = wave_sum(dot4(wr, wr) + dot4(wi, wi));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) npart[(long)b * nchunk + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// the adjoint cycle's start: w = A^H x comes without a source operand -- w -= rhs (w = -r, as spec_apply leaves it), then k_norm_part's partial sums
+__global__ __launch_bounds__(256) void k_minus_rhs(float* __restrict__ w, const float* __restrict__ rhs, long rhs_sb, float* __restrict__ npart, long P,
+                                                   int nchunk) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    const bool on = off < P;
+    float* pw = w + (long)b * 2 * P + off;
+    const float* pr = rhs + (long)b * rhs_sb + off;
+    float4 wr = ld4(pw, on), wi = ld4(pw + P, on);
+    const float4 rr = ld4(pr, on), ri = ld4(pr + P, on);
+    wr.x -= rr.x; wr.y -= rr.y; wr.z -= rr.z; wr.w -= rr.w;
+    wi.x -= ri.x; wi.y -= ri.y; wi.z -= ri.z; wi.w -= ri.w;
+    if (on) {
+        *reinterpret_cast<float4*>(pw) = wr;
+        *reinterpret_cast<float4*>(pw + P) = wi;
+    }
     const float s = wave_sum(dot4(wr, wr) + dot4(wi, wi));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -386,6 +425,66 @@ __global__ __launch_bounds__(256) void k_take_copy(const float* __restrict__ vin
     *reinterpret_cast<float4*>(pz + P) = *reinterpret_cast<const float4*>(pv + P);
 }
 
+// ---- the adjoint cycle's twins of k_seed / k_take: the same traffic plus the two planes of 1 / W resp. W (shared by the samples) ----
+// each component is an fp32 product sum as written (a * b + c * d, contraction as the compiler has it), then ONE multiply by alpha resp. a true division
+
+// src = alpha * (conj(v) * winv): re = vr ir + vi ii, im = vr ii - vi ir; res = 0 - src, wf = 0
+__global__ __launch_bounds__(256) void k_seed_adj(const float* __restrict__ vin, const float* __restrict__ winv, float alpha, float* __restrict__ src,
+                                                  float* __restrict__ res, float* __restrict__ wf, long P) {
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)blockIdx.y * 2 * P + off;
+    const float4 vr = *reinterpret_cast<const float4*>(vin + at), vi = *reinterpret_cast<const float4*>(vin + at + P);
+    const float4 ir = *reinterpret_cast<const float4*>(winv + off), ii = *reinterpret_cast<const float4*>(winv + P + off);
+    const float4 sr = mul4(make_float4(vr.x * ir.x + vi.x * ii.x, vr.y * ir.y + vi.y * ii.y, vr.z * ir.z + vi.z * ii.z, vr.w * ir.w + vi.w * ii.w), alpha);
+    const float4 si = mul4(make_float4(vr.x * ii.x - vi.x * ir.x, vr.y * ii.y - vi.y * ir.y, vr.z * ii.z - vi.z * ir.z, vr.w * ii.w - vi.w * ir.w), alpha);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(src + at) = sr; *reinterpret_cast<float4*>(src + at + P) = si;
+    *reinterpret_cast<float4*>(res + at) = zero_minus4(sr); *reinterpret_cast<float4*>(res + at + P) = zero_minus4(si);
+    *reinterpret_cast<float4*>(wf + at) = z; *reinterpret_cast<float4*>(wf + at + P) = z;
+}
+
+// z = conj(w * wf) / alpha: re = (wr fr - wi fi) / alpha, im = (0 - (wr fi + wi fr)) / alpha, into slot `slot` of zbasis and into the dense operator input
+__global__ __launch_bounds__(256) void k_take_adj(const float* __restrict__ wf, const float* __restrict__ w, float alpha, float* __restrict__ vin,
+                                                  float* __restrict__ zbasis, long P, int slot, int restart) {
+    const int b = blockIdx.y;
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)b * 2 * P + off;
+    const float4 fr = *reinterpret_cast<const float4*>(wf + at), fi = *reinterpret_cast<const float4*>(wf + at + P);
+    const float4 wr = *reinterpret_cast<const float4*>(w + off), wi = *reinterpret_cast<const float4*>(w + P + off);
+    const float4 zr = div4(make_float4(wr.x * fr.x - wi.x * fi.x, wr.y * fr.y - wi.y * fi.y, wr.z * fr.z - wi.z * fi.z, wr.w * fr.w - wi.w * fi.w), alpha);
+    const float4 zi = div4(zero_minus4(make_float4(wr.x * fi.x + wi.x * fr.x, wr.y * fi.y + wi.y * fr.y, wr.z * fi.z + wi.z * fr.z, wr.w * fi.w + wi.w * fr.w)), alpha);
+    float* pz = zbasis + ((long)b * restart + slot) * 2 * P + off;
+    *reinterpret_cast<float4*>(vin + at) = zr; *reinterpret_cast<float4*>(vin + at + P) = zi;
+    *reinterpret_cast<float4*>(pz) = zr; *reinterpret_cast<float4*>(pz + P) = zi;
+}
+
+// g_k_sq[b] = -(l_re u_re + l_im u_im); g_src (nullable): lambda per sample (per == 1), or its sum over the `per` samples of the batch in sample order
+__global__ __launch_bounds__(256) void k_adjoint_grad(const float* __restrict__ lam, const float* __restrict__ u, float* __restrict__ g_ksq,
+                                                      float* __restrict__ g_src, long P, int per) {
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    float4 ar = make_float4(0.f, 0.f, 0.f, 0.f), ai = ar;
+    for (int i = 0; i < per; ++i) {
+        const int b = blockIdx.y * per + i;
+        const long at = (long)b * 2 * P + off;
+        const float4 lr = *reinterpret_cast<const float4*>(lam + at), li = *reinterpret_cast<const float4*>(lam + at + P);
+        const float4 ur = *reinterpret_cast<const float4*>(u + at), ui = *reinterpret_cast<const float4*>(u + at + P);
+        *reinterpret_cast<float4*>(g_ksq + (long)b * P + off) =
+            zero_minus4(make_float4(lr.x * ur.x + li.x * ui.x, lr.y * ur.y + li.y * ui.y, lr.z * ur.z + li.z * ui.z, lr.w * ur.w + li.w * ui.w));
+        if (i == 0) { ar = lr; ai = li; }
+        else { ar.x += lr.x; ar.y += lr.y; ar.z += lr.z; ar.w += lr.w; ai.x += li.x; ai.y += li.y; ai.z += li.z; ai.w += li.w; }
+    }
+    if (g_src != nullptr) {
+        const long at = (long)blockIdx.y * 2 * P + off;
+        *reinterpret_cast<float4*>(g_src + at) = ar; *reinterpret_cast<float4*>(g_src + at + P) = ai;
+    }
+}
+
+// which operator a cycle runs on: A (spec_apply, the four forward entry points) or A^H (spec_adjoint)
+enum class Op { Forward, Adjoint };
+
 // The preconditioner of a flexible cycle as launch_cycle takes it; zbasis nullptr: none, the cycle is plain GMRES
 struct Precond {
     float* zbasis = nullptr;   // [B][restart][2 n^2], the caller's
@@ -429,6 +528,47 @@ int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, int batch, 
     return step_named(ctx, who, hn_step(ctx, ws->wf, ws->res, ws->states, k_sq, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
 }
 
+void adjoint_w_free(hn_ctx* ctx) {
+    if (ctx->adjw == nullptr) return;
+    ctx->adjw->block.free();
+    delete ctx->adjw;
+    ctx->adjw = nullptr;
+}
+
+// W and 1 / W of the current domain -- the caller has refused stream capture; built once per domain (hn_set_domain frees it)
+int adjoint_w_prepare(hn_ctx* ctx, const char* who) {
+    const SpecTables& t = ctx->tab;
+    const int n = t.n;
+    if (ctx->adjw != nullptr && ctx->adjw->n == n) return HN_OK;
+    adjoint_w_free(ctx);
+    AdjointW* aw = new (std::nothrow) AdjointW();
+    if (!aw) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
+    ctx->adjw = aw;
+    const size_t P = (size_t)n * n;
+    const size_t sizes[] = {2 * P * 4, 2 * P * 4};
+    if (const int rc = aw->block.alloc(ctx, who, sizes, 2); rc != HN_OK) { adjoint_w_free(ctx); return rc; }
+    aw->w = (float*)aw->block.take(); aw->winv = (float*)aw->block.take();
+    aw->n = n;
+    const AxisHost ax = spec_axis_host(n, t.pml, t.sigma_max, t.k);
+    std::vector<std::complex<double>> gamma(n);
+    for (int i = 0; i < n; ++i) gamma[i] = std::complex<double>(1.0, (double)(float)ax.sigma[i] / t.k);   // the sigma maps' fp32 values
+    std::vector<float> hw(2 * P), hi(2 * P);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const std::complex<double> w = gamma[i] * gamma[j], iw = 1.0 / w;
+            const size_t at = (size_t)i * n + j;
+            hw[at] = (float)w.real(); hw[P + at] = (float)w.imag();
+            hi[at] = (float)iw.real(); hi[P + at] = (float)iw.imag();
+        }
+    hipError_t e = hipMemcpy(aw->w, hw.data(), 2 * P * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(aw->winv, hi.data(), 2 * P * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        adjoint_w_free(ctx);
+        return fail(ctx, HN_ERR_HIP, "%s: uploading the similarity weight failed: %s", who, hipGetErrorString(e));
+    }
+    return HN_OK;
+}
+
 void cycle_ws_free(hn_ctx* ctx) {
     if (ctx->kry == nullptr) return;
     ctx->kry->block.free();
@@ -466,8 +606,9 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
 // The restart cycle's launches, the workspace prepared.  tol_dev / pre_stopped: see SmallArgs (nullptr: hn_gmres_cycle, whose bits they leave alone --
 // the comparison est < tol is the same one on the same doubles); x, rhs and the outputs may lie in a workspace of the library's.  pc: the flexible
 // cycle's preconditioner (its workspace prepared when pc.iters > 0); the operator input then holds z_k while A is applied and v_{k+1} after k_scale.
-int launch_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol, const double* tol_dev,
-                 const int* pre_stopped, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
+// op: Op::Adjoint runs the same cycle on A^H (and, with pc.iters > 0, needs ctx->adjw prepared); Op::Forward is every launch and argument of before.
+int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+                 const double* tol_dev, const int* pre_stopped, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
     const KrylovWs& ws = *ctx->kry;
     const long P = (long)ws.n * ws.n;
     int rc;
@@ -476,23 +617,32 @@ int launch_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int
     const dim3 grid(nchunk, batch), blk(256);
     SmallArgs a{ws.part, ws.npart, ws.scale, ws.g, ws.cs, ws.R, ws.y, ws.stopped, hess, rmse, k_used, batch, restart, nchunk,
                 tol, 1.0 / sqrt(2.0 * (double)P), tol_dev, pre_stopped};
+    const bool adj = op == Op::Adjoint;
     // w = A x - rhs = -r
-    if ((rc = spec_apply(ctx, x, ws.w, k_sq, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
-    hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
+    if (adj) {
+        if ((rc = spec_adjoint(ctx, x, ws.w, k_sq, nullptr, batch, s)) != HN_OK) return rc;
+        hipLaunchKernelGGL(k_minus_rhs, grid, blk, 0, s, ws.w, rhs, rhs_batch == 1 ? 0L : 2 * P, ws.npart, P, nchunk);
+    } else {
+        if ((rc = spec_apply(ctx, x, ws.w, k_sq, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
+        hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
+    }
     hipLaunchKernelGGL(k_small_init, dim3(batch), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_scale, grid, blk, 0, s, ws.w, ws.scale, -1.f, ws.vin, basis, P, 0, restart);
     for (int k = 0; k < restart; ++k) {
         if (pc.zbasis != nullptr && pc.iters > 0) {
             const PrecondWs& p = *ctx->pcw;
-            hipLaunchKernelGGL(k_seed, grid, blk, 0, s, ws.vin, pc.alpha, p.src, p.res, p.wf, P);
+            if (adj) hipLaunchKernelGGL(k_seed_adj, grid, blk, 0, s, ws.vin, ctx->adjw->winv, pc.alpha, p.src, p.res, p.wf, P);
+            else hipLaunchKernelGGL(k_seed, grid, blk, 0, s, ws.vin, pc.alpha, p.src, p.res, p.wf, P);
             if ((rc = zero_async(ctx, p.states, sizeof(float) * (size_t)batch * kState * (size_t)p.state_len, s)) != HN_OK) return rc;
             rc = hn_step(ctx, p.wf, p.res, p.states, k_sq, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s);
             if (rc != HN_OK) return step_named(ctx, pc.who, rc);
-            hipLaunchKernelGGL(k_take, grid, blk, 0, s, p.wf, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
+            if (adj) hipLaunchKernelGGL(k_take_adj, grid, blk, 0, s, p.wf, ctx->adjw->w, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
+            else hipLaunchKernelGGL(k_take, grid, blk, 0, s, p.wf, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
         } else if (pc.zbasis != nullptr) {
             hipLaunchKernelGGL(k_take_copy, grid, blk, 0, s, ws.vin, pc.zbasis, P, k, restart);
         }
-        if ((rc = spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s)) != HN_OK) return rc;
+        rc = adj ? spec_adjoint(ctx, ws.vin, ws.w, k_sq, nullptr, batch, s) : spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s);
+        if (rc != HN_OK) return rc;
         hipLaunchKernelGGL(k_dots, grid, blk, 0, s, ws.w, basis, ws.part, P, k, restart, nchunk);
         hipLaunchKernelGGL(k_sub<0>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
         hipLaunchKernelGGL(k_sub<1>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
@@ -641,10 +791,10 @@ int check_precond(hn_ctx* ctx, const char* who, int precond_iters, float precond
 }
 
 // hn_gmres_cycle and hn_fgmres_cycle, the arguments checked
-int run_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol, const Precond& pc, float* basis,
+int run_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol, const Precond& pc, float* basis,
               float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
     if (const int rc = prepare(ctx, batch, restart, s); rc != HN_OK) return rc;
-    return launch_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, pc, basis, hess, rmse, k_used, s);
+    return launch_cycle(ctx, op, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, pc, basis, hess, rmse, k_used, s);
 }
 
 // hn_gmres_refine_cycle and hn_fgmres_refine_cycle, the arguments but tol and inner_floor checked
@@ -662,7 +812,7 @@ int run_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs
     hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + nr4 + 255) / 256)), blk, 0, s, k_sq, ws.ksq64, nk4, rhs, ws.rhs64, nr4);
     if ((rc = f64_apply(ctx, x, ws.res64, ws.ksq64, ws.rhs64, rhs_batch, rmse64, batch, s)) != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_rhs, grid, blk, 0, s, ws.res64, rmse64, tol, (double)inner_floor, ws.rhs32, ws.d32, ws.tol, ws.stop, P);
-    if ((rc = launch_cycle(ctx, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, pc, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
+    if ((rc = launch_cycle(ctx, Op::Forward, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, pc, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_update, grid, blk, 0, s, x, ws.d32, rmse64, k_used, P);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
@@ -680,6 +830,7 @@ void krylov_free(hn_ctx* ctx) {
     cycle_ws_free(ctx);
     refine_ws_free(ctx);
     precond_ws_free(ctx);
+    adjoint_w_free(ctx);
 }
 void precond_free(hn_ctx* ctx) { precond_ws_free(ctx); }
 
@@ -692,7 +843,7 @@ extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const fl
     const int rc = check_cycle_args(ctx, "hn_gmres_cycle", false, false, x, k_sq, rhs, rhs_batch, batch, restart, basis, nullptr, hess, rmse, k_used, nullptr);
     if (rc != HN_OK) return rc;
     DeviceGuard guard(ctx);
-    return run_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{}, basis, hess, rmse, k_used, (hipStream_t)stream);
+    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{}, basis, hess, rmse, k_used, (hipStream_t)stream);
 }
 
 extern "C" int hn_fgmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
@@ -704,7 +855,43 @@ extern "C" int hn_fgmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const f
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
-    return run_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse, k_used, s);
+    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse, k_used, s);
+}
+
+extern "C" int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                                       int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
+                                       void* stream) {
+    const char* who = "hn_fgmres_adjoint_cycle";
+    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
+    if (rc != HN_OK) return rc;
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
+    if (precond_iters > 0 && (rc = adjoint_w_prepare(ctx, who)) != HN_OK) return rc;
+    return run_cycle(ctx, Op::Adjoint, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse,
+                     k_used, s);
+}
+
+extern "C" int hn_adjoint_grad(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_src, void* stream) {
+    const char* who = "hn_adjoint_grad";
+    if (!ctx || !lambda || !u || !g_k_sq) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (ctx->rect) return rect_unsupported(ctx, who);
+    if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain has not been called", who);
+    if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
+    if (src_batch != 1 && src_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: src batch %d must be 1 or equal to the batch %d", who, src_batch, batch);
+    const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
+    const MemRange r[] = {{lambda, B * 2 * P * 4, false, "lambda"}, {u, B * 2 * P * 4, false, "u"}, {g_k_sq, B * P * 4, true, "g_k_sq"},
+                          {g_src, (size_t)src_batch * 2 * P * 4, true, "g_src"}};
+    for (int i = 0; i < 4; ++i)   // read and written as float4; a NULL g_src is aligned
+        if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
+    const char *na, *nb;
+    if (first_overlap(r, 4, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    DeviceGuard guard(ctx);
+    const int per = (g_src != nullptr && src_batch == 1) ? batch : 1;
+    hipLaunchKernelGGL(k_adjoint_grad, dim3((unsigned)((P + kKryChunk - 1) / kKryChunk), batch / per), dim3(256), 0, (hipStream_t)stream, lambda, u, g_k_sq,
+                       g_src, (long)P, per);
+    HN_HIP(ctx, hipGetLastError());
+    return HN_OK;
 }
 
 extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,

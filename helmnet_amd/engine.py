@@ -380,6 +380,32 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_fgmres_refine_cycle")
         return rmse64, rmse, k_used
 
+    def fgmres_adjoint_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float, precond_iters: int,
+                             precond_scale: float, basis: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None,
+                             hess: Optional[torch.Tensor] = None):
+        """One flexible restart cycle on the ADJOINT system A^H x = rhs (hn_fgmres_adjoint_cycle), A^H the operator of ``residual_vjp``: arguments and
+        returns as ``fgmres_cycle``.  ``precond_iters`` 0 is plain restarted GMRES on A^H; >= 1 preconditions with the learned iteration between the
+        similarity weight of ``laplacian.adjoint_weight``: z_k = conj(W * M(conj(v_k) / W)).  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_adjoint_cycle", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        zbasis = self._zbasis(b, restart, zbasis)
+        rc = self.lib.hn_fgmres_adjoint_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters),
+                                              float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used), self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_adjoint_cycle")
+        return rmse, k_used
+
+    def adjoint_grad(self, lam: torch.Tensor, u: torch.Tensor, src_batch: Optional[int]):
+        """The pointwise half of the adjoint-state gradient (hn_adjoint_grad): returns (g_k_sq [B,1,n,n] = -(lam_re u_re + lam_im u_im), g_src) with
+        g_src = lam per sample [B,2,n,n] (``src_batch`` == B), its sum over the batch [1,2,n,n] (``src_batch`` == 1) or None (``src_batch`` None)."""
+        b = lam.shape[0]
+        self._chk(lam, (b, 2, *self.hw), "lam")
+        self._chk(u, (b, 2, *self.hw), "u")
+        g_k_sq = torch.empty(b, 1, *self.hw, device=self.device, dtype=torch.float32)
+        g_src = None if src_batch is None else torch.empty(int(src_batch), 2, *self.hw, device=self.device, dtype=torch.float32)
+        rc = self.lib.hn_adjoint_grad(self.ctx, _ptr(lam), _ptr(u), 1 if src_batch is None else int(src_batch), b, _ptr(g_k_sq), _ptr(g_src), self._stream())
+        _lib.check(rc, self.ctx, "hn_adjoint_grad")
+        return g_k_sq, g_src
+
     # ---- the same operators in float64: the check the fp32 residual is measured against (hn_f64.hip) ----
     def laplacian64(self, wf: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]

@@ -193,6 +193,74 @@ def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None):
             "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
 
 
+def check_adjoint_rhs(solver, sos_maps, rhs):
+    """The shapes ``gmres_adjoint`` takes, checked on the host before anything touches the device: ``sos_maps`` [B,1,n,n] and ``rhs`` [B or 1,2,n,n]
+    on the solver's (square) n x n domain."""
+    n = int(solver.hparams.domain_size)
+    if not isinstance(sos_maps, torch.Tensor) or sos_maps.dim() != 4 or tuple(sos_maps.shape[1:]) != (1, n, n):
+        raise ValueError(f"sos_maps must be [B, 1, {n}, {n}], got {tuple(getattr(sos_maps, 'shape', ()))}")
+    b = int(sos_maps.shape[0])
+    if not isinstance(rhs, torch.Tensor) or rhs.dim() != 4 or tuple(rhs.shape[1:]) != (2, n, n) or rhs.shape[0] not in (1, b):
+        raise ValueError(f"the adjoint right-hand side must be [1 or {b}, 2, {n}, {n}], got {tuple(getattr(rhs, 'shape', ()))}")
+
+
+def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
+                  x0: Optional[torch.Tensor] = None, precondition: Optional[str] = None, precond_iterations: int = 10,
+                  precond_scale: Optional[float] = None, backend: str = "hip"):
+    """Solve the ADJOINT system A^H lam = rhs for every map of ``sos_maps`` [B,1,n,n]: A u = L(u) + k_sq * u is the operator of ``gmres``, A^H its
+    conjugate transpose (``hn_residual_vjp``), ``rhs`` [B or 1,2,n,n] a cotangent dJ/du as two real planes.  Restarted GMRES with the cycle fused
+    on the device (hn_fgmres_adjoint_cycle), on the host loop of ``gmres(backend="hip")`` (``drive_cycles``): one synchronisation per cycle, every
+    sample stopping on its own, and once every sample's estimate is below ``tol`` the TRUE residual ||rhs - A^H x|| (hn_residual_vjp) decides.
+
+    ``precondition="learned"``: flexible GMRES with the learned iteration between the similarity weight W of ``laplacian.adjoint_weight`` --
+    z_k = conj(W * M(conj(v_k) / W)), M = ``precond_iterations`` iterations of the network from rest on a right-hand side scaled by
+    ``precond_scale`` (None: ``default_precond_scale(solver.source)``, the magnitude the network was trained on, as for the forward system).
+    Returns the keys of ``gmres(backend="hip")`` -- ``wavefield`` is the adjoint state lam -- plus ``cycles``.  No gradients; there is no other
+    backend."""
+    if precondition not in (None, "learned"):
+        raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
+    if precondition is not None and backend != "hip":
+        raise ValueError("precondition='learned' needs backend='hip'")
+    if backend != "hip":
+        raise ValueError(f"gmres_adjoint has the 'hip' backend only (got {backend!r})")
+    if precondition is not None and int(precond_iterations) < 0:
+        raise ValueError(f"precond_iterations must be >= 0 (got {precond_iterations})")
+    solver._require_square("gmres_adjoint")
+    check_adjoint_rhs(solver, sos_maps, rhs)
+    _require_no_grad("gmres_adjoint", sos_maps, rhs, x0)
+    restart, max_outer, tol = int(restart), int(max_outer), float(tol)
+    iters = 0 if precondition is None else int(precond_iterations)
+    alpha = 1.0
+    if precondition is not None:
+        alpha = default_precond_scale(solver.source) if precond_scale is None else float(precond_scale)
+    eng = solver.engine()
+    sos_maps = sos_maps.to(eng.device).float().contiguous()
+    k_sq = solver.get_initials(sos_maps)[0].contiguous()
+    rhs = rhs.detach().to(eng.device).float().contiguous()
+    bsz, n, dev = sos_maps.shape[0], sos_maps.shape[-1], eng.device
+    x = (torch.zeros(bsz, 2, n, n, device=dev) if x0 is None else x0.detach().to(dev, torch.float32)).contiguous().clone()
+    basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=dev)
+    zbasis = torch.empty(bsz, restart, 2 * n * n, dtype=torch.float32, device=dev)
+    hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
+
+    def cycle():
+        rmse, k_used = eng.fgmres_adjoint_cycle(x, k_sq, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
+        both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
+        eng.check_async_errors()
+        return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
+
+    def true_rmse():
+        return eng.rmse(rhs - eng.residual_vjp(x, k_sq)).cpu().numpy()
+
+    out = drive_cycles(cycle, true_rmse, max_outer, tol)
+    # converged: the last history row IS the true residual of the returned iterate; else its last update is still unchecked
+    final = torch.from_numpy(out["history"][-1]).to(dev) if out["converged"] else eng.rmse(rhs - eng.residual_vjp(x, k_sq))
+    return {"wavefield": x, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
+            "operator_applications": out["cycles"] * (restart + 1) + out["true_checks"] + (0 if out["converged"] else 1), "converged": out["converged"],
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"],
+            "residual_norm": final, "unet_evaluations": unet_evaluations(out["cycles"], restart, iters)}
+
+
 def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
           x0: Optional[torch.Tensor] = None, backend: str = "torch", refine: bool = False, inner_floor: float = 1e-6,
           precondition: Optional[str] = None, precond_iterations: int = 10, precond_scale: Optional[float] = None):

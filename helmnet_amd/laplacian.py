@@ -79,6 +79,15 @@ def f64_route(n: int, f64_fft: int = 0):
     return "fft", n // q, q
 
 
+def adjoint_weight(n: int, pml: int, sigma_max: float, k: float) -> np.ndarray:
+    """W[i, j] = gamma_y[i] * gamma_x[j] with gamma = 1 + i sigma / k, complex128 [n, n]: the diagonal similarity under which the PML operator is
+    complex-symmetric up to its discretisation (A^T ~ W A W^-1, hence A^-H g ~ conj(W * A^-1 (conj(g) / W))).  Context-free like ``spectral_route``:
+    hn_fgmres_adjoint_cycle holds the same table (and 1 / W) on the device, formed from the fp32 value of sigma and rounded once to fp32."""
+    sigma, _, _ = pml_profile(int(n), int(pml), float(sigma_max), float(k))
+    gamma = 1.0 + (1j / float(k)) * sigma
+    return np.outer(gamma, gamma)
+
+
 def domain_hw(domain_size):
     """(rows, columns) of a domain size given as an int (n x n) or a pair (H, W)."""
     if isinstance(domain_size, (tuple, list)):

@@ -392,6 +392,42 @@ int hn_fgmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const floa
                            double tol, float inner_floor, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
                            float* rmse, int32_t* k_used, double* rmse64, void* stream);
 
+/* ---- adjoint-state gradients of a converged solve (added within ABI v7: new entry points, nothing existing changes; square domains, fp32) ----
+ * With A u = src (A u = L(u) + k_sq * u), a real loss J(u) and its cotangent g = dJ/du (two real planes, g = dJ/du_re + i dJ/du_im), the adjoint
+ * state is the solution of A^H lambda = g, A^H the conjugate transpose hn_residual_vjp applies.  From dJ = Re <g, du> and A du = dsrc - dk_sq * u:
+ *   dJ/dsrc  = lambda                              (two real planes again)
+ *   dJ/dk_sq = -Re(conj(lambda) * u) = -(lambda_re u_re + lambda_im u_im)
+ * and, with k_sq = (omega / sos)^2, dJ/dsos = dJ/dk_sq * (-2 omega^2 / sos^3).  One extra linear solve and a pointwise product, whatever converged u.
+ *
+ * hn_fgmres_adjoint_cycle is hn_fgmres_cycle on the system A^H x = rhs: the same arguments, stop rule, outputs, workspaces and refusals (HN_ERR_UNSUPPORTED
+ * on a rectangular domain), with these differences:
+ *   - the operator of the start residual rhs - A^H x and of every inner step is A^H, on the route the domain's forward operator takes (power of two,
+ *     prime-factor, mixed, dense);
+ *   - precond_iters == 0: plain restarted GMRES on A^H, zbasis[:, j] == basis[:, j] bit for bit;
+ *   - precond_iters >= 1: the learned network approximates A^-1, not A^-H.  Per axis the PML operator is (1/gamma) d (1/gamma) d with
+ *     gamma = 1 + i sigma / k, so that W A is complex-symmetric up to the discretisation for W = diag(gamma_y[i] * gamma_x[j]): A^T ~ W A W^-1 and
+ *     A^-H v ~ conj(W * A^-1 (conj(v) / W)).  Inner step k therefore runs the SAME learned solve as hn_fgmres_cycle on
+ *       src = alpha * (conj(v_k) * Winv)     re = vr Wr' + vi Wi',  im = vr Wi' - vi Wr'   (Winv = Wr' + i Wi'; fp32 product sums, then one multiply)
+ *       wf = 0, states = 0, res = 0 - src, hn_step's launches for precond_iters iterations,
+ *       z_k = conj(W * wf) / alpha           re = (Wr fr - Wi fi) / alpha,  im = (0 - (Wr fi + Wi fr)) / alpha   (a true division)
+ *     W and Winv = 1 / W are tables of the domain: gamma in double from the fp32 value of sigma (what hn_get_sigmas returns) and k, the product
+ *     gamma_y[i] gamma_x[j] and its reciprocal in double, each rounded once to fp32.  They are built by the first call with precond_iters >= 1 on a
+ *     domain (one allocation of 4 n^2 floats, a blocking copy) and freed by hn_set_domain / hn_destroy.
+ * The preconditioner only has to be approximate: A^H Z_k = V_{k+1} H_k holds by construction, so the residual estimate stays that of the truncated
+ * iterate.  Fixed-order sums, no float atomics: two calls on equal inputs give equal bits, and a sample's bits do not depend on its batch mates.
+ * NOT capturable, like hn_fgmres_cycle, and the first call with precond_iters >= 1 on a stream blocks the host once. */
+int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                            int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
+                            void* stream);
+/* The pointwise half of the adjoint-state gradient, one launch, no atomics, nothing synchronised:
+ *   lambda, u [B,2,n,n]   the adjoint state and the wavefield
+ *   g_k_sq   [B,1,n,n]    out: -(lambda_re * u_re + lambda_im * u_im)
+ *   g_src    [src_batch,2,n,n] or NULL   out: lambda (src_batch == batch), or its sum over the batch in sample order (src_batch == 1: the source
+ *                         every sample shared)
+ * HN_ERR_ARG: a NULL pointer but g_src, batch < 1, src_batch not in {1, batch}, a pointer that is not 16-byte aligned, an output overlapping any other
+ * argument (lambda may equal u).  HN_ERR_STATE before hn_set_domain, HN_ERR_UNSUPPORTED on a rectangular domain. */
+int hn_adjoint_grad(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_src, void* stream);
+
 /* d[B,2,n,n] = HybridNet(in6[B,6,n,n]); the hidden states are read from `states_in` and the new
  * ones written to `states_out`, both in the reference's flat layout [B, 2, hn_state_len()]
  * (architectures.py:419-437).  states_out and d_out must not overlap each other, states_in or in6 -- states_out is written level by level while
