@@ -92,7 +92,10 @@ enum hn_precision { HN_PREC_FP32 = 0, HN_PREC_BF16X3 = 1, HN_PREC_FP16 = 2, HN_P
  * 2e-6 * max), SPECTRAL_PFA and SPECTRAL_MIXED (FFT instead of the dense operator), SPECTRAL_RADIX16 (other butterfly order), DC_VALU. */
 enum hn_option {
     HN_OPT_LANES = 0,        /* 1..8 sub-batches pipelined on internal streams (default 1; [measured, r5] 2 loses 3 % at 256^2 x 32 and 2 % at
-                              * 256^2 x 64 -- one chain of 64 maps is the faster form since the r5 level-0 kernels --, +1 % at batch 128) */
+                              * 256^2 x 64 -- one chain of 64 maps is the faster form since the r5 level-0 kernels --, +1 % at batch 128).
+                              * Lane j of `lanes` takes samples [batch * j / lanes, batch * (j + 1) / lanes) (integer division); a call whose
+                              * batch < 2 * lanes runs as ONE lane (with HN_EXP_GRAPH as set, but with event hand-overs: HN_OPT_SIDE_SYNC asks
+                              * for the option to be 1).  Several lanes launch every kernel: HN_EXP_GRAPH does not apply to them */
     HN_OPT_SIDE_STREAM = 1,  /* conv_state kernels: 0 in line; on a library side stream released 1 after the last `down`,
                               * 2 level by level behind conv_signal, 3 behind the fused deep level               */
     HN_OPT_DEEP = 3,         /* the deep levels as one launch.  1: deepest level (32^2) + bottleneck in one per-sample LDS kernel (hn_deep.hip; 256^2 at
@@ -132,7 +135,9 @@ enum hn_option {
     HN_OPT_SIDE_SYNC = 13,   /* 0/1 (default 1): between the iterations of ONE hn_step call the side stream is joined -- and, at 256^2, released -- through
                               * device words that kernels of the main chain store / poll on their way (one thread each) instead of event packets,
                               * each of which holds the main stream for ~7 us; a call forks the side stream with one event and its LAST iteration uses events.
-                              * hn_step's single-lane eager path, fp32, HN_OPT_SIDE_STREAM 1; waits are bounded (2 s, then hn_step fails: the call in
+                              * hn_step's single-lane eager path -- HN_OPT_LANES 1, a call that replays no graph (HN_EXP_GRAPH 0, or a call that form
+                              * stands down for), HN_PREC_FP32, HN_OPT_SIDE_STREAM 1, no st_hist (a state history reads the new states right behind
+                              * every iteration); waits are bounded (2 s, then hn_step fails: the call in
                               * which a wait gave up returns HN_ERR_STATE if the error word is up by the time its launches are enqueued, else the next
                               * call does; hn_check_async_errors after a stream synchronise is the reliable test).
                               * The same option switches hn_train_grad's side stream (HN_OPT_TRAIN_OVERLAP 2) to device words (words 64 .. 160 of the
@@ -175,7 +180,15 @@ enum hn_option {
     /* ---- laboratory knobs (same setter): implemented, tested bit-identical / equal within rounding, and MEASURED NOT TO HELP; they stay for A/B runs
      * and are not part of the supported surface (DESIGN_NOTEBOOK.md has the measurements) ---- */
     HN_EXP_GRAPH = 100,      /* 0: launch every kernel (default; measured 4 % faster); 1: replay one captured iteration per HIP graph
-                              * launch; even n <= 64: n iterations per graph.  Bit-identical                              */
+                              * launch; even n <= 64: n iterations per graph.  Bit-identical.  One lane only, and only in a call of at least
+                              * 4 * n iterations (4 for the value 1): a shorter call launches every kernel, as 0 does.  With n > 1 a call
+                              * replays floor(n_iter / n) graphs and launches the left-over iterations kernel by kernel, and it stands down
+                              * altogether (every kernel launched) when the call has a res_hist, wf_hist or st_hist or while hn_profile_enable
+                              * selects a kernel.  The side stream's kernels are part of the captured iteration under every HN_OPT_SIDE_STREAM
+                              * policy.  A graph is captured once per set of (wf, res, states, k_sq, src, rmse_hist, src_batch, batch, precision,
+                              * HN_OPT_SIDE_STREAM, HN_EXP_GRAPH) and kept (eight sets, least recently used first out) until the next hn_set_option, change of precision mode,
+                              * hn_load_weights or hn_set_domain, each of which drops them all; HN_CNT_GRAPHS_CAPTURED counts
+                              * the captures, so a call that should have replayed and could not shows up in the counters                  */
     HN_EXP_TRAIN_LANES = 101, /* hn_train_grad: 1 (default) the whole batch as one chain of launches; 2: the two halves of the batch as
                               * two chains on two streams.  Same gradient up to the order of the final sum over the halves; measured equal to 1 */
     HN_EXP_SPECTRAL_PLAIN = 102 /* 0 (default): the 256-point 8x4x8 row pass, the 256-point transposed column pass and both 512-point passes multiply and
@@ -184,13 +197,18 @@ enum hn_option {
                               * (same products, same fused multiply-adds); for the bit-identity test and in-process A/B runs                 */
 };
 /* Diagnostics counters (hn_get_counter). */
-enum hn_counter { HN_CNT_GRAPH_REPLAYS = 0, HN_CNT_EAGER_ITERATIONS = 1, HN_CNT_GRAPHS_CAPTURED = 2,
+enum hn_counter { HN_CNT_GRAPH_REPLAYS = 0,     /* hn_step iterations that ran as (part of) a graph replay (HN_EXP_GRAPH) */
+                  HN_CNT_EAGER_ITERATIONS = 1,  /* hn_step iterations launched kernel by kernel; with several lanes one per iteration, not per lane.  Every
+                                                 * iteration of every call counts in exactly one of the two */
+                  HN_CNT_GRAPHS_CAPTURED = 2,   /* captures (one per new set of buffers and options, see HN_EXP_GRAPH) */
                   HN_CNT_STREAM_PROBES = 3,     /* reference-stream sets probed so far (see "side streams" in the conventions above) */
                   HN_CNT_SIDE_CANDIDATE = 4,    /* candidate (0 .. 3) hn_step's side stream was last picked from; -1 before the first pick */
                   HN_CNT_TRAIN_FWD_EVENTS = 5,  /* times hn_train_grad recorded the registered forward event (hn_train_set_forward_event): a caller compares the
                                                  * counter before and after a call to know whether event and table are valid for it (not under capture) */
                   HN_CNT_FLAG_SYNC_ITERATIONS = 6,  /* hn_step iterations whose side-stream hand-overs went through device words (HN_OPT_SIDE_SYNC): n_iter - 1 per
-                                                 * eligible call, 0 with the option off, under stream capture, under counter collection, with several lanes */
+                                                 * eligible call (see HN_OPT_SIDE_SYNC), 0 with the option off, under stream capture and in a call that replays
+                                                 * graphs, under counter collection, with HN_OPT_LANES > 1 (also where a small batch runs as one lane), with another
+                                                 * HN_OPT_SIDE_STREAM policy than 1, in the 16-bit and HN_PREC_FP32_VALU modes, with a st_hist */
                   HN_CNT_SPECTRAL_ROUTE = 7,    /* not a count: the kernels the current domain's spectral operator runs on.  0 no domain, 1 power of two,
                                                  * 2 prime-factor (HN_OPT_SPECTRAL_PFA), 3 dense, 4 mixed (HN_OPT_SPECTRAL_MIXED),
                                                  * 5 rectangular (hn_set_domain_rect with h != w) */
@@ -466,7 +484,10 @@ int hn_step_f64(hn_ctx* ctx, double* wf, double* res, double* states, const doub
  *   hn_conv8x8      transposed = 0: Conv2d(8, 8, 8, stride 2, padding 3), x[B,8,H,W] -> out[B,8,H/2,W/2] (H, W even), weights =
  *                   weight [8,8,8,8] (out, in, kh, kw), bias [8];  transposed = 1: ConvTranspose2d(8, 8, 8, stride 2, padding 3),
  *                   x[B,8,H,W] -> out[B,8,2H,2W], weight [8,8,8,8] (in, out, kh, kw), bias [8]
- *   hn_out_conv     Conv2d(8, 2, 1): x[B,8,H,W] -> out[B,2,H,W], weights = weight [2,8], bias [2]                                  */
+ *   hn_out_conv     Conv2d(8, 2, 1): x[B,8,H,W] -> out[B,2,H,W], weights = weight [2,8], bias [2]
+ * Always the direct fp32 kernels (those of HN_PREC_FP32_VALU), whatever the context's precision mode; any H, W >= 1.  Refusals enqueue nothing and leave
+ * `out` untouched: HN_ERR_UNSUPPORTED for another (cin, cout), an act_kind outside enum hn_act and an odd H or W of the stride-2 form; HN_ERR_ARG for a
+ * NULL pointer or a non-positive batch, H or W. */
 int hn_double_conv(hn_ctx* ctx, const float* x, int cin, int cout, const float* weights_host, int act_kind, float* out,
                    int batch, int h, int w, void* stream);
 int hn_conv8x8(hn_ctx* ctx, const float* x, const float* weights_host, int transposed, float* out, int batch, int h, int w,
