@@ -488,6 +488,7 @@ void hn_destroy(hn_ctx* ctx) {
     f64_fft_free(ctx);
     spec_free(ctx->tab);
     spec_rect_free(ctx);
+    spec_lossy_free(ctx);
     (void)hipFree(ctx->wdev);
     (void)hipFree(ctx->fragdev);
     for (int j = 0; j < ctx->n_streams; ++j) {
@@ -614,6 +615,7 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     jvp_free(ctx);
     krylov_free(ctx);
     f64_fft_free(ctx);
+    spec_lossy_free(ctx);
     ctx->f64_route = 0;
     if (n % 16 != 0) return fail(ctx, HN_ERR_ARG, "domain size %d must be divisible by 16", n);
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
@@ -643,6 +645,7 @@ int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, floa
     jvp_free(ctx);
     krylov_free(ctx);
     f64_fft_free(ctx);
+    spec_lossy_free(ctx);
     ctx->f64_route = 0;
     free_workspace(ctx);
     spec_free(ctx->tab);
@@ -726,6 +729,24 @@ int hn_residual(hn_ctx* ctx, const float* wf, const float* k_sq, const float* sr
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
     DeviceGuard guard(ctx);
     return spec_apply(ctx, wf, res, k_sq, src, src_batch, batch, nullptr, (hipStream_t)stream);
+}
+
+int hn_residual_lossy(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, float* res, int batch,
+                      void* stream) {
+    const char* who = "hn_residual_lossy";
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_residual)", who);
+    if (!ctx || !wf || !k_sq || !src || !res) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
+    if (src_batch != 1 && src_batch != batch)
+        return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
+    {
+        const size_t plane = (size_t)ctx->geo.plane();
+        const MemRange r[] = {{k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}, {res, sizeof(float) * (size_t)batch * 2 * plane, true, "res"}};
+        const char *a, *b;
+        if (first_overlap(r, 2, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
+    }
+    DeviceGuard guard(ctx);
+    return spec_apply_lossy(ctx, who, wf, res, k_sq, k_sq_im, src, src_batch, batch, nullptr, (hipStream_t)stream);
 }
 
 int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, int batch, void* stream) {
@@ -826,6 +847,7 @@ struct StepArgs {
     int src_batch, batch;
     float* rmse_hist;   // base of the [n_iter, batch] table (rows are selected on the device through it_counter)
     bool side_stream;   // the hidden-state kernels may leave the main chain for the lane's side stream (hn_step's route)
+    const float* k_sq_im = nullptr;   // non-null (hn_step_lossy): the residual is the lossy operator's, spec_apply_lossy
 };
 
 __global__ void k_probe_spin(long ticks) {
@@ -981,6 +1003,10 @@ int one_iteration(hn_ctx* ctx, const StepArgs& a, int parity, int b0, int nb, in
     int rc = unet_forward(ctx, c);
     if (rc != HN_OK) return rc;
     const float* src_j = a.src_batch == 1 ? a.src : a.src + (size_t)b0 * 2 * plane;
+    if (a.k_sq_im != nullptr)
+        return spec_apply_lossy(ctx, "hn_step_lossy", wf_j, res_j, a.k_sq + (size_t)b0 * plane, a.k_sq_im + (size_t)b0 * plane, src_j,
+                                a.src_batch == 1 ? 1 : nb, nb, a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj,
+                                a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
     HN_REP(KID_SPEC_PAIR)
     rc = spec_apply(ctx, wf_j, res_j, a.k_sq + (size_t)b0 * plane, src_j, a.src_batch == 1 ? 1 : nb, nb,
                     a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj, a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
@@ -1051,16 +1077,22 @@ void clear_step_graphs(hn_ctx* ctx) {
 
 }  // namespace hn
 
-extern "C" {
+namespace hn {
+namespace {
 
-int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* src, int src_batch, int batch,
-            int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
-    if (!ctx || !wf || !res || !states || !k_sq || !src) return fail(ctx, HN_ERR_ARG, "hn_step: NULL argument");
+// hn_step (k_sq_im nullptr, who "hn_step": every check, launch and message of before) and hn_step_lossy (k_sq_im non-null: the same UNet launches, the
+// residual by spec_apply_lossy; one lane, never a captured iteration)
+int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* src, int src_batch,
+               int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
+    const bool lossy = k_sq_im != nullptr;
+    if (!ctx || !wf || !res || !states || !k_sq || !src) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (n_iter < 0) return fail(ctx, HN_ERR_ARG, "n_iter must be >= 0");
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
-    int rc = check_ready_unet(ctx, "hn_step", batch);
+    int rc = check_ready_unet(ctx, who, batch);
     if (rc != HN_OK) return rc;
+    if (lossy && ctx->opt_lanes > 1)
+        return fail(ctx, HN_ERR_UNSUPPORTED, "%s: HN_OPT_LANES %d is not implemented for the lossy loop (one lane only)", who, ctx->opt_lanes);
     // The route.  A rectangular domain takes the plainest one whatever the options say: one lane, every kernel launched on the caller's stream (no side
     // stream, so no flag sync; no captured iterations) and the copying form of the histories.  The same launches whatever n_iter is, so n_iter in one call
     // equals the same iterations in several calls bit for bit.
@@ -1068,7 +1100,7 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
     if (rect && ctx->opt_lanes > 1)
         return fail(ctx, HN_ERR_UNSUPPORTED, "hn_step: HN_OPT_LANES %d is not implemented on a rectangular domain (one lane only)", ctx->opt_lanes);
     const bool use_side = !rect && ctx->opt_side_stream != 0;
-    const int opt_graph = rect ? 0 : ctx->opt_graph;
+    const int opt_graph = rect || lossy ? 0 : ctx->opt_graph;
     const bool hist_copy = rect || ctx->opt_hist_copy != 0;
     const long plane = ctx->geo.plane();
     const long L = ctx->state_len;
@@ -1082,15 +1114,17 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
                               {states, sc, true, "states"}, {k_sq, sizeof(float) * (size_t)batch * plane, false, "k_sq"},
                               {src, sizeof(float) * (size_t)src_batch * 2 * plane, false, "src"}, {res_hist, it * fc, true, "res_hist"},
                               {wf_hist, it * fc, true, "wf_hist"}, {st_hist, it * sc, true, "st_hist"},
-                              {rmse_hist, sizeof(float) * it * batch, true, "rmse_hist"}};
-        const char *who, *other;
-        if (first_overlap(r, 9, &who, &other)) return fail(ctx, HN_ERR_ARG, "hn_step: %s overlaps %s", who, other);
+                              {rmse_hist, sizeof(float) * it * batch, true, "rmse_hist"},
+                              {k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}};
+        const char *one, *other;
+        if (first_overlap(r, 10, &one, &other)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, one, other);
     }
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
+    if (lossy && (rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (before the workspace: a refused call builds nothing)
     if ((rc = reserve_workspace(ctx, batch, s)) != HN_OK) return rc;
     if (n_iter == 0) return HN_OK;
-    if ((rc = check_async(ctx, "hn_step (an earlier call)")) != HN_OK) return rc;
+    if ((rc = check_async(ctx, lossy ? "hn_step_lossy (an earlier call)" : "hn_step (an earlier call)")) != HN_OK) return rc;
     int ns = ctx->opt_lanes;
     if (batch < 2 * ns) ns = 1;                       // tiny batches: not worth splitting
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
@@ -1100,7 +1134,7 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
         if ((rc = zero_async(ctx, rmse_hist, sizeof(float) * (size_t)n_iter * batch, s)) != HN_OK) return rc;
         if ((rc = zero_async(ctx, ctx->it_counter, 8 * sizeof(int), s)) != HN_OK) return rc;
     }
-    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist, use_side};
+    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist, use_side, k_sq_im};
     const size_t fb_all = sizeof(float) * (size_t)batch * 2 * plane, sb_all = sizeof(float) * (size_t)batch * kState * L;
     if (ns == 1) {
         // One lane: an iteration is a fixed kernel sequence over fixed buffers (the hidden states ping-pong between the
@@ -1205,7 +1239,23 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
         hipLaunchKernelGGL(k_rmse_finalize, dim3((count + 255) / 256), dim3(256), 0, s, rmse_hist, count, 1.0f / (float)(2 * plane));
         HN_HIP(ctx, hipGetLastError());
     }
-    return check_async(ctx, "hn_step");   // (what is up by now; hn_check_async_errors after a synchronise sees the rest)
+    return check_async(ctx, who);   // (what is up by now; hn_check_async_errors after a synchronise sees the rest)
+}
+
+}  // namespace
+}  // namespace hn
+
+extern "C" {
+
+int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* src, int src_batch, int batch,
+            int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
+    return step_entry(ctx, "hn_step", wf, res, states, k_sq, nullptr, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
+}
+
+int hn_step_lossy(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, int batch,
+                  int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_step_lossy: k_sq_im is NULL (a lossless medium is hn_step)");
+    return step_entry(ctx, "hn_step_lossy", wf, res, states, k_sq, k_sq_im, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
 }
 
 // Laboratory accessor (tools/deepx_check.py; not part of the ABI of include/helmnet_hip.h): the workspace tensor kind (0 x_d / upsampled, 1 skip out_d,

@@ -332,6 +332,8 @@ struct hn_ctx {
     int opt_f64_fft = 0;              // HN_OPT_F64_FFT: 0 the dense kernel k_helm_f64, 1 the two line passes of hn_f64_fft.hip; read by every float64 call
     int f64_route = 0;                // HN_CNT_F64_ROUTE: 0 no float64 call on this domain yet, 1 the last one ran dense, 2 by FFT
     hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty
+    hn::RectAxis* lossy_axis = nullptr;   // square domain: the one axis' tables the lossy operator's kernels run on (hn_spectral_rect.hip), built by the first
+                                          // lossy call; freed by hn_set_domain, hn_set_domain_rect, hn_destroy.  Never set on a rectangular domain
     // what either kind of domain is to the entry points and to unet_forward: rows, columns and the device's [2, h, w] sigma maps (they belong to tab or
     // to rect).  Set by hn_set_domain / hn_set_domain_rect, cleared (h == 0) when the domain goes.
     struct Geometry {
@@ -548,6 +550,13 @@ int spec_rect_build(hn_ctx* ctx, int h, int w, int pml, double sigma_max, double
 void spec_rect_free(hn_ctx* ctx);
 int spec_rect_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch, int batch, float* accum_sumsq,
                     hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);   // as spec_apply
+// ---- absorbing media (hn_spectral_rect.hip): out = L(wf) + (ksq + i ksq_im) wf - src, both planes of k_sq and src required; the rest as spec_apply ----
+// On a rectangular domain the tables exist; on a square one spec_lossy_reserve builds ctx->lossy_axis once per domain (HN_ERR_STATE under stream capture,
+// nothing enqueued): an entry point that launches before it reaches spec_apply_lossy asks there first.  `who`: the entry point, for the messages.
+int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s);
+int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
+                     int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
+void spec_lossy_free(hn_ctx* ctx);   // (the caller has synchronised the device)
 // HN_ERR_UNSUPPORTED "<who>: not implemented on a rectangular domain ..." (every entry point that reads the domain and has no rectangular path)
 int rect_unsupported(hn_ctx* ctx, const char* who);
 // ---- float64 residual check (hn_f64.hip) ----

@@ -36,11 +36,13 @@ struct RectTabs {
 //   AXIS 0: along x (row pass: line `r` is row r; adds the column part with flags & 1, the residual terms with flags & 2, the sum of squares)
 //   AXIS 1: along y (column pass: line `c` is column c; the block's L adjacent columns are loaded and stored as row segments of L floats)
 // Dynamic LDS: (P == 1 ? 3 : 4) buffers of L * len float2, then the Q and P twiddles.
-template <int AXIS>
+// KsqIm: empty (the lossless kernels, whose instantiations <0> and <1> are what they were before the pack existed), or one const float*: the row pass of
+// hn_residual_lossy / hn_step_lossy / hn_fgmres_cycle_lossy, whose pointwise term is complex, (ksq + i ksq_im) u.
+template <int AXIS, typename... KsqIm>
 __global__ __launch_bounds__(kMixThreads) void k_spec_rect(const float* __restrict__ wf, float* out, const float* __restrict__ ksq,
                                                            const float* __restrict__ src, long src_sb, RectTabs t, int len, int count, int pitch, int P,
                                                            int logq, int logl, int flags, float* __restrict__ sumsq,
-                                                           const int* __restrict__ it_counter, int sumsq_stride) {
+                                                           const int* __restrict__ it_counter, int sumsq_stride, KsqIm... ksq_im) {
     extern __shared__ float2 rbuf[];
     __shared__ float red[kMixThreads / 64];
     const int tid = threadIdx.x, b = blockIdx.y;
@@ -142,8 +144,16 @@ __global__ __launch_bounds__(kMixThreads) void k_spec_rect(const float* __restri
             if (flags & 1) { re += po[o]; im += po[o + plane]; }
             if (flags & 2) {
                 const float kq = ksq[(long)b * plane + o];
-                re = re + kq * pre[o];          // the line itself again (an L2 hit) instead of a copy held through the transforms
-                im = im + kq * pre[o + plane];
+                if constexpr (sizeof...(KsqIm) != 0) {
+                    const float* const kim[] = {ksq_im...};
+                    const float ki = kim[0][(long)b * plane + o];
+                    const float ur = pre[o], ui = pre[o + plane];
+                    re = re + (kq * ur - ki * ui);
+                    im = im + (kq * ui + ki * ur);
+                } else {
+                    re = re + kq * pre[o];          // the line itself again (an L2 hit) instead of a copy held through the transforms
+                    im = im + kq * pre[o + plane];
+                }
                 if (src != nullptr) {
                     const float* ps = src + (long)b * src_sb + o;
                     re -= ps[0];
@@ -283,37 +293,101 @@ int spec_rect_build(hn_ctx* ctx, int h, int w, int pml, double sigma_max, double
     // here and not at the first launch: a first call under stream capture is then nothing but launches
     HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_rect<0>), hipFuncAttributeMaxDynamicSharedMemorySize, kRectLdsAttr));
     HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_rect<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kRectLdsAttr));
+    HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_rect<0, const float*>), hipFuncAttributeMaxDynamicSharedMemorySize, kRectLdsAttr));
     return HN_OK;
 }
+
+namespace {
+
+// both passes on `s` for an h x w field: `cols` lines of length h, `rows` lines of length w.  ksq_im nullptr: the launches of spec_rect_apply as they have
+// always been; else the row pass is k_spec_rect<0, const float*> (ksq non-null)
+int rect_launch(hn_ctx* ctx, const RectAxis& cols, const RectAxis& rows, int h, int w, const float* wf, float* out, const float* ksq, const float* ksq_im,
+                const float* src, int src_batch, int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
+    const bool resid = ksq != nullptr;
+    const long src_sb = src_batch == 1 ? 0 : 2L * h * w;
+    const int Lc = rect_lines(h, w, axis_buffers(cols), batch), Lr = rect_lines(w, h, axis_buffers(rows), batch);
+    const size_t lds_c = axis_lds(cols, Lc), lds_r = axis_lds(rows, Lr);
+    if (lds_c > (size_t)kRectLdsAttr || lds_r > (size_t)kRectLdsAttr)
+        return fail(ctx, HN_ERR_ARG, "internal: rectangular spectral kernel needs %zu / %zu bytes of LDS at %d x %d", lds_c, lds_r, h, w);
+    const RectTabs tc{cols.tw_q, cols.wp, cols.k1m, cols.k2m, cols.a, cols.b, cols.slot};
+    const RectTabs tr{rows.tw_q, rows.wp, rows.k1m, rows.k2m, rows.a, rows.b, rows.slot};
+    ProfScope pair(ctx, KID_SPEC_PAIR, s);
+    if (it_counter != nullptr) hipLaunchKernelGGL(k_rect_bump, dim3(1), dim3(1), 0, s, it_counter);
+    {
+        ProfScope ps(ctx, KID_SPEC_COLS, s);
+        hipLaunchKernelGGL((k_spec_rect<1>), dim3((w + Lc - 1) / Lc, batch), dim3(kMixThreads), lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, cols.P,
+                           ilog2(cols.Q), ilog2(Lc), 0, nullptr, nullptr, 0);
+    }
+    {
+        ProfScope ps(ctx, KID_SPEC_ROWS, s);
+        if (ksq_im != nullptr)
+            hipLaunchKernelGGL((k_spec_rect<0, const float*>), dim3((h + Lr - 1) / Lr, batch), dim3(kMixThreads), lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P,
+                               ilog2(rows.Q), ilog2(Lr), 1 | 2, sumsq, it_counter, sumsq_stride, ksq_im);
+        else
+            hipLaunchKernelGGL((k_spec_rect<0>), dim3((h + Lr - 1) / Lr, batch), dim3(kMixThreads), lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P,
+                               ilog2(rows.Q), ilog2(Lr), 1 | (resid ? 2 : 0), sumsq, it_counter, sumsq_stride);
+    }
+    HN_HIP(ctx, hipGetLastError());
+    return HN_OK;
+}
+
+}  // namespace
 
 int spec_rect_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch, int batch, float* sumsq,
                     hipStream_t s, int* it_counter, int sumsq_stride) {
     const RectDomain* r = ctx->rect;
     if (r == nullptr || r->rows.len == 0 || r->cols.len == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
     if (batch <= 0) return HN_OK;
-    const int h = r->h, w = r->w;
-    const bool resid = ksq != nullptr;
-    const long src_sb = src_batch == 1 ? 0 : 2L * h * w;
-    const int Lc = rect_lines(h, w, axis_buffers(r->cols), batch), Lr = rect_lines(w, h, axis_buffers(r->rows), batch);
-    const size_t lds_c = axis_lds(r->cols, Lc), lds_r = axis_lds(r->rows, Lr);
-    if (lds_c > (size_t)kRectLdsAttr || lds_r > (size_t)kRectLdsAttr)
-        return fail(ctx, HN_ERR_ARG, "internal: rectangular spectral kernel needs %zu / %zu bytes of LDS at %d x %d", lds_c, lds_r, h, w);
-    const RectTabs tc{r->cols.tw_q, r->cols.wp, r->cols.k1m, r->cols.k2m, r->cols.a, r->cols.b, r->cols.slot};
-    const RectTabs tr{r->rows.tw_q, r->rows.wp, r->rows.k1m, r->rows.k2m, r->rows.a, r->rows.b, r->rows.slot};
-    ProfScope pair(ctx, KID_SPEC_PAIR, s);
-    if (it_counter != nullptr) hipLaunchKernelGGL(k_rect_bump, dim3(1), dim3(1), 0, s, it_counter);
-    {
-        ProfScope ps(ctx, KID_SPEC_COLS, s);
-        hipLaunchKernelGGL((k_spec_rect<1>), dim3((w + Lc - 1) / Lc, batch), dim3(kMixThreads), lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, r->cols.P,
-                           ilog2(r->cols.Q), ilog2(Lc), 0, nullptr, nullptr, 0);
+    return rect_launch(ctx, r->cols, r->rows, r->h, r->w, wf, out, ksq, nullptr, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
+}
+
+// ---- the lossy operator: res = L(u) + (ksq + i ksq_im) u - src on either kind of domain ----
+// A rectangular domain has its tables.  A square one gets ONE axis' tables of this file's kernels (both axes of an n x n domain are the same axis), built
+// by the first lossy call -- never under stream capture -- and held in ctx->lossy_axis beside ctx->rect, which stays null: the domain stays square.
+void spec_lossy_free(hn_ctx* ctx) {
+    if (ctx->lossy_axis == nullptr) return;
+    free_axis(*ctx->lossy_axis);
+    delete ctx->lossy_axis;
+    ctx->lossy_axis = nullptr;
+}
+
+int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s) {
+    if (ctx->rect != nullptr) return HN_OK;
+    const SpecTables& t = ctx->tab;
+    if (t.n == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain has not been called", who);
+    if (ctx->lossy_axis != nullptr && ctx->lossy_axis->len == t.n) return HN_OK;
+    if (stream_capturing(s))
+        return fail(ctx, HN_ERR_STATE, "%s: the tables of the lossy operator on a square domain are built by the first lossy call, which must not be under "
+                    "stream capture", who);
+    int P = 0, Q = 0;
+    if (!spec_rect_factor(t.n, &P, &Q)) return fail(ctx, HN_ERR_ARG, "internal: no factorisation of the domain size %d", t.n);
+    spec_lossy_free(ctx);
+    RectAxis* ax = new (std::nothrow) RectAxis();
+    if (ax == nullptr) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
+    int rc = build_axis(ctx, *ax, spec_axis_host(t.n, t.pml, t.sigma_max, t.k), P, Q);
+    for (const void* k : {reinterpret_cast<const void*>(k_spec_rect<1>), reinterpret_cast<const void*>(k_spec_rect<0, const float*>)})
+        if (rc == HN_OK && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kRectLdsAttr) != hipSuccess)
+            rc = fail(ctx, HN_ERR_HIP, "%s: hipFuncSetAttribute failed", who);
+    if (rc != HN_OK) {
+        free_axis(*ax);
+        delete ax;
+        return rc;
     }
-    {
-        ProfScope ps(ctx, KID_SPEC_ROWS, s);
-        hipLaunchKernelGGL((k_spec_rect<0>), dim3((h + Lr - 1) / Lr, batch), dim3(kMixThreads), lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, r->rows.P,
-                           ilog2(r->rows.Q), ilog2(Lr), 1 | (resid ? 2 : 0), sumsq, it_counter, sumsq_stride);
-    }
-    HN_HIP(ctx, hipGetLastError());
+    ctx->lossy_axis = ax;
     return HN_OK;
+}
+
+int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
+                     int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
+    if (ksq == nullptr || ksq_im == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
+    if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
+    if (batch <= 0) return HN_OK;
+    if (const RectDomain* r = ctx->rect) {
+        if (r->rows.len == 0 || r->cols.len == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
+        return rect_launch(ctx, r->cols, r->rows, r->h, r->w, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
+    }
+    const RectAxis& ax = *ctx->lossy_axis;
+    return rect_launch(ctx, ax, ax, ax.len, ax.len, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
 }
 
 int rect_unsupported(hn_ctx* ctx, const char* who) {

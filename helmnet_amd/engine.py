@@ -524,6 +524,45 @@ class Engine:
         """n_iter solver iterations; wf, res, states updated in place."""
         self._step(self.lib.hn_step, "hn_step", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
 
+    # ---- absorbing media: complex k_sq = k_sq + i k_sq_im (hn_residual_lossy / hn_step_lossy / hn_fgmres_cycle_lossy) ----
+    def residual_lossy(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+        """``residual`` with the complex pointwise term: L(wf) + (k_sq + i k_sq_im) wf - src; ``k_sq_im`` [B,1,h,w] fp32, any sign."""
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, *self.hw), "wavefield")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
+        self._chk(src, (src.shape[0], 2, *self.hw), "source")
+        out = torch.empty_like(wf)
+        rc = self.lib.hn_residual_lossy(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(k_sq_im), _ptr(src), src.shape[0], _ptr(out), b, self._stream())
+        _lib.check(rc, self.ctx, "hn_residual_lossy")
+        return out
+
+    def step_lossy(self, wf, res, states, k_sq, k_sq_im, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
+        """``step`` on the lossy residual (hn_step_lossy): the same UNet launches, one lane, never a captured iteration."""
+        self._chk(k_sq_im, (wf.shape[0], 1, *self.hw), "k_sq_im")
+
+        def entry(ctx, wf_p, res_p, st_p, k_p, *rest):
+            return self.lib.hn_step_lossy(ctx, wf_p, res_p, st_p, k_p, _ptr(k_sq_im), *rest)
+
+        self._step(entry, "hn_step_lossy", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
+
+    def fgmres_cycle_lossy(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
+                           precond_iters: int, precond_scale: float, basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None,
+                           zbasis: Optional[torch.Tensor] = None):
+        """``fgmres_cycle`` on the lossy operator (hn_fgmres_cycle_lossy), preconditioned by ``precond_iters`` iterations of ``step_lossy``;
+        ``precond_iters`` 0: plain restarted GMRES on the lossy operator.  Square domains.  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_cycle_lossy", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        if isinstance(k_sq_im, torch.Tensor) and k_sq_im.requires_grad:
+            raise RuntimeError("fgmres_cycle_lossy: k_sq_im requires grad; the GMRES cycle is not differentiable")
+        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
+        zbasis = self._zbasis(b, restart, zbasis)
+        rc = self.lib.hn_fgmres_cycle_lossy(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rhs), rhs.shape[0], b, restart, float(tol),
+                                            int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used),
+                                            self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_cycle_lossy")
+        return rmse, k_used
+
     # ---- training step (hn_train_grad / hn_adam_step; SURVEY.md 8 f4) -------------------------------------------------
     def train_reserve(self, batch: int, n_unroll: int):
         _lib.check(self.lib.hn_train_reserve(self.ctx, int(batch), int(n_unroll)), self.ctx, "hn_train_reserve")

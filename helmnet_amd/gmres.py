@@ -126,17 +126,23 @@ def default_precond_scale(source) -> float:
     return float(np.sqrt((src ** 2).sum() / src.shape[0]))
 
 
-def _hip_setup(solver, sos_maps, restart, x0, dtype):
-    """What both HIP drivers start from: (engine, k_sq, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess)."""
-    _require_no_grad("gmres(backend='hip')", sos_maps, x0)
+def _hip_setup(solver, sos_maps, restart, x0, dtype, absorption=None):
+    """What both HIP drivers start from: (engine, k_sq, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess).
+    With ``absorption`` k_sq is the pair (k_sq, k_sq_im) of the lossy medium."""
+    _require_no_grad("gmres(backend='hip')", sos_maps, x0, absorption)
     eng = solver.engine()
-    sos_maps = sos_maps.float().contiguous()
-    k_sq, wf0 = solver.get_initials(sos_maps)
+    if absorption is not None:
+        k_sq, k_sq_im, wf0 = solver._lossy_initials("gmres", sos_maps, absorption)
+    else:
+        sos_maps = sos_maps.float().contiguous()
+        k_sq, wf0 = solver.get_initials(sos_maps)
     rhs = solver.source.detach().float().contiguous()
     bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
     x = (wf0 if x0 is None else x0.detach()).to(rhs.device, dtype).contiguous().clone()
     basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=rhs.device)
     hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=rhs.device)
+    if absorption is not None:
+        return eng, (k_sq.contiguous(), k_sq_im.contiguous()), rhs, x, basis, hess
     return eng, k_sq.contiguous(), rhs, x, basis, hess
 
 
@@ -167,15 +173,20 @@ def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor, pr
             "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
 
 
-def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None):
+def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, absorption=None):
     """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own.
-    ``precond`` (iterations, alpha): the flexible cycle (hn_fgmres_cycle)."""
-    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32)
+    ``precond`` (iterations, alpha): the flexible cycle (hn_fgmres_cycle).  ``absorption``: the lossy operator (hn_fgmres_cycle_lossy, with zero
+    preconditioner iterations when ``precond`` is None)."""
+    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32, absorption)
     bsz, dev = x.shape[0], x.device
-    zbasis = None if precond is None else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
+    lossy = absorption is not None
+    zbasis = None if precond is None and not lossy else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
 
     def cycle():
-        if precond is None:
+        if lossy:
+            iters, alpha = (0, 1.0) if precond is None else precond
+            rmse, k_used = eng.fgmres_cycle_lossy(x, k_sq[0], k_sq[1], rhs, restart, tol, iters, alpha, basis, hess, zbasis)
+        elif precond is None:
             rmse, k_used = eng.gmres_cycle(x, k_sq, rhs, restart, tol, basis, hess)
         else:
             rmse, k_used = eng.fgmres_cycle(x, k_sq, rhs, restart, tol, precond[0], precond[1], basis, hess, zbasis)
@@ -184,12 +195,15 @@ def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None):
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
 
     def true_rmse():
+        if lossy:
+            return eng.rmse(eng.residual_lossy(x, k_sq[0], k_sq[1], rhs)).cpu().numpy()
         return eng.rmse(eng.residual(x, k_sq, rhs)).cpu().numpy()
 
     out = drive_cycles(cycle, true_rmse, max_outer, tol)
+    extra = {"cycles": out["cycles"]} if lossy else {}
     return {"wavefield": x, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
             "operator_applications": out["cycles"] * (restart + 1) + out["true_checks"], "converged": out["converged"],
-            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"],
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], **extra,
             "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
 
 
@@ -263,7 +277,7 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
 
 def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
           x0: Optional[torch.Tensor] = None, backend: str = "torch", refine: bool = False, inner_floor: float = 1e-6,
-          precondition: Optional[str] = None, precond_iterations: int = 10, precond_scale: Optional[float] = None):
+          precondition: Optional[str] = None, precond_iterations: int = 10, precond_scale: Optional[float] = None, absorption=None):
     """Solve (L + k_sq) u = source for every map of ``sos_maps`` [B, 1, N, N] (the reference's classical baseline:
     matlab/spectral_gmres_solver.m:86-115, MATLAB's ``gmres`` with restarts).
 
@@ -293,7 +307,17 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
     (hn_fgmres_cycle / hn_fgmres_refine_cycle) -- per inner step ``precond_iterations`` iterations of the solver's network on A z = alpha v_k from
     rest, z_k = wf / alpha.  ``precond_scale`` is alpha; None: ``default_precond_scale(solver.source)``.  The result gains ``unet_evaluations``
     (cycles x restart x precond_iterations, all enqueued in lock step; 0 without a preconditioner).  ``precondition=None`` is the code path and the
-    bits of before."""
+    bits of before.
+
+    ``absorption`` (alpha in nepers per grid point, a number or a tensor broadcastable to ``sos_maps``; helmnet_amd.absorption): the medium is lossy,
+    k~ = omega / sos + i alpha, and the cycles run on hn_fgmres_cycle_lossy.  ``backend="hip"`` with ``precondition`` None or "learned"; the torch
+    backend raises ValueError, ``refine=True`` NotImplementedError (there is no float64 lossy operator).  The result gains ``cycles``.  None: the code
+    path and the bits of before."""
+    if absorption is not None:
+        if backend != "hip":
+            raise ValueError("absorption needs backend='hip' (the torch backend has the lossless operator only)")
+        if refine:
+            raise NotImplementedError("gmres(refine=True) is not implemented with absorption: the library has no float64 lossy operator")
     if refine and backend != "hip":
         raise ValueError("refine=True needs backend='hip'")
     if precondition not in (None, "learned"):
@@ -309,7 +333,7 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
     if backend == "hip" and refine:
         return _gmres_refine(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, float(inner_floor), precond)
     if backend == "hip":
-        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, precond)
+        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, precond, absorption)
     if backend != "torch":
         raise ValueError(f"unknown GMRES backend {backend!r} (choose 'torch' or 'hip')")
     eng = solver.engine()

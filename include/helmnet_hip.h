@@ -518,6 +518,40 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
             int src_batch, int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist,
             float* rmse_hist, void* stream);
 
+/* ---- absorbing media: a complex k_sq (an extension like the rectangular domains; the reference's Python side has no counterpart, its MATLAB side
+ * carries skull absorption in matlab/skull2medium.m).  The three entry points below take the medium as two real planes and evaluate
+ *     res = L(wf) + (k_sq + i * k_sq_im) * wf - src:   re += k_sq * wf_re - k_sq_im * wf_im,   im += k_sq * wf_im + k_sq_im * wf_re.
+ * Sign: the PML stretches with gamma = 1 + i sigma / k, so outgoing waves are e^{+ikx} and a medium ABSORBS for Im(k~) > 0.  With k~ = omega / c + i alpha
+ * (alpha in nepers per grid point): k_sq = (omega / c)^2 - alpha^2, k_sq_im = 2 (omega / c) alpha >= 0.  A negative k_sq_im amplifies; it is accepted.
+ * k_sq_im: fp32 [B,1,h,w], read only, any sign; NULL returns HN_ERR_ARG with a message that names the lossless sibling.  Its alignment and overlap rules
+ * are those k_sq has in the sibling call, and it may overlap nothing that is written.  The UNet never sees k_sq (its six input channels are the
+ * wavefield, 1e3 * residual and the two sigma maps), so absorption enters the residual alone.
+ * Route: both line passes run on the general LDS-line kernel of the rectangular domains (any length P * 2^k), the row pass with the complex term.  On a
+ * rectangular domain the tables exist; on a SQUARE domain they are built by the first lossy call on that domain -- which must not be under stream
+ * capture: HN_ERR_STATE, nothing enqueued -- kept until hn_set_domain / hn_set_domain_rect / hn_destroy, and change nothing of the lossless entry
+ * points: hn_residual, hn_step and the cycles keep their kernels and their bits.  With k_sq_im = 0 the results agree with the lossless siblings to fp32
+ * rounding, not bit for bit (another factorisation of the transforms).
+ * No entry point exists for: gradients of any kind (d / d k_sq_im included), the adjoint cycle, the float64 operator and refinement, training. */
+
+/* hn_residual with the complex pointwise term; every legal square size and every rectangular domain.  HN_ERR_ARG "hn_residual_lossy: k_sq_im overlaps res". */
+int hn_residual_lossy(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, float* res, int batch,
+                      void* stream);
+
+/* hn_step on the lossy residual: per iteration exactly the UNet launches of hn_step, then the lossy spectral pair.  Arguments, in-place updates, the four
+ * histories and rmse_hist mean what they mean in hn_step; k_sq_im joins k_sq and src as a read-only tensor of the overlap rule ("hn_step_lossy: <a>
+ * overlaps <b>").  Square domains: every UNet precision mode; rectangular domains: the two fp32 modes, as hn_step.  Runs eagerly on one lane:
+ * HN_OPT_LANES > 1 returns HN_ERR_UNSUPPORTED, HN_EXP_GRAPH is ignored. */
+int hn_step_lossy(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, int batch,
+                  int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream);
+
+/* hn_fgmres_cycle with the lossy operator in both places, w = A z and the true residual of row 0, and precond_iters iterations of hn_step_lossy on
+ * A z = precond_scale * v as the preconditioner; precond_iters = 0 is plain restarted GMRES on the lossy operator.  Square domains only
+ * (HN_ERR_UNSUPPORTED on a rectangular one).  Workspaces, the capture refusal and every argument check are hn_fgmres_cycle's; k_sq_im must be 16-byte
+ * aligned and overlap no other argument, as k_sq. */
+int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch, int restart,
+                          float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
+                          void* stream);
+
 /* ---- training step (hybridnet.py:385-413 training_step, :250-283 configure_optimizers, :172-176
  * on_after_backward).  The caller owns every training tensor: the weights as ONE flat device blob in the order of
  * hn_load_weights (PyTorch layouts inside: conv [out,in,kh,kw], transposed conv [in,out,kh,kw]), its gradient, and the
