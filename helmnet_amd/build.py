@@ -16,8 +16,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libhelmnet_hip.so")
-SOURCES = ["hn_api.hip", "hn_spectral.hip", "hn_spectral_mixed.hip", "hn_spectral_rect.hip", "hn_unet.hip", "hn_mfma.hip", "hn_deep.hip", "hn_deepx.hip", "hn_dcv.hip", "hn_dca.hip", "hn_cs.hip", "hn_train.hip", "hn_rows.hip", "hn_stream.hip", "hn_f64.hip", "hn_f64_fft.hip", "hn_unet_f64.hip", "hn_krylov.hip", "hn_jvp.hip"]
-HEADERS = [os.path.join(CSRC, "hn_internal.h"), os.path.join(CSRC, "hn_vec.h"), os.path.join(CSRC, "hn_dca_pass.inc"), os.path.join(CSRC, "hn_spectral_lds.inc"), os.path.join(REPO, "include", "helmnet_hip.h")]
+SOURCES = ["hn_api.hip", "hn_spectral.hip", "hn_spectral_line.hip", "hn_unet.hip", "hn_mfma.hip", "hn_deep.hip", "hn_deepx.hip", "hn_dcv.hip", "hn_dca.hip", "hn_cs.hip", "hn_train.hip", "hn_rows.hip", "hn_stream.hip", "hn_f64.hip", "hn_f64_fft.hip", "hn_unet_f64.hip", "hn_krylov.hip", "hn_jvp.hip"]
+HEADERS = [os.path.join(CSRC, "hn_internal.h"), os.path.join(CSRC, "hn_vec.h"), os.path.join(CSRC, "hn_dca_pass.inc"), os.path.join(REPO, "include", "helmnet_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(REPO, "include"), "-I" + CSRC,
          "-Wall", "-Wno-unused-function"]
 

@@ -467,7 +467,7 @@ int64_t hn_get_counter(const hn_ctx* ctx, int counter) {
         case HN_CNT_TRAIN_FWD_EVENTS: return ctx->train_fwd_events;
         case HN_CNT_FLAG_SYNC_ITERATIONS: return ctx->flag_sync_iterations;
         case HN_CNT_SIDE_CANDIDATE: return ctx->picks[0].known.empty() ? -1 : ctx->picks[0].last_chosen;
-        case HN_CNT_SPECTRAL_ROUTE: return ctx->rect != nullptr ? 5 : ctx->tab.n == 0 ? 0 : ctx->tab.pow2 ? 1 : ctx->tab.pfa_p != 0 ? 2 : ctx->tab.mix_p != 0 ? 4 : 3;
+        case HN_CNT_SPECTRAL_ROUTE: return ctx->rect != nullptr ? 5 : ctx->tab.n == 0 ? 0 : ctx->tab.pow2 ? 1 : ctx->tab.pfa_p != 0 ? 2 : ctx->tab.mixed ? 4 : 3;
         case HN_CNT_F64_ROUTE: return ctx->f64_route;
         default: return -1;
     }
@@ -486,9 +486,8 @@ void hn_destroy(hn_ctx* ctx) {
     jvp_free(ctx);
     krylov_free(ctx);
     f64_fft_free(ctx);
-    spec_free(ctx->tab);
+    spec_free(ctx);
     spec_rect_free(ctx);
-    spec_lossy_free(ctx);
     (void)hipFree(ctx->wdev);
     (void)hipFree(ctx->fragdev);
     for (int j = 0; j < ctx->n_streams; ++j) {
@@ -615,7 +614,6 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     jvp_free(ctx);
     krylov_free(ctx);
     f64_fft_free(ctx);
-    spec_lossy_free(ctx);
     ctx->f64_route = 0;
     if (n % 16 != 0) return fail(ctx, HN_ERR_ARG, "domain size %d must be divisible by 16", n);
     if (!(k > 0.f) || !(sigma_max >= 0.f)) return fail(ctx, HN_ERR_ARG, "k must be > 0 and sigma_max >= 0");
@@ -627,7 +625,7 @@ int hn_set_domain(hn_ctx* ctx, int n, int pml, float sigma_max, float k) {
     return build_inc_sigma_map(ctx);
 }
 
-// h == w is hn_set_domain itself; otherwise the per-axis tables of hn_spectral_rect.hip, and tab stays empty
+// h == w is hn_set_domain itself; otherwise the per-axis tables of hn_spectral_line.hip, and tab stays empty
 int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, float k) {
     if (!ctx) return HN_ERR_ARG;
     if (h == w) return hn_set_domain(ctx, h, pml, sigma_max, k);
@@ -645,10 +643,9 @@ int hn_set_domain_rect(hn_ctx* ctx, int h, int w, int pml, float sigma_max, floa
     jvp_free(ctx);
     krylov_free(ctx);
     f64_fft_free(ctx);
-    spec_lossy_free(ctx);
     ctx->f64_route = 0;
     free_workspace(ctx);
-    spec_free(ctx->tab);
+    spec_free(ctx);
     int rc = build_inc_sigma_map(ctx);   // (no n x n domain: frees the map)
     if (rc == HN_OK) rc = spec_rect_build(ctx, h, w, pml, (double)sigma_max, (double)k);
     set_geometry(ctx);   // (also after a failure: whatever is left)

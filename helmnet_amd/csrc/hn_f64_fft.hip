@@ -1,5 +1,5 @@
-// hn_f64_fft.hip -- the float64 Helmholtz operator of hn_f64.hip by FFT (HN_OPT_F64_FFT 1): two line passes in the algorithm of k_spec_rect
-// (hn_spectral_rect.hip; read its header comment and hn_spectral_mixed.hip's), in double.
+// hn_f64_fft.hip -- the float64 Helmholtz operator of hn_f64.hip by FFT (HN_OPT_F64_FFT 1): two line passes in the algorithm of k_spec_line
+// (hn_spectral_line.hip; read its header comment), in double.
 //   column pass   lines along the first spatial axis:   mid = ay . D1y u + by . D2y u
 //   row pass      lines along the second:               out = mid + ax . D1x u + bx . D2x u [+ k_sq . u - src], one sum of squares per line
 // Every legal n = P * Q, P odd in [1, 127], Q = 2^k in [16, 2048] (spec_rect_factor).  A line lives in LDS as [P][Q] double2 (Good-Thomas input map): in-place
@@ -301,7 +301,7 @@ Tabs tabs_of(const F64Fft& f) {
     return Tabs{c, c + f.Q, c + f.Q + f.P, c + f.Q + f.P + n, d, d + n, reinterpret_cast<const int*>(d + 2 * (size_t)n)};
 }
 
-// the tables of build_axis (hn_spectral_rect.hip) in double: the twiddles computed in double, the operator values up-cast from what the reference holds in fp32
+// the tables of build_axis (hn_spectral_line.hip) in double: the twiddles computed in double, the operator values up-cast from what the reference holds in fp32
 int build_tables(hn_ctx* ctx, F64Fft& f, int n, int P, int Q) {
     const SpecTables& st = ctx->tab;
     const AxisHost ax = spec_axis_host(n, st.pml, st.sigma_max, st.k);

@@ -190,11 +190,9 @@ struct SpecTables {
     float2* tw_q = nullptr;    // exp(-2 pi i m / Q)
     float* k1_pfa = nullptr;   // [P][Q]
     float* k2_pfa = nullptr;
-    // mixed path (hn_spectral_mixed.hip; n = P * Q, P any odd factor, HN_OPT_SPECTRAL_MIXED): tw_q as above; k1_pfa / k2_pfa in the order the
-    // kernel meets the spectrum (Good-Thomas output map, k2 bit-reversed); a / b in natural order
-    int mix_p = 0, mix_q = 0;
-    int* mix_slot = nullptr;   // [n]: where element i of a line sits in the [P][Q] layout (Good-Thomas input map)
-    float2* mix_wp = nullptr;  // exp(-2 pi i m / P), m in [0, P)
+    // mixed path (HN_OPT_SPECTRAL_MIXED; n = P * Q, P any odd factor >= 3): the LDS-line kernels of hn_spectral_line.hip on ctx->sq_axis, which holds
+    // every table of this route
+    bool mixed = false;
     // dense fallback (any other n): complex n x n operator, stored transposed
     float2* dense_t = nullptr; // dense_t[m*n + j] = M[j][m]
     float2* dense_adj_t = nullptr; // the same for the adjoint operator M^H (training, hn_train.hip)
@@ -214,18 +212,19 @@ struct AxisHost {
     std::vector<float2> fa, fb;
 };
 AxisHost spec_axis_host(int n, int pml, double sigma_max, double k);
-// A rectangular h x w domain (hn_set_domain_rect with h != w): one factorisation len = P * Q and one set of tables per axis (hn_spectral_rect.hip).
-// While it exists ctx->tab is empty (tab.n == 0): whatever is built for n x n cannot run on it by accident.
-struct RectAxis {
+// One axis of the LDS-line kernels (hn_spectral_line.hip): the factorisation len = P * Q and the tables of lines of that length (all device pointers).
+struct LineAxis {
     int len = 0, P = 0, Q = 0;   // P odd in [1, 127], Q = 2^k in [16, 2048]
     float2 *tw_q = nullptr, *wp = nullptr;   // exp(-2 pi i m / Q), exp(-2 pi i m / P)
     float *k1m = nullptr, *k2m = nullptr;    // [P][Q]: k and -k^2 in the order the kernel meets the spectrum (Good-Thomas output map, k2 bit-reversed)
     float2 *a = nullptr, *b = nullptr;       // PML coefficients, natural order
-    int* slot = nullptr;                     // [len]: where element i of a line sits in the [P][Q] layout
+    int* slot = nullptr;                     // [len]: where element i of a line sits in the [P][Q] layout (Good-Thomas input map)
 };
+// A rectangular h x w domain (hn_set_domain_rect with h != w): one axis per direction.
+// While it exists ctx->tab is empty (tab.n == 0): whatever is built for n x n cannot run on it by accident.
 struct RectDomain {
     int h = 0, w = 0;
-    RectAxis cols, rows;       // cols: lines of length h (the y axis); rows: lines of length w (the x axis)
+    LineAxis cols, rows;       // cols: lines of length h (the y axis); rows: lines of length w (the x axis)
     float* sigmas = nullptr;   // [2, h, w]
 };
 struct KrylovWs;  // GMRES cycle (hn_krylov.hip): partial sums, the small least-squares problem, two dense fields for the operator
@@ -332,8 +331,8 @@ struct hn_ctx {
     int opt_f64_fft = 0;              // HN_OPT_F64_FFT: 0 the dense kernel k_helm_f64, 1 the two line passes of hn_f64_fft.hip; read by every float64 call
     int f64_route = 0;                // HN_CNT_F64_ROUTE: 0 no float64 call on this domain yet, 1 the last one ran dense, 2 by FFT
     hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty
-    hn::RectAxis* lossy_axis = nullptr;   // square domain: the one axis' tables the lossy operator's kernels run on (hn_spectral_rect.hip), built by the first
-                                          // lossy call; freed by hn_set_domain, hn_set_domain_rect, hn_destroy.  Never set on a rectangular domain
+    hn::LineAxis* sq_axis = nullptr;  // square domain: the one axis the LDS-line kernels run on (hn_spectral_line.hip) -- the mixed route (tab.mixed; built with
+                                      // tab) and the lossy operator (else built by the first lossy call); freed with tab (spec_free).  Never set on a rectangular domain
     // what either kind of domain is to the entry points and to unet_forward: rows, columns and the device's [2, h, w] sigma maps (they belong to tab or
     // to rect).  Set by hn_set_domain / hn_set_domain_rect, cleared (h == 0) when the domain goes.
     struct Geometry {
@@ -477,6 +476,14 @@ void set_global_error(const char* msg);
                             hipGetErrorString(e_), __FILE__, __LINE__);                     \
     } while (0)
 
+// a new device array holding `h` (the spectral tables)
+template <typename T>
+int upload(hn_ctx* ctx, T** dst, const std::vector<T>& h) {
+    HN_HIP(ctx, hipMalloc((void**)dst, h.size() * sizeof(T)));
+    HN_HIP(ctx, hipMemcpy(*dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return HN_OK;
+}
+
 // Kernel ids of the per-iteration launch sequence (hn_profile_*).
 enum KernelId : int {
     KID_INC = 0,          // DoubleConv 6->8->8 at level 0
@@ -526,37 +533,34 @@ struct ProfScope {
 
 // ---- spectral (hn_spectral.hip) ----
 int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k);
-void spec_free(SpecTables& t);
+void spec_free(hn_ctx* ctx);   // ctx->tab and, with it, the square domain's line axis (ctx->sq_axis); the caller has synchronised the device
 // out = L(wf) [+ ksq*wf - src]; `accum_sumsq` (nullable) receives sum over (c,h,w) of out^2 per sample, in row
 // `*it_counter - 1` of a [.., sumsq_stride] table when `it_counter` is given (the column pass increments it: one
-// captured iteration can then be replayed for every row of the RMSE history), else in row 0.  On a rectangular domain: spec_rect_apply.
+// captured iteration can then be replayed for every row of the RMSE history), else in row 0.  On a rectangular domain and on the mixed route: spec_line_apply.
 int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch,
                int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
 // out = L^H(g) + ksq * g [+ add]: the adjoint (conjugate transpose) of the residual operator, i.e. the vector-Jacobian product
 // of hn_residual with respect to the wavefield (training).  `add` may alias `out`.
 int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
-// ---- spectral, runtime odd factor (hn_spectral_mixed.hip) ----
-// (P, Q) with n = P * Q, P odd in [3, 127], Q a power of two in [16, 512]: the sizes the mixed kernels take; false otherwise
-bool spec_mixed_factor(int n, int* P, int* Q);
-// the tables of ctx->tab for n = P * Q (tw_q, k1_pfa, k2_pfa, a, b, mix_slot, mix_wp) and the kernels' dynamic-LDS attribute
-int spec_mixed_build(hn_ctx* ctx, const AxisHost& ax, int P, int Q);
-int spec_mixed_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, long src_sb, int batch, bool resid,
-                     float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride);
-int spec_mixed_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
-// ---- spectral, rectangular domain (hn_spectral_rect.hip) ----
+// ---- spectral, lines in LDS (hn_spectral_line.hip): rectangular domains, the mixed route of a square one, the lossy operator on both ----
 // (P, Q) with len = P * Q, P odd in [1, 127], Q a power of two in [16, 2048]: every multiple of 16 in [16, 2048]; false otherwise
 bool spec_rect_factor(int len, int* P, int* Q);
 int spec_rect_build(hn_ctx* ctx, int h, int w, int pml, double sigma_max, double k);   // ctx->rect: both axes' tables, the sigma maps, the kernels' LDS attribute
 void spec_rect_free(hn_ctx* ctx);
-int spec_rect_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch, int batch, float* accum_sumsq,
-                    hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);   // as spec_apply
-// ---- absorbing media (hn_spectral_rect.hip): out = L(wf) + (ksq + i ksq_im) wf - src, both planes of k_sq and src required; the rest as spec_apply ----
-// On a rectangular domain the tables exist; on a square one spec_lossy_reserve builds ctx->lossy_axis once per domain (HN_ERR_STATE under stream capture,
-// nothing enqueued): an entry point that launches before it reaches spec_apply_lossy asks there first.  `who`: the entry point, for the messages.
+// ctx->sq_axis for ctx->tab's (n, pml, sigma_max, k) and the kernels' LDS attribute (not under stream capture); spec_free is its only destructor
+int spec_sq_axis_build(hn_ctx* ctx);
+void spec_sq_axis_free(hn_ctx* ctx);
+// as spec_apply / spec_adjoint, on ctx->rect (forward only) or ctx->sq_axis (adjoint: P >= 3, which the mixed route has)
+int spec_line_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch, int batch, float* accum_sumsq,
+                    hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
+int spec_line_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
+// ---- absorbing media: out = L(wf) + (ksq + i ksq_im) wf - src, both planes of k_sq and src required; the rest as spec_apply ----
+// On a rectangular domain and on the mixed route the tables exist; on any other square domain spec_lossy_reserve builds ctx->sq_axis once per domain
+// (HN_ERR_STATE under stream capture, nothing enqueued): an entry point that launches before it reaches spec_apply_lossy asks there first.  `who`: the
+// entry point, for the messages.
 int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s);
 int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
                      int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
-void spec_lossy_free(hn_ctx* ctx);   // (the caller has synchronised the device)
 // HN_ERR_UNSUPPORTED "<who>: not implemented on a rectangular domain ..." (every entry point that reads the domain and has no rectangular path)
 int rect_unsupported(hn_ctx* ctx, const char* who);
 // ---- float64 residual check (hn_f64.hip) ----

@@ -1989,19 +1989,15 @@ int pfa_factor(int n) {
     return 0;
 }
 
-template <typename T>
-int upload(hn_ctx* ctx, T** dst, const std::vector<T>& h) {
-    HN_HIP(ctx, hipMalloc((void**)dst, h.size() * sizeof(T)));
-    HN_HIP(ctx, hipMemcpy(*dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return HN_OK;
-}
-
 }  // namespace
 
-void spec_free(SpecTables& t) {
+// the axis goes with the tables it was built for: it cannot outlive them, and tab.mixed cannot point at an axis that has gone
+void spec_free(hn_ctx* ctx) {
+    SpecTables& t = ctx->tab;
     for (void* p : {(void*)t.tw, (void*)t.k1, (void*)t.k2, (void*)t.a, (void*)t.b, (void*)t.dense_t, (void*)t.dense_adj_t, (void*)t.sigmas, (void*)t.tw_q,
-                    (void*)t.k1_pfa, (void*)t.k2_pfa, (void*)t.mix_slot, (void*)t.mix_wp, (void*)t.f64_tab, (void*)t.f64_part}) (void)hipFree(p);
+                    (void*)t.k1_pfa, (void*)t.k2_pfa, (void*)t.f64_tab, (void*)t.f64_part}) (void)hipFree(p);
     t = SpecTables{};
+    spec_sq_axis_free(ctx);
 }
 
 // Host-side construction of every constant, float64 then cast -- the formulas of
@@ -2068,7 +2064,7 @@ void spec_circulant_host(const AxisHost& ax, std::vector<std::complex<double>>& 
 int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
     if (n < 16 || n > 2048) return fail(ctx, HN_ERR_ARG, "domain size %d outside [16, 2048]", n);
     if (pml < 1 || 2 * pml > n) return fail(ctx, HN_ERR_ARG, "PML size %d does not fit domain %d", pml, n);
-    spec_free(ctx->tab);
+    spec_free(ctx);
     ctx->pfa_attr_set = ctx->pfa_adj_attr_set = false;   // another (P, Q) kernel instance from now on
     SpecTables& t = ctx->tab;
     t.n = n;
@@ -2120,9 +2116,11 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
         if ((rc = upload(ctx, &t.k2_pfa, k2p)) != HN_OK) return rc;
         if ((rc = upload(ctx, &t.a, fa)) != HN_OK) return rc;
         if ((rc = upload(ctx, &t.b, fb)) != HN_OK) return rc;
-    } else if (int mp = 0, mq = 0; ctx->opt_mixed && spec_mixed_factor(n, &mp, &mq)) {
-        // HN_OPT_SPECTRAL_MIXED: any other n = P * 2^k with P odd (hn_spectral_mixed.hip); with HN_OPT_SPECTRAL_PFA 0 that includes P = 3, 5, 7
-        if ((rc = spec_mixed_build(ctx, ax, mp, mq)) != HN_OK) return rc;
+    } else if (int mp = 0, mq = 0; ctx->opt_mixed && spec_rect_factor(n, &mp, &mq) && mp >= 3) {
+        // HN_OPT_SPECTRAL_MIXED: any other n = P * 2^k with P odd in [3, 127] (hn_spectral_line.hip; Q <= 512 follows from n <= 2048); with
+        // HN_OPT_SPECTRAL_PFA 0 that includes P = 3, 5, 7
+        if ((rc = spec_sq_axis_build(ctx)) != HN_OK) return rc;
+        t.mixed = true;
     } else {
         // M[j][m] = (1/n) sum_p (a_j * i*k_p + b_j * k2_p) exp(2 pi i p (j - m) / n), k2_p = -(k_p^2)
         std::vector<std::complex<double>> g1, g2;
@@ -2151,7 +2149,8 @@ int spec_build(hn_ctx* ctx, int n, int pml, double sigma_max, double k) {
 
 int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch,
                int batch, float* accum_sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
-    if (ctx->rect) return spec_rect_apply(ctx, wf, out, ksq, src, src_batch, batch, accum_sumsq, s, it_counter, sumsq_stride);
+    // rectangles and the mixed route: the LDS-line kernels, under an event pair of their own
+    if (ctx->rect || ctx->tab.mixed) return spec_line_apply(ctx, wf, out, ksq, src, src_batch, batch, accum_sumsq, s, it_counter, sumsq_stride);
     const SpecTables& t = ctx->tab;
     if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return HN_OK;
@@ -2233,9 +2232,6 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
         }
 #undef HN_PFA
         if (rc != HN_OK) return rc;
-    } else if (t.mix_p != 0) {
-        const int rc = spec_mixed_apply(ctx, wf, out, ksq, src, src_sb, batch, resid, accum_sumsq, s, it_counter, sumsq_stride);
-        if (rc != HN_OK) return rc;
     } else {
         if (it_counter != nullptr) hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, s, it_counter);
         ProfScope ps(ctx, KID_SPEC_ROWS, s);
@@ -2253,6 +2249,7 @@ int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, cons
     if (t.n == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
     if (batch <= 0) return HN_OK;
     if (g == out) return fail(ctx, HN_ERR_ARG, "spec_adjoint: input and output must not alias");
+    if (t.mixed) return spec_line_adjoint(ctx, g, out, ksq, add, batch, s);
     if (t.pow2) {
         const SpecPtrs p{t.tw, t.k1, t.k2, t.a, t.b};
         switch (t.n) {
@@ -2271,9 +2268,6 @@ int spec_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, cons
             default: return fail(ctx, HN_ERR_ARG, "internal: no prime-factor kernel for %d x %d", t.pfa_p, t.pfa_q);
         }
 #undef HN_PFA
-        if (rc != HN_OK) return rc;
-    } else if (t.mix_p != 0) {
-        const int rc = spec_mixed_adjoint(ctx, g, out, ksq, add, batch, s);
         if (rc != HN_OK) return rc;
     } else {
         if (add == out) return fail(ctx, HN_ERR_ARG, "spec_adjoint: the dense operator cannot accumulate in place");

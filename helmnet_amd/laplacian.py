@@ -45,7 +45,7 @@ def spectral_route(n: int, pfa: int = 1, mixed: int = 0):
     spec_build (hn_spectral.hip), whose outcome Engine.counter('spectral_route') reports as 1 .. 4.  n = P * Q, P odd, Q a power of two.
         'pow2'          P == 1: the power-of-two kernels
         'prime_factor'  P in (3, 5, 7), Q >= 16 (up to 512 for P = 3, 256 for 5 and 7) and spectral_pfa: k_spec_pfa<Q, P>
-        'mixed'         any other P in [3, 127] with Q in [16, 512] and spectral_mixed: k_spec_mixed (runtime P)
+        'mixed'         any other P in [3, 127] with Q in [16, 512] and spectral_mixed: k_spec_line (runtime P)
         'dense'         everything else: the n x n operator
     Every multiple of 16 in [16, 2048] that is neither 'pow2' nor 'prime_factor' has P in [9, 127] and Q in {16, 32, 64, 128}; no size was taken
     out of the mixed rule after measurement (profiles/spectral_mixed_bench.txt)."""
@@ -99,7 +99,7 @@ def domain_hw(domain_size):
 
 def spectral_route_rect(h: int, w: int):
     """('rectangular', (P_h, Q_h), (P_w, Q_w)): the factorisation hn_set_domain_rect uses for an h x w domain with h != w -- the rule of
-    spec_rect_factor (hn_spectral_rect.hip), reported by Engine.counter('spectral_route') as 5.  Each axis on its own: len = P * Q with Q the
+    spec_rect_factor (hn_spectral_line.hip), reported by Engine.counter('spectral_route') as 5.  Each axis on its own: len = P * Q with Q the
     largest power of two dividing it, which for every multiple of 16 in [16, 2048] gives P odd in [1, 127] and Q in [16, 2048]; every such
     length runs by FFT (P = 1: a plain power-of-two transform) and neither option 'spectral_pfa' nor 'spectral_mixed' is read.  h == w is
     hn_set_domain itself: see ``spectral_route``."""

@@ -108,7 +108,7 @@ enum hn_option {
                               * read by the next hn_set_domain)                                                     */
     HN_OPT_SPECTRAL_MIXED = 17, /* 0/1 (default 0): FFT for every other size n = P * 2^k, P odd >= 9 (2^k >= 16: all multiples of 16 that are neither a power
                               * of two nor taken by HN_OPT_SPECTRAL_PFA; with HN_OPT_SPECTRAL_PFA 0 also P = 3, 5, 7) instead of the dense n x n operator:
-                              * P interleaved 2^k-point transforms in LDS and a direct P-point DFT across them (hn_spectral_mixed.hip).  Agrees with
+                              * P interleaved 2^k-point transforms in LDS and a direct P-point DFT across them (hn_spectral_line.hip).  Agrees with
                               * the dense operator to fp32 rounding, not bit for bit; read by the next hn_set_domain.  HN_CNT_SPECTRAL_ROUTE tells
                               * which route the current domain took                                                            */
     HN_OPT_F64_FFT = 18,     /* 0/1 (default 0; environment default HN_F64_FFT): the route of the float64 operator (hn_laplacian_f64, hn_residual_f64, hn_step_f64,
@@ -527,8 +527,9 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
  * are those k_sq has in the sibling call, and it may overlap nothing that is written.  The UNet never sees k_sq (its six input channels are the
  * wavefield, 1e3 * residual and the two sigma maps), so absorption enters the residual alone.
  * Route: both line passes run on the general LDS-line kernel of the rectangular domains (any length P * 2^k), the row pass with the complex term.  On a
- * rectangular domain the tables exist; on a SQUARE domain they are built by the first lossy call on that domain -- which must not be under stream
- * capture: HN_ERR_STATE, nothing enqueued -- kept until hn_set_domain / hn_set_domain_rect / hn_destroy, and change nothing of the lossless entry
+ * rectangular domain the tables exist; on a SQUARE domain they are built at the latest by the first lossy call on that domain -- which, where it has
+ * them to build (every route but HN_OPT_SPECTRAL_MIXED's, whose own tables they are), must not be under stream capture: HN_ERR_STATE, nothing
+ * enqueued -- kept until hn_set_domain / hn_set_domain_rect / hn_destroy, and change nothing of the lossless entry
  * points: hn_residual, hn_step and the cycles keep their kernels and their bits.  With k_sq_im = 0 the results agree with the lossless siblings to fp32
  * rounding, not bit for bit (another factorisation of the transforms).
  * No entry point exists for: gradients of any kind (d / d k_sq_im included), the adjoint cycle, the float64 operator and refinement, training. */

@@ -1,7 +1,7 @@
 """What test_spectral_mixed_host.py and test_spectral_mixed_gpu.py share, built on tests/spectral_probes.py: the same four probes, the same float64
 reference (SP.forward_case, SP.adjoint_case) and the same bar (SP.BAR = 1e-5 of scale(n) * max|u|) -- the project's bar for every spectral route.
 
-Added here for the mixed route (HN_OPT_SPECTRAL_MIXED, n = P * Q with a runtime odd P; hn_spectral_mixed.hip):
+Added here for the mixed route (HN_OPT_SPECTRAL_MIXED, n = P * Q with a runtime odd P; k_spec_line of hn_spectral_line.hip):
 
   * a second pair of mode fields.  SP.mode_indices(n) adds the P / Q specific modes only where P is 3, 5 or 7, so these carry, one Fourier mode per
     line by SP.mode_field's own formula, the indices P, Q, Q -+ 1, 2 Q + P, n - Q, n - P, P * (Q / 2) and Q * ((P - 1) / 2): the modes whose
@@ -146,7 +146,8 @@ def mutate_k1p_entry(t, j):
 
 
 def mixed_lines(n, nbuf, batch):
-    """Lines per block of launch_mixed (hn_spectral_mixed.hip): nbuf = 4 forward, 3 adjoint."""
+    """Lines per block on the mixed route: rect_lines(n, n, nbuf, batch) of hn_spectral_line.hip, the one rule of every LDS-line launch; nbuf = 4
+    forward, 3 adjoint."""
     lines = 16
     while lines > 1 and lines * nbuf * n * 8 > 80 * 1024:
         lines //= 2

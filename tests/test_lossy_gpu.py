@@ -350,11 +350,24 @@ def _lossless(e, n, b=2):
     return [res0, wf, res, st, rmse] + hist
 
 
-@pytest.mark.parametrize("n", [96, 144])
-def test_lossy_calls_leave_the_lossless_entry_points_alone(blob, n):
-    used, fresh = _engine(n, n, blob), _engine(n, n, blob)
+def _same_lossless(got, want):
+    for i, (p, q) in enumerate(zip(got, want)):
+        assert not bool(torch.isnan(p).any())
+        if i == 4:      # the RMSE rows: one atomicAdd per block
+            assert torch.allclose(p, q, rtol=1e-5, atol=0)
+        else:
+            assert torch.equal(p, q), i
+
+
+@pytest.mark.parametrize("n,mixed", [pytest.param(96, 0, id="96"), pytest.param(144, 0, id="144"), pytest.param(144, 1, id="144-mixed")])
+def test_lossy_calls_leave_the_lossless_entry_points_alone(blob, n, mixed):
+    used, fresh = _engine(blob=blob), _engine(blob=blob)
     try:
+        for e in (used, fresh):
+            e.set_option("spectral_mixed", mixed)
+            e.set_domain(n, *R.DOMAIN)
         route = fresh.counter("spectral_route")
+        assert (route == 4) == bool(mixed)
         a = _raw_args((n, n))
         used.residual_lossy(a["wf"], a["k_sq"], a["k_im"], a["src"])
         wf, res, st = a["wf"].clone(), a["res"].clone(), a["st"].clone()
@@ -364,15 +377,64 @@ def test_lossy_calls_leave_the_lossless_entry_points_alone(blob, n):
         torch.cuda.synchronize()
         used.check_async_errors()
         assert used.counter("spectral_route") == route
-        for i, (p, q) in enumerate(zip(_lossless(used, n), _lossless(fresh, n))):
-            assert not bool(torch.isnan(p).any())
-            if i == 4:      # the RMSE rows: one atomicAdd per block
-                assert torch.allclose(p, q, rtol=1e-5, atol=0)
-            else:
-                assert torch.equal(p, q), i
+        _same_lossless(_lossless(used, n), _lossless(fresh, n))
     finally:
         used.close()
         fresh.close()
+
+
+def test_one_line_axis_serves_the_mixed_route_and_the_lossy_operator(blob):
+    """n = 144 = 9 * 16 with spectral_mixed 1: the lossless operator and the lossy one run on ONE set of line tables (ctx->sq_axis), built by
+    hn_set_domain -- so the first lossy call may be captured -- and freed with the domain's tables, whatever the order of re-builds.  Every comparison
+    is with an engine that has done nothing else."""
+    n = 144
+    used, mixed, dense = _engine(blob=blob), _engine(blob=blob), _engine(blob=blob)
+    try:
+        for e, opt in ((used, 1), (mixed, 1), (dense, 0)):
+            e.set_option("spectral_mixed", opt)
+            e.set_domain(n, *R.DOMAIN)
+        assert used.counter("spectral_route") == mixed.counter("spectral_route") == 4 and dense.counter("spectral_route") == 3
+        want_mixed, want_dense = _lossless(mixed, n), _lossless(dense, n)
+        a = _raw_args((n, n))
+        g = a["res"]
+        want_vjp = mixed.residual_vjp(g, a["k_sq"])
+        # the first lossy call of this engine, under capture: its tables are the mixed route's, nothing is left to build
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(side):
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                rc = _residual(used, a, a["k_im"])
+            assert rc == OK, _err(used)
+            _untouched(a)
+            graph.replay()
+            torch.cuda.synchronize()
+        first = a["out"].clone()
+        assert not bool(torch.isnan(first).any())
+        assert torch.equal(used.residual_lossy(a["wf"], a["k_sq"], a["k_im"], a["src"]), first)
+        _same_lossless(_lossless(used, n), want_mixed)
+        # off the mixed route: the lossy operator re-builds the same tables at its first call, the lossless one is the dense operator
+        used.set_option("spectral_mixed", 0)
+        assert used.counter("spectral_route") == 3
+        assert torch.equal(used.residual_lossy(a["wf"], a["k_sq"], a["k_im"], a["src"]), first)
+        _same_lossless(_lossless(used, n), want_dense)
+        # ... and back, with the axis the lossy call left replaced by the domain's own
+        used.set_option("spectral_mixed", 1)
+        assert used.counter("spectral_route") == 4
+        _same_lossless(_lossless(used, n), want_mixed)
+        assert torch.equal(used.residual_vjp(g, a["k_sq"]), want_vjp)
+        # through a rectangular domain, which has axes of its own
+        used.set_domain_rect(32, 80, *R.DOMAIN)
+        assert used.counter("spectral_route") == 5
+        used.set_domain(n, *R.DOMAIN)
+        assert used.counter("spectral_route") == 4
+        _same_lossless(_lossless(used, n), want_mixed)
+        assert torch.equal(used.residual_lossy(a["wf"], a["k_sq"], a["k_im"], a["src"]), first)
+        torch.cuda.synchronize()
+        used.check_async_errors()
+    finally:
+        for e in (used, mixed, dense):
+            e.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------------ 8: Python front end

@@ -14,7 +14,7 @@ the bar is the one between two fp32 routes, 4e-6 of max.  RMSE rows rtol 1e-5.
 The depth-5 network runs at (32, 96), not at (32, 80): 80 is not a multiple of 2^5, and hn_set_domain_rect asks of each side what hn_set_domain asks
 of n (test_contract_arguments asserts that (32, 80) is refused at depth 5).
 
-Spectral lines per block (rect_lines of hn_spectral_rect.hip: 16 at most, 80 KB of line buffers at most, halved while ceil(count / lines) * batch
+Spectral lines per block (rect_lines of hn_spectral_line.hip: 16 at most, 80 KB of line buffers at most, halved while ceil(count / lines) * batch
 < 512): 1 wherever count * batch < 1024, which is every solver case here and, with its four probes, most of the operator cases; the operator cases
 with 2048 or 2032 lines run their short axis at 16 lines per block and (1040, 48) its row pass at 8.  A batch of 3 does not change the lines per
 block at (32, 80) or (144, 64), so test_a_sample_does_not_depend_on_its_batch adds the spectral pair at batch 384, where both passes take 16.

@@ -1,4 +1,4 @@
-"""The mixed spectral route (HN_OPT_SPECTRAL_MIXED 1: k_spec_mixed of hn_spectral_mixed.hip, n = P * 2^k with a runtime odd P) against the
+"""The mixed spectral route (HN_OPT_SPECTRAL_MIXED 1: k_spec_line of hn_spectral_line.hip, n = P * 2^k with a runtime odd P) against the
 float64 CPU oracle.  Needs a real MI355X.
 
 Probes, reference and bar: tests/spectral_probes.py, unchanged (1e-5 of scale(n) * max|u|), plus the two extra mode fields of
@@ -8,7 +8,7 @@ the mixed kernels (Engine.counter("spectral_route") == 4): a case that silently 
 
 Sizes: the smallest at which each thing can go wrong -- spectral_mixed_probes.GPU_SIZES says why each is there.
 
-Lines per block of launch_mixed (16 at most, 80 KB of line buffers at most, halved while ceil(n / lines) * batch < 512), by (n, batch):
+Lines per block (rect_lines of hn_spectral_line.hip: 16 at most, 80 KB of line buffers at most, halved while ceil(n / lines) * batch < 512), by (n, batch):
     (144, 1) and (144, 3) -> 1,  (144, 33) -> 8,  (144, 64) -> 16,  (576, 1) -> 1,  (576, 5) -> 4       (test_a_sample_does_not_depend_on_its_batch)
     the forward cases (four probes per call): 144, 176, 240 -> 1;  288, 400, 1152 -> 2;  576 -> 4;  one sample per call: 1040 -> 2, 2032 -> 1.
 
@@ -203,7 +203,7 @@ def test_environment_default_goes_through_the_option_validator(monkeypatch):
 # ------------------------------------------------------------------------------------------------------------------- 5: batch independence
 @pytest.mark.parametrize("n", sorted(BATCH_CASES))
 def test_a_sample_does_not_depend_on_its_batch(eng, n):
-    """Batch 1 against the batches of BATCH_CASES: every lines-per-block choice of launch_mixed (module docstring), forward and adjoint."""
+    """Batch 1 against the batches of BATCH_CASES: every lines-per-block choice of rect_lines (module docstring), forward and adjoint."""
     c, x, a = SP.forward_case(n), MP.extra_case(n), SP.adjoint_case(n)
     _set_mixed_domain(eng, n)
     assert len({MP.mixed_lines(n, 4, b) for b in (1,) + BATCH_CASES[n]}) > 1 and len({MP.mixed_lines(n, 3, b) for b in (1,) + BATCH_CASES[n]}) > 1

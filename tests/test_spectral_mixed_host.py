@@ -54,7 +54,11 @@ def test_binding_tables_carry_the_option_and_the_counter():
     assert _lib.HN_COUNTER["spectral_route"] == enums["HN_CNT_SPECTRAL_ROUTE"]
     assert list(_lib.HN_OPTION.values()).count(_lib.HN_OPTION["spectral_mixed"]) == 1
     assert "n = P * 2^k, P odd >= 9" in hdr
-    assert "hn_spectral_mixed.hip" in open(os.path.join(REPO, "helmnet_amd", "build.py")).read()
+    from helmnet_amd import build
+    assert "hn_spectral_line.hip" in build.SOURCES
+    assert "hn_spectral_mixed.hip" not in build.SOURCES and "hn_spectral_rect.hip" not in build.SOURCES
+    assert not any(h.endswith("hn_spectral_lds.inc") for h in build.HEADERS)
+    assert all(os.path.exists(h) for h in build.HEADERS) and all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
 
 
 def _ratios(n, tables=None):
@@ -105,7 +109,7 @@ def test_launch_shapes_named_by_the_gpu_test():
     assert MP.mixed_lines(1040, 4, 1) == 2
     assert [MP.mixed_lines(576, 4, b) for b in (1, 5)] == [1, 4]
     assert MP.mixed_lines(144, 4, 1000) == 16 and MP.mixed_lines(2032, 4, 1000) == 1
-    # the dynamic LDS of every mixed size stays within the attribute spec_mixed_build sets
+    # the dynamic LDS of every mixed size stays within the attribute build_axis sets
     for n in MP.legal_sizes() + SP.pfa_sizes():
         name, p, q = MP.spectral_route(n, pfa=0, mixed=1)
         if name == "mixed":

@@ -4,7 +4,7 @@ square domain, in this process, alternating.
     python tools/bench_lossy.py [--regions 7] [--rounds 2] [--cases 256x32,512x16,400x16] [--out profiles/lossy_bench.txt]
 
 Per case n x batch one context with the shipped weights.  The lossless calls run on the domain's own spectral route (256, 512: the register-resident
-kernels; 400 = 25 * 16: the dense operator), the lossy ones on the general LDS-line kernel of hn_spectral_rect.hip with the complex pointwise term.
+kernels; 400 = 25 * 16: the dense operator), the lossy ones on the general LDS-line kernel of hn_spectral_line.hip with the complex pointwise term.
 5 warm-up calls, then --regions timed regions (device events on the caller's stream around enough back-to-back calls to fill ~30 ms); the two calls
 take turns --rounds times and the figure is the median over all regions, in ms per call (residual) or per iteration (step, 4 iterations per call,
 fp32).  Beside it the median shader clock (the board's hwmon readings while that call's regions ran).

@@ -1,5 +1,5 @@
 """Time of the spectral residual at domain sizes n = P * 2^k with an odd P >= 9: the dense n x n operator (spectral_mixed 0: k_spec_dense) next
-to the mixed FFT kernels (spectral_mixed 1: k_spec_mixed, hn_spectral_mixed.hip), both in this process on the same inputs.
+to the mixed FFT kernels (spectral_mixed 1: k_spec_line, hn_spectral_line.hip), both in this process on the same inputs.
 
     python tools/bench_spectral_sizes.py [--regions 7] [--rounds 2] [--sizes 144x32,...] [--step-sizes 400x16,1040x2] [--out profiles/spectral_mixed_bench.txt]
 
