@@ -353,3 +353,37 @@ class SolveImplicit(torch.autograd.Function):
         ctx.adjoint_info.update({"cycles": adj["cycles"], "rmse": adj["residual_norm"], "converged": adj["converged"], "iterations": adj["iterations"],
                              "unet_evaluations": adj["unet_evaluations"]})
         return None, g_sos, g_src
+
+
+class SolveImplicitLossy(torch.autograd.Function):
+    """``SolveImplicit`` for an absorbing medium: (sos, alpha, src) -> the converged wavefield of A u = L(u) + (k_sq + i k_sq_im) u = src, the two
+    planes from ``absorption.complex_k_sq``.  backward solves A^H lam = g on the lossy adjoint (gmres_adjoint with ``absorption``), forms dJ/dk_sq,
+    dJ/dk_sq_im and dJ/dsrc in one launch (hn_adjoint_grad_lossy) and applies ``absorption.complex_k_sq_grads``; the gradient of ``alpha`` is summed
+    over the dimensions it was broadcast along."""
+
+    @staticmethod
+    def forward(ctx, spec, sos, alpha, src):
+        ctx.spec, ctx.src_batch, ctx.adjoint_info = spec, src.shape[0], spec["info"]
+        ctx.save_for_backward(sos.detach(), alpha.detach())
+        return spec["wavefield"].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        _no_double_backward()
+        from .absorption import complex_k_sq_grads
+        from .gmres import gmres_adjoint
+        spec = ctx.spec
+        sos, alpha = ctx.saved_tensors
+        solver, u = spec["solver"], spec["wavefield"]
+        with torch.no_grad():
+            adj = gmres_adjoint(solver, sos, g.detach().float().contiguous(), absorption=alpha, **spec["adjoint_kwargs"])
+            lam = adj["wavefield"]
+            g_k_sq, g_k_sq_im, g_src = solver.engine().adjoint_grad_lossy(lam, u, ctx.src_batch if ctx.needs_input_grad[3] else None)
+            g_sos = g_alpha = None
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                g_sos, g_alpha = complex_k_sq_grads(g_k_sq, g_k_sq_im, sos, alpha, float(solver.hparams.omega))
+                g_sos = g_sos if ctx.needs_input_grad[1] else None
+                g_alpha = (g_alpha.sum_to_size(alpha.shape) if alpha.dim() else g_alpha.sum()) if ctx.needs_input_grad[2] else None
+        ctx.adjoint_info.update({"cycles": adj["cycles"], "rmse": adj["residual_norm"], "converged": adj["converged"], "iterations": adj["iterations"],
+                                 "unet_evaluations": adj["unet_evaluations"]})
+        return None, g_sos, g_alpha, g_src

@@ -754,6 +754,22 @@ int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, 
     return spec_adjoint(ctx, g, out, k_sq, nullptr, batch, (hipStream_t)stream);
 }
 
+int hn_residual_vjp_lossy(hn_ctx* ctx, const float* g, const float* k_sq, const float* k_sq_im, float* out, int batch, void* stream) {
+    const char* who = "hn_residual_vjp_lossy";
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_residual_vjp)", who);
+    if (!ctx || !g || !k_sq || !out) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
+    if (g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);
+    {
+        const size_t plane = (size_t)ctx->geo.plane();
+        const MemRange r[] = {{k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}, {out, sizeof(float) * (size_t)batch * 2 * plane, true, "out"}};
+        const char *a, *b;
+        if (first_overlap(r, 2, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
+    }
+    DeviceGuard guard(ctx);
+    return spec_adjoint_lossy(ctx, who, g, out, k_sq, k_sq_im, nullptr, batch, (hipStream_t)stream);
+}
+
 int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream) {
     if (!ctx || !res || !rmse) return fail(ctx, HN_ERR_ARG, "hn_rmse: NULL argument");
     if (ctx->geo.h == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");

@@ -561,6 +561,9 @@ int spec_line_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq,
 int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s);
 int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
                      int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
+// out = A^H g [+ add] = L^H(g) + (ksq - i ksq_im) g [+ add], the adjoint of the operator above on the same kernel and tables (g != out; `add` may alias out)
+int spec_adjoint_lossy(hn_ctx* ctx, const char* who, const float* g, float* out, const float* ksq, const float* ksq_im, const float* add, int batch,
+                       hipStream_t s);
 // HN_ERR_UNSUPPORTED "<who>: not implemented on a rectangular domain ..." (every entry point that reads the domain and has no rectangular path)
 int rect_unsupported(hn_ctx* ctx, const char* who);
 // ---- float64 residual check (hn_f64.hip) ----

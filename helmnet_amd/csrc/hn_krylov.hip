@@ -461,8 +461,11 @@ __global__ __launch_bounds__(256) void k_take_adj(const float* __restrict__ wf, 
 }
 
 // g_k_sq[b] = -(l_re u_re + l_im u_im); g_src (nullable): lambda per sample (per == 1), or its sum over the `per` samples of the batch in sample order
+// GIm: empty (hn_adjoint_grad), or one float* (hn_adjoint_grad_lossy): g_k_sq_im[b] = l_re u_im - l_im u_re from the same loads; the pack stands last, so
+// the lossless kernel keeps its arguments, and the other two outputs their expressions and bits
+template <typename... GIm>
 __global__ __launch_bounds__(256) void k_adjoint_grad(const float* __restrict__ lam, const float* __restrict__ u, float* __restrict__ g_ksq,
-                                                      float* __restrict__ g_src, long P, int per) {
+                                                      float* __restrict__ g_src, long P, int per, GIm... g_ksq_im) {
     const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
     if (off >= P) return;
     float4 ar = make_float4(0.f, 0.f, 0.f, 0.f), ai = ar;
@@ -473,6 +476,11 @@ __global__ __launch_bounds__(256) void k_adjoint_grad(const float* __restrict__ 
         const float4 ur = *reinterpret_cast<const float4*>(u + at), ui = *reinterpret_cast<const float4*>(u + at + P);
         *reinterpret_cast<float4*>(g_ksq + (long)b * P + off) =
             zero_minus4(make_float4(lr.x * ur.x + li.x * ui.x, lr.y * ur.y + li.y * ui.y, lr.z * ur.z + li.z * ui.z, lr.w * ur.w + li.w * ui.w));
+        if constexpr (sizeof...(GIm) != 0) {
+            float* const gim[] = {g_ksq_im...};
+            *reinterpret_cast<float4*>(gim[0] + (long)b * P + off) =
+                make_float4(lr.x * ui.x - li.x * ur.x, lr.y * ui.y - li.y * ur.y, lr.z * ui.z - li.z * ur.z, lr.w * ui.w - li.w * ur.w);
+        }
         if (i == 0) { ar = lr; ai = li; }
         else { ar.x += lr.x; ar.y += lr.y; ar.z += lr.z; ar.w += lr.w; ai.x += li.x; ai.y += li.y; ai.z += li.z; ai.w += li.w; }
     }
@@ -491,7 +499,8 @@ struct Precond {
     int iters = 0;             // hn_step iterations per inner step; 0: z = v
     float alpha = 1.f;         // the learned solve sees alpha v
     const char* who = "";      // the entry point, for what hn_step reports from inside the cycle
-    const float* k_sq_im = nullptr;   // non-null (hn_fgmres_cycle_lossy): A is the lossy operator and the learned iteration hn_step_lossy, also with iters 0
+    const float* k_sq_im = nullptr;   // non-null (hn_fgmres_cycle_lossy, hn_fgmres_adjoint_cycle_lossy): A is the lossy operator (Op::Adjoint: its A^H)
+                                      // and the learned iteration hn_step_lossy, also with iters 0
 };
 
 // what hn_step reported, under the name of the entry point that called it
@@ -621,9 +630,12 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
     SmallArgs a{ws.part, ws.npart, ws.scale, ws.g, ws.cs, ws.R, ws.y, ws.stopped, hess, rmse, k_used, batch, restart, nchunk,
                 tol, 1.0 / sqrt(2.0 * (double)P), tol_dev, pre_stopped};
     const bool adj = op == Op::Adjoint;
-    const float* k_im = pc.k_sq_im;   // (Op::Forward only)
+    const float* k_im = pc.k_sq_im;
     // w = A x - rhs = -r
-    if (k_im != nullptr) {
+    if (k_im != nullptr && adj) {
+        if ((rc = spec_adjoint_lossy(ctx, pc.who, x, ws.w, k_sq, k_im, nullptr, batch, s)) != HN_OK) return rc;
+        hipLaunchKernelGGL(k_minus_rhs, grid, blk, 0, s, ws.w, rhs, rhs_batch == 1 ? 0L : 2 * P, ws.npart, P, nchunk);
+    } else if (k_im != nullptr) {
         if ((rc = spec_apply_lossy(ctx, pc.who, x, ws.w, k_sq, k_im, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
         hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
     } else if (adj) {
@@ -649,9 +661,10 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
         } else if (pc.zbasis != nullptr) {
             hipLaunchKernelGGL(k_take_copy, grid, blk, 0, s, ws.vin, pc.zbasis, P, k, restart);
         }
-        rc = k_im != nullptr ? spec_apply_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, ws.zero, 1, batch, nullptr, s)
-             : adj           ? spec_adjoint(ctx, ws.vin, ws.w, k_sq, nullptr, batch, s)
-                             : spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s);
+        rc = k_im != nullptr && adj ? spec_adjoint_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, nullptr, batch, s)
+             : k_im != nullptr      ? spec_apply_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, ws.zero, 1, batch, nullptr, s)
+             : adj                  ? spec_adjoint(ctx, ws.vin, ws.w, k_sq, nullptr, batch, s)
+                                    : spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s);
         if (rc != HN_OK) return rc;
         hipLaunchKernelGGL(k_dots, grid, blk, 0, s, ws.w, basis, ws.part, P, k, restart, nchunk);
         hipLaunchKernelGGL(k_sub<0>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
@@ -801,6 +814,22 @@ int check_precond(hn_ctx* ctx, const char* who, int precond_iters, float precond
     return precond_prepare(ctx, who, k_sq, k_sq_im, batch, s);
 }
 
+// k_sq_im of the two lossy cycles by k_sq's rules, after check_cycle_args: 16-byte aligned, overlapping none of the other arguments
+int check_cycle_k_sq_im(hn_ctx* ctx, const char* who, const float* k_sq_im, const float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch,
+                        int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used) {
+    const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
+    if (reinterpret_cast<uintptr_t>(k_sq_im) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is not 16-byte aligned", who);
+    const MemRange others[] = {{x, B * 2 * P * 4, true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
+                               {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
+                               {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"}};
+    for (const MemRange& o : others) {
+        const MemRange pair[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, o};
+        const char *na, *nb;
+        if (first_overlap(pair, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    }
+    return HN_OK;
+}
+
 // hn_gmres_cycle and hn_fgmres_cycle, the arguments checked
 int run_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol, const Precond& pc, float* basis,
               float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
@@ -876,18 +905,7 @@ extern "C" int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, c
     if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_fgmres_cycle)", who);
     int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
     if (rc != HN_OK) return rc;
-    {   // k_sq_im by k_sq's rules: 16-byte aligned, overlapping none of the other arguments
-        const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
-        if (reinterpret_cast<uintptr_t>(k_sq_im) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is not 16-byte aligned", who);
-        const MemRange others[] = {{x, B * 2 * P * 4, true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
-                                   {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
-                                   {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"}};
-        for (const MemRange& o : others) {
-            const MemRange pair[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, o};
-            const char *na, *nb;
-            if (first_overlap(pair, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
-        }
-    }
+    if ((rc = check_cycle_k_sq_im(ctx, who, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK) return rc;
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im)) != HN_OK) return rc;
@@ -895,6 +913,24 @@ extern "C" int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, c
     Precond pc{zbasis, precond_iters, precond_scale, who};
     pc.k_sq_im = k_sq_im;
     return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
+}
+
+extern "C" int hn_fgmres_adjoint_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch,
+                                             int restart, float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
+                                             float* rmse, int32_t* k_used, void* stream) {
+    const char* who = "hn_fgmres_adjoint_cycle_lossy";
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_fgmres_adjoint_cycle)", who);
+    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
+    if (rc != HN_OK) return rc;
+    if ((rc = check_cycle_k_sq_im(ctx, who, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK) return rc;
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im)) != HN_OK) return rc;
+    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;
+    if (precond_iters > 0 && (rc = adjoint_w_prepare(ctx, who)) != HN_OK) return rc;
+    Precond pc{zbasis, precond_iters, precond_scale, who};
+    pc.k_sq_im = k_sq_im;
+    return run_cycle(ctx, Op::Adjoint, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
 }
 
 extern "C" int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
@@ -911,26 +947,40 @@ extern "C" int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq,
                      k_used, s);
 }
 
-extern "C" int hn_adjoint_grad(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_src, void* stream) {
-    const char* who = "hn_adjoint_grad";
-    if (!ctx || !lambda || !u || !g_k_sq) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+// hn_adjoint_grad (g_k_sq_im nullptr, lossy false) and hn_adjoint_grad_lossy
+static int adjoint_grad_entry(hn_ctx* ctx, const char* who, bool lossy, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq,
+                              float* g_k_sq_im, float* g_src, void* stream) {
+    if (!ctx || !lambda || !u || !g_k_sq || (lossy && !g_k_sq_im)) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (ctx->rect) return rect_unsupported(ctx, who);
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain has not been called", who);
     if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
     if (src_batch != 1 && src_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: src batch %d must be 1 or equal to the batch %d", who, src_batch, batch);
     const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
     const MemRange r[] = {{lambda, B * 2 * P * 4, false, "lambda"}, {u, B * 2 * P * 4, false, "u"}, {g_k_sq, B * P * 4, true, "g_k_sq"},
-                          {g_src, (size_t)src_batch * 2 * P * 4, true, "g_src"}};
-    for (int i = 0; i < 4; ++i)   // read and written as float4; a NULL g_src is aligned
+                          {g_src, (size_t)src_batch * 2 * P * 4, true, "g_src"}, {g_k_sq_im, B * P * 4, true, "g_k_sq_im"}};
+    const int nr = lossy ? 5 : 4;
+    for (int i = 0; i < nr; ++i)   // read and written as float4; a NULL g_src is aligned
         if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
     const char *na, *nb;
-    if (first_overlap(r, 4, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    if (first_overlap(r, nr, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     DeviceGuard guard(ctx);
     const int per = (g_src != nullptr && src_batch == 1) ? batch : 1;
-    hipLaunchKernelGGL(k_adjoint_grad, dim3((unsigned)((P + kKryChunk - 1) / kKryChunk), batch / per), dim3(256), 0, (hipStream_t)stream, lambda, u, g_k_sq,
-                       g_src, (long)P, per);
+    const dim3 grid((unsigned)((P + kKryChunk - 1) / kKryChunk), batch / per);
+    if (lossy)
+        hipLaunchKernelGGL((k_adjoint_grad<float*>), grid, dim3(256), 0, (hipStream_t)stream, lambda, u, g_k_sq, g_src, (long)P, per, g_k_sq_im);
+    else
+        hipLaunchKernelGGL((k_adjoint_grad<>), grid, dim3(256), 0, (hipStream_t)stream, lambda, u, g_k_sq, g_src, (long)P, per);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
+}
+
+extern "C" int hn_adjoint_grad(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_src, void* stream) {
+    return adjoint_grad_entry(ctx, "hn_adjoint_grad", false, lambda, u, src_batch, batch, g_k_sq, nullptr, g_src, stream);
+}
+
+extern "C" int hn_adjoint_grad_lossy(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_k_sq_im,
+                                     float* g_src, void* stream) {
+    return adjoint_grad_entry(ctx, "hn_adjoint_grad_lossy", true, lambda, u, src_batch, batch, g_k_sq, g_k_sq_im, g_src, stream);
 }
 
 extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,

@@ -2,8 +2,8 @@
 // k_spec_line, serves three routes:
 //   the mixed route of a square domain (HN_OPT_SPECTRAL_MIXED): the sizes 144, 240, 400, 576, 1040, ... that neither the power-of-two kernels nor
 //       k_spec_pfa<Q, P> (P = 3, 5, 7 held in registers) of hn_spectral.hip take, and that otherwise run the dense n x n operator; forward and adjoint
-//   a rectangular h x w domain (hn_set_domain_rect, h != w): each axis factored on its own, with its own tables; forward only
-//   the lossy operator (complex k_sq) on either kind of domain; forward only
+//   a rectangular h x w domain (hn_set_domain_rect, h != w): each axis factored on its own, with its own tables; the lossless operator forward only
+//   the lossy operator (complex k_sq) on either kind of domain; forward and adjoint
 // Line length, line count and row pitch are three arguments:
 //   column pass   lines of length h, w of them, element stride w:   out  = ay d/dy + by d2/dy2
 //   row pass      lines of length w, h of them:                      out += ax d/dx + bx d2/dx2 [+ k_sq u - src], per-sample sum of squares
@@ -18,8 +18,9 @@
 //   4  inverse P-point DFT: buffers 0 and 3 (adjoint: buffer 0)
 //   5  inverse Q-point transforms in place: decimation in time from bit-reversed input, the mirror image of 2
 //   6  PML coefficients at the natural index (forward), the row pass's residual terms and sum of squares, store the way the line was loaded
-// P = 1 (a power of two; forward only) has no P-point DFT: the derivative multipliers are applied where the forward transforms left the spectrum and the
-// inverse transforms run on those two buffers, so such a line needs three buffers instead of four, as the adjoint does.  The longest line, 2048 points in
+// P = 1 (a power of two) has no P-point DFT: the derivative multipliers are applied where the forward transforms left the spectrum and the
+// inverse transforms run on those two buffers, so such a line needs three buffers instead of four, as the adjoint does.  (The adjoint of such a line
+// combines its two spectra in place in buffer 0 and runs the one inverse transform there; it is sized like every adjoint pass, as three.)  The longest line, 2048 points in
 // three buffers plus its twiddles, takes 64 KB; the longest four-buffer line, 2032 = 127 * 16, 63.6 KB + 1.1 KB: both inside the 96 KB attribute.
 // The P-point DFT uses W_P^(s (P - k)) = conj(W_P^(s k)): one work item computes A = sum x cos and B = sum x (-+sin) once and emits outputs k and P - k
 // (A +- i B): half the multiply-adds and half the LDS reads of the plain double loop.  Each sum runs in two interleaved partial
@@ -153,16 +154,16 @@ struct LineTabs {
 //   AXIS 0: along x (row pass: line `r` is row r; adds the column part with flags & 1, the residual terms with flags & 2, the sum of squares)
 //   AXIS 1: along y (column pass: line `c` is column c; the block's L adjacent columns are loaded and stored as row segments of L floats)
 // Dynamic LDS: (ADJ || P == 1 ? 3 : 4) buffers of L * len float2, then the Q and P twiddles.
-// ADJ: the adjoint operator (P > 1 only: the launcher refuses the rest); `add` (nullable, may alias `out`) is added by its column pass and read by nothing else.
-// KsqIm: empty (the lossless kernels), or one const float*: the forward row pass of hn_residual_lossy / hn_step_lossy / hn_fgmres_cycle_lossy, whose
-// pointwise term is complex, (ksq + i ksq_im) u.  The pack stands in front of `add` (legal: every use names the template arguments) so that the forward
+// ADJ: the adjoint operator; `add` (nullable, may alias `out`) is added by its column pass and read by nothing else.
+// KsqIm: empty (the lossless kernels), or one const float*: the row pass of the lossy operator, whose pointwise term is complex -- (ksq + i ksq_im) u
+// forward (hn_residual_lossy / hn_step_lossy / hn_fgmres_cycle_lossy), conj(ksq + i ksq_im) g with ADJ (hn_residual_vjp_lossy /
+// hn_fgmres_adjoint_cycle_lossy).  The pack stands in front of `add` (legal: every use names the template arguments) so that the forward
 // kernels' arguments keep the offsets they had before `add` existed.
 template <int AXIS, bool ADJ, typename... KsqIm>
 __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restrict__ wf, float* out, const float* __restrict__ ksq,
                                                             const float* __restrict__ src, long src_sb, LineTabs t, int len, int count, int pitch, int P,
                                                             int logq, int logl, int flags, float* __restrict__ sumsq,
                                                             const int* __restrict__ it_counter, int sumsq_stride, KsqIm... ksq_im, const float* add) {
-    static_assert(!ADJ || sizeof...(KsqIm) == 0, "the lossy operator has no adjoint kernel");
     constexpr int NF = ADJ ? 2 : 1;       // buffers through the forward transforms
     extern __shared__ float2 lbuf[];
     __shared__ float red[kLineThreads / 64];
@@ -204,14 +205,21 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
     // the buffers the inverse transforms run on and the results are read from: first- and second-derivative spectrum (adjoint: D1 alone, their sum)
     float2* const D1 = !ADJ && P == 1 ? B1 : B0;
     float2* const D2 = !ADJ && P == 1 ? B2 : B3;
-    if (!ADJ && P == 1) {
+    if (P == 1) {
         // ---- 3 (P = 1): derivative multipliers in place of the P-point DFT pair
         for (int e = tid; e < ln; e += kLineThreads) {
             const int r = e & (Q - 1);
             const float kk1 = t.k1m[r], kk2 = t.k2m[r];
             const float2 Y = B0[e];
-            B1[e] = make_float2(-Y.y * kk1, Y.x * kk1);   // (0, k) * U     (spectral.py:50, 281)
-            B2[e] = make_float2(kk2 * Y.x, kk2 * Y.y);    // (-k^2, 0) * U  (spectral.py:52, 283)
+            if constexpr (!ADJ) {
+                B1[e] = make_float2(-Y.y * kk1, Y.x * kk1);   // (0, k) * U     (spectral.py:50, 281)
+                B2[e] = make_float2(kk2 * Y.x, kk2 * Y.y);    // (-k^2, 0) * U  (spectral.py:52, 283)
+            } else {                                          // (-i k) Z1 + (-k^2) Z2, in place: the element is this thread's alone.  Buffer 2 stays
+                                                              // unused here: the launcher sizes every adjoint pass as three buffers, which at
+                                                              // len = 256 gives a block 8 lines where two buffers would allow 16 (rect_lines)
+                const float2 Y2 = B1[e];
+                B0[e] = make_float2(kk1 * Y.y + kk2 * Y2.x, -kk1 * Y.x + kk2 * Y2.y);
+            }
         }
         __syncthreads();
     } else {
@@ -287,8 +295,13 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
                     const float* const kim[] = {ksq_im...};
                     const float ki = kim[0][(long)b * plane + o];
                     const float ur = pre[o], ui = pre[o + plane];
-                    re = re + (kq * ur - ki * ui);
-                    im = im + (kq * ui + ki * ur);
+                    if constexpr (!ADJ) {
+                        re = re + (kq * ur - ki * ui);
+                        im = im + (kq * ui + ki * ur);
+                    } else {                        // conj(ksq + i ksq_im) g: `pre` is the cotangent
+                        re = re + (kq * ur + ki * ui);
+                        im = im + (kq * ui - ki * ur);
+                    }
                 } else {
                     re = re + kq * pre[o];          // the line itself again (an L2 hit) instead of a copy held through the transforms
                     im = im + kq * pre[o + plane];
@@ -342,7 +355,7 @@ int rect_lines(int len, int count, int nbuf, int batch) {
 int line_kernels_lds_attr(hn_ctx* ctx) {
     for (const void* k : {reinterpret_cast<const void*>(k_spec_line<1, false>), reinterpret_cast<const void*>(k_spec_line<0, false>),
                           reinterpret_cast<const void*>(k_spec_line<0, false, const float*>), reinterpret_cast<const void*>(k_spec_line<1, true>),
-                          reinterpret_cast<const void*>(k_spec_line<0, true>)})
+                          reinterpret_cast<const void*>(k_spec_line<0, true>), reinterpret_cast<const void*>(k_spec_line<0, true, const float*>)})
         HN_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLineLdsAttr));
     return HN_OK;
 }
@@ -402,13 +415,14 @@ bool line_domain(const hn_ctx* ctx, LineDomain* d) {
 
 // Both passes on `s`: the counter's bump, the column pass, the row pass.
 //   forward           ksq nullptr: the Laplacian alone; ksq_im non-null (ksq too): the row pass with the complex pointwise term
-//   adj               out = L^H(wf) + ksq wf [+ add]: three buffers, `add` on the column pass, no sum of squares (P > 1 on both axes)
+//   adj               out = L^H(wf) + ksq wf [+ add]: three buffers, `add` on the column pass, no sum of squares; ksq_im non-null: the row pass with the
+//                     conjugate pointwise term, conj(ksq + i ksq_im) wf
 int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
                 int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride, bool adj = false, const float* add = nullptr) {
     const LineAxis &cols = *d.cols, &rows = *d.rows;
     const int h = d.h, w = d.w;
-    if (adj && (cols.P == 1 || rows.P == 1 || ksq == nullptr || ksq_im != nullptr || sumsq != nullptr))
-        return fail(ctx, HN_ERR_ARG, "internal: no adjoint LDS-line kernel for %d x %d (P = %d, %d) or for these arguments", h, w, cols.P, rows.P);
+    if (adj && (ksq == nullptr || src != nullptr || sumsq != nullptr || it_counter != nullptr))
+        return fail(ctx, HN_ERR_ARG, "internal: the adjoint LDS-line kernels (%d x %d) take k_sq and neither a source, a sum of squares nor a counter", h, w);
     const bool resid = ksq != nullptr;
     const long src_sb = src_batch == 1 ? 0 : 2L * h * w;
     const int nbuf_c = adj || cols.P == 1 ? 3 : 4, nbuf_r = adj || rows.P == 1 ? 3 : 4;
@@ -434,7 +448,10 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
     }
     {
         ProfScope ps(ctx, KID_SPEC_ROWS, s);
-        if (adj)
+        if (adj && ksq_im != nullptr)
+            hipLaunchKernelGGL((k_spec_line<0, true, const float*>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P, logq_r, logl_r,
+                               rflags, sumsq, it_counter, sumsq_stride, ksq_im, nullptr);
+        else if (adj)
             hipLaunchKernelGGL((k_spec_line<0, true>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P, logq_r, logl_r, rflags, sumsq,
                                it_counter, sumsq_stride, nullptr);
         else if (ksq_im != nullptr)
@@ -556,6 +573,18 @@ int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, 
     LineDomain d;
     if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
     return rect_launch(ctx, d, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
+}
+
+// out = A^H g = L^H(g) + (ksq - i ksq_im) g [+ add] on either kind of domain: the adjoint of the operator above, on the same tables
+int spec_adjoint_lossy(hn_ctx* ctx, const char* who, const float* g, float* out, const float* ksq, const float* ksq_im, const float* add, int batch,
+                       hipStream_t s) {
+    if (ksq == nullptr || ksq_im == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
+    if (g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);
+    if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
+    if (batch <= 0) return HN_OK;
+    LineDomain d;
+    if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
+    return rect_launch(ctx, d, g, out, ksq, ksq_im, nullptr, 1, batch, nullptr, s, nullptr, 0, true, add);
 }
 
 int rect_unsupported(hn_ctx* ctx, const char* who) {

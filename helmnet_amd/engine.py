@@ -563,6 +563,49 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_fgmres_cycle_lossy")
         return rmse, k_used
 
+    def residual_vjp_lossy(self, g: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor) -> torch.Tensor:
+        """A^H g of the lossy operator (hn_residual_vjp_lossy): L^H(g) + (k_sq - i k_sq_im) g, the J^T g of ``residual_lossy`` with respect to the
+        wavefield.  Square and rectangular domains."""
+        b = g.shape[0]
+        self._chk(g, (b, 2, *self.hw), "cotangent")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
+        out = torch.empty_like(g)
+        rc = self.lib.hn_residual_vjp_lossy(self.ctx, _ptr(g), _ptr(k_sq), _ptr(k_sq_im), _ptr(out), b, self._stream())
+        _lib.check(rc, self.ctx, "hn_residual_vjp_lossy")
+        return out
+
+    def fgmres_adjoint_cycle_lossy(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
+                                   precond_iters: int, precond_scale: float, basis: Optional[torch.Tensor] = None,
+                                   zbasis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
+        """``fgmres_adjoint_cycle`` on the lossy system A^H x = rhs (hn_fgmres_adjoint_cycle_lossy), A^H the operator of ``residual_vjp_lossy``,
+        preconditioned by ``precond_iters`` iterations of ``step_lossy`` between the similarity weight.  Square domains.  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_adjoint_cycle_lossy", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        if isinstance(k_sq_im, torch.Tensor) and k_sq_im.requires_grad:
+            raise RuntimeError("fgmres_adjoint_cycle_lossy: k_sq_im requires grad; the GMRES cycle is not differentiable")
+        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
+        zbasis = self._zbasis(b, restart, zbasis)
+        rc = self.lib.hn_fgmres_adjoint_cycle_lossy(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rhs), rhs.shape[0], b, restart, float(tol),
+                                                    int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse),
+                                                    _ptr(k_used), self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_adjoint_cycle_lossy")
+        return rmse, k_used
+
+    def adjoint_grad_lossy(self, lam: torch.Tensor, u: torch.Tensor, src_batch: Optional[int]):
+        """``adjoint_grad`` for the lossy operator (hn_adjoint_grad_lossy): returns (g_k_sq, g_k_sq_im, g_src) with
+        g_k_sq_im [B,1,n,n] = lam_re u_im - lam_im u_re; the other two as ``adjoint_grad`` returns them, bit for bit."""
+        b = lam.shape[0]
+        self._chk(lam, (b, 2, *self.hw), "lam")
+        self._chk(u, (b, 2, *self.hw), "u")
+        g_k_sq = torch.empty(b, 1, *self.hw, device=self.device, dtype=torch.float32)
+        g_k_sq_im = torch.empty_like(g_k_sq)
+        g_src = None if src_batch is None else torch.empty(int(src_batch), 2, *self.hw, device=self.device, dtype=torch.float32)
+        rc = self.lib.hn_adjoint_grad_lossy(self.ctx, _ptr(lam), _ptr(u), 1 if src_batch is None else int(src_batch), b, _ptr(g_k_sq), _ptr(g_k_sq_im),
+                                            _ptr(g_src), self._stream())
+        _lib.check(rc, self.ctx, "hn_adjoint_grad_lossy")
+        return g_k_sq, g_k_sq_im, g_src
+
     # ---- training step (hn_train_grad / hn_adam_step; SURVEY.md 8 f4) -------------------------------------------------
     def train_reserve(self, batch: int, n_unroll: int):
         _lib.check(self.lib.hn_train_reserve(self.ctx, int(batch), int(n_unroll)), self.ctx, "hn_train_reserve")

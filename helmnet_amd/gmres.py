@@ -220,7 +220,7 @@ def check_adjoint_rhs(solver, sos_maps, rhs):
 
 def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
                   x0: Optional[torch.Tensor] = None, precondition: Optional[str] = None, precond_iterations: int = 10,
-                  precond_scale: Optional[float] = None, backend: str = "hip"):
+                  precond_scale: Optional[float] = None, backend: str = "hip", absorption=None):
     """Solve the ADJOINT system A^H lam = rhs for every map of ``sos_maps`` [B,1,n,n]: A u = L(u) + k_sq * u is the operator of ``gmres``, A^H its
     conjugate transpose (``hn_residual_vjp``), ``rhs`` [B or 1,2,n,n] a cotangent dJ/du as two real planes.  Restarted GMRES with the cycle fused
     on the device (hn_fgmres_adjoint_cycle), on the host loop of ``gmres(backend="hip")`` (``drive_cycles``): one synchronisation per cycle, every
@@ -230,7 +230,14 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
     z_k = conj(W * M(conj(v_k) / W)), M = ``precond_iterations`` iterations of the network from rest on a right-hand side scaled by
     ``precond_scale`` (None: ``default_precond_scale(solver.source)``, the magnitude the network was trained on, as for the forward system).
     Returns the keys of ``gmres(backend="hip")`` -- ``wavefield`` is the adjoint state lam -- plus ``cycles``.  No gradients; there is no other
-    backend."""
+    backend.
+
+    ``absorption`` (alpha, as in ``gmres``): the medium is lossy, A u = L(u) + (k_sq + i k_sq_im) u with both planes from
+    ``helmnet_amd.absorption.complex_k_sq``, and A^H g = L^H(g) + (k_sq - i k_sq_im) g.  The cycles run on hn_fgmres_adjoint_cycle_lossy (the learned
+    preconditioner is the lossy iteration between the same W) and the true-residual check on hn_residual_vjp_lossy.  None: the code path and the bits
+    of before."""
+    if absorption is not None and backend != "hip":
+        raise ValueError("absorption needs backend='hip' (gmres_adjoint has no other backend)")
     if precondition not in (None, "learned"):
         raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
     if precondition is not None and backend != "hip":
@@ -241,7 +248,7 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
         raise ValueError(f"precond_iterations must be >= 0 (got {precond_iterations})")
     solver._require_square("gmres_adjoint")
     check_adjoint_rhs(solver, sos_maps, rhs)
-    _require_no_grad("gmres_adjoint", sos_maps, rhs, x0)
+    _require_no_grad("gmres_adjoint", sos_maps, rhs, x0, absorption)
     restart, max_outer, tol = int(restart), int(max_outer), float(tol)
     iters = 0 if precondition is None else int(precond_iterations)
     alpha = 1.0
@@ -249,7 +256,14 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
         alpha = default_precond_scale(solver.source) if precond_scale is None else float(precond_scale)
     eng = solver.engine()
     sos_maps = sos_maps.to(eng.device).float().contiguous()
-    k_sq = solver.get_initials(sos_maps)[0].contiguous()
+    lossy = absorption is not None
+    if lossy:
+        from .absorption import complex_k_sq
+        if isinstance(absorption, torch.Tensor):
+            absorption = absorption.detach().to(eng.device, torch.float32)
+        k_sq, k_sq_im = complex_k_sq(sos_maps, absorption, solver.hparams.omega)
+    else:
+        k_sq = solver.get_initials(sos_maps)[0].contiguous()
     rhs = rhs.detach().to(eng.device).float().contiguous()
     bsz, n, dev = sos_maps.shape[0], sos_maps.shape[-1], eng.device
     x = (torch.zeros(bsz, 2, n, n, device=dev) if x0 is None else x0.detach().to(dev, torch.float32)).contiguous().clone()
@@ -258,17 +272,23 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
     hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
 
     def cycle():
-        rmse, k_used = eng.fgmres_adjoint_cycle(x, k_sq, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
+        if lossy:
+            rmse, k_used = eng.fgmres_adjoint_cycle_lossy(x, k_sq, k_sq_im, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
+        else:
+            rmse, k_used = eng.fgmres_adjoint_cycle(x, k_sq, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
         both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
 
+    def true_residual():
+        return eng.rmse(rhs - (eng.residual_vjp_lossy(x, k_sq, k_sq_im) if lossy else eng.residual_vjp(x, k_sq)))
+
     def true_rmse():
-        return eng.rmse(rhs - eng.residual_vjp(x, k_sq)).cpu().numpy()
+        return true_residual().cpu().numpy()
 
     out = drive_cycles(cycle, true_rmse, max_outer, tol)
     # converged: the last history row IS the true residual of the returned iterate; else its last update is still unchecked
-    final = torch.from_numpy(out["history"][-1]).to(dev) if out["converged"] else eng.rmse(rhs - eng.residual_vjp(x, k_sq))
+    final = torch.from_numpy(out["history"][-1]).to(dev) if out["converged"] else true_residual()
     return {"wavefield": x, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
             "operator_applications": out["cycles"] * (restart + 1) + out["true_checks"] + (0 if out["converged"] else 1), "converged": out["converged"],
             "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"],

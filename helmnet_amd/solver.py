@@ -435,8 +435,9 @@ class IterativeSolver(nn.Module):
         return self.engine().laplacian(x.float().contiguous())
 
     def _refuse_lossy_grad(self, what: str, *tensors):
-        """Absorbing media have no differentiable path (no entry point of the library differentiates the lossy operator): an input that requires
-        grad -- or differentiable(True) under grad mode -- raises before anything touches the device."""
+        """Absorbing media have one differentiable path, the adjoint-state gradients of ``solve_implicit`` (which detaches before it comes here);
+        the library has no derivative of the lossy solver LOOP: an input that requires grad -- or differentiable(True) under grad mode -- raises
+        before anything touches the device."""
         if any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors) or (self._differentiable and torch.is_grad_enabled()):
             raise RuntimeError(f"{what} with absorption runs without gradients (the library has no derivative of the lossy operator): pass detached "
                                "tensors, or run under torch.no_grad() after differentiable(True)")
@@ -818,13 +819,14 @@ class IterativeSolver(nn.Module):
         """Solve the adjoint system A^H lam = ``cotangent`` [B or 1,2,n,n] (dJ/du as two real planes) on the maps ``sos`` [B,1,n,n]: restarted GMRES on
         the conjugate transpose of ``gmres``'s operator (``helmnet_amd.gmres.gmres_adjoint``, whose keyword arguments pass through).
         ``precondition="learned"`` (the default here: measured faster than the plain cycle at 96^2 and at 256^2): the flexible cycle
-        with this solver's network between the similarity weight W; None: plain restarted GMRES.  ``out["wavefield"]`` is lam.  No gradients."""
+        with this solver's network between the similarity weight W; None: plain restarted GMRES.  ``out["wavefield"]`` is lam.  No gradients.
+        ``absorption=alpha`` among the keyword arguments: the adjoint of the lossy operator (hn_fgmres_adjoint_cycle_lossy)."""
         from .gmres import gmres_adjoint
         self._require_square("adjoint_solve")
         return gmres_adjoint(self, sos, cotangent, precondition=precondition, **kwargs)
 
     def solve_implicit(self, sos, tol: float = 1e-4, adjoint_tol: Optional[float] = None, restart: int = 20, max_cycles: int = 50,
-                       precondition: Optional[str] = "learned", precond_iterations: int = 10, x0=None) -> dict:
+                       precondition: Optional[str] = "learned", precond_iterations: int = 10, x0=None, absorption=None) -> dict:
         """The solution of A u = source to ``tol`` with the gradient of the SOLUTION, by the adjoint-state method: the forward solve is ``gmres`` (fused
         cycles on the device, under no_grad on detached inputs, nothing taped), and ``out["wavefield"]`` carries one autograd node whose backward solves
         A^H lam = dJ/du to ``adjoint_tol`` (default ``tol``; ``adjoint_solve`` with the same restart, max_cycles, precondition and precond_iterations),
@@ -832,8 +834,13 @@ class IterativeSolver(nn.Module):
         where they require grad.  One extra linear solve and O(1) memory whatever converged u; the weights get no gradient (u does not depend on them).
         Returns the dictionary of ``gmres`` plus ``"adjoint"``: a dictionary filled by backward with cycles, rmse (final true RMSE per sample),
         converged, iterations and unet_evaluations of the adjoint solve.  Square domains; 16-bit UNet precision modes are allowed (the network
-        only preconditions).  ``create_graph=True`` raises RuntimeError."""
-        from .autograd import SolveImplicit
+        only preconditions).  ``create_graph=True`` raises RuntimeError.
+        ``absorption`` (alpha, as in ``gmres``): the medium is lossy.  The forward solve is ``gmres(..., absorption=...)`` on detached inputs, and the
+        one autograd node solves the lossy adjoint system (hn_fgmres_adjoint_cycle_lossy), forms dJ/dk_sq, dJ/dk_sq_im and dJ/dsource
+        (hn_adjoint_grad_lossy) and chains through ``absorption.complex_k_sq`` to ``sos``, to ``absorption`` when it is a tensor that requires grad
+        (summed over the dimensions it broadcasts along) and to ``self.source``.  A number gets no gradient.  None: the code path and the bits of
+        before."""
+        from .autograd import SolveImplicit, SolveImplicitLossy
         from .gmres import gmres
         self._require_square("solve_implicit")
         n = int(self.hparams.domain_size)
@@ -845,13 +852,28 @@ class IterativeSolver(nn.Module):
             raise ValueError(f"x0 must be [{sos.shape[0]}, 2, {n}, {n}], got {tuple(x0.shape)}")
         if precondition not in (None, "learned"):
             raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
+        alpha = None
+        if absorption is not None:
+            alpha = absorption if isinstance(absorption, torch.Tensor) else torch.as_tensor(float(absorption))
+            try:
+                fits = tuple(torch.broadcast_shapes(tuple(alpha.shape), tuple(sos.shape))) == tuple(sos.shape)
+            except RuntimeError:
+                fits = False
+            if not fits:
+                raise ValueError(f"absorption of shape {tuple(alpha.shape)} does not broadcast to sos {tuple(sos.shape)}")
         common = dict(restart=int(restart), precondition=precondition, precond_iterations=int(precond_iterations))
+        lossy = {} if alpha is None else {"absorption": alpha.detach()}
         with torch.no_grad():
-            out = gmres(self, sos.detach(), max_outer=int(max_cycles), tol=float(tol), x0=None if x0 is None else x0.detach(), backend="hip", **common)
+            out = gmres(self, sos.detach(), max_outer=int(max_cycles), tol=float(tol), x0=None if x0 is None else x0.detach(), backend="hip", **common,
+                        **lossy)
         info: dict = {}
         spec = {"solver": self, "wavefield": out["wavefield"], "info": info,
                 "adjoint_kwargs": dict(common, max_outer=int(max_cycles), tol=float(tol if adjoint_tol is None else adjoint_tol))}
-        out["wavefield"] = SolveImplicit.apply(spec, sos.float(), self._src_graph())
+        if alpha is None:
+            out["wavefield"] = SolveImplicit.apply(spec, sos.float(), self._src_graph())
+        else:
+            dev = out["wavefield"].device
+            out["wavefield"] = SolveImplicitLossy.apply(spec, sos.to(dev).float(), alpha.to(dev).float(), self._src_graph())
         out["adjoint"] = info
         return out
 

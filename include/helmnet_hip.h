@@ -532,7 +532,9 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
  * enqueued -- kept until hn_set_domain / hn_set_domain_rect / hn_destroy, and change nothing of the lossless entry
  * points: hn_residual, hn_step and the cycles keep their kernels and their bits.  With k_sq_im = 0 the results agree with the lossless siblings to fp32
  * rounding, not bit for bit (another factorisation of the transforms).
- * No entry point exists for: gradients of any kind (d / d k_sq_im included), the adjoint cycle, the float64 operator and refinement, training. */
+ * Adjoint-state gradients of a converged lossy solve have the chain the lossless operator has: hn_residual_vjp_lossy (A^H g), hn_fgmres_adjoint_cycle_lossy
+ * (A^H lambda = g) and hn_adjoint_grad_lossy (dJ/dk_sq, dJ/dk_sq_im, dJ/dsrc), further down.
+ * No entry point exists for: gradients through the solver loop (a lossy hn_step_vjp / hn_step_jvp), the float64 operator and refinement, training. */
 
 /* hn_residual with the complex pointwise term; every legal square size and every rectangular domain.  HN_ERR_ARG "hn_residual_lossy: k_sq_im overlaps res". */
 int hn_residual_lossy(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, float* res, int batch,
@@ -551,6 +553,33 @@ int hn_step_lossy(hn_ctx* ctx, float* wf, float* res, float* states, const float
  * aligned and overlap no other argument, as k_sq. */
 int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch, int restart,
                           float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
+                          void* stream);
+
+/* ---- absorbing media: the adjoint operator and adjoint-state gradients (added within ABI v7: new entry points, nothing existing changes) ----
+ * With A u = L(u) + (k_sq + i k_sq_im) u the conjugate transpose is A^H g = L^H(g) + (k_sq - i k_sq_im) g:
+ *     re = L^H(g)_re + k_sq g_re + k_sq_im g_im,   im = L^H(g)_im + k_sq g_im - k_sq_im g_re.
+ * For A u = src, a real loss J, g = dJ/du (two real planes) and A^H lambda = g:
+ *     dJ/dk_sq = -(lambda_re u_re + lambda_im u_im),   dJ/dk_sq_im = lambda_re u_im - lambda_im u_re,   dJ/dsrc = lambda.
+ * Both line passes run on the LDS-line kernel the forward lossy operator runs on, at every size, the row pass with the conjugate pointwise term.
+ *
+ * hn_residual_vjp_lossy: out = A^H g; every legal square size and every rectangular domain.  Arguments as hn_residual_vjp, k_sq_im by k_sq's rules.
+ * HN_ERR_ARG: a NULL pointer (a NULL k_sq_im with a message that names hn_residual_vjp), batch < 1, g == out, k_sq_im overlapping out.  On a square
+ * domain that has tables to build, the first lossy call must not be under stream capture (HN_ERR_STATE, nothing enqueued), as for hn_residual_lossy. */
+int hn_residual_vjp_lossy(hn_ctx* ctx, const float* g, const float* k_sq, const float* k_sq_im, float* out, int batch, void* stream);
+
+/* hn_fgmres_adjoint_cycle on the lossy system A^H x = rhs: the start residual and every w = A^H z by the lossy adjoint; the preconditioner is
+ * precond_iters iterations of hn_step_lossy between the same two similarity kernels and tables (a complex diagonal term commutes with W, so
+ * A^T ~ W A W^-1 still holds); precond_iters == 0 is plain restarted GMRES on A^H with zbasis[:, j] == basis[:, j] bit for bit.  Square domains only
+ * (HN_ERR_UNSUPPORTED on a rectangular one).  Workspaces, the capture refusal and every argument check are hn_fgmres_adjoint_cycle's; k_sq_im must be
+ * 16-byte aligned and overlap no other argument, as k_sq. */
+int hn_fgmres_adjoint_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch, int restart,
+                                  float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse,
+                                  int32_t* k_used, void* stream);
+
+/* hn_adjoint_grad with the third output g_k_sq_im [B,1,n,n] = lambda_re * u_im - lambda_im * u_re; one launch, no atomics.  g_k_sq and g_src are
+ * hn_adjoint_grad's bit for bit.  g_k_sq_im is required, 16-byte aligned, and overlaps no other argument; every other rule is hn_adjoint_grad's
+ * (HN_ERR_UNSUPPORTED on a rectangular domain).  A refused call leaves the outputs alone. */
+int hn_adjoint_grad_lossy(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_k_sq_im, float* g_src,
                           void* stream);
 
 /* ---- training step (hybridnet.py:385-413 training_step, :250-283 configure_optimizers, :172-176

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """What the adjoint-state gradient of a converged solve costs, next to back-propagation through the learned iterations.
 
-    python tools/bench_adjoint.py [--out profiles/adjoint_bench.txt]
+    python tools/bench_adjoint.py [--out profiles/adjoint_bench.txt] [--absorption A0]
 
 At 96^2 x 4 (source [82, 48]) and 256^2 x 4 (source [194, 128]), ring phantoms, the loss J = c/2 sum |u[row 20]|^2 with the constant c chosen so that
 the cotangent dJ/du has the source's 2-norm (the adjoint system then asks of the solver what the forward one does), everything to 1e-4:
@@ -15,7 +15,10 @@ the cotangent dJ/du has the source's 2-norm (the adjoint system then asks of the
 Time: device events around the whole call on the current stream, the drivers' host reads included; one warm-up, then the median of ``--repeats``
 runs.  Peak memory: ``torch.cuda.max_memory_allocated`` over the timed call minus what was allocated before it (the library's own workspaces are
 allocated by the warm-up and are not torch's; they are reported as the growth of the device's used memory over the first call).  The shader clock is
-the median of the board's hwmon readings while the tool runs (bench.py's sampler), null where the board does not expose it."""
+the median of the board's hwmon readings while the tool runs (bench.py's sampler), null where the board does not expose it.
+
+``--absorption A0``: the medium absorbs, alpha = A0 nepers per grid point inside the ring (sos > 1.05) and a quarter of it elsewhere.  The implicit and
+the adjoint rows then run on the lossy operator and its adjoint; the unrolled row is left out (the solver loop has no gradients with absorption)."""
 import argparse
 import json
 import os
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--max-cycles", type=int, default=1500)
     ap.add_argument("--learned-iterations", type=int, default=1000)
+    ap.add_argument("--absorption", type=float, default=None, metavar="A0")
     a = ap.parse_args()
     from bench import Hwmon
     from helmnet_amd import IterativeSolver
@@ -71,7 +75,10 @@ def main():
             s.set_domain_size(n, source_location=[82, 48] if n == 96 else [n - 62, n // 2])
             sos = torch.from_numpy(ring_sos_batch(n, a.batch, seed=11)).to(dev)
             src_norm = float(torch.linalg.vector_norm(s.source.detach().double()))
-            u0 = s.gmres(sos, restart=a.restart, max_cycles=a.max_cycles, tol=a.tol, precondition="learned")["wavefield"]
+            lossy = {}
+            if a.absorption is not None:
+                lossy = {"absorption": torch.where(sos > 1.05, torch.full_like(sos, a.absorption), torch.full_like(sos, 0.25 * a.absorption))}
+            u0 = s.gmres(sos, restart=a.restart, max_cycles=a.max_cycles, tol=a.tol, precondition="learned", **lossy)["wavefield"]
             c = src_norm / float(torch.linalg.vector_norm(u0[:, :, row, :].double()) / a.batch ** 0.5)
 
             def loss(u):
@@ -83,7 +90,7 @@ def main():
 
             def implicit(precondition):
                 x = sos.clone().requires_grad_(True)
-                out = s.solve_implicit(x, tol=a.tol, restart=a.restart, max_cycles=a.max_cycles, precondition=precondition)
+                out = s.solve_implicit(x, tol=a.tol, restart=a.restart, max_cycles=a.max_cycles, precondition=precondition, **lossy)
                 loss(out["wavefield"]).backward()
                 return out, x.grad
 
@@ -98,19 +105,21 @@ def main():
                 (out, g), t, spread, peak, lib = _measure(lambda: implicit(pre), a.repeats)
                 grads[name] = g
                 info = out["adjoint"]
-                rows.append({"n": n, "batch": a.batch, "what": "implicit", "precondition": pre, "tol": a.tol, "restart": a.restart, "seconds": t,
+                rows.append({"n": n, "batch": a.batch, "what": "implicit", "absorption": a.absorption, "precondition": pre, "tol": a.tol, "restart": a.restart, "seconds": t,
                              "seconds_spread": spread, "peak_torch_bytes": peak, "first_call_device_bytes": lib, "forward_cycles": len(out["cycle_tables"]),
                              "forward_converged": bool(out["converged"]), "forward_final_rmse": out["residual_norms"][-1].tolist(),
                              "forward_unet_evaluations": out["unet_evaluations"], "adjoint_cycles": info["cycles"], "adjoint_converged": bool(info["converged"]),
                              "adjoint_final_true_rmse": info["rmse"].tolist(), "adjoint_unet_evaluations": info["unet_evaluations"]})
                 print(json.dumps(rows[-1]), flush=True)
-                out, t, spread, peak, _ = _measure(lambda: s.adjoint_solve(cot, sos, restart=a.restart, max_outer=a.max_cycles, tol=a.tol, precondition=pre),
-                                                   a.repeats)
-                rows.append({"n": n, "batch": a.batch, "what": "adjoint solve alone", "precondition": pre, "tol": a.tol, "restart": a.restart, "seconds": t,
+                out, t, spread, peak, _ = _measure(lambda: s.adjoint_solve(cot, sos, restart=a.restart, max_outer=a.max_cycles, tol=a.tol, precondition=pre,
+                                                                           **lossy), a.repeats)
+                rows.append({"n": n, "batch": a.batch, "what": "adjoint solve alone", "absorption": a.absorption, "precondition": pre, "tol": a.tol, "restart": a.restart, "seconds": t,
                              "seconds_spread": spread, "peak_torch_bytes": peak, "cycles": out["cycles"], "lockstep_inner_iterations": out["iterations"],
                              "operator_applications": out["operator_applications"], "unet_evaluations": out["unet_evaluations"],
                              "converged": bool(out["converged"]), "final_true_rmse": out["residual_norm"].tolist()})
                 print(json.dumps(rows[-1]), flush=True)
+            if lossy:
+                continue
             target = max(rows[-4]["forward_final_rmse"])
             with torch.no_grad():
                 norms = s.forward(sos, num_iterations=a.learned_iterations, residuals="norms")["residual_norms"].float().cpu().max(1).values
