@@ -3,6 +3,8 @@
 //   L(u) = ax . D1x u + bx . D2x u + ay . D1y u + by . D2y u        (spectral.py:31-79 under .double())
 //   res  = L(u) + k_sq . u - src                                    (hybridnet.py:544-556)
 //
+// Absorbing media (hn_residual_f64_lossy: res = L(u) + (k_sq + i k_sq_im) . u - src, square and rectangular domains) have no dense form: f64_apply_lossy
+// always runs the line transforms of hn_f64_fft.hip.
 // ONE dense code path for every legal n (the default; HN_OPT_F64_FFT 1 routes f64_reserve / f64_apply to the line transforms of hn_f64_fft.hip instead).  D1 = F^-1 diag(i k) F and D2 = F^-1 diag(-k^2) F are circulant, D[j][m] = g[(j - m) mod n], so an axis'
 // operator is its first column: g2 real, g1 real but for the Nyquist term (the reference keeps k = -pi there, which makes Im g1[d] = k1[n/2] (-1)^d / n).
 // The kernel keeps Re g1, Im g1 and g2 in LDS (24 n bytes) and reads matrix elements from there; only the wavefield is streamed.  The values are the
@@ -256,7 +258,7 @@ int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, con
     if (int rc = f64_reserve(ctx, batch, rmse != nullptr, s, out != nullptr); rc != HN_OK) return rc;
     if (ctx->opt_f64_fft) {
         double* lines = nullptr;   // one partial sum per line: k_rmse_f64 adds a sample's n of them
-        if (int rc = f64_fft_launch(ctx, wf, out, ksq, src, src_batch == 1 ? 0L : 2 * plane, rmse != nullptr, batch, s, &lines); rc != HN_OK) return rc;
+        if (int rc = f64_fft_launch(ctx, wf, out, ksq, nullptr, src, src_batch == 1 ? 0L : 2 * plane, rmse != nullptr, batch, s, &lines); rc != HN_OK) return rc;
         if (rmse != nullptr) hipLaunchKernelGGL(k_rmse_f64, dim3(batch), dim3(256), 0, s, lines, n, 1.0 / (2.0 * (double)plane), rmse);
         HN_HIP(ctx, hipGetLastError());
         ctx->f64_route = 2;
@@ -272,6 +274,30 @@ int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, con
     if (rmse != nullptr) hipLaunchKernelGGL(k_rmse_f64, dim3(batch), dim3(256), 0, s, part, tiles, 1.0 / (2.0 * (double)plane), rmse);
     HN_HIP(ctx, hipGetLastError());
     ctx->f64_route = 1;
+    return HN_OK;
+}
+
+int f64_lossy_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s, bool want_out) {
+    if (ctx->geo.h == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    return f64_fft_reserve(ctx, batch, want_rmse, want_out, s);
+}
+
+// the lossy operator has no dense form: the two line passes whatever HN_OPT_F64_FFT says, on ctx->geo (a square domain's dense tables are not touched)
+int f64_apply_lossy(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* ksq_im, const double* src, int src_batch, double* rmse,
+                    int batch, hipStream_t s) {
+    if (ctx->geo.h == 0) return fail(ctx, HN_ERR_STATE, "hn_set_domain has not been called");
+    const int h = ctx->geo.h;
+    const long plane = ctx->geo.plane();
+    const size_t bytes = (size_t)batch * 2 * plane * sizeof(double);
+    const MemRange r[] = {{out, bytes, true, "res"}, {wf, bytes, false, "wf"}, {ksq_im, bytes / 2, false, "k_sq_im"}};
+    const char *na, *nb;
+    if (first_overlap(r, 3, &na, &nb)) return fail(ctx, HN_ERR_ARG, "float64 lossy residual: %s must not alias the output", nb);
+    if (int rc = f64_lossy_reserve(ctx, batch, rmse != nullptr, s, out != nullptr); rc != HN_OK) return rc;
+    double* lines = nullptr;   // one partial sum per row: k_rmse_f64 adds a sample's h of them
+    if (int rc = f64_fft_launch(ctx, wf, out, ksq, ksq_im, src, src_batch == 1 ? 0L : 2 * plane, rmse != nullptr, batch, s, &lines); rc != HN_OK) return rc;
+    if (rmse != nullptr) hipLaunchKernelGGL(k_rmse_f64, dim3(batch), dim3(256), 0, s, lines, h, 1.0 / (2.0 * (double)plane), rmse);
+    HN_HIP(ctx, hipGetLastError());
+    ctx->f64_route = 2;
     return HN_OK;
 }
 
@@ -297,6 +323,18 @@ int hn_residual_f64(hn_ctx* ctx, const double* wf, const double* k_sq, const dou
         return hn::fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
     hn::DeviceGuard guard(ctx);
     return hn::f64_apply(ctx, wf, res, k_sq, src, src_batch, rmse, batch, (hipStream_t)stream);
+}
+
+int hn_residual_f64_lossy(hn_ctx* ctx, const double* wf, const double* k_sq, const double* k_sq_im, const double* src, int src_batch, double* res,
+                          double* rmse, int batch, void* stream) {
+    if (ctx && !k_sq_im) return hn::fail(ctx, HN_ERR_ARG, "hn_residual_f64_lossy: k_sq_im is NULL (a lossless medium is hn_residual_f64)");
+    if (!ctx || !wf || !k_sq || !src) return hn::fail(ctx, HN_ERR_ARG, "hn_residual_f64_lossy: NULL argument");
+    if (!res && !rmse) return hn::fail(ctx, HN_ERR_ARG, "hn_residual_f64_lossy: res and rmse are both NULL");
+    if (batch <= 0) return hn::fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
+    if (src_batch != 1 && src_batch != batch)
+        return hn::fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
+    hn::DeviceGuard guard(ctx);
+    return hn::f64_apply_lossy(ctx, wf, res, k_sq, k_sq_im, src, src_batch, rmse, batch, (hipStream_t)stream);
 }
 
 // test aid (not part of the ABI, needs no device): the dense n x n operators the kernel's circulant columns stand for, row-major, D1 = d1_re + i d1_im

@@ -1,8 +1,11 @@
-// hn_f64_fft.hip -- the float64 Helmholtz operator of hn_f64.hip by FFT (HN_OPT_F64_FFT 1): two line passes in the algorithm of k_spec_line
-// (hn_spectral_line.hip; read its header comment), in double.
-//   column pass   lines along the first spatial axis:   mid = ay . D1y u + by . D2y u
-//   row pass      lines along the second:               out = mid + ax . D1x u + bx . D2x u [+ k_sq . u - src], one sum of squares per line
-// Every legal n = P * Q, P odd in [1, 127], Q = 2^k in [16, 2048] (spec_rect_factor).  A line lives in LDS as [P][Q] double2 (Good-Thomas input map): in-place
+// hn_f64_fft.hip -- the float64 Helmholtz operator of hn_f64.hip by FFT (HN_OPT_F64_FFT 1; always for hn_residual_f64_lossy): two line passes in the
+// algorithm of k_spec_line (hn_spectral_line.hip; read its header comment), in double, on an h x w field (h == w: a square domain).
+//   column pass   w lines of length h along the first spatial axis:   mid = ay . D1y u + by . D2y u
+//   row pass      h lines of length w along the second:               out = mid + ax . D1x u + bx . D2x u [+ k_sq . u - src], one sum of squares per line
+//   lossy row pass (absorbing media, LOSSY): the value above formed exactly as above, then re -= k_sq_im . u_im and im += k_sq_im . u_re as two further
+//                 operations of their own -- with k_sq_im == 0 the lossless bits on finite inputs
+// Each axis has its own tables (a square domain: one set for both), its own lines per block, buffer count and dynamic LDS, and is normalised by its own length.
+// Every legal length n = P * Q, P odd in [1, 127], Q = 2^k in [16, 2048] (spec_rect_factor).  A line lives in LDS as [P][Q] double2 (Good-Thomas input map): in-place
 // Q-point transforms (natural in, bit-reversed out), a direct P-point DFT across them, the derivative multipliers i k and -k^2 in the order the spectrum is met,
 // and the inverses.  P = 1 has no P-point DFT and needs three line buffers instead of four.  The operator values are k_helm_f64's: the fp32 wavenumber grid
 // up-cast, its fp32 square up-cast, the fp32-rounded PML coefficients up-cast.  The Nyquist bin keeps k = -pi as the reference does; as a multiplier on the
@@ -14,7 +17,7 @@
 // lines run up to 16 per block inside an 80 KiB budget (two blocks per CU), fewer while the launch would not give every CU two blocks (the rule of rect_lines).
 // All 512 threads of a block work through the items of all its lines between block barriers; which thread computes an element does not change the element's
 // arithmetic.  The row pass leaves the squares of a line's results in a line buffer that is free by then, and ONE wave adds a line in a fixed order (lane j:
-// elements j, j + 64, ... in turn, then a fixed butterfly): a line's partial sum, and with it a sample's rmse (k_rmse_f64 adds the n partials in its fixed
+// elements j, j + 64, ... in turn, then a fixed butterfly): a line's partial sum, and with it a sample's rmse (k_rmse_f64 adds the h partials in its fixed
 // order), depends neither on the lines per block nor on the batch.
 // Lines are independent: no flags, no cross-workgroup waits, no atomics.  Plain C++ on v_fma_f64; the caller's tensors are read and written as scalar doubles
 // (8-byte alignment is all they need).
@@ -27,12 +30,16 @@
 namespace hn {
 
 // what the first FFT-route call on a domain builds (f64_fft_reserve) and hn_set_domain / hn_set_domain_rect / hn_destroy free (f64_fft_free)
-struct F64Fft {
-    int n = 0, P = 0, Q = 0;
+struct F64Axis {
+    int n = 0, P = 0, Q = 0;    // lines of length n = P * Q
     char* tabs = nullptr;       // one allocation: tw_q [Q], wp [P], a [n], b [n] (double2), k1m [n], k2m [n] (double), slot [n] (int)
-    double* part = nullptr;     // [part_cap]: one sum of squares per line and sample, [batch][n]
+};
+struct F64Fft {
+    int h = 0, w = 0;
+    F64Axis cols, rows;         // cols: lines of length h (the y axis); rows: lines of length w (the x axis).  h == w: rows.tabs == cols.tabs, one allocation
+    double* part = nullptr;     // [part_cap]: one sum of squares per row and sample, [batch][h]
     long part_cap = 0;
-    double* mid = nullptr;      // [mid_cap]: the column pass's result [batch, 2, n, n] of a call that returns no field (res == NULL)
+    double* mid = nullptr;      // [mid_cap]: the column pass's result [batch, 2, h, w] of a call that returns no field (res == NULL)
     long mid_cap = 0;
 };
 
@@ -150,16 +157,20 @@ struct Tabs {
     const int* slot;       // [n]: n1 * Q + n2 of element i
 };
 
-// One kernel for both axes of the n x n field; L = 1 << logl lines per block (L divides 16 and with it n: no block has lines past the last one).
+// One kernel for both axes of the h x w field; n = the line's length (AXIS 1: h, AXIS 0: w), t, P, logq that axis' tables and factors; L = 1 << logl lines
+// per block (L divides 16 and with it the number of lines, a multiple of 16: no block has lines past the last one).
 //   AXIS 1: along y (column pass: line c is column c; the block's L adjacent columns are loaded and stored as row segments of L doubles); dst = the pass's result
-//   AXIS 0: along x (row pass: line r is row r): dst (nullable) = mid + the pass's result [+ k_sq u - src with RESID]; part (nullable): [batch][n] sums of
+//   AXIS 0: along x (row pass: line r is row r): dst (nullable) = mid + the pass's result [+ k_sq u - src with RESID]; part (nullable): [batch][h] sums of
 //           squares of a line.  mid may be dst: every element is read and then written by one thread.
+//   LOSSY (AXIS 0 with resid): ksq_im, the imaginary part of k_sq, applied to the finished lossless value.
 // Dynamic LDS: (P == 1 ? 3 : 4) buffers of L * n double2, then the Q and P twiddles.
-template <int AXIS>
-__global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__ wf, const double* mid, double* dst, const double* ksq, const double* src,
-                                                       long src_sb, Tabs t, int n, int P, int logq, int logl, int resid, double* __restrict__ part) {
+template <int AXIS, bool LOSSY>
+__global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__ wf, const double* mid, double* dst, const double* ksq, const double* ksq_im,
+                                                       const double* src, long src_sb, Tabs t, int h, int w, int P, int logq, int logl, int resid,
+                                                       double* __restrict__ part) {
     extern __shared__ double2 fbuf[];
     const int tid = threadIdx.x, b = blockIdx.y;
+    const int n = AXIS == 0 ? w : h;
     const int Q = 1 << logq, L = 1 << logl, PH = (P + 1) >> 1;
     const int ln = L * n;                 // double2 per buffer
     double2* const B0 = fbuf;
@@ -168,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__
     double2* const B3 = fbuf + 3 * ln;    // (P > 1 only)
     double2* const twq = fbuf + (P == 1 ? 3 : 4) * ln;
     double2* const wp = twq + Q;
-    const long plane = (long)n * n;
+    const long plane = (long)h * w;
     const int line0 = blockIdx.x * L;
     for (int i = tid; i < Q; i += kThreads) twq[i] = t.tw_q[i];
     for (int i = tid; i < P; i += kThreads) wp[i] = t.wp[i];
@@ -177,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__
     for (int e = tid; e < ln; e += kThreads) {
         const int l = AXIS == 0 ? e / n : e & (L - 1);
         const int i = AXIS == 0 ? e - l * n : e >> logl;
-        const long o = AXIS == 0 ? (long)(line0 + l) * n + i : (long)i * n + line0 + l;
+        const long o = AXIS == 0 ? (long)(line0 + l) * w + i : (long)i * w + line0 + l;
         B0[l * n + t.slot[i]] = make_double2(pre[o], pre[o + plane]);
     }
     __syncthreads();
@@ -246,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__
         const double2 p = cmul(t.a[i], D1[sl]), r = cmul(t.b[i], D2[sl]);
         double re = (p.x + r.x) * inv_n;
         double im = (p.y + r.y) * inv_n;
-        const long o = AXIS == 0 ? (long)(line0 + l) * n + i : (long)i * n + line0 + l;
+        const long o = AXIS == 0 ? (long)(line0 + l) * w + i : (long)i * w + line0 + l;
         if (AXIS == 0) {
             const double* pm = mid + (long)b * 2 * plane;
             re += pm[o];
@@ -256,6 +267,12 @@ __global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__
                 const double* ps = src + (long)b * src_sb + o;
                 re += kq * pre[o] - ps[0];          // the line itself again (an L2 hit) instead of a copy held through the transforms
                 im += kq * pre[o + plane] - ps[plane];
+                if constexpr (LOSSY) {                  // (k_sq + i k_sq_im) u: the imaginary part's share, after the lossless value is complete
+                    const double ki = ksq_im[(long)b * plane + o];
+                    const double lre = ki * pre[o + plane], lim = ki * pre[o];
+                    re = __dsub_rn(re, lre);
+                    im = __dadd_rn(im, lim);
+                }
             }
             sq[l * n + i] = re * re + im * im;
         }
@@ -272,7 +289,7 @@ __global__ __launch_bounds__(kThreads) void k_f64_fft(const double* __restrict__
             for (int i = lane; i < n; i += 64) s += sq[l * n + i];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            if (lane == 0) part[(long)b * n + line0 + l] = s;
+            if (lane == 0) part[(long)b * h + line0 + l] = s;
         }
     }
 }
@@ -285,16 +302,17 @@ int ilog2(int v) {
 
 // Lines per block (a power of two), the rule of rect_lines with 16-byte points: at most 16 -- the column pass then moves 128-byte row segments -- and at most
 // kLdsLines of line buffers; fewer while the launch would not give every CU two blocks.  One line per block may take more than kLdsLines (the long lines).
-int lines_per_block(int n, int nbuf, int batch) {
+// Per pass: `lines` lines of length n (a square domain: lines == n in both).
+int lines_per_block(int n, int lines, int nbuf, int batch) {
     int L = 16;
     while (L > 1 && (size_t)L * nbuf * n * sizeof(double2) > (size_t)kLdsLines) L >>= 1;
-    while (L > 1 && (long)(n / L) * batch < 512) L >>= 1;
+    while (L > 1 && (long)(lines / L) * batch < 512) L >>= 1;
     return L;
 }
 
 size_t lds_bytes(int n, int P, int Q, int L) { return ((size_t)L * (P == 1 ? 3 : 4) * n + Q + P) * sizeof(double2); }
 
-Tabs tabs_of(const F64Fft& f) {
+Tabs tabs_of(const F64Axis& f) {
     const int n = f.n;
     const double2* c = reinterpret_cast<const double2*>(f.tabs);
     const double* d = reinterpret_cast<const double*>(c + f.Q + f.P + 2 * (size_t)n);
@@ -302,9 +320,11 @@ Tabs tabs_of(const F64Fft& f) {
 }
 
 // the tables of build_axis (hn_spectral_line.hip) in double: the twiddles computed in double, the operator values up-cast from what the reference holds in fp32
-int build_tables(hn_ctx* ctx, F64Fft& f, int n, int P, int Q) {
-    const SpecTables& st = ctx->tab;
-    const AxisHost ax = spec_axis_host(n, st.pml, st.sigma_max, st.k);
+int build_tables(hn_ctx* ctx, F64Axis& f, int n, int P, int Q) {
+    // what the domain was set with: a square one keeps it in tab, a rectangular one in rect
+    const int pml = ctx->rect ? ctx->rect->pml : ctx->tab.pml;
+    const double sigma_max = ctx->rect ? ctx->rect->sigma_max : ctx->tab.sigma_max, k = ctx->rect ? ctx->rect->k : ctx->tab.k;
+    const AxisHost ax = spec_axis_host(n, pml, sigma_max, k);
     const int logq = ilog2(Q);
     const double pi = 3.14159265358979323846;
     int qinv = 0, pinv = 1;
@@ -331,8 +351,9 @@ int build_tables(hn_ctx* ctx, F64Fft& f, int n, int P, int Q) {
             d[(size_t)n + (size_t)a1 * Q + r] = (double)ax.k2[kk];
         }
     // here and not at the first launch: the launches themselves are then capturable
-    HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_f64_fft<0>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsAttr));
-    HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_f64_fft<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsAttr));
+    HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_f64_fft<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsAttr));
+    HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_f64_fft<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsAttr));
+    HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_f64_fft<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsAttr));
     char* dev = nullptr;
     HN_HIP(ctx, hipMalloc((void**)&dev, bytes));
     if (hipError_t e = hipMemcpy(dev, h.data(), bytes, hipMemcpyHostToDevice); e != hipSuccess) {
@@ -360,16 +381,18 @@ int grow(hn_ctx* ctx, double** p, long* cap, long needed) {
 
 void f64_fft_free(hn_ctx* ctx) {
     if (ctx->f64fft == nullptr) return;
-    for (void* p : {(void*)ctx->f64fft->tabs, (void*)ctx->f64fft->part, (void*)ctx->f64fft->mid}) (void)hipFree(p);
+    F64Fft& f = *ctx->f64fft;
+    if (f.rows.tabs != f.cols.tabs) (void)hipFree(f.rows.tabs);   // (a square domain's one allocation serves both axes)
+    for (void* p : {(void*)f.cols.tabs, (void*)f.part, (void*)f.mid}) (void)hipFree(p);
     delete ctx->f64fft;
     ctx->f64fft = nullptr;
 }
 
 int f64_fft_reserve(hn_ctx* ctx, int batch, bool want_rmse, bool want_out, hipStream_t s) {
-    const int n = ctx->tab.n;
-    const long part_needed = want_rmse ? (long)batch * n : 0, mid_needed = want_out ? 0 : (long)batch * 2 * n * n;
+    const int h = ctx->geo.h, w = ctx->geo.w;
+    const long part_needed = want_rmse ? (long)batch * h : 0, mid_needed = want_out ? 0 : (long)batch * 2 * h * w;
     F64Fft* f = ctx->f64fft;
-    if (f != nullptr && f->tabs != nullptr && part_needed <= f->part_cap && mid_needed <= f->mid_cap) return HN_OK;
+    if (f != nullptr && f->cols.tabs != nullptr && f->rows.tabs != nullptr && part_needed <= f->part_cap && mid_needed <= f->mid_cap) return HN_OK;
     if (stream_capturing(s))
         return fail(ctx, HN_ERR_STATE, "the float64 FFT tables of this domain (or a larger batch's partial sums or intermediate field) are built by the first call, which must not be under stream capture");
     if (f == nullptr) {
@@ -377,29 +400,42 @@ int f64_fft_reserve(hn_ctx* ctx, int batch, bool want_rmse, bool want_out, hipSt
         if (f == nullptr) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
         ctx->f64fft = f;
     }
-    if (f->tabs == nullptr) {
+    f->h = h;
+    f->w = w;
+    for (F64Axis* ax : {&f->cols, &f->rows}) {
+        if (ax->tabs != nullptr) continue;
+        const int n = ax == &f->cols ? h : w;
+        if (ax == &f->rows && h == w) { f->rows = f->cols; continue; }   // (the same pointer: freed once)
         int P = 0, Q = 0;
         if (!spec_rect_factor(n, &P, &Q)) return fail(ctx, HN_ERR_ARG, "internal: no factorisation of the domain size %d", n);
         if (lds_bytes(n, P, Q, 1) > (size_t)kLdsAttr)
             return fail(ctx, HN_ERR_UNSUPPORTED, "float64 FFT route: a line of %d = %d * %d points needs %zu bytes of LDS, more than a workgroup may declare", n, P, Q,
                         lds_bytes(n, P, Q, 1));
-        if (int rc = build_tables(ctx, *f, n, P, Q); rc != HN_OK) return rc;
+        if (int rc = build_tables(ctx, *ax, n, P, Q); rc != HN_OK) return rc;
     }
     if (int rc = grow(ctx, &f->part, &f->part_cap, part_needed); rc != HN_OK) return rc;
     return grow(ctx, &f->mid, &f->mid_cap, mid_needed);
 }
 
-int f64_fft_launch(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, long src_sb, bool want_part, int batch, hipStream_t s,
-                   double** part) {
+int f64_fft_launch(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* ksq_im, const double* src, long src_sb, bool want_part,
+                   int batch, hipStream_t s, double** part) {
     const F64Fft& f = *ctx->f64fft;
-    const int n = f.n, nbuf = f.P == 1 ? 3 : 4, L = lines_per_block(n, nbuf, batch), logq = ilog2(f.Q), logl = ilog2(L);
-    const size_t lds = lds_bytes(n, f.P, f.Q, L);
-    const Tabs t = tabs_of(f);
+    const int h = f.h, w = f.w;
     double* mid = out != nullptr ? out : f.mid;
     *part = want_part ? f.part : nullptr;
-    const dim3 grid(n / L, batch);
-    hipLaunchKernelGGL((k_f64_fft<1>), grid, dim3(kThreads), lds, s, wf, nullptr, mid, nullptr, nullptr, 0L, t, n, f.P, logq, logl, 0, nullptr);
-    hipLaunchKernelGGL((k_f64_fft<0>), grid, dim3(kThreads), lds, s, wf, mid, out, ksq, src, src_sb, t, n, f.P, logq, logl, ksq != nullptr ? 1 : 0, *part);
+    // each pass by its own axis: lines per block, buffers, LDS
+    const F64Axis &ay = f.cols, &ax = f.rows;
+    const int Ly = lines_per_block(h, w, ay.P == 1 ? 3 : 4, batch), Lx = lines_per_block(w, h, ax.P == 1 ? 3 : 4, batch);
+    hipLaunchKernelGGL((k_f64_fft<1, false>), dim3(w / Ly, batch), dim3(kThreads), lds_bytes(h, ay.P, ay.Q, Ly), s, wf, nullptr, mid, nullptr, nullptr, nullptr,
+                       0L, tabs_of(ay), h, w, ay.P, ilog2(ay.Q), ilog2(Ly), 0, nullptr);
+    const dim3 grid(h / Lx, batch);
+    const size_t lds = lds_bytes(w, ax.P, ax.Q, Lx);
+    const int logq = ilog2(ax.Q), logl = ilog2(Lx);
+    if (ksq_im != nullptr)
+        hipLaunchKernelGGL((k_f64_fft<0, true>), grid, dim3(kThreads), lds, s, wf, mid, out, ksq, ksq_im, src, src_sb, tabs_of(ax), h, w, ax.P, logq, logl, 1, *part);
+    else
+        hipLaunchKernelGGL((k_f64_fft<0, false>), grid, dim3(kThreads), lds, s, wf, mid, out, ksq, nullptr, src, src_sb, tabs_of(ax), h, w, ax.P, logq, logl,
+                           ksq != nullptr ? 1 : 0, *part);
     return HN_OK;
 }
 

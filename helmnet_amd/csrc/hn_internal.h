@@ -224,6 +224,8 @@ struct LineAxis {
 // While it exists ctx->tab is empty (tab.n == 0): whatever is built for n x n cannot run on it by accident.
 struct RectDomain {
     int h = 0, w = 0;
+    int pml = 0;               // what hn_set_domain_rect was called with (the float64 lossy residual builds its per-axis tables from it)
+    double sigma_max = 0.0, k = 0.0;
     LineAxis cols, rows;       // cols: lines of length h (the y axis); rows: lines of length w (the x axis)
     float* sigmas = nullptr;   // [2, h, w]
 };
@@ -573,11 +575,17 @@ int f64_apply(hn_ctx* ctx, const double* wf, double* out, const double* ksq, con
 // stream capture): an entry point that launches before it reaches f64_apply asks here first
 // (want_out false: the call will pass out == NULL, for which the FFT route needs an intermediate field of its own)
 int f64_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s, bool want_out = true);
-// ---- the same operator by FFT (hn_f64_fft.hip; HN_OPT_F64_FFT 1).  f64_reserve / f64_apply are the only callers ----
+// absorbing media: out = L(wf) + (ksq + i ksq_im) wf - src in float64 on a square or rectangular domain, always by FFT (HN_CNT_F64_ROUTE 2), out and / or
+// rmse as f64_apply; f64_lossy_reserve is f64_reserve's counterpart for it
+int f64_lossy_reserve(hn_ctx* ctx, int batch, bool want_rmse, hipStream_t s, bool want_out = true);
+int f64_apply_lossy(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* ksq_im, const double* src, int src_batch, double* rmse,
+                    int batch, hipStream_t s);
+// ---- the same operator by FFT (hn_f64_fft.hip; HN_OPT_F64_FFT 1).  f64_reserve / f64_apply and their lossy counterparts are the only callers ----
 int f64_fft_reserve(hn_ctx* ctx, int batch, bool want_rmse, bool want_out, hipStream_t s);
-// the two passes on `s` (everything reserved); *part = the [batch][n] per-line sums of squares if want_part, else NULL
-int f64_fft_launch(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* src, long src_sb, bool want_part, int batch, hipStream_t s,
-                   double** part);
+// the two passes on `s` (everything reserved); *part = the [batch][h] per-row sums of squares if want_part, else NULL
+// ksq_im non-null (with ksq and src): the lossy row pass.  The domain is ctx->geo's, square or rectangular
+int f64_fft_launch(hn_ctx* ctx, const double* wf, double* out, const double* ksq, const double* ksq_im, const double* src, long src_sb, bool want_part,
+                   int batch, hipStream_t s, double** part);
 void f64_fft_free(hn_ctx* ctx);   // (the caller has synchronised the device)
 // ---- what the float64 and GMRES entry points share (defined in hn_f64.hip) ----
 bool stream_capturing(hipStream_t s);   // a non-null stream under capture: nothing may be built, grown or freed

@@ -15,7 +15,8 @@
 // whoever consumes them -- no float atomics, nothing depends on the batch a sample shares (grid.y is the sample), two calls give the same bits.
 //
 // hn_gmres_refine_cycle (at the end of this file) wraps the same launches into one step of iterative refinement: the true residual (hn_f64.hip) and the
-// update in float64, the cycle in fp32 on the scaled correction equation A d = r / s.
+// update in float64, the cycle in fp32 on the scaled correction equation A d = r / s.  hn_fgmres_refine_cycle_lossy is that step for an absorbing
+// medium: Precond.k_sq_im set, the float64 residual f64_apply_lossy's, the cycle and the preconditioner the lossy ones.
 //
 // hn_fgmres_cycle / hn_fgmres_refine_cycle are the same launches as a FLEXIBLE cycle (Saad 1993), right-preconditioned by the learned iteration: per inner
 // step z_k = M(v_k) -- precond_iters iterations of hn_step on A z = alpha v_k from rest, z_k = wf / alpha --, w = A z_k, the orthogonalisation and the small
@@ -56,6 +57,7 @@ struct RefineWs {
     int batch = 0, n = 0;
     DeviceBlock block;        // one allocation; the pointers below lead into it
     double* ksq64 = nullptr;  // [B][n^2]    k_sq up-cast
+    double* ksq_im64 = nullptr;   // [B][n^2]  k_sq_im up-cast: only once hn_fgmres_refine_cycle_lossy has asked for it
     double* rhs64 = nullptr;  // [B][2 n^2]  rhs up-cast (the first rhs_batch samples)
     double* res64 = nullptr;  // [B][2 n^2]  A x - b
     float* rhs32 = nullptr;   // [B][2 n^2]  -res / s: the cycle's right-hand side
@@ -755,10 +757,14 @@ void refine_ws_free(hn_ctx* ctx) {
 }
 
 // the refinement's own fields for `batch` samples on the current domain -- never built or grown under stream capture
-int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s) {
+int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s, bool lossy) {
     const int n = ctx->tab.n;
     RefineWs* ws = ctx->rfn;
-    if (ws != nullptr && ws->n == n && batch <= ws->batch) return HN_OK;
+    if (ws != nullptr && ws->n == n && batch <= ws->batch && (!lossy || ws->ksq_im64 != nullptr)) return HN_OK;
+    if (ws != nullptr && ws->n == n) {   // a rebuilt workspace keeps what the old one could do
+        lossy = lossy || ws->ksq_im64 != nullptr;
+        batch = batch > ws->batch ? batch : ws->batch;
+    }
     if (stream_capturing(s))
         return fail(ctx, HN_ERR_STATE, "hn_gmres_refine_cycle: the workspace (or a larger batch's) is built by the first call, which must not be under stream capture");
     refine_ws_free(ctx);
@@ -766,11 +772,12 @@ int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s) {
     if (!ws) return fail(ctx, HN_ERR_NOMEM, "out of host memory");
     ctx->rfn = ws;
     const size_t P = (size_t)n * n, B = (size_t)batch;
-    const size_t sizes[] = {B * P * 8, B * 2 * P * 8, B * 2 * P * 8, B * 2 * P * 4, B * 2 * P * 4, B * 8, B * 4};
+    const size_t sizes[] = {B * P * 8, B * 2 * P * 8, B * 2 * P * 8, B * 2 * P * 4, B * 2 * P * 4, B * 8, B * 4, B * P * 8};
     DeviceBlock& k = ws->block;
-    if (const int rc = k.alloc(ctx, "hn_gmres_refine_cycle", sizes, 7); rc != HN_OK) { refine_ws_free(ctx); return rc; }
+    if (const int rc = k.alloc(ctx, "hn_gmres_refine_cycle", sizes, lossy ? 8 : 7); rc != HN_OK) { refine_ws_free(ctx); return rc; }
     ws->ksq64 = (double*)k.take(); ws->rhs64 = (double*)k.take(); ws->res64 = (double*)k.take(); ws->rhs32 = (float*)k.take(); ws->d32 = (float*)k.take();
     ws->tol = (double*)k.take(); ws->stop = (int*)k.take();
+    if (lossy) ws->ksq_im64 = (double*)k.take();
     ws->batch = batch; ws->n = n;
     return HN_OK;
 }
@@ -837,20 +844,28 @@ int run_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* rhs,
     return launch_cycle(ctx, op, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, pc, basis, hess, rmse, k_used, s);
 }
 
-// hn_gmres_refine_cycle and hn_fgmres_refine_cycle, the arguments but tol and inner_floor checked
+// hn_gmres_refine_cycle, hn_fgmres_refine_cycle and (pc.k_sq_im non-null: the lossy operator in the float64 residual, the cycle and the preconditioner)
+// hn_fgmres_refine_cycle_lossy, the arguments but tol and inner_floor checked
 int run_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
                      float inner_floor, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, hipStream_t s) {
     const long P = (long)ctx->tab.n * ctx->tab.n;
     // all three workspaces before the first launch: a call that has to build one under capture leaves nothing behind
     int rc = prepare(ctx, batch, restart, s);
-    if (rc == HN_OK) rc = refine_prepare(ctx, batch, s);
-    if (rc == HN_OK) rc = f64_reserve(ctx, batch, true, s);
+    const bool lossy = pc.k_sq_im != nullptr;
+    if (rc == HN_OK) rc = refine_prepare(ctx, batch, s, lossy);
+    if (rc == HN_OK) rc = lossy ? f64_lossy_reserve(ctx, batch, true, s) : f64_reserve(ctx, batch, true, s);
     if (rc != HN_OK) return rc;
     const RefineWs& ws = *ctx->rfn;
     const long nk4 = (long)batch * P / 4, nr4 = (long)rhs_batch * 2 * P / 4;   // (n is a multiple of 16)
     const dim3 grid(ctx->kry->nchunk, batch), blk(256);
     hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + nr4 + 255) / 256)), blk, 0, s, k_sq, ws.ksq64, nk4, rhs, ws.rhs64, nr4);
-    if ((rc = f64_apply(ctx, x, ws.res64, ws.ksq64, ws.rhs64, rhs_batch, rmse64, batch, s)) != HN_OK) return rc;
+    if (lossy) {
+        hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + 255) / 256)), blk, 0, s, pc.k_sq_im, ws.ksq_im64, nk4, nullptr, nullptr, 0L);
+        rc = f64_apply_lossy(ctx, x, ws.res64, ws.ksq64, ws.ksq_im64, ws.rhs64, rhs_batch, rmse64, batch, s);
+    } else {
+        rc = f64_apply(ctx, x, ws.res64, ws.ksq64, ws.rhs64, rhs_batch, rmse64, batch, s);
+    }
+    if (rc != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_rhs, grid, blk, 0, s, ws.res64, rmse64, tol, (double)inner_floor, ws.rhs32, ws.d32, ws.tol, ws.stop, P);
     if ((rc = launch_cycle(ctx, Op::Forward, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, pc, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_update, grid, blk, 0, s, x, ws.d32, rmse64, k_used, P);
@@ -1006,4 +1021,31 @@ extern "C" int hn_fgmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq,
     if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
     return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{zbasis, precond_iters, precond_scale, who}, basis,
                             hess, rmse, k_used, rmse64, s);
+}
+
+extern "C" int hn_fgmres_refine_cycle_lossy(hn_ctx* ctx, double* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch,
+                                            int restart, double tol, float inner_floor, int precond_iters, float precond_scale, float* basis,
+                                            float* zbasis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
+    const char* who = "hn_fgmres_refine_cycle_lossy";
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_fgmres_refine_cycle)", who);
+    int rc = check_cycle_args(ctx, who, true, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, rmse64);
+    if (rc == HN_OK) rc = check_refine_tols(ctx, who, tol, inner_floor);
+    if (rc != HN_OK) return rc;
+    // (x is float64 here: k_sq_im against its second half and against rmse64, which check_cycle_k_sq_im does not see)
+    if ((rc = check_cycle_k_sq_im(ctx, who, k_sq_im, reinterpret_cast<const float*>(x), k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse,
+                                  k_used)) != HN_OK)
+        return rc;
+    {
+        const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
+        const MemRange r[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, {x, B * 2 * P * 8, true, "x"}, {rmse64, B * 8, true, "rmse64"}};
+        const char *na, *nb;
+        if (first_overlap(r, 3, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    }
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im)) != HN_OK) return rc;
+    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (precond_iters 0 has not asked hn_step_lossy)
+    Precond pc{zbasis, precond_iters, precond_scale, who};
+    pc.k_sq_im = k_sq_im;
+    return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, pc, basis, hess, rmse, k_used, rmse64, s);
 }

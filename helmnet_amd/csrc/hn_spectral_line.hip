@@ -497,6 +497,9 @@ int spec_rect_build(hn_ctx* ctx, int h, int w, int pml, double sigma_max, double
     ctx->rect = r;   // (a failure below leaves a domain whose launches are refused: line_domain checks the tables)
     r->h = h;
     r->w = w;
+    r->pml = pml;
+    r->sigma_max = sigma_max;
+    r->k = k;
     const AxisHost ah = spec_axis_host(h, pml, sigma_max, k), aw = spec_axis_host(w, pml, sigma_max, k);
     std::vector<float> sig((size_t)2 * h * w);
     for (int y = 0; y < h; ++y)

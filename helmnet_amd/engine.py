@@ -188,7 +188,7 @@ class Engine:
 
     def set_domain_rect(self, h: int, w: int, pml: int, sigma_max: float, k: float):
         """An h x w domain (hn_set_domain_rect): h rows by w columns, tensors [B, C, h, w].  h == w is ``set_domain(h, ...)`` itself.  On h != w the
-        operators, ``unet`` and ``step`` work in the 'fp32' and 'valu' precision modes; every other method that reads the domain raises
+        operators, ``unet`` and ``step`` work in the 'fp32' and 'valu' precision modes, and ``residual64_lossy`` in float64; every other method that reads the domain raises
         NotImplementedError naming the rectangular domain.  ``domain_key`` carries both sizes: ((h, w), pml, sigma_max, k)."""
         if int(h) == int(w):
             return self.set_domain(h, pml, sigma_max, k)
@@ -562,6 +562,40 @@ class Engine:
                                             self._stream())
         _lib.check(rc, self.ctx, "hn_fgmres_cycle_lossy")
         return rmse, k_used
+
+    def residual64_lossy(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, src: torch.Tensor, want_res: bool = True,
+                         want_rmse: bool = True):
+        """``residual64`` with the complex pointwise term (hn_residual_f64_lossy): (res [B,2,h,w] or None, rmse [B] or None), both float64, of
+        L(wf) + (k_sq + i k_sq_im) wf - src.  Square and rectangular domains; always the float64 FFT route."""
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, *self.hw), "wavefield", torch.float64)
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq", torch.float64)
+        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im", torch.float64)
+        self._chk(src, (src.shape[0], 2, *self.hw), "source", torch.float64)
+        res = torch.empty_like(wf) if want_res else None
+        rmse = torch.empty(b, device=self.device, dtype=torch.float64) if want_rmse else None
+        rc = self.lib.hn_residual_f64_lossy(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(k_sq_im), _ptr(src), src.shape[0], _ptr(res), _ptr(rmse), b,
+                                            self._stream())
+        _lib.check(rc, self.ctx, "hn_residual_f64_lossy")
+        return res, rmse
+
+    def fgmres_refine_cycle_lossy(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
+                                  precond_iters: int, precond_scale: float, inner_floor: float = 1e-6, basis: Optional[torch.Tensor] = None,
+                                  hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
+        """``fgmres_refine_cycle`` on the lossy operator (hn_fgmres_refine_cycle_lossy): the float64 residual of ``residual64_lossy``, the fp32 cycle of
+        ``fgmres_cycle_lossy``, the preconditioner ``step_lossy``.  Returns (rmse64, rmse, k_used).  Square domains.  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_refine_cycle_lossy", x, torch.float64, k_sq, rhs, restart, basis, hess)
+        if isinstance(k_sq_im, torch.Tensor) and k_sq_im.requires_grad:
+            raise RuntimeError("fgmres_refine_cycle_lossy: k_sq_im requires grad; the GMRES cycle is not differentiable")
+        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
+        zbasis = self._zbasis(b, restart, zbasis)
+        rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
+        rc = self.lib.hn_fgmres_refine_cycle_lossy(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rhs), rhs.shape[0], b, restart, float(tol),
+                                                   float(inner_floor), int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess),
+                                                   _ptr(rmse), _ptr(k_used), _ptr(rmse64), self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_refine_cycle_lossy")
+        return rmse64, rmse, k_used
 
     def residual_vjp_lossy(self, g: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor) -> torch.Tensor:
         """A^H g of the lossy operator (hn_residual_vjp_lossy): L^H(g) + (k_sq - i k_sq_im) g, the J^T g of ``residual_lossy`` with respect to the

@@ -173,6 +173,47 @@ def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor, pr
             "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
 
 
+def gmres_refine_lossy(solver, sos_maps: torch.Tensor, absorption, restart: int = 20, max_outer: int = 400, tol: float = 1e-10,
+                       x0: Optional[torch.Tensor] = None, inner_floor: float = 1e-6, precondition: Optional[str] = None, precond_iterations: int = 10,
+                       precond_scale: Optional[float] = None):
+    """GMRES to float64 accuracy on the LOSSY operator A u = L(u) + (k_sq + i k_sq_im) u (``absorption``: alpha, as in ``gmres``): the refinement of
+    ``gmres(backend="hip", refine=True)`` on hn_fgmres_refine_cycle_lossy -- per cycle the float64 lossy residual (hn_residual_f64_lossy's), the fp32
+    lossy cycle on the scaled correction equation (``precondition="learned"``: preconditioned by the lossy learned iteration; None: zero
+    preconditioner iterations, plain refined GMRES) and x += s d in float64.  Returns the dictionary of the lossless refinement.  Square domains;
+    no gradients."""
+    if absorption is None:
+        raise ValueError("gmres_refine_lossy needs absorption (a lossless medium is gmres(backend='hip', refine=True))")
+    if precondition not in (None, "learned"):
+        raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
+    if precondition is not None and int(precond_iterations) < 0:
+        raise ValueError(f"precond_iterations must be >= 0 (got {precond_iterations})")
+    restart, max_outer, tol, inner_floor = int(restart), int(max_outer), float(tol), float(inner_floor)
+    solver._refuse_lossy_grad("gmres64", sos_maps, absorption, x0)
+    solver._require_square("gmres64 with absorption")
+    iters, alpha = 0, 1.0
+    if precondition is not None:
+        iters, alpha = int(precond_iterations), default_precond_scale(solver.source) if precond_scale is None else float(precond_scale)
+    eng, (k_sq, k_sq_im), rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float64, absorption)
+    bsz, dev = x.shape[0], x.device
+    zbasis = torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
+
+    def cycle():
+        rmse64, rmse, k_used = eng.fgmres_refine_cycle_lossy(x, k_sq, k_sq_im, rhs, restart, tol, iters, alpha, inner_floor, basis, hess, zbasis)
+        both = torch.cat([rmse64, rmse.reshape(-1).double(), k_used.double()]).cpu().numpy()          # the one synchronisation of the cycle
+        eng.check_async_errors()
+        m = (restart + 1) * bsz
+        return both[:bsz], both[bsz: bsz + m].reshape(restart + 1, bsz), both[bsz + m:].astype(np.int64)
+
+    out = drive_refinement(cycle, max_outer, tol)
+    # converged: the last cycle checked the returned iterate and wrote nothing; else its last update is still unchecked
+    final = (torch.from_numpy(out["history"][-1]).to(dev) if out["converged"]
+             else eng.residual64_lossy(x, k_sq.double(), k_sq_im.double(), rhs.double(), False, True)[1])
+    return {"wavefield": x, "residual_norm64": final, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
+            "operator_applications": out["cycles"] * (restart + 1), "operator_applications64": out["cycles"], "converged": out["converged"],
+            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"],
+            "unet_evaluations": unet_evaluations(out["cycles"], restart, iters)}
+
+
 def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, absorption=None):
     """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own.
     ``precond`` (iterations, alpha): the flexible cycle (hn_fgmres_cycle).  ``absorption``: the lossy operator (hn_fgmres_cycle_lossy, with zero
@@ -331,13 +372,14 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
 
     ``absorption`` (alpha in nepers per grid point, a number or a tensor broadcastable to ``sos_maps``; helmnet_amd.absorption): the medium is lossy,
     k~ = omega / sos + i alpha, and the cycles run on hn_fgmres_cycle_lossy.  ``backend="hip"`` with ``precondition`` None or "learned"; the torch
-    backend raises ValueError, ``refine=True`` NotImplementedError (there is no float64 lossy operator).  The result gains ``cycles``.  None: the code
+    backend raises ValueError, ``refine=True`` NotImplementedError (the float64 lossy refinement is ``gmres_refine_lossy``).  The result gains ``cycles``.  None: the code
     path and the bits of before."""
     if absorption is not None:
         if backend != "hip":
             raise ValueError("absorption needs backend='hip' (the torch backend has the lossless operator only)")
         if refine:
-            raise NotImplementedError("gmres(refine=True) is not implemented with absorption: the library has no float64 lossy operator")
+            raise NotImplementedError("gmres(refine=True) is not implemented with absorption: the float64 lossy refinement is gmres_refine_lossy "
+                                      "(IterativeSolver.gmres64(absorption=...))")
     if refine and backend != "hip":
         raise ValueError("refine=True needs backend='hip'")
     if precondition not in (None, "learned"):

@@ -463,10 +463,19 @@ class IterativeSolver(nn.Module):
             return Residual.apply(self.engine(), x.float(), k_sq.float(), self._src_graph())
         return self.engine().residual(x.float().contiguous(), k_sq.float().contiguous(), self._src())
 
-    def get_residual64(self, wavefield: torch.Tensor, k_sq: torch.Tensor) -> torch.Tensor:
+    def get_residual64(self, wavefield: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The residual of ``get_residual`` evaluated in float64 on the GPU (the reference's ``solver.double().get_residual``), [B,2,n,n] float64.
-        fp32 inputs are up-cast exactly: the problem checked is the one with the fp32 ``k_sq`` and source the solver ran.  No gradients."""
+        fp32 inputs are up-cast exactly: the problem checked is the one with the fp32 ``k_sq`` and source the solver ran.  No gradients.
+        ``k_sq_im`` (extension, [B,1,H,W]): the lossy float64 residual L(x) + (k_sq + i k_sq_im) x - source (hn_residual_f64_lossy), on square and
+        rectangular domains; None: the code path and the bits of before."""
+        if k_sq_im is not None:
+            return self._residual64_lossy(wavefield, k_sq, k_sq_im, True, False)[0]
         return self._residual64(wavefield, k_sq, True, False)[0]
+
+    def _residual64_lossy(self, wavefield, k_sq, k_sq_im, want_res: bool, want_rmse: bool):
+        _require_no_grad("the float64 residual check", wavefield, k_sq, k_sq_im)
+        return self.engine().residual64_lossy(wavefield.double().contiguous(), k_sq.double().contiguous(), k_sq_im.double().contiguous(),
+                                              self.source.detach().double().contiguous(), want_res, want_rmse)
 
     def _residual64(self, wavefield, k_sq, want_res: bool, want_rmse: bool):
         _require_no_grad("the float64 residual check", wavefield, k_sq)
@@ -474,10 +483,16 @@ class IterativeSolver(nn.Module):
         return self.engine().residual64(wavefield.double().contiguous(), k_sq.double().contiguous(), self.source.detach().double().contiguous(),
                                         want_res, want_rmse)
 
-    def verify(self, wavefield: torch.Tensor, sos_maps: Optional[torch.Tensor] = None, k_sq: Optional[torch.Tensor] = None) -> dict:
+    def verify(self, wavefield: torch.Tensor, sos_maps: Optional[torch.Tensor] = None, k_sq: Optional[torch.Tensor] = None, absorption=None,
+               k_sq_im: Optional[torch.Tensor] = None) -> dict:
         """How far the fp32 residual norm of ``wavefield`` can be trusted.  Pass exactly one of ``sos_maps`` / ``k_sq`` (the fp32 problem the solver ran).
         Returns per sample: ``residual_norm64`` (float64 RMSE of the float64 residual), ``residual_norm32`` (what hn_residual + hn_rmse give) and
-        ``evaluator_error`` = RMSE of (fp32 residual - float64 residual), the floor below which an fp32 residual norm carries no information."""
+        ``evaluator_error`` = RMSE of (fp32 residual - float64 residual), the floor below which an fp32 residual norm carries no information.
+        Absorbing media: ``absorption`` (alpha, as in ``forward``) goes with ``sos_maps``, ``k_sq_im`` with ``k_sq``; any other pairing raises
+        ValueError.  The same three keys come from hn_residual_lossy and hn_residual_f64_lossy, on square and rectangular domains.  With both None:
+        the code path and the bits of before."""
+        if absorption is not None or k_sq_im is not None:
+            return self._verify_lossy(wavefield, sos_maps, k_sq, absorption, k_sq_im)
         self._require_square("verify")
         if (sos_maps is None) == (k_sq is None):
             raise ValueError("pass exactly one of sos_maps and k_sq")
@@ -488,6 +503,25 @@ class IterativeSolver(nn.Module):
         wf32, k32 = wavefield.float().contiguous(), k_sq.float().contiguous()
         res32 = eng.residual(wf32, k32, self._src())
         res64, norm64 = self._residual64(wavefield, k32, True, True)
+        diff = res32.double() - res64
+        return {"residual_norm64": norm64, "residual_norm32": eng.rmse(res32), "evaluator_error": diff.pow(2).mean((1, 2, 3)).sqrt()}
+
+    def _verify_lossy(self, wavefield, sos_maps, k_sq, absorption, k_sq_im) -> dict:
+        if (sos_maps is None) == (k_sq is None):
+            raise ValueError("pass exactly one of sos_maps and k_sq")
+        if absorption is not None and k_sq_im is not None:
+            raise ValueError("pass one of absorption (with sos_maps) and k_sq_im (with k_sq), not both")
+        if absorption is not None and sos_maps is None:
+            raise ValueError("absorption goes with sos_maps (with k_sq pass k_sq_im)")
+        if k_sq_im is not None and k_sq is None:
+            raise ValueError("k_sq_im goes with k_sq (with sos_maps pass absorption)")
+        self._refuse_lossy_grad("verify", wavefield, sos_maps, k_sq, absorption, k_sq_im)
+        if k_sq is None:
+            k_sq, k_sq_im, _ = self._lossy_initials("verify", sos_maps, absorption)
+        eng = self.engine()
+        wf32, k32, ki32 = wavefield.float().contiguous(), k_sq.float().contiguous(), k_sq_im.float().contiguous()
+        res32 = eng.residual_lossy(wf32, k32, ki32, self._src())
+        res64, norm64 = self._residual64_lossy(wavefield, k32, ki32, True, True)
         diff = res32.double() - res64
         return {"residual_norm64": norm64, "residual_norm32": eng.rmse(res32), "evaluator_error": diff.pow(2).mean((1, 2, 3)).sqrt()}
 
@@ -750,12 +784,13 @@ class IterativeSolver(nn.Module):
         ``norm_reduce`` (e.g. helmnet_amd.distributed.allreduce_residual_norms) the test is global over ranks.
         Returns wavefield, last residual, per-iteration RMSE trace [K, B], iterations run and whether it converged.  ``verify=True`` adds the keys of
         ``verify()`` for the final wavefield and ``converged64``: the worst float64 residual norm is below ``tol``.
-        ``absorption``: alpha, as in ``forward`` (None: the code path and the bits of before); there is no float64 lossy operator, so together
-        with ``verify=True`` it raises NotImplementedError."""
+        ``absorption``: alpha, as in ``forward`` (None: the code path and the bits of before); together with ``verify=True`` it raises
+        NotImplementedError: check the returned wavefield with ``verify(wavefield, sos_maps, absorption=...)``."""
         if max_iterations is None:
             max_iterations = self.hparams.max_iterations
         if verify and absorption is not None:
-            raise NotImplementedError("solve_to_tolerance(verify=True) is not implemented with absorption: the library has no float64 lossy operator")
+            raise NotImplementedError("solve_to_tolerance(verify=True) is not implemented with absorption: call verify(wavefield, sos_maps, "
+                                      "absorption=...) on the result")
         if verify:
             self._require_square("solve_to_tolerance(verify=True)")
         k_sq_im = None
@@ -803,14 +838,22 @@ class IterativeSolver(nn.Module):
                      precond_iterations=precond_iterations, precond_scale=precond_scale, absorption=absorption)
 
     def gmres64(self, sos_maps, restart: int = 20, max_cycles: int = 400, tol: float = 1e-10, x0=None, precondition=None, precond_iterations: int = 10,
-                precond_scale=None) -> dict:
+                precond_scale=None, absorption=None) -> dict:
         """GMRES to float64 accuracy on this solver's operator and source (the role MATLAB's double-precision ``gmres`` has in the reference,
         matlab/spectral_gmres_solver.m:86-115: the ground truth the learned solver is measured against): iterative refinement with the fused fp32
         restart cycle inside and the residual and the update in float64 (``helmnet_amd.gmres.gmres(backend="hip", refine=True)``).  ``tol`` is the
         float64 residual RMSE to reach; ``x0`` [B,2,n,n], fp32 or float64: the starting iterate, e.g. the learned solver's wavefield to be polished
         (default: zeros; it is not written).  Returns ``wavefield`` and ``residual_norms`` in float64.  ``precondition``, ``precond_iterations``,
-        ``precond_scale``: as ``gmres`` (the flexible cycle inside the refinement).  No gradients."""
-        from .gmres import gmres
+        ``precond_scale``: as ``gmres`` (the flexible cycle inside the refinement).  No gradients.
+        ``absorption`` (alpha, as in ``gmres``): the lossy operator in the float64 residual, the fp32 cycle and the preconditioner
+        (``helmnet_amd.gmres.gmres_refine_lossy``, hn_fgmres_refine_cycle_lossy); the same dictionary comes back.  None: the code path and the bits
+        of before."""
+        from .gmres import gmres, gmres_refine_lossy
+        if absorption is not None:
+            self._refuse_lossy_grad("gmres64", sos_maps, absorption, x0)
+            self._require_square("gmres64")
+            return gmres_refine_lossy(self, sos_maps, absorption, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, precondition=precondition,
+                                      precond_iterations=precond_iterations, precond_scale=precond_scale)
         self._require_square("gmres64")
         return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", refine=True, precondition=precondition,
                      precond_iterations=precond_iterations, precond_scale=precond_scale)
@@ -878,15 +921,18 @@ class IterativeSolver(nn.Module):
         return out
 
     def reference_error(self, wavefield, sos_maps, tol: float = 1e-10, restart: int = 20, max_cycles: int = 400, precondition=None,
-                        precond_iterations: int = 10, precond_scale=None) -> dict:
+                        precond_iterations: int = 10, precond_scale=None, absorption=None) -> dict:
         """How far ``wavefield`` [B,2,n,n] is from the solution of the discrete problem: ``gmres64`` started from it is the ground truth.  Returns per
         sample ``linf`` (max |wavefield - reference| over both planes) and ``rms`` of the same difference, ``reference_rmse64`` (the float64
         residual RMSE of the reference: how good the ground truth is; below ``tol`` when ``converged``), ``reference`` (the float64 wavefield),
-        ``converged`` and ``cycles``.  ``wavefield`` is not written."""
+        ``converged`` and ``cycles``.  ``wavefield`` is not written.  ``absorption``: the lossy problem, as in ``gmres64``."""
+        if absorption is not None:
+            self._refuse_lossy_grad("reference_error", wavefield, sos_maps, absorption)
         _require_no_grad("reference_error", wavefield, sos_maps)
         self._require_square("reference_error")
+        lossy = {} if absorption is None else {"absorption": absorption}
         out = self.gmres64(sos_maps, restart=restart, max_cycles=max_cycles, tol=tol, x0=wavefield, precondition=precondition,
-                           precond_iterations=precond_iterations, precond_scale=precond_scale)
+                           precond_iterations=precond_iterations, precond_scale=precond_scale, **lossy)
         ref = out["wavefield"]
         diff = wavefield.detach().to(ref.device).double() - ref
         return {"linf": diff.abs().amax((1, 2, 3)), "rms": diff.pow(2).mean((1, 2, 3)).sqrt(), "reference_rmse64": out["residual_norm64"],

@@ -534,7 +534,8 @@ int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq
  * rounding, not bit for bit (another factorisation of the transforms).
  * Adjoint-state gradients of a converged lossy solve have the chain the lossless operator has: hn_residual_vjp_lossy (A^H g), hn_fgmres_adjoint_cycle_lossy
  * (A^H lambda = g) and hn_adjoint_grad_lossy (dJ/dk_sq, dJ/dk_sq_im, dJ/dsrc), further down.
- * No entry point exists for: gradients through the solver loop (a lossy hn_step_vjp / hn_step_jvp), the float64 operator and refinement, training. */
+ * The float64 half -- the residual check and GMRES to float64 accuracy -- is hn_residual_f64_lossy and hn_fgmres_refine_cycle_lossy, further down.
+ * No entry point exists for: gradients through the solver loop (a lossy hn_step_vjp / hn_step_jvp), a lossy hn_step_f64, training. */
 
 /* hn_residual with the complex pointwise term; every legal square size and every rectangular domain.  HN_ERR_ARG "hn_residual_lossy: k_sq_im overlaps res". */
 int hn_residual_lossy(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, float* res, int batch,
@@ -581,6 +582,31 @@ int hn_fgmres_adjoint_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, cons
  * (HN_ERR_UNSUPPORTED on a rectangular domain).  A refused call leaves the outputs alone. */
 int hn_adjoint_grad_lossy(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_k_sq_im, float* g_src,
                           void* stream);
+
+/* ---- absorbing media in float64 (added within ABI v7: new entry points, nothing existing changes) ----
+ * hn_residual_f64_lossy: res = L(wf) + (k_sq + i k_sq_im) wf - src in float64, hn_residual_f64's contract (res and / or rmse, the fixed-order
+ * bit-reproducible sum, a first or growing call under stream capture HN_ERR_STATE with nothing enqueued, later calls capturable, wf may not overlap res,
+ * 8-byte alignment) on every legal square size AND every rectangular domain, tensors [B,.,h,w].  It always runs the two float64 line passes (the FFT
+ * route; there is no lossy dense kernel), whatever HN_OPT_F64_FFT says, and HN_CNT_F64_ROUTE reads 2 afterwards; on a square domain the dense route's
+ * tables and bits are untouched and coexist with it.  On an h x w domain the column pass transforms w lines of length h with the y tables and the row
+ * pass h lines of length w with the x tables; each pass has its own lines per block and LDS.  The lossy term is applied to the finished lossless value
+ * (re -= k_sq_im * wf_im, im += k_sq_im * wf_re), so with k_sq_im == 0 res and rmse are bit for bit hn_residual_f64's on the FFT route (finite inputs).
+ * k_sq_im: [B,1,h,w] double, read only; NULL returns HN_ERR_ARG with a message that names hn_residual_f64; overlapping res returns HN_ERR_ARG.  What
+ * the first call builds is freed by hn_set_domain / hn_set_domain_rect / hn_destroy.
+ * [measured, MI355X, profiles/f64_lossy_bench.txt] lossy / lossless time on the FFT route (res + rmse, alternating in one process): 1.009 at
+ * 256^2 x 32 (0.106 ms), 1.013 at 512^2 x 16 (0.258 ms), 1.029 at 2048^2 x 1 (0.470 ms): the one more plane read; 256 x 1024 x 8: 0.130 ms. */
+int hn_residual_f64_lossy(hn_ctx* ctx, const double* wf, const double* k_sq, const double* k_sq_im, const double* src, int src_batch,
+                          double* res, double* rmse, int batch, void* stream);
+
+/* hn_fgmres_refine_cycle with the lossy operator in all three places: the float64 residual (hn_residual_f64_lossy's, k_sq_im up-cast exactly beside
+ * k_sq), the fp32 cycle (hn_fgmres_cycle_lossy's launches) and the preconditioner (hn_step_lossy); precond_iters == 0 is plain refined GMRES.  rmse64
+ * is bit for bit hn_residual_f64_lossy's; basis, zbasis, hess, rmse and k_used are bit for bit hn_fgmres_cycle_lossy's on the scaled right-hand side
+ * from x = 0.  Square domains only (HN_ERR_UNSUPPORTED on a rectangular one).  Every other refusal, the workspaces and "not capturable" are
+ * hn_fgmres_refine_cycle's; k_sq_im must be 16-byte aligned and overlap no other argument, as k_sq; NULL returns HN_ERR_ARG with a message that names
+ * hn_fgmres_refine_cycle. */
+int hn_fgmres_refine_cycle_lossy(hn_ctx* ctx, double* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch, int restart,
+                                 double tol, float inner_floor, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
+                                 float* rmse, int32_t* k_used, double* rmse64, void* stream);
 
 /* ---- training step (hybridnet.py:385-413 training_step, :250-283 configure_optimizers, :172-176
  * on_after_backward).  The caller owns every training tensor: the weights as ONE flat device blob in the order of
