@@ -746,6 +746,27 @@ int hn_residual_lossy(hn_ctx* ctx, const float* wf, const float* k_sq, const flo
     return spec_apply_lossy(ctx, who, wf, res, k_sq, k_sq_im, src, src_batch, batch, nullptr, (hipStream_t)stream);
 }
 
+int hn_residual_medium(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* src, int src_batch,
+                       float* res, int batch, void* stream) {
+    const char* who = "hn_residual_medium";
+    if (ctx && !rho_grad)
+        return fail(ctx, HN_ERR_ARG, "%s: rho_grad is NULL (a medium of constant density is hn_residual_lossy, or hn_residual without absorption)", who);
+    if (!ctx || !wf || !k_sq || !src || !res) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
+    if (src_batch != 1 && src_batch != batch)
+        return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
+    {
+        const size_t plane = (size_t)ctx->geo.plane();
+        const MemRange r[] = {{k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
+                              {rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"},
+                              {res, sizeof(float) * (size_t)batch * 2 * plane, true, "res"}};
+        const char *a, *b;
+        if (first_overlap(r, 3, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
+    }
+    DeviceGuard guard(ctx);
+    return spec_apply_medium(ctx, who, wf, res, k_sq, k_sq_im, rho_grad, src, src_batch, batch, nullptr, (hipStream_t)stream);
+}
+
 int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, int batch, void* stream) {
     if (!ctx || !g || !k_sq || !out) return fail(ctx, HN_ERR_ARG, "hn_residual_vjp: NULL argument");
     if (ctx->rect) return rect_unsupported(ctx, "hn_residual_vjp");
@@ -861,6 +882,7 @@ struct StepArgs {
     float* rmse_hist;   // base of the [n_iter, batch] table (rows are selected on the device through it_counter)
     bool side_stream;   // the hidden-state kernels may leave the main chain for the lane's side stream (hn_step's route)
     const float* k_sq_im = nullptr;   // non-null (hn_step_lossy): the residual is the lossy operator's, spec_apply_lossy
+    const float* rho_grad = nullptr;  // non-null (hn_step_medium): the residual is the variable-density operator's, spec_apply_medium; k_sq_im may be null
 };
 
 __global__ void k_probe_spin(long ticks) {
@@ -1016,6 +1038,10 @@ int one_iteration(hn_ctx* ctx, const StepArgs& a, int parity, int b0, int nb, in
     int rc = unet_forward(ctx, c);
     if (rc != HN_OK) return rc;
     const float* src_j = a.src_batch == 1 ? a.src : a.src + (size_t)b0 * 2 * plane;
+    if (a.rho_grad != nullptr)
+        return spec_apply_medium(ctx, "hn_step_medium", wf_j, res_j, a.k_sq + (size_t)b0 * plane, a.k_sq_im ? a.k_sq_im + (size_t)b0 * plane : nullptr,
+                                 a.rho_grad + (size_t)b0 * 2 * plane, src_j, a.src_batch == 1 ? 1 : nb, nb, a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj,
+                                 a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
     if (a.k_sq_im != nullptr)
         return spec_apply_lossy(ctx, "hn_step_lossy", wf_j, res_j, a.k_sq + (size_t)b0 * plane, a.k_sq_im + (size_t)b0 * plane, src_j,
                                 a.src_batch == 1 ? 1 : nb, nb, a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj,
@@ -1094,16 +1120,20 @@ namespace hn {
 namespace {
 
 // hn_step (k_sq_im nullptr, who "hn_step": every check, launch and message of before) and hn_step_lossy (k_sq_im non-null: the same UNet launches, the
-// residual by spec_apply_lossy; one lane, never a captured iteration)
+// residual by spec_apply_lossy; one lane, never a captured iteration) and hn_step_medium (rho_grad non-null, k_sq_im nullable: as the lossy loop, the
+// residual by spec_apply_medium)
 int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* src, int src_batch,
-               int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
-    const bool lossy = k_sq_im != nullptr;
+               int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream, const float* rho_grad = nullptr) {
+    const bool medium = rho_grad != nullptr;
+    const bool lossy = k_sq_im != nullptr || medium;   // the LDS-line residual and its route
     if (!ctx || !wf || !res || !states || !k_sq || !src) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (n_iter < 0) return fail(ctx, HN_ERR_ARG, "n_iter must be >= 0");
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
     int rc = check_ready_unet(ctx, who, batch);
     if (rc != HN_OK) return rc;
+    if (medium && ctx->opt_lanes > 1)
+        return fail(ctx, HN_ERR_UNSUPPORTED, "%s: HN_OPT_LANES %d is not implemented for the variable-density loop (one lane only)", who, ctx->opt_lanes);
     if (lossy && ctx->opt_lanes > 1)
         return fail(ctx, HN_ERR_UNSUPPORTED, "%s: HN_OPT_LANES %d is not implemented for the lossy loop (one lane only)", who, ctx->opt_lanes);
     // The route.  A rectangular domain takes the plainest one whatever the options say: one lane, every kernel launched on the caller's stream (no side
@@ -1128,16 +1158,18 @@ int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* state
                               {src, sizeof(float) * (size_t)src_batch * 2 * plane, false, "src"}, {res_hist, it * fc, true, "res_hist"},
                               {wf_hist, it * fc, true, "wf_hist"}, {st_hist, it * sc, true, "st_hist"},
                               {rmse_hist, sizeof(float) * it * batch, true, "rmse_hist"},
-                              {k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}};
+                              {k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
+                              {rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"}};
         const char *one, *other;
-        if (first_overlap(r, 10, &one, &other)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, one, other);
+        if (first_overlap(r, 11, &one, &other)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, one, other);
     }
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     if (lossy && (rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (before the workspace: a refused call builds nothing)
     if ((rc = reserve_workspace(ctx, batch, s)) != HN_OK) return rc;
     if (n_iter == 0) return HN_OK;
-    if ((rc = check_async(ctx, lossy ? "hn_step_lossy (an earlier call)" : "hn_step (an earlier call)")) != HN_OK) return rc;
+    if ((rc = check_async(ctx, medium ? "hn_step_medium (an earlier call)" : lossy ? "hn_step_lossy (an earlier call)" : "hn_step (an earlier call)")) != HN_OK)
+        return rc;
     int ns = ctx->opt_lanes;
     if (batch < 2 * ns) ns = 1;                       // tiny batches: not worth splitting
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
@@ -1147,7 +1179,7 @@ int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* state
         if ((rc = zero_async(ctx, rmse_hist, sizeof(float) * (size_t)n_iter * batch, s)) != HN_OK) return rc;
         if ((rc = zero_async(ctx, ctx->it_counter, 8 * sizeof(int), s)) != HN_OK) return rc;
     }
-    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist, use_side, k_sq_im};
+    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist, use_side, k_sq_im, rho_grad};
     const size_t fb_all = sizeof(float) * (size_t)batch * 2 * plane, sb_all = sizeof(float) * (size_t)batch * kState * L;
     if (ns == 1) {
         // One lane: an iteration is a fixed kernel sequence over fixed buffers (the hidden states ping-pong between the
@@ -1269,6 +1301,14 @@ int hn_step_lossy(hn_ctx* ctx, float* wf, float* res, float* states, const float
                   int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
     if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_step_lossy: k_sq_im is NULL (a lossless medium is hn_step)");
     return step_entry(ctx, "hn_step_lossy", wf, res, states, k_sq, k_sq_im, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
+}
+
+int hn_step_medium(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* src,
+                   int src_batch, int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
+    if (ctx && !rho_grad)
+        return fail(ctx, HN_ERR_ARG, "hn_step_medium: rho_grad is NULL (a medium of constant density is hn_step_lossy, or hn_step without absorption)");
+    return step_entry(ctx, "hn_step_medium", wf, res, states, k_sq, k_sq_im, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream,
+                      rho_grad);
 }
 
 // Laboratory accessor (tools/deepx_check.py; not part of the ABI of include/helmnet_hip.h): the workspace tensor kind (0 x_d / upsampled, 1 skip out_d,

@@ -563,6 +563,10 @@ int spec_line_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq,
 int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s);
 int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
                      int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
+// variable density: out = L(wf) - b_x q_x d_x wf - b_y q_y d_y wf + (ksq [+ i ksq_im]) wf - src, q = rho_grad [B][2][h][w] (plane 0 along x, plane 1 along y);
+// ksq_im may be null (then it is not read); tables, reserve rule and the remaining arguments as spec_apply_lossy
+int spec_apply_medium(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* rho_grad, const float* src,
+                      int src_batch, int batch, float* sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
 // out = A^H g [+ add] = L^H(g) + (ksq - i ksq_im) g [+ add], the adjoint of the operator above on the same kernel and tables (g != out; `add` may alias out)
 int spec_adjoint_lossy(hn_ctx* ctx, const char* who, const float* g, float* out, const float* ksq, const float* ksq_im, const float* add, int batch,
                        hipStream_t s);

@@ -503,6 +503,8 @@ struct Precond {
     const char* who = "";      // the entry point, for what hn_step reports from inside the cycle
     const float* k_sq_im = nullptr;   // non-null (hn_fgmres_cycle_lossy, hn_fgmres_adjoint_cycle_lossy): A is the lossy operator (Op::Adjoint: its A^H)
                                       // and the learned iteration hn_step_lossy, also with iters 0
+    const float* rho_grad = nullptr;  // non-null (hn_fgmres_cycle_medium, Op::Forward only): A is the variable-density operator and the learned iteration
+                                      // hn_step_medium; k_sq_im may then be null
 };
 
 // what hn_step reported, under the name of the entry point that called it
@@ -520,7 +522,7 @@ void precond_ws_free(hn_ctx* ctx) {
 }
 
 // the learned preconditioner's problem for `batch` samples on the current domain and network -- the caller has refused stream capture
-int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, const float* k_sq_im, int batch, hipStream_t s) {
+int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, const float* k_sq_im, int batch, hipStream_t s, const float* rho_grad = nullptr) {
     const int n = ctx->tab.n;
     PrecondWs* ws = ctx->pcw;
     if (ws == nullptr || ws->n != n || ws->state_len != ctx->state_len || batch > ws->batch) {
@@ -537,6 +539,9 @@ int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, const float
     }
     // hn_step's own refusals (a domain the network's depth does not divide) and its workspace now, with nothing enqueued: the call of the cycle with
     // zero iterations, which launches nothing
+    if (rho_grad != nullptr)
+        return step_named(ctx, who, hn_step_medium(ctx, ws->wf, ws->res, ws->states, k_sq, k_sq_im, rho_grad, ws->src, batch, batch, 0, nullptr, nullptr, nullptr,
+                                                   nullptr, s));
     if (k_sq_im != nullptr)
         return step_named(ctx, who, hn_step_lossy(ctx, ws->wf, ws->res, ws->states, k_sq, k_sq_im, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
     return step_named(ctx, who, hn_step(ctx, ws->wf, ws->res, ws->states, k_sq, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
@@ -633,8 +638,13 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
                 tol, 1.0 / sqrt(2.0 * (double)P), tol_dev, pre_stopped};
     const bool adj = op == Op::Adjoint;
     const float* k_im = pc.k_sq_im;
+    const float* rho = pc.rho_grad;
+    if (rho != nullptr && adj) return fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator has no adjoint cycle", pc.who);
     // w = A x - rhs = -r
-    if (k_im != nullptr && adj) {
+    if (rho != nullptr) {
+        if ((rc = spec_apply_medium(ctx, pc.who, x, ws.w, k_sq, k_im, rho, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
+        hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
+    } else if (k_im != nullptr && adj) {
         if ((rc = spec_adjoint_lossy(ctx, pc.who, x, ws.w, k_sq, k_im, nullptr, batch, s)) != HN_OK) return rc;
         hipLaunchKernelGGL(k_minus_rhs, grid, blk, 0, s, ws.w, rhs, rhs_batch == 1 ? 0L : 2 * P, ws.npart, P, nchunk);
     } else if (k_im != nullptr) {
@@ -655,7 +665,8 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
             if (adj) hipLaunchKernelGGL(k_seed_adj, grid, blk, 0, s, ws.vin, ctx->adjw->winv, pc.alpha, p.src, p.res, p.wf, P);
             else hipLaunchKernelGGL(k_seed, grid, blk, 0, s, ws.vin, pc.alpha, p.src, p.res, p.wf, P);
             if ((rc = zero_async(ctx, p.states, sizeof(float) * (size_t)batch * kState * (size_t)p.state_len, s)) != HN_OK) return rc;
-            rc = k_im != nullptr ? hn_step_lossy(ctx, p.wf, p.res, p.states, k_sq, k_im, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s)
+            rc = rho != nullptr  ? hn_step_medium(ctx, p.wf, p.res, p.states, k_sq, k_im, rho, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s)
+               : k_im != nullptr ? hn_step_lossy(ctx, p.wf, p.res, p.states, k_sq, k_im, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s)
                                  : hn_step(ctx, p.wf, p.res, p.states, k_sq, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s);
             if (rc != HN_OK) return step_named(ctx, pc.who, rc);
             if (adj) hipLaunchKernelGGL(k_take_adj, grid, blk, 0, s, p.wf, ctx->adjw->w, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
@@ -663,7 +674,8 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
         } else if (pc.zbasis != nullptr) {
             hipLaunchKernelGGL(k_take_copy, grid, blk, 0, s, ws.vin, pc.zbasis, P, k, restart);
         }
-        rc = k_im != nullptr && adj ? spec_adjoint_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, nullptr, batch, s)
+        rc = rho != nullptr         ? spec_apply_medium(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, rho, ws.zero, 1, batch, nullptr, s)
+             : k_im != nullptr && adj ? spec_adjoint_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, nullptr, batch, s)
              : k_im != nullptr      ? spec_apply_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, ws.zero, 1, batch, nullptr, s)
              : adj                  ? spec_adjoint(ctx, ws.vin, ws.w, k_sq, nullptr, batch, s)
                                     : spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s);
@@ -811,30 +823,36 @@ int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, c
 // What the two flexible entry points refuse beyond check_cycle_args, and the preconditioner's workspace: nothing is enqueued before this has passed.
 // Not capturable: hn_step's first call on a new stream probes its side stream and synchronises.
 int check_precond(hn_ctx* ctx, const char* who, int precond_iters, float precond_scale, const float* k_sq, int batch, hipStream_t s,
-                  const float* k_sq_im = nullptr) {
+                  const float* k_sq_im = nullptr, const float* rho_grad = nullptr) {
     if (precond_iters < 0) return fail(ctx, HN_ERR_ARG, "%s: precond_iters must be >= 0 (got %d)", who, precond_iters);
     if (!(precond_scale > 0.f) || !(precond_scale <= 3.402823466e38f))
         return fail(ctx, HN_ERR_ARG, "%s: precond_scale must be finite and > 0 (got %g)", who, (double)precond_scale);
     if (stream_capturing(s)) return fail(ctx, HN_ERR_STATE, "%s: not capturable (the preconditioner calls hn_step, whose first call on a stream synchronises)", who);
     if (precond_iters == 0) return HN_OK;
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "%s: hn_load_weights has not been called (precond_iters %d needs the network)", who, precond_iters);
-    return precond_prepare(ctx, who, k_sq, k_sq_im, batch, s);
+    return precond_prepare(ctx, who, k_sq, k_sq_im, batch, s, rho_grad);
 }
 
-// k_sq_im of the two lossy cycles by k_sq's rules, after check_cycle_args: 16-byte aligned, overlapping none of the other arguments
-int check_cycle_k_sq_im(hn_ctx* ctx, const char* who, const float* k_sq_im, const float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch,
-                        int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used) {
+// A further read-only field of `planes` planes per sample (k_sq_im of the lossy cycles, rho_grad of the variable-density one) by k_sq's rules, after
+// check_cycle_args: 16-byte aligned, overlapping none of the other arguments
+int check_cycle_field(hn_ctx* ctx, const char* who, const char* name, int planes, const float* field, const float* x, const float* k_sq, const float* rhs,
+                      int rhs_batch, int batch, int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse,
+                      const int32_t* k_used) {
     const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
-    if (reinterpret_cast<uintptr_t>(k_sq_im) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is not 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(field) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, name);
     const MemRange others[] = {{x, B * 2 * P * 4, true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
                                {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
                                {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"}};
     for (const MemRange& o : others) {
-        const MemRange pair[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, o};
+        const MemRange pair[] = {{field, B * (size_t)planes * P * 4, true, name}, o};
         const char *na, *nb;
         if (first_overlap(pair, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     }
     return HN_OK;
+}
+int check_cycle_k_sq_im(hn_ctx* ctx, const char* who, const float* k_sq_im, const float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch,
+                        int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used) {
+    return check_cycle_field(ctx, who, "k_sq_im", 1, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used);
 }
 
 // hn_gmres_cycle and hn_fgmres_cycle, the arguments checked
@@ -927,6 +945,34 @@ extern "C" int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, c
     if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (precond_iters 0 has not asked hn_step_lossy)
     Precond pc{zbasis, precond_iters, precond_scale, who};
     pc.k_sq_im = k_sq_im;
+    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
+}
+
+extern "C" int hn_fgmres_cycle_medium(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* rhs, int rhs_batch,
+                                      int batch, int restart, float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
+                                      float* rmse, int32_t* k_used, void* stream) {
+    const char* who = "hn_fgmres_cycle_medium";
+    if (ctx && !rho_grad)
+        return fail(ctx, HN_ERR_ARG, "%s: rho_grad is NULL (a medium of constant density is hn_fgmres_cycle_lossy, or hn_fgmres_cycle without absorption)", who);
+    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
+    if (rc != HN_OK) return rc;
+    if (k_sq_im != nullptr &&
+        (rc = check_cycle_k_sq_im(ctx, who, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK)
+        return rc;
+    if ((rc = check_cycle_field(ctx, who, "rho_grad", 2, rho_grad, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK) return rc;
+    {
+        const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
+        const MemRange pair[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, {rho_grad, B * 2 * P * 4, true, "rho_grad"}};
+        const char *na, *nb;
+        if (first_overlap(pair, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    }
+    DeviceGuard guard(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im, rho_grad)) != HN_OK) return rc;
+    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (precond_iters 0 has not asked hn_step_medium)
+    Precond pc{zbasis, precond_iters, precond_scale, who};
+    pc.k_sq_im = k_sq_im;
+    pc.rho_grad = rho_grad;
     return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
 }
 

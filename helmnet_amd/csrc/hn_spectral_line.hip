@@ -4,6 +4,7 @@
 //       k_spec_pfa<Q, P> (P = 3, 5, 7 held in registers) of hn_spectral.hip take, and that otherwise run the dense n x n operator; forward and adjoint
 //   a rectangular h x w domain (hn_set_domain_rect, h != w): each axis factored on its own, with its own tables; the lossless operator forward only
 //   the lossy operator (complex k_sq) on either kind of domain; forward and adjoint
+//       and on its tables the variable-density operator (rho_grad: a - q b on the first derivative in step 6, one more plane read per pass); forward only
 // Line length, line count and row pitch are three arguments:
 //   column pass   lines of length h, w of them, element stride w:   out  = ay d/dy + by d2/dy2
 //   row pass      lines of length w, h of them:                      out += ax d/dx + bx d2/dx2 [+ k_sq u - src], per-sample sum of squares
@@ -159,12 +160,19 @@ struct LineTabs {
 // forward (hn_residual_lossy / hn_step_lossy / hn_fgmres_cycle_lossy), conj(ksq + i ksq_im) g with ADJ (hn_residual_vjp_lossy /
 // hn_fgmres_adjoint_cycle_lossy).  The pack stands in front of `add` (legal: every use names the template arguments) so that the forward
 // kernels' arguments keep the offsets they had before `add` existed.
+// KsqIm of TWO pointers, (ksq_im, rho_grad): the forward passes of the variable-density operator (hn_residual_medium / hn_step_medium /
+// hn_fgmres_cycle_medium).  rho_grad is [B][2][h][w], q = d ln rho along x in plane 0 and along y in plane 1; the pass of AXIS reads plane AXIS at the
+// element it stores, and step 6 multiplies the first derivative with a[i] - q b[i] instead of a[i]: rho (1/gamma) d((1/rho)(1/gamma) du) in expanded
+// form is a du + b d2u - b q du.  ksq_im may then be null (a lossless medium: the plane is not read, the pointwise term is the lossless kernels');
+// the column pass is handed null.  Nothing else differs: no further LDS, no further transform.
 template <int AXIS, bool ADJ, typename... KsqIm>
 __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restrict__ wf, float* out, const float* __restrict__ ksq,
                                                             const float* __restrict__ src, long src_sb, LineTabs t, int len, int count, int pitch, int P,
                                                             int logq, int logl, int flags, float* __restrict__ sumsq,
                                                             const int* __restrict__ it_counter, int sumsq_stride, KsqIm... ksq_im, const float* add) {
     constexpr int NF = ADJ ? 2 : 1;       // buffers through the forward transforms
+    constexpr bool RHO = sizeof...(KsqIm) == 2;
+    static_assert(sizeof...(KsqIm) <= 2 && !(RHO && ADJ), "k_spec_line: (ksq_im) or, forward only, (ksq_im, rho_grad)");
     extern __shared__ float2 lbuf[];
     __shared__ float red[kLineThreads / 64];
     const int tid = threadIdx.x, b = blockIdx.y;
@@ -280,6 +288,12 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
         float2 v;
         if constexpr (ADJ) {                    // (the coefficients went in with the load)
             v = B0[sl];
+        } else if constexpr (RHO) {             // a - q b on the first derivative, q from this axis' plane at the element stored below
+            const float* const kr[] = {ksq_im...};
+            const float q = kr[1][((long)b * 2 + AXIS) * plane + (AXIS == 0 ? (long)line * pitch + i : (long)i * pitch + line)];
+            const float2 ca = t.a[i], cb = t.b[i];
+            const float2 p = cmul(make_float2(ca.x - q * cb.x, ca.y - q * cb.y), D1[sl]), r = cmul(cb, D2[sl]);
+            v = make_float2(p.x + r.x, p.y + r.y);
         } else {
             const float2 p = cmul(t.a[i], D1[sl]), r = cmul(t.b[i], D2[sl]);
             v = make_float2(p.x + r.x, p.y + r.y);
@@ -293,14 +307,19 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
                 const float kq = ksq[(long)b * plane + o];
                 if constexpr (sizeof...(KsqIm) != 0) {
                     const float* const kim[] = {ksq_im...};
-                    const float ki = kim[0][(long)b * plane + o];
-                    const float ur = pre[o], ui = pre[o + plane];
-                    if constexpr (!ADJ) {
-                        re = re + (kq * ur - ki * ui);
-                        im = im + (kq * ui + ki * ur);
-                    } else {                        // conj(ksq + i ksq_im) g: `pre` is the cotangent
-                        re = re + (kq * ur + ki * ui);
-                        im = im + (kq * ui - ki * ur);
+                    if (RHO && kim[0] == nullptr) { // a lossless medium with density: the branch below
+                        re = re + kq * pre[o];
+                        im = im + kq * pre[o + plane];
+                    } else {
+                        const float ki = kim[0][(long)b * plane + o];
+                        const float ur = pre[o], ui = pre[o + plane];
+                        if constexpr (!ADJ) {
+                            re = re + (kq * ur - ki * ui);
+                            im = im + (kq * ui + ki * ur);
+                        } else {                    // conj(ksq + i ksq_im) g: `pre` is the cotangent
+                            re = re + (kq * ur + ki * ui);
+                            im = im + (kq * ui - ki * ur);
+                        }
                     }
                 } else {
                     re = re + kq * pre[o];          // the line itself again (an L2 hit) instead of a copy held through the transforms
@@ -355,7 +374,9 @@ int rect_lines(int len, int count, int nbuf, int batch) {
 int line_kernels_lds_attr(hn_ctx* ctx) {
     for (const void* k : {reinterpret_cast<const void*>(k_spec_line<1, false>), reinterpret_cast<const void*>(k_spec_line<0, false>),
                           reinterpret_cast<const void*>(k_spec_line<0, false, const float*>), reinterpret_cast<const void*>(k_spec_line<1, true>),
-                          reinterpret_cast<const void*>(k_spec_line<0, true>), reinterpret_cast<const void*>(k_spec_line<0, true, const float*>)})
+                          reinterpret_cast<const void*>(k_spec_line<0, true>), reinterpret_cast<const void*>(k_spec_line<0, true, const float*>),
+                          reinterpret_cast<const void*>(k_spec_line<1, false, const float*, const float*>),
+                          reinterpret_cast<const void*>(k_spec_line<0, false, const float*, const float*>)})
         HN_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLineLdsAttr));
     return HN_OK;
 }
@@ -417,12 +438,16 @@ bool line_domain(const hn_ctx* ctx, LineDomain* d) {
 //   forward           ksq nullptr: the Laplacian alone; ksq_im non-null (ksq too): the row pass with the complex pointwise term
 //   adj               out = L^H(wf) + ksq wf [+ add]: three buffers, `add` on the column pass, no sum of squares; ksq_im non-null: the row pass with the
 //                     conjugate pointwise term, conj(ksq + i ksq_im) wf
+//   rho_grad          non-null (forward, with ksq; ksq_im may be null): both passes of the variable-density operator
 int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
-                int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride, bool adj = false, const float* add = nullptr) {
+                int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride, bool adj = false, const float* add = nullptr,
+                const float* rho_grad = nullptr) {
     const LineAxis &cols = *d.cols, &rows = *d.rows;
     const int h = d.h, w = d.w;
     if (adj && (ksq == nullptr || src != nullptr || sumsq != nullptr || it_counter != nullptr))
         return fail(ctx, HN_ERR_ARG, "internal: the adjoint LDS-line kernels (%d x %d) take k_sq and neither a source, a sum of squares nor a counter", h, w);
+    if (rho_grad != nullptr && (adj || ksq == nullptr))
+        return fail(ctx, HN_ERR_ARG, "internal: the variable-density LDS-line kernels (%d x %d) are forward only and take k_sq", h, w);
     const bool resid = ksq != nullptr;
     const long src_sb = src_batch == 1 ? 0 : 2L * h * w;
     const int nbuf_c = adj || cols.P == 1 ? 3 : 4, nbuf_r = adj || rows.P == 1 ? 3 : 4;
@@ -442,6 +467,9 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
         if (adj)
             hipLaunchKernelGGL((k_spec_line<1, true>), grid_c, block, lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, cols.P, logq_c, logl_c, 0, nullptr,
                                nullptr, 0, add);
+        else if (rho_grad != nullptr)
+            hipLaunchKernelGGL((k_spec_line<1, false, const float*, const float*>), grid_c, block, lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, cols.P,
+                               logq_c, logl_c, 0, nullptr, nullptr, 0, nullptr, rho_grad, nullptr);
         else
             hipLaunchKernelGGL((k_spec_line<1, false>), grid_c, block, lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, cols.P, logq_c, logl_c, 0, nullptr,
                                nullptr, 0, nullptr);
@@ -451,6 +479,9 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
         if (adj && ksq_im != nullptr)
             hipLaunchKernelGGL((k_spec_line<0, true, const float*>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P, logq_r, logl_r,
                                rflags, sumsq, it_counter, sumsq_stride, ksq_im, nullptr);
+        else if (rho_grad != nullptr)
+            hipLaunchKernelGGL((k_spec_line<0, false, const float*, const float*>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P,
+                               logq_r, logl_r, rflags, sumsq, it_counter, sumsq_stride, ksq_im, rho_grad, nullptr);
         else if (adj)
             hipLaunchKernelGGL((k_spec_line<0, true>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P, logq_r, logl_r, rflags, sumsq,
                                it_counter, sumsq_stride, nullptr);
@@ -576,6 +607,17 @@ int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, 
     LineDomain d;
     if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
     return rect_launch(ctx, d, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
+}
+
+// ---- variable density: res = L(u) - b_x q_x d_x u - b_y q_y d_y u + (ksq [+ i ksq_im]) u - src on either kind of domain, on the lossy operator's tables ----
+int spec_apply_medium(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* rho_grad, const float* src,
+                      int src_batch, int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
+    if (ksq == nullptr || rho_grad == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator needs k_sq and rho_grad", who);
+    if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
+    if (batch <= 0) return HN_OK;
+    LineDomain d;
+    if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
+    return rect_launch(ctx, d, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride, false, nullptr, rho_grad);
 }
 
 // out = A^H g = L^H(g) + (ksq - i ksq_im) g [+ add] on either kind of domain: the adjoint of the operator above, on the same tables

@@ -563,6 +563,54 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_fgmres_cycle_lossy")
         return rmse, k_used
 
+    # ---- heterogeneous density: A_rho u = L(u) - b q . grad u + (k_sq [+ i k_sq_im]) u (hn_residual_medium / hn_step_medium / hn_fgmres_cycle_medium) ----
+    def _chk_medium(self, b: int, k_sq_im, rho_grad) -> None:
+        if k_sq_im is not None:
+            self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
+        self._chk(rho_grad, (b, 2, *self.hw), "rho_grad")
+
+    def residual_medium(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor], rho_grad: torch.Tensor,
+                        src: torch.Tensor) -> torch.Tensor:
+        """``residual_lossy`` with the density term: ``rho_grad`` [B,2,h,w] fp32 holds d ln rho / dx (the last index) in plane 0 and d ln rho / dy in
+        plane 1, per grid point (``helmnet_amd.density.log_density_gradient``).  ``k_sq_im`` may be None: a lossless medium."""
+        b = wf.shape[0]
+        self._chk(wf, (b, 2, *self.hw), "wavefield")
+        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk_medium(b, k_sq_im, rho_grad)
+        self._chk(src, (src.shape[0], 2, *self.hw), "source")
+        out = torch.empty_like(wf)
+        rc = self.lib.hn_residual_medium(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(k_sq_im), _ptr(rho_grad), _ptr(src), src.shape[0], _ptr(out), b,
+                                         self._stream())
+        _lib.check(rc, self.ctx, "hn_residual_medium")
+        return out
+
+    def step_medium(self, wf, res, states, k_sq, k_sq_im, rho_grad, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
+        """``step_lossy`` on the variable-density residual (hn_step_medium); ``k_sq_im`` may be None."""
+        self._chk_medium(wf.shape[0], k_sq_im, rho_grad)
+
+        def entry(ctx, wf_p, res_p, st_p, k_p, *rest):
+            return self.lib.hn_step_medium(ctx, wf_p, res_p, st_p, k_p, _ptr(k_sq_im), _ptr(rho_grad), *rest)
+
+        self._step(entry, "hn_step_medium", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
+
+    def fgmres_cycle_medium(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor], rho_grad: torch.Tensor, rhs: torch.Tensor,
+                            restart: int, tol: float, precond_iters: int, precond_scale: float, basis: Optional[torch.Tensor] = None,
+                            hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
+        """``fgmres_cycle_lossy`` on the variable-density operator (hn_fgmres_cycle_medium), preconditioned by ``precond_iters`` iterations of
+        ``step_medium``; ``precond_iters`` 0: plain restarted GMRES.  ``k_sq_im`` may be None.  Square domains.  Not capturable."""
+        restart = int(restart)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_cycle_medium", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        for name, t in (("k_sq_im", k_sq_im), ("rho_grad", rho_grad)):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise RuntimeError(f"fgmres_cycle_medium: {name} requires grad; the GMRES cycle is not differentiable")
+        self._chk_medium(b, k_sq_im, rho_grad)
+        zbasis = self._zbasis(b, restart, zbasis)
+        rc = self.lib.hn_fgmres_cycle_medium(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rho_grad), _ptr(rhs), rhs.shape[0], b, restart,
+                                             float(tol), int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse),
+                                             _ptr(k_used), self._stream())
+        _lib.check(rc, self.ctx, "hn_fgmres_cycle_medium")
+        return rmse, k_used
+
     def residual64_lossy(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, src: torch.Tensor, want_res: bool = True,
                          want_rmse: bool = True):
         """``residual64`` with the complex pointwise term (hn_residual_f64_lossy): (res [B,2,h,w] or None, rmse [B] or None), both float64, of

@@ -126,12 +126,15 @@ def default_precond_scale(source) -> float:
     return float(np.sqrt((src ** 2).sum() / src.shape[0]))
 
 
-def _hip_setup(solver, sos_maps, restart, x0, dtype, absorption=None):
+def _hip_setup(solver, sos_maps, restart, x0, dtype, absorption=None, density=None):
     """What both HIP drivers start from: (engine, k_sq, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess).
-    With ``absorption`` k_sq is the pair (k_sq, k_sq_im) of the lossy medium."""
-    _require_no_grad("gmres(backend='hip')", sos_maps, x0, absorption)
+    With ``absorption`` k_sq is the pair (k_sq, k_sq_im) of the lossy medium; with ``density`` the triple (k_sq, k_sq_im or None, rho_grad)."""
+    _require_no_grad("gmres(backend='hip')", sos_maps, x0, absorption, density)
     eng = solver.engine()
-    if absorption is not None:
+    rho_grad = None
+    if density is not None:
+        k_sq, k_sq_im, rho_grad, wf0 = solver._medium_initials("gmres", sos_maps, absorption, density)
+    elif absorption is not None:
         k_sq, k_sq_im, wf0 = solver._lossy_initials("gmres", sos_maps, absorption)
     else:
         sos_maps = sos_maps.float().contiguous()
@@ -141,6 +144,8 @@ def _hip_setup(solver, sos_maps, restart, x0, dtype, absorption=None):
     x = (wf0 if x0 is None else x0.detach()).to(rhs.device, dtype).contiguous().clone()
     basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=rhs.device)
     hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=rhs.device)
+    if density is not None:
+        return eng, (k_sq.contiguous(), None if k_sq_im is None else k_sq_im.contiguous(), rho_grad), rhs, x, basis, hess
     if absorption is not None:
         return eng, (k_sq.contiguous(), k_sq_im.contiguous()), rhs, x, basis, hess
     return eng, k_sq.contiguous(), rhs, x, basis, hess
@@ -214,17 +219,22 @@ def gmres_refine_lossy(solver, sos_maps: torch.Tensor, absorption, restart: int 
             "unet_evaluations": unet_evaluations(out["cycles"], restart, iters)}
 
 
-def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, absorption=None):
+def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, absorption=None, density=None):
     """``gmres`` with the restart cycle as fused HIP launches (hn_gmres_cycle): one host synchronisation per cycle, every sample stopping on its own.
     ``precond`` (iterations, alpha): the flexible cycle (hn_fgmres_cycle).  ``absorption``: the lossy operator (hn_fgmres_cycle_lossy, with zero
-    preconditioner iterations when ``precond`` is None)."""
-    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32, absorption)
+    preconditioner iterations when ``precond`` is None).  ``density``: the variable-density operator (hn_fgmres_cycle_medium, likewise), with or
+    without ``absorption``."""
+    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32, absorption, density)
     bsz, dev = x.shape[0], x.device
-    lossy = absorption is not None
+    medium = density is not None
+    lossy = absorption is not None or medium
     zbasis = None if precond is None and not lossy else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
 
     def cycle():
-        if lossy:
+        if medium:
+            iters, alpha = (0, 1.0) if precond is None else precond
+            rmse, k_used = eng.fgmres_cycle_medium(x, k_sq[0], k_sq[1], k_sq[2], rhs, restart, tol, iters, alpha, basis, hess, zbasis)
+        elif lossy:
             iters, alpha = (0, 1.0) if precond is None else precond
             rmse, k_used = eng.fgmres_cycle_lossy(x, k_sq[0], k_sq[1], rhs, restart, tol, iters, alpha, basis, hess, zbasis)
         elif precond is None:
@@ -236,6 +246,8 @@ def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, abso
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
 
     def true_rmse():
+        if medium:
+            return eng.rmse(eng.residual_medium(x, k_sq[0], k_sq[1], k_sq[2], rhs)).cpu().numpy()
         if lossy:
             return eng.rmse(eng.residual_lossy(x, k_sq[0], k_sq[1], rhs)).cpu().numpy()
         return eng.rmse(eng.residual(x, k_sq, rhs)).cpu().numpy()
@@ -338,7 +350,8 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
 
 def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
           x0: Optional[torch.Tensor] = None, backend: str = "torch", refine: bool = False, inner_floor: float = 1e-6,
-          precondition: Optional[str] = None, precond_iterations: int = 10, precond_scale: Optional[float] = None, absorption=None):
+          precondition: Optional[str] = None, precond_iterations: int = 10, precond_scale: Optional[float] = None, absorption=None,
+          density=None):
     """Solve (L + k_sq) u = source for every map of ``sos_maps`` [B, 1, N, N] (the reference's classical baseline:
     matlab/spectral_gmres_solver.m:86-115, MATLAB's ``gmres`` with restarts).
 
@@ -373,7 +386,18 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
     ``absorption`` (alpha in nepers per grid point, a number or a tensor broadcastable to ``sos_maps``; helmnet_amd.absorption): the medium is lossy,
     k~ = omega / sos + i alpha, and the cycles run on hn_fgmres_cycle_lossy.  ``backend="hip"`` with ``precondition`` None or "learned"; the torch
     backend raises ValueError, ``refine=True`` NotImplementedError (the float64 lossy refinement is ``gmres_refine_lossy``).  The result gains ``cycles``.  None: the code
-    path and the bits of before."""
+    path and the bits of before.
+
+    ``density`` (rho, a tensor broadcastable to ``sos_maps``; helmnet_amd.density): the cycles run on the variable-density operator
+    (hn_fgmres_cycle_medium), with or without ``absorption``.  ``backend="hip"`` with ``precondition`` None or "learned"; the torch backend raises
+    ValueError, ``refine=True`` NotImplementedError (the operator has no float64 counterpart).  The result gains ``cycles``.  None: the code path and
+    the bits of before."""
+    if density is not None:
+        if backend != "hip":
+            raise ValueError("density needs backend='hip' (the torch backend has the constant-density operator only)")
+        if refine:
+            raise NotImplementedError("gmres(refine=True) is not implemented with density: the variable-density operator has no float64 residual")
+        solver._refuse_density_grad("gmres", sos_maps, x0, absorption, density)
     if absorption is not None:
         if backend != "hip":
             raise ValueError("absorption needs backend='hip' (the torch backend has the lossless operator only)")
@@ -395,7 +419,7 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
     if backend == "hip" and refine:
         return _gmres_refine(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, float(inner_floor), precond)
     if backend == "hip":
-        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, precond, absorption)
+        return _gmres_hip(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, precond, absorption, density)
     if backend != "torch":
         raise ValueError(f"unknown GMRES backend {backend!r} (choose 'torch' or 'hip')")
     eng = solver.engine()

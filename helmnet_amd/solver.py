@@ -452,9 +452,45 @@ class IterativeSolver(nn.Module):
         k_sq, k_sq_im = complex_k_sq(sos, absorption, self.hparams.omega)
         return k_sq, k_sq_im, torch.zeros(sos.shape[0], 2, sos.shape[2], sos.shape[3], device=sos.device)
 
-    def get_residual(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor] = None):
+    def _refuse_density_grad(self, what: str, *tensors):
+        """Variable density has no differentiable path at all: an input that requires grad -- or differentiable(True) under grad mode -- raises
+        before anything touches the device."""
+        if any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors) or (self._differentiable and torch.is_grad_enabled()):
+            raise RuntimeError(f"{what} with density runs without gradients (the library has no derivative of the variable-density operator): pass "
+                               "detached tensors, or run under torch.no_grad() after differentiable(True)")
+
+    @staticmethod
+    def _rho_grad(density, like: torch.Tensor) -> torch.Tensor:
+        """``rho_grad`` [B,2,H,W] fp32 of a ``density`` broadcastable to ``like`` [B,1,H,W]: helmnet_amd.density.log_density_gradient."""
+        from .density import log_density_gradient
+        if not isinstance(density, torch.Tensor):
+            raise TypeError("density must be a tensor broadcastable to the sound-speed maps")
+        rho = density.detach().to(like.device, torch.float32)
+        try:
+            rho = rho.expand_as(like)
+        except RuntimeError as e:
+            raise ValueError(f"density of shape {tuple(density.shape)} does not broadcast to {tuple(like.shape)}") from e
+        return log_density_gradient(rho.contiguous())
+
+    def _medium_initials(self, what: str, sos_maps, absorption, density):
+        """(k_sq, k_sq_im or None, rho_grad, wf = 0) for the medium (sos_maps, absorption or None, density)."""
+        self._refuse_density_grad(what, sos_maps, absorption, density)
+        if absorption is not None:
+            k_sq, k_sq_im, wf = self._lossy_initials(what, sos_maps, absorption)
+        else:
+            k_sq, wf = self.get_initials(sos_maps.float().contiguous())
+            k_sq, k_sq_im = k_sq.contiguous(), None
+        return k_sq, k_sq_im, self._rho_grad(density, k_sq), wf
+
+    def get_residual(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor] = None, rho_grad: Optional[torch.Tensor] = None):
         """hybridnet.py:544-556.  ``k_sq_im`` (extension, [B,1,H,W]): the imaginary plane of an absorbing medium's squared wavenumber
-        (helmnet_amd.absorption.complex_k_sq); the residual is then L(x) + (k_sq + i k_sq_im) x - source, without gradients."""
+        (helmnet_amd.absorption.complex_k_sq); the residual is then L(x) + (k_sq + i k_sq_im) x - source, without gradients.
+        ``rho_grad`` (extension, [B,2,H,W]): the gradient of ln rho (helmnet_amd.density.log_density_gradient); the residual is then the
+        variable-density operator's (hn_residual_medium), with or without ``k_sq_im``, without gradients."""
+        if rho_grad is not None:
+            self._refuse_density_grad("get_residual", x, k_sq, k_sq_im, rho_grad)
+            return self.engine().residual_medium(x.float().contiguous(), k_sq.float().contiguous(),
+                                                 None if k_sq_im is None else k_sq_im.float().contiguous(), rho_grad.float().contiguous(), self._src())
         if k_sq_im is not None:
             self._refuse_lossy_grad("get_residual", x, k_sq, k_sq_im)
             return self.engine().residual_lossy(x.float().contiguous(), k_sq.float().contiguous(), k_sq_im.float().contiguous(), self._src())
@@ -547,9 +583,9 @@ class IterativeSolver(nn.Module):
         return (wf, res) if get_residual else wf
 
     # ------------------------------------------------------------------ loops ------------
-    def _loop(self, wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals: str, k_sq_im=None):
+    def _loop(self, wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals: str, k_sq_im=None, rho_grad=None):
         """K iterations on wf / res / st, updated in place -- Engine.step for fp32 tensors, Engine.step64 for float64 ones, Engine.step_lossy with a
-        ``k_sq_im`` -- with the histories asked for, in wf's dtype; the result dictionary of ``forward``."""
+        ``k_sq_im``, Engine.step_medium with a ``rho_grad`` -- with the histories asked for, in wf's dtype; the result dictionary of ``forward``."""
         eng = self.engine()
         b, hw, K = wf.shape[0], tuple(wf.shape[-2:]), int(num_iterations)
 
@@ -568,7 +604,9 @@ class IterativeSolver(nn.Module):
         rmse = torch.empty((K, b), device=wf.device, dtype=wf.dtype) if K > 0 else None
         if K > 0:
             keep = self.f.to_engine_states(st)      # levels without state: zeros in, the caller's values back out
-            if k_sq_im is not None:
+            if rho_grad is not None:
+                eng.step_medium(wf, res, st, k_sq, k_sq_im, rho_grad, src, K, res_hist, wf_hist, st_hist, rmse)
+            elif k_sq_im is not None:
                 eng.step_lossy(wf, res, st, k_sq, k_sq_im, src, K, res_hist, wf_hist, st_hist, rmse)
             else:
                 step = eng.step64 if wf.dtype == torch.float64 else eng.step
@@ -585,13 +623,13 @@ class IterativeSolver(nn.Module):
             out["last_residual"] = res
         return out
 
-    def _run(self, wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals: str, k_sq_im=None):
-        out = self._loop(wf, res, st, k_sq, self._src(), num_iterations, return_wavefields, return_states, residuals, k_sq_im)
+    def _run(self, wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals: str, k_sq_im=None, rho_grad=None):
+        out = self._loop(wf, res, st, k_sq, self._src(), num_iterations, return_wavefields, return_states, residuals, k_sq_im, rho_grad)
         self.f.adopt_states(st)
         return out
 
     def forward(self, sos_maps, return_wavefields=False, return_states=False, num_iterations=None,
-                stop_if_diverge=False, residuals: str = "all", checkpoint_every: int = 1, absorption=None):
+                stop_if_diverge=False, residuals: str = "all", checkpoint_every: int = 1, absorption=None, density=None):
         """hybridnet.py:654-697.  ``residuals``: "all" keeps every residual tensor like the
         reference (K x B x 2 x N x N floats), "norms" keeps only the per-iteration per-sample RMSE
         (``out["residual_norms"]``), "last" only the final residual.
@@ -604,11 +642,21 @@ class IterativeSolver(nn.Module):
 
         ``absorption`` (extension; None: the code path and the bits of before): alpha in nepers per grid point, a number or a tensor broadcastable
         to ``sos_maps`` -- the medium is k~ = omega / sos + i alpha (helmnet_amd.absorption) and the loop runs on ``hn_step_lossy``.  Same keys and
-        shapes; no gradients: an input that requires grad raises RuntimeError."""
+        shapes; no gradients: an input that requires grad raises RuntimeError.
+
+        ``density`` (extension; None: the code path and the bits of before): rho, a tensor broadcastable to ``sos_maps`` -- only its ratios matter,
+        and a map with jumps should be smoothed first (helmnet_amd.density).  The loop runs on ``hn_step_medium``, with or without ``absorption``;
+        no gradients, as with ``absorption``."""
         if residuals not in ("all", "norms", "last"):
             raise ValueError("residuals must be 'all', 'norms' or 'last'")
         if num_iterations is None:
             num_iterations = self.hparams.max_iterations
+        if density is not None:
+            k_sq, k_sq_im, rho_grad, wf = self._medium_initials("forward", sos_maps, absorption, density)
+            self.f.clear_states(wf)
+            res = self.get_residual(wf, k_sq, k_sq_im, rho_grad)
+            st = self.f.get_states(flatten=True).contiguous()
+            return self._run(wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals, k_sq_im, rho_grad)
         if absorption is not None:
             k_sq, k_sq_im, wf = self._lossy_initials("forward", sos_maps, absorption)
             self.f.clear_states(wf)
@@ -628,19 +676,30 @@ class IterativeSolver(nn.Module):
         return self._run(wf, res, st, k_sq.contiguous(), num_iterations, return_wavefields, return_states, residuals)
 
     def n_steps(self, wavefield, k_sq, residual, num_iterations, return_wavefields=False, return_states=False,
-                residuals: str = "all", checkpoint_every: int = 1, absorption=None):
+                residuals: str = "all", checkpoint_every: int = 1, absorption=None, density=None):
         """hybridnet.py:586-623: continue from given wavefield / residual and the states held in f.  Differentiable as ``forward``
         when an input, a state held in f or the source requires grad (``checkpoint_every``: see ``forward``).
 
         ``absorption`` (extension; None: the code path and the bits of before): alpha, as in ``forward``.  ``k_sq`` is then the REAL plane of the
         medium, (omega / sos)^2 - alpha^2 as ``complex_k_sq`` returns it, and the imaginary plane is formed from the two:
-        2 sqrt(k_sq + alpha^2) alpha.  No gradients."""
+        2 sqrt(k_sq + alpha^2) alpha.  No gradients.
+
+        ``density`` (extension; None: the code path and the bits of before): rho, as in ``forward``, broadcastable to ``k_sq``.  No gradients."""
+        if density is not None:
+            self._refuse_density_grad("n_steps", wavefield, k_sq, residual, absorption, density)
         if absorption is not None:
             self._refuse_lossy_grad("n_steps", wavefield, k_sq, residual, absorption)
             kq = k_sq.float().contiguous()
             alpha = torch.as_tensor(absorption, dtype=kq.dtype, device=kq.device).expand_as(kq)
             k_sq_im = (2.0 * (kq + alpha * alpha).sqrt() * alpha).contiguous()
+            if density is not None:
+                return self._n_steps_lossy(wavefield, kq, k_sq_im, residual, num_iterations, return_wavefields, return_states, residuals,
+                                           self._rho_grad(density, kq))
             return self._n_steps_lossy(wavefield, kq, k_sq_im, residual, num_iterations, return_wavefields, return_states, residuals)
+        if density is not None:
+            kq = k_sq.float().contiguous()
+            return self._n_steps_lossy(wavefield, kq, None, residual, num_iterations, return_wavefields, return_states, residuals,
+                                       self._rho_grad(density, kq))
         if self._wants_grad(wavefield, k_sq, residual, states=True):
             return self._run_autograd(wavefield, residual, k_sq, num_iterations, return_wavefields, return_states, residuals, checkpoint_every)
         wf = wavefield.detach().float().clone().contiguous()
@@ -648,12 +707,13 @@ class IterativeSolver(nn.Module):
         st = self.f.get_states(flatten=True).float().contiguous().clone()
         return self._run(wf, res, st, k_sq.float().contiguous(), num_iterations, return_wavefields, return_states, residuals)
 
-    def _n_steps_lossy(self, wavefield, k_sq, k_sq_im, residual, num_iterations, return_wavefields=False, return_states=False, residuals: str = "all"):
-        """``n_steps`` without gradients on the medium (k_sq, k_sq_im): the inputs are not modified."""
+    def _n_steps_lossy(self, wavefield, k_sq, k_sq_im, residual, num_iterations, return_wavefields=False, return_states=False, residuals: str = "all",
+                       rho_grad=None):
+        """``n_steps`` without gradients on the medium (k_sq, k_sq_im [, rho_grad: k_sq_im may then be None]): the inputs are not modified."""
         wf = wavefield.detach().float().clone().contiguous()
         res = residual.detach().float().clone().contiguous()
         st = self.f.get_states(flatten=True).float().contiguous().clone()
-        return self._run(wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals, k_sq_im)
+        return self._run(wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals, k_sq_im, rho_grad)
 
     # ------------------------------------------------------------------ forward mode ----
     def _jvp_setup(self, sos_maps):
@@ -777,7 +837,7 @@ class IterativeSolver(nn.Module):
         return {"iterations": torch.tensor(want), "linf": torch.stack([rows[c] for c in want]), "rmse32": torch.cat(r32), "rmse64": torch.cat(r64)}
 
     def solve_to_tolerance(self, sos_maps, tol: float, max_iterations: int = None, check_every: int = 50,
-                           norm_reduce=None, verify: bool = False, absorption=None) -> dict:
+                           norm_reduce=None, verify: bool = False, absorption=None, density=None) -> dict:
         """Extension (BASELINE.json configs[4], "convergence-to-tolerance"): iterate in chunks of
         ``check_every`` until the WORST per-sample residual RMSE (hybridnet.py:295-297) is below ``tol`` or
         ``max_iterations`` is reached.  One device-to-host read of a single float per chunk; with
@@ -785,27 +845,36 @@ class IterativeSolver(nn.Module):
         Returns wavefield, last residual, per-iteration RMSE trace [K, B], iterations run and whether it converged.  ``verify=True`` adds the keys of
         ``verify()`` for the final wavefield and ``converged64``: the worst float64 residual norm is below ``tol``.
         ``absorption``: alpha, as in ``forward`` (None: the code path and the bits of before); together with ``verify=True`` it raises
-        NotImplementedError: check the returned wavefield with ``verify(wavefield, sos_maps, absorption=...)``."""
+        NotImplementedError: check the returned wavefield with ``verify(wavefield, sos_maps, absorption=...)``.
+        ``density``: rho, as in ``forward`` (None: the code path and the bits of before); together with ``verify=True`` it raises
+        NotImplementedError (the variable-density operator has no float64 counterpart)."""
         if max_iterations is None:
             max_iterations = self.hparams.max_iterations
+        if verify and density is not None:
+            raise NotImplementedError("solve_to_tolerance(verify=True) is not implemented with density: the variable-density operator has no float64 "
+                                      "residual")
         if verify and absorption is not None:
             raise NotImplementedError("solve_to_tolerance(verify=True) is not implemented with absorption: call verify(wavefield, sos_maps, "
                                       "absorption=...) on the result")
         if verify:
             self._require_square("solve_to_tolerance(verify=True)")
-        k_sq_im = None
-        if absorption is not None:
+        k_sq_im = rho_grad = None
+        if density is not None:
+            k_sq, k_sq_im, rho_grad, wf = self._medium_initials("solve_to_tolerance", sos_maps, absorption, density)
+        elif absorption is not None:
             k_sq, k_sq_im, wf = self._lossy_initials("solve_to_tolerance", sos_maps, absorption)
         else:
             sos_maps = sos_maps.float().contiguous()
             k_sq, wf = self.get_initials(sos_maps)
         self.f.clear_states(wf)
-        res = self.get_residual(wf, k_sq, k_sq_im)
+        res = self.get_residual(wf, k_sq, k_sq_im, rho_grad)
         k_sq = k_sq.contiguous()
         done, traces, converged = 0, [], False
         while done < max_iterations:
             chunk = min(int(check_every), max_iterations - done)
-            if k_sq_im is not None:
+            if rho_grad is not None:
+                out = self._n_steps_lossy(wf, k_sq, k_sq_im, res, chunk, residuals="norms", rho_grad=rho_grad)
+            elif k_sq_im is not None:
                 out = self._n_steps_lossy(wf, k_sq, k_sq_im, res, chunk, residuals="norms")
             else:
                 out = self.n_steps(wf, k_sq, res, chunk, residuals="norms")
@@ -824,18 +893,21 @@ class IterativeSolver(nn.Module):
         return out
 
     def gmres(self, sos_maps, restart: int = 20, max_cycles: int = 50, tol: float = 1e-4, x0=None, precondition=None, precond_iterations: int = 10,
-              precond_scale=None, absorption=None) -> dict:
+              precond_scale=None, absorption=None, density=None) -> dict:
         """The reference's classical baseline (matlab/spectral_gmres_solver.m:86-115) on this solver's operator and source: restarted GMRES with the
         restart cycle fused on the device (``helmnet_amd.gmres.gmres(backend="hip")``), every map stopping on its own.  ``x0`` [B,2,n,n]: the
         starting iterate, e.g. a learned solve's wavefield to be continued by Krylov iterations (default: zeros).  ``precondition="learned"``:
         flexible GMRES with this solver's network as right preconditioner, ``precond_iterations`` iterations per inner step on a right-hand side
         scaled by ``precond_scale`` (None: the source's RMS 2-norm); see ``helmnet_amd.gmres.gmres``.  No gradients.
         ``absorption``: alpha, as in ``forward`` -- the cycles then run on the lossy operator (hn_fgmres_cycle_lossy), preconditioned by the lossy
-        learned iteration with ``precondition="learned"``; None: the code path and the bits of before."""
+        learned iteration with ``precondition="learned"``; None: the code path and the bits of before.
+        ``density``: rho, as in ``forward`` -- the cycles then run on the variable-density operator (hn_fgmres_cycle_medium), with or without
+        ``absorption``; None: the code path and the bits of before."""
         from .gmres import gmres
         self._require_square("gmres")
+        medium = {} if density is None else {"density": density}
         return gmres(self, sos_maps, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, backend="hip", precondition=precondition,
-                     precond_iterations=precond_iterations, precond_scale=precond_scale, absorption=absorption)
+                     precond_iterations=precond_iterations, precond_scale=precond_scale, absorption=absorption, **medium)
 
     def gmres64(self, sos_maps, restart: int = 20, max_cycles: int = 400, tol: float = 1e-10, x0=None, precondition=None, precond_iterations: int = 10,
                 precond_scale=None, absorption=None) -> dict:

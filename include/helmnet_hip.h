@@ -556,6 +556,47 @@ int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float*
                           float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
                           void* stream);
 
+/* ---- heterogeneous density (added within ABI v7: new entry points, nothing existing changes) ----
+ * matlab/skull2medium.m produces three maps, sound speed, absorption and density; this is the third.  With the PML stretch gamma = 1 + i sigma / k the
+ * reference expands each axis of (1/gamma) d((1/gamma) du) as a du + b d2u, b = 1 / gamma^2, a = -gamma' / gamma^3.  Variable density in the same form:
+ *     rho (1/gamma) d( (1/rho) (1/gamma) du ) = a du + b d2u - b q du,     q = d ln rho  (real, per axis, per pixel)
+ *     A_rho u = L(u) - b_x q_x d_x u - b_y q_y d_y u + (k_sq + i k_sq_im) u
+ * with d_x, d_y the Fourier derivatives and b_x, b_y the tables L itself uses.  This is the EXPANDED form, not the conservative discretisation
+ * rho div((1/rho) grad u): products alias, and the two differ by 1-2 % for a smooth u and by O(1) for white noise.  Only ratios of rho matter.  A jump
+ * in rho makes q ring; smooth the map as k-Wave users do.
+ * rho_grad: fp32 [B,2,h,w], read only.  Plane 0 is q_x = d ln rho / dx, x the LAST index (length w, the axis of sigma_x); plane 1 is q_y, along the
+ * first spatial index (length h).  Units: per grid point.  The library takes any gradient the caller prefers (helmnet_amd.density has the spectral
+ * one).  NULL returns HN_ERR_ARG with a message that names the constant-density siblings.  k_sq_im MAY be NULL here: a lossless medium, the plane is not
+ * read.  The UNet never sees the medium, so density enters the residual alone.
+ * Route: the LDS-line kernel of the lossy operator, on its tables and under its capture rule (a square domain's are built at the latest by the first
+ * lossy or variable-density call, which must not be under stream capture: HN_ERR_STATE, nothing enqueued).  Each pass reads its plane of rho_grad at the
+ * element it stores and multiplies the first derivative with a - q b: one more fp32 plane read per pass, no further LDS, no further transform.
+ * Nothing of the other entry points changes: they keep their kernels and their bits.  With rho_grad = 0 the results agree with the lossy (k_sq_im
+ * NULL: the lossless) siblings to fp32 rounding.
+ * [measured, MI355X, profiles/density_bench.txt] hn_residual_medium / hn_residual_lossy, alternating in one process: 1.060 at 256^2 x 32, 1.108 at
+ * 512^2 x 16, 1.070 at 400^2 x 16 (from the traffic alone, 8 more bytes on about 56 per pixel: at most 1.14); one hn_step_medium iteration /
+ * one hn_step_lossy iteration 1.023, 1.018, 1.019.
+ * No entry point exists for: the adjoint of A_rho and adjoint-state gradients, anything float64, gradients through the loop, training, the stream of maps (hn_stream_swap). */
+
+/* hn_residual_lossy with the density term; every legal square size and every rectangular domain.  rho_grad and k_sq_im may overlap nothing written
+ * ("hn_residual_medium: rho_grad overlaps res"); 4-byte alignment suffices. */
+int hn_residual_medium(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* src, int src_batch,
+                       float* res, int batch, void* stream);
+
+/* hn_step_lossy on the variable-density residual: per iteration exactly the UNet launches of hn_step, then the density pair.  Histories, rmse_hist,
+ * precision modes, the one lane (HN_OPT_LANES > 1: HN_ERR_UNSUPPORTED) and the overlap rule are hn_step_lossy's, rho_grad one more read-only tensor.
+ * n_iter iterations in one call equal the same iterations in several calls bit for bit. */
+int hn_step_medium(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* src,
+                   int src_batch, int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream);
+
+/* hn_fgmres_cycle_lossy with A_rho in its three places: the start residual, every w = A z, and the precond_iters iterations of hn_step_medium on
+ * A z = precond_scale * v that make z_k (zero start, zero hidden states, z_k = wf / precond_scale, as hn_fgmres_cycle composes it).  precond_iters = 0
+ * is plain restarted GMRES with zbasis == basis bit for bit.  Square domains only (HN_ERR_UNSUPPORTED on a rectangular one); not capturable; sums in a
+ * fixed order.  rho_grad must be 16-byte aligned and overlap no other argument, as k_sq; so must k_sq_im where it is given. */
+int hn_fgmres_cycle_medium(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* rhs, int rhs_batch,
+                           int batch, int restart, float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
+                           float* rmse, int32_t* k_used, void* stream);
+
 /* ---- absorbing media: the adjoint operator and adjoint-state gradients (added within ABI v7: new entry points, nothing existing changes) ----
  * With A u = L(u) + (k_sq + i k_sq_im) u the conjugate transpose is A^H g = L^H(g) + (k_sq - i k_sq_im) g:
  *     re = L^H(g)_re + k_sq g_re + k_sq_im g_im,   im = L^H(g)_im + k_sq g_im - k_sq_im g_re.
