@@ -719,76 +719,62 @@ int hn_laplacian(hn_ctx* ctx, const float* wf, float* out, int batch, void* stre
     return spec_apply(ctx, wf, out, nullptr, nullptr, 1, batch, nullptr, (hipStream_t)stream);
 }
 
-int hn_residual(hn_ctx* ctx, const float* wf, const float* k_sq, const float* src, int src_batch, float* res, int batch, void* stream) {
-    if (!ctx || !wf || !k_sq || !src || !res) return fail(ctx, HN_ERR_ARG, "hn_residual: NULL argument");
+// hn_residual, hn_residual_lossy and hn_residual_medium behind their own NULL refusals.  The medium's extra planes are read while res is written: they
+// must not overlap it (a lossless call has none)
+static int residual_entry(hn_ctx* ctx, const char* who, const Medium& m, const float* wf, const float* src, int src_batch, float* res, int batch,
+                          void* stream) {
+    if (!ctx || !wf || !m.k_sq || !src || !res) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
+    const size_t plane = (size_t)ctx->geo.plane();
+    const MemRange r[] = {{m.k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
+                          {m.rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"},
+                          {res, sizeof(float) * (size_t)batch * 2 * plane, true, "res"}};
+    const char *a, *b;
+    if (first_overlap(r, 3, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
     DeviceGuard guard(ctx);
-    return spec_apply(ctx, wf, res, k_sq, src, src_batch, batch, nullptr, (hipStream_t)stream);
+    return spec_forward(ctx, who, m, wf, res, src, src_batch, batch, nullptr, (hipStream_t)stream);
+}
+
+int hn_residual(hn_ctx* ctx, const float* wf, const float* k_sq, const float* src, int src_batch, float* res, int batch, void* stream) {
+    return residual_entry(ctx, "hn_residual", Medium{k_sq}, wf, src, src_batch, res, batch, stream);
 }
 
 int hn_residual_lossy(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, float* res, int batch,
                       void* stream) {
-    const char* who = "hn_residual_lossy";
-    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_residual)", who);
-    if (!ctx || !wf || !k_sq || !src || !res) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
-    if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
-    if (src_batch != 1 && src_batch != batch)
-        return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
-    {
-        const size_t plane = (size_t)ctx->geo.plane();
-        const MemRange r[] = {{k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}, {res, sizeof(float) * (size_t)batch * 2 * plane, true, "res"}};
-        const char *a, *b;
-        if (first_overlap(r, 2, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
-    }
-    DeviceGuard guard(ctx);
-    return spec_apply_lossy(ctx, who, wf, res, k_sq, k_sq_im, src, src_batch, batch, nullptr, (hipStream_t)stream);
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_residual_lossy: k_sq_im is NULL (a lossless medium is hn_residual)");
+    return residual_entry(ctx, "hn_residual_lossy", Medium{k_sq, k_sq_im}, wf, src, src_batch, res, batch, stream);
 }
 
 int hn_residual_medium(hn_ctx* ctx, const float* wf, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* src, int src_batch,
                        float* res, int batch, void* stream) {
-    const char* who = "hn_residual_medium";
     if (ctx && !rho_grad)
-        return fail(ctx, HN_ERR_ARG, "%s: rho_grad is NULL (a medium of constant density is hn_residual_lossy, or hn_residual without absorption)", who);
-    if (!ctx || !wf || !k_sq || !src || !res) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+        return fail(ctx, HN_ERR_ARG, "hn_residual_medium: rho_grad is NULL (a medium of constant density is hn_residual_lossy, or hn_residual without absorption)");
+    return residual_entry(ctx, "hn_residual_medium", Medium{k_sq, k_sq_im, rho_grad}, wf, src, src_batch, res, batch, stream);
+}
+
+// hn_residual_vjp (rect_ok false: its adjoint kernels are a square domain's) and hn_residual_vjp_lossy (the LDS-line kernels, either kind of domain)
+static int residual_vjp_entry(hn_ctx* ctx, const char* who, bool rect_ok, const Medium& m, const float* g, float* out, int batch, void* stream) {
+    if (!ctx || !g || !m.k_sq || !out) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+    if (ctx->rect && !rect_ok) return rect_unsupported(ctx, who);
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
-    if (src_batch != 1 && src_batch != batch)
-        return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
-    {
-        const size_t plane = (size_t)ctx->geo.plane();
-        const MemRange r[] = {{k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
-                              {rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"},
-                              {res, sizeof(float) * (size_t)batch * 2 * plane, true, "res"}};
-        const char *a, *b;
-        if (first_overlap(r, 3, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
-    }
+    if (m.k_sq_im != nullptr && g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);   // (ahead of the overlap below)
+    const size_t plane = (size_t)ctx->geo.plane();
+    const MemRange r[] = {{m.k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}, {out, sizeof(float) * (size_t)batch * 2 * plane, true, "out"}};
+    const char *a, *b;
+    if (first_overlap(r, 2, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
     DeviceGuard guard(ctx);
-    return spec_apply_medium(ctx, who, wf, res, k_sq, k_sq_im, rho_grad, src, src_batch, batch, nullptr, (hipStream_t)stream);
+    return spec_backward(ctx, who, m, g, out, nullptr, batch, (hipStream_t)stream);
 }
 
 int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, int batch, void* stream) {
-    if (!ctx || !g || !k_sq || !out) return fail(ctx, HN_ERR_ARG, "hn_residual_vjp: NULL argument");
-    if (ctx->rect) return rect_unsupported(ctx, "hn_residual_vjp");
-    if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
-    DeviceGuard guard(ctx);
-    return spec_adjoint(ctx, g, out, k_sq, nullptr, batch, (hipStream_t)stream);
+    return residual_vjp_entry(ctx, "hn_residual_vjp", false, Medium{k_sq}, g, out, batch, stream);
 }
 
 int hn_residual_vjp_lossy(hn_ctx* ctx, const float* g, const float* k_sq, const float* k_sq_im, float* out, int batch, void* stream) {
-    const char* who = "hn_residual_vjp_lossy";
-    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_residual_vjp)", who);
-    if (!ctx || !g || !k_sq || !out) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
-    if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
-    if (g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);
-    {
-        const size_t plane = (size_t)ctx->geo.plane();
-        const MemRange r[] = {{k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}, {out, sizeof(float) * (size_t)batch * 2 * plane, true, "out"}};
-        const char *a, *b;
-        if (first_overlap(r, 2, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
-    }
-    DeviceGuard guard(ctx);
-    return spec_adjoint_lossy(ctx, who, g, out, k_sq, k_sq_im, nullptr, batch, (hipStream_t)stream);
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_residual_vjp_lossy: k_sq_im is NULL (a lossless medium is hn_residual_vjp)");
+    return residual_vjp_entry(ctx, "hn_residual_vjp_lossy", true, Medium{k_sq, k_sq_im}, g, out, batch, stream);
 }
 
 int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream) {
@@ -877,12 +863,11 @@ namespace {
 
 struct StepArgs {
     float *wf, *res, *states;
-    const float *k_sq, *src;
+    Medium medium;
+    const float* src;
     int src_batch, batch;
     float* rmse_hist;   // base of the [n_iter, batch] table (rows are selected on the device through it_counter)
     bool side_stream;   // the hidden-state kernels may leave the main chain for the lane's side stream (hn_step's route)
-    const float* k_sq_im = nullptr;   // non-null (hn_step_lossy): the residual is the lossy operator's, spec_apply_lossy
-    const float* rho_grad = nullptr;  // non-null (hn_step_medium): the residual is the variable-density operator's, spec_apply_medium; k_sq_im may be null
 };
 
 __global__ void k_probe_spin(long ticks) {
@@ -1038,17 +1023,9 @@ int one_iteration(hn_ctx* ctx, const StepArgs& a, int parity, int b0, int nb, in
     int rc = unet_forward(ctx, c);
     if (rc != HN_OK) return rc;
     const float* src_j = a.src_batch == 1 ? a.src : a.src + (size_t)b0 * 2 * plane;
-    if (a.rho_grad != nullptr)
-        return spec_apply_medium(ctx, "hn_step_medium", wf_j, res_j, a.k_sq + (size_t)b0 * plane, a.k_sq_im ? a.k_sq_im + (size_t)b0 * plane : nullptr,
-                                 a.rho_grad + (size_t)b0 * 2 * plane, src_j, a.src_batch == 1 ? 1 : nb, nb, a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj,
-                                 a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
-    if (a.k_sq_im != nullptr)
-        return spec_apply_lossy(ctx, "hn_step_lossy", wf_j, res_j, a.k_sq + (size_t)b0 * plane, a.k_sq_im + (size_t)b0 * plane, src_j,
-                                a.src_batch == 1 ? 1 : nb, nb, a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj,
-                                a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
     HN_REP(KID_SPEC_PAIR)
-    rc = spec_apply(ctx, wf_j, res_j, a.k_sq + (size_t)b0 * plane, src_j, a.src_batch == 1 ? 1 : nb, nb,
-                    a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj, a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
+    rc = spec_forward(ctx, a.medium.step_name(), a.medium.from_sample(b0, (size_t)plane), wf_j, res_j, src_j, a.src_batch == 1 ? 1 : nb, nb,
+                      a.rmse_hist ? a.rmse_hist + b0 : nullptr, sj, a.rmse_hist ? ctx->it_counter + lane : nullptr, a.batch);
     return rc;
 }
 
@@ -1061,7 +1038,7 @@ void destroy_graph_entry(hn_ctx::StepGraph& g) {
 hn_ctx::StepGraph* step_graph(hn_ctx* ctx, const StepArgs& a) {
     ++ctx->graph_clock;
     for (auto& g : ctx->graphs)
-        if (g.wf == a.wf && g.res == a.res && g.states == a.states && g.k_sq == a.k_sq && g.src == a.src && g.rmse == a.rmse_hist &&
+        if (g.wf == a.wf && g.res == a.res && g.states == a.states && g.k_sq == a.medium.k_sq && g.src == a.src && g.rmse == a.rmse_hist &&
             g.src_batch == a.src_batch && g.batch == a.batch && g.precision == ctx->precision && g.side == ctx->opt_side_stream &&
             g.lanes == ctx->opt_graph) {
             g.last_use = ctx->graph_clock;
@@ -1069,7 +1046,7 @@ hn_ctx::StepGraph* step_graph(hn_ctx* ctx, const StepArgs& a) {
         }
     if (!ctx->cap_stream && hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
     hn_ctx::StepGraph g;
-    g.wf = a.wf; g.res = a.res; g.states = a.states; g.k_sq = a.k_sq; g.src = a.src; g.rmse = a.rmse_hist;
+    g.wf = a.wf; g.res = a.res; g.states = a.states; g.k_sq = a.medium.k_sq; g.src = a.src; g.rmse = a.rmse_hist;
     g.src_batch = a.src_batch; g.batch = a.batch; g.precision = ctx->precision; g.side = ctx->opt_side_stream;
     g.lanes = ctx->opt_graph;   // iterations per graph (the field doubles as part of the key)
     const int per_graph = ctx->opt_graph > 1 ? ctx->opt_graph : 1;
@@ -1117,16 +1094,14 @@ void clear_step_graphs(hn_ctx* ctx) {
 }  // namespace hn
 
 namespace hn {
-namespace {
 
-// hn_step (k_sq_im nullptr, who "hn_step": every check, launch and message of before) and hn_step_lossy (k_sq_im non-null: the same UNet launches, the
-// residual by spec_apply_lossy; one lane, never a captured iteration) and hn_step_medium (rho_grad non-null, k_sq_im nullable: as the lossy loop, the
-// residual by spec_apply_medium)
-int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* src, int src_batch,
-               int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream, const float* rho_grad = nullptr) {
-    const bool medium = rho_grad != nullptr;
-    const bool lossy = k_sq_im != nullptr || medium;   // the LDS-line residual and its route
-    if (!ctx || !wf || !res || !states || !k_sq || !src) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+// hn_step (a lossless medium: every check, launch and message of before), hn_step_lossy (the same UNet launches, the residual the lossy operator's; one
+// lane, never a captured iteration) and hn_step_medium (as the lossy loop, the residual the variable-density operator's)
+int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* states, const Medium& m, const float* src, int src_batch, int batch, int n_iter,
+               float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
+    const bool medium = m.kind() == Medium::Kind::Density;
+    const bool lossy = m.kind() != Medium::Kind::Lossless;   // the LDS-line residual and its route
+    if (!ctx || !wf || !res || !states || !m.k_sq || !src) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (n_iter < 0) return fail(ctx, HN_ERR_ARG, "n_iter must be >= 0");
     if (src_batch != 1 && src_batch != batch)
         return fail(ctx, HN_ERR_ARG, "source batch %d must be 1 or equal to the batch %d", src_batch, batch);
@@ -1154,12 +1129,12 @@ int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* state
         // need it, in the zero-copy and in the copying form alike: refused before anything is enqueued.
         const size_t fc = sizeof(float) * (size_t)batch * 2 * plane, sc = sizeof(float) * (size_t)batch * kState * L, it = (size_t)n_iter;
         const MemRange r[] = {{wf_hist != nullptr && wf_hist == wf ? nullptr : wf, fc, true, "wf"}, {res_hist != nullptr && res_hist == res ? nullptr : res, fc, true, "res"},
-                              {states, sc, true, "states"}, {k_sq, sizeof(float) * (size_t)batch * plane, false, "k_sq"},
+                              {states, sc, true, "states"}, {m.k_sq, sizeof(float) * (size_t)batch * plane, false, "k_sq"},
                               {src, sizeof(float) * (size_t)src_batch * 2 * plane, false, "src"}, {res_hist, it * fc, true, "res_hist"},
                               {wf_hist, it * fc, true, "wf_hist"}, {st_hist, it * sc, true, "st_hist"},
                               {rmse_hist, sizeof(float) * it * batch, true, "rmse_hist"},
-                              {k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
-                              {rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"}};
+                              {m.k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
+                              {m.rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"}};
         const char *one, *other;
         if (first_overlap(r, 11, &one, &other)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, one, other);
     }
@@ -1168,8 +1143,7 @@ int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* state
     if (lossy && (rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (before the workspace: a refused call builds nothing)
     if ((rc = reserve_workspace(ctx, batch, s)) != HN_OK) return rc;
     if (n_iter == 0) return HN_OK;
-    if ((rc = check_async(ctx, medium ? "hn_step_medium (an earlier call)" : lossy ? "hn_step_lossy (an earlier call)" : "hn_step (an earlier call)")) != HN_OK)
-        return rc;
+    if ((rc = check_async(ctx, (std::string(m.step_name()) + " (an earlier call)").c_str())) != HN_OK) return rc;
     int ns = ctx->opt_lanes;
     if (batch < 2 * ns) ns = 1;                       // tiny batches: not worth splitting
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
@@ -1179,7 +1153,7 @@ int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* state
         if ((rc = zero_async(ctx, rmse_hist, sizeof(float) * (size_t)n_iter * batch, s)) != HN_OK) return rc;
         if ((rc = zero_async(ctx, ctx->it_counter, 8 * sizeof(int), s)) != HN_OK) return rc;
     }
-    const StepArgs a{wf, res, states, k_sq, src, src_batch, batch, rmse_hist, use_side, k_sq_im, rho_grad};
+    const StepArgs a{wf, res, states, m, src, src_batch, batch, rmse_hist, use_side};
     const size_t fb_all = sizeof(float) * (size_t)batch * 2 * plane, sb_all = sizeof(float) * (size_t)batch * kState * L;
     if (ns == 1) {
         // One lane: an iteration is a fixed kernel sequence over fixed buffers (the hidden states ping-pong between the
@@ -1287,28 +1261,27 @@ int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* state
     return check_async(ctx, who);   // (what is up by now; hn_check_async_errors after a synchronise sees the rest)
 }
 
-}  // namespace
 }  // namespace hn
 
 extern "C" {
 
 int hn_step(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* src, int src_batch, int batch,
             int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
-    return step_entry(ctx, "hn_step", wf, res, states, k_sq, nullptr, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
+    return step_entry(ctx, "hn_step", wf, res, states, Medium{k_sq}, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
 }
 
 int hn_step_lossy(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* src, int src_batch, int batch,
                   int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
     if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_step_lossy: k_sq_im is NULL (a lossless medium is hn_step)");
-    return step_entry(ctx, "hn_step_lossy", wf, res, states, k_sq, k_sq_im, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
+    return step_entry(ctx, "hn_step_lossy", wf, res, states, Medium{k_sq, k_sq_im}, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream);
 }
 
 int hn_step_medium(hn_ctx* ctx, float* wf, float* res, float* states, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* src,
                    int src_batch, int batch, int n_iter, float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream) {
     if (ctx && !rho_grad)
         return fail(ctx, HN_ERR_ARG, "hn_step_medium: rho_grad is NULL (a medium of constant density is hn_step_lossy, or hn_step without absorption)");
-    return step_entry(ctx, "hn_step_medium", wf, res, states, k_sq, k_sq_im, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist, stream,
-                      rho_grad);
+    return step_entry(ctx, "hn_step_medium", wf, res, states, Medium{k_sq, k_sq_im, rho_grad}, src, src_batch, batch, n_iter, res_hist, wf_hist, st_hist, rmse_hist,
+                      stream);
 }
 
 // Laboratory accessor (tools/deepx_check.py; not part of the ABI of include/helmnet_hip.h): the workspace tensor kind (0 x_d / upsampled, 1 skip out_d,

@@ -556,20 +556,35 @@ void spec_sq_axis_free(hn_ctx* ctx);
 int spec_line_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const float* src, int src_batch, int batch, float* accum_sumsq,
                     hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
 int spec_line_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq, const float* add, int batch, hipStream_t s);
-// ---- absorbing media: out = L(wf) + (ksq + i ksq_im) wf - src, both planes of k_sq and src required; the rest as spec_apply ----
-// On a rectangular domain and on the mixed route the tables exist; on any other square domain spec_lossy_reserve builds ctx->sq_axis once per domain
-// (HN_ERR_STATE under stream capture, nothing enqueued): an entry point that launches before it reaches spec_apply_lossy asks there first.  `who`: the
-// entry point, for the messages.
+// ---- the medium of a call: what multiplies (and, with a density, differentiates) the wavefield beside the Laplacian ----
+// An entry point builds it from its arguments; everything below passes it on and asks kind() where the routes part ("The Medium record").
+struct Medium {
+    const float* k_sq;                 // [B][h][w]
+    const float* k_sq_im = nullptr;    // [B][h][w], absorbing media: the operator's pointwise term is (k_sq + i k_sq_im) wf; null: lossless
+    const float* rho_grad = nullptr;   // [B][2][h][w], variable density: q = grad(log rho), plane 0 along x, plane 1 along y; null: constant density
+    enum class Kind { Lossless, Lossy, Density };   // Density: k_sq_im may be null (it is then not read)
+    Kind kind() const { return rho_grad != nullptr ? Kind::Density : k_sq_im != nullptr ? Kind::Lossy : Kind::Lossless; }
+    // the samples from b0 on, `plane` pixels each (a pipeline lane's share of the batch)
+    Medium from_sample(int b0, size_t plane) const {
+        return {k_sq + b0 * plane, k_sq_im ? k_sq_im + b0 * plane : nullptr, rho_grad ? rho_grad + b0 * 2 * plane : nullptr};
+    }
+    const char* step_name() const {   // the hn_step entry point of this kind of medium, for the messages
+        return rho_grad != nullptr ? "hn_step_medium" : k_sq_im != nullptr ? "hn_step_lossy" : "hn_step";
+    }
+};
+// On a rectangular domain and on the mixed route the tables of the lossy and the variable-density operator exist; on any other square domain
+// spec_lossy_reserve builds ctx->sq_axis once per domain (HN_ERR_STATE under stream capture, nothing enqueued): an entry point that launches before it
+// reaches spec_forward / spec_backward with such a medium asks there first.  `who`: the entry point, for the messages.
 int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s);
-int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
-                     int batch, float* accum_sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
-// variable density: out = L(wf) - b_x q_x d_x wf - b_y q_y d_y wf + (ksq [+ i ksq_im]) wf - src, q = rho_grad [B][2][h][w] (plane 0 along x, plane 1 along y);
-// ksq_im may be null (then it is not read); tables, reserve rule and the remaining arguments as spec_apply_lossy
-int spec_apply_medium(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* rho_grad, const float* src,
-                      int src_batch, int batch, float* sumsq, hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
-// out = A^H g [+ add] = L^H(g) + (ksq - i ksq_im) g [+ add], the adjoint of the operator above on the same kernel and tables (g != out; `add` may alias out)
-int spec_adjoint_lossy(hn_ctx* ctx, const char* who, const float* g, float* out, const float* ksq, const float* ksq_im, const float* add, int batch,
-                       hipStream_t s);
+// The residual operator of medium m; the remaining arguments as spec_apply.
+//   Lossless: spec_apply itself, with its own choice of route
+//   Lossy:    out = L(wf) + (ksq + i ksq_im) wf - src on the LDS-line kernels, k_sq and src required
+//   Density:  out = L(wf) - b_x q_x d_x wf - b_y q_y d_y wf + (ksq [+ i ksq_im]) wf - src on the same kernels and tables
+int spec_forward(hn_ctx* ctx, const char* who, const Medium& m, const float* wf, float* out, const float* src, int src_batch, int batch, float* sumsq,
+                 hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
+// Its adjoint: out = A^H g [+ add].  Lossless: spec_adjoint itself; Lossy: L^H(g) + (ksq - i ksq_im) g on the LDS-line kernels (g != out; `add` may alias
+// out); Density: refused, the variable-density operator has no adjoint
+int spec_backward(hn_ctx* ctx, const char* who, const Medium& m, const float* g, float* out, const float* add, int batch, hipStream_t s);
 // HN_ERR_UNSUPPORTED "<who>: not implemented on a rectangular domain ..." (every entry point that reads the domain and has no rectangular path)
 int rect_unsupported(hn_ctx* ctx, const char* who);
 // ---- float64 residual check (hn_f64.hip) ----
@@ -723,6 +738,10 @@ bool side_flags_apply(hn_ctx* ctx, hipStream_t s);
 // flag sync, the side stream's halves (hn_unet.hip): a one-wave kernel that holds stream s until *flag has reached epoch / a one-thread kernel that stores it
 int ensure_sync_words(hn_ctx* ctx);
 int build_inc_sigma_map(hn_ctx* ctx);   // (hn_api.hip; needs weights and domain, synchronises)
+// The solver loop behind hn_step, hn_step_lossy and hn_step_medium (hn_api.hip); the flexible GMRES cycles call it for their preconditioner, with
+// who = m.step_name().  The arguments around the medium as hn_step's.
+int step_entry(hn_ctx* ctx, const char* who, float* wf, float* res, float* states, const Medium& m, const float* src, int src_batch, int batch, int n_iter,
+               float* res_hist, float* wf_hist, float* st_hist, float* rmse_hist, void* stream);
 int check_async(hn_ctx* ctx, const char* who);   // HN_ERR_STATE once a bounded device-side wait has given up (sticky word: 1 side-stream flag, 2 merged level-0 launch, 3 deep kernel)
 int zero_async(hn_ctx* ctx, void* p, size_t bytes, hipStream_t s);   // (hn_api.hip: a kernel of this library, never hipMemsetAsync, on a caller's stream)
 void launch_sync_gate(hn_ctx* ctx, const unsigned* flag, unsigned epoch, hipStream_t s);

@@ -2,7 +2,7 @@
 //
 // The method is the one helmnet_amd/gmres.py runs with torch (matlab/spectral_gmres_solver.m:86-115 is the reference's classical baseline):
 // r = rhs - A x, v_0 = r / |r|; per inner step w = A v_k, two passes of classical Gram-Schmidt, H[:k+1, k] = h + h2, H[k+1, k] = |w|, v_{k+1} = w / |w|;
-// progressive Givens rotations per sample with the residual estimate |g[k+1]| / sqrt(2 n^2).  A u = L(u) + k_sq * u is spec_apply, the launcher
+// progressive Givens rotations per sample with the residual estimate |g[k+1]| / sqrt(2 n^2).  A u = L(u) + k_sq * u is spec_forward, the launcher
 // hn_residual uses, with a source of zeros (the 256- and 512-point row kernels read their source operand unconditionally: the zeros are a page of the
 // workspace, and x - 0 is x bit for bit).  spec_apply's tensors have dense sample strides, the caller's basis has not: the operator reads v_k from and
 // writes w to two dense fields of the workspace, and the scale kernel stores v_{k+1} into both places.
@@ -16,15 +16,18 @@
 //
 // hn_gmres_refine_cycle (at the end of this file) wraps the same launches into one step of iterative refinement: the true residual (hn_f64.hip) and the
 // update in float64, the cycle in fp32 on the scaled correction equation A d = r / s.  hn_fgmres_refine_cycle_lossy is that step for an absorbing
-// medium: Precond.k_sq_im set, the float64 residual f64_apply_lossy's, the cycle and the preconditioner the lossy ones.
+// medium: the float64 residual f64_apply_lossy's, the cycle and the preconditioner the lossy ones.
+//
+// The medium (hn_internal.h: Medium) is built by the entry point and passed down: A is spec_forward, A^H spec_backward and the learned iteration
+// step_entry on it, whichever kind it is.
 //
 // hn_fgmres_cycle / hn_fgmres_refine_cycle are the same launches as a FLEXIBLE cycle (Saad 1993), right-preconditioned by the learned iteration: per inner
 // step z_k = M(v_k) -- precond_iters iterations of hn_step on A z = alpha v_k from rest, z_k = wf / alpha --, w = A z_k, the orthogonalisation and the small
 // problem on V as before, the update x += sum y_j z_j over the caller's zbasis.  The preconditioner is a parameter of launch_cycle (Precond); without one
 // (zbasis nullptr) not one launch or argument of hn_gmres_cycle differs.  Three streaming kernels (k_seed, k_take, k_take_copy) move the vectors; none sums.
 //
-// hn_fgmres_adjoint_cycle is the flexible cycle on A^H (spec_adjoint): the operator is a parameter of launch_cycle (Op), and with Op::Forward not one launch
-// or argument of the four entry points above differs.  spec_adjoint has no source operand: the start residual is its output minus rhs (k_minus_rhs, which
+// hn_fgmres_adjoint_cycle is the flexible cycle on A^H (spec_backward): the operator is a parameter of launch_cycle (Op), and with Op::Forward not one launch
+// or argument of the four entry points above differs.  spec_backward has no source operand: the start residual is its output minus rhs (k_minus_rhs, which
 // also leaves the partial sums of |w|^2 that k_norm_part leaves for the forward operator).  The learned network approximates A^-1, not A^-H; the PML
 // operator is complex-symmetric up to the diagonal similarity W = gamma_y[i] gamma_x[j] (A^T ~ W A W^-1), so A^-H v ~ conj(W A^-1 (conj(v) / W)): the
 // preconditioner is the SAME hn_step problem between two streaming kernels (k_seed_adj, k_take_adj) that conjugate and scale by 1 / W and W.
@@ -492,7 +495,7 @@ __global__ __launch_bounds__(256) void k_adjoint_grad(const float* __restrict__ 
     }
 }
 
-// which operator a cycle runs on: A (spec_apply, the four forward entry points) or A^H (spec_adjoint)
+// which operator a cycle runs on: A (spec_forward) or A^H (spec_backward)
 enum class Op { Forward, Adjoint };
 
 // The preconditioner of a flexible cycle as launch_cycle takes it; zbasis nullptr: none, the cycle is plain GMRES
@@ -500,11 +503,7 @@ struct Precond {
     float* zbasis = nullptr;   // [B][restart][2 n^2], the caller's
     int iters = 0;             // hn_step iterations per inner step; 0: z = v
     float alpha = 1.f;         // the learned solve sees alpha v
-    const char* who = "";      // the entry point, for what hn_step reports from inside the cycle
-    const float* k_sq_im = nullptr;   // non-null (hn_fgmres_cycle_lossy, hn_fgmres_adjoint_cycle_lossy): A is the lossy operator (Op::Adjoint: its A^H)
-                                      // and the learned iteration hn_step_lossy, also with iters 0
-    const float* rho_grad = nullptr;  // non-null (hn_fgmres_cycle_medium, Op::Forward only): A is the variable-density operator and the learned iteration
-                                      // hn_step_medium; k_sq_im may then be null
+    const char* who = "";      // the entry point, for what the operator and hn_step report from inside the cycle
 };
 
 // what hn_step reported, under the name of the entry point that called it
@@ -522,7 +521,7 @@ void precond_ws_free(hn_ctx* ctx) {
 }
 
 // the learned preconditioner's problem for `batch` samples on the current domain and network -- the caller has refused stream capture
-int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, const float* k_sq_im, int batch, hipStream_t s, const float* rho_grad = nullptr) {
+int precond_prepare(hn_ctx* ctx, const char* who, const Medium& m, int batch, hipStream_t s) {
     const int n = ctx->tab.n;
     PrecondWs* ws = ctx->pcw;
     if (ws == nullptr || ws->n != n || ws->state_len != ctx->state_len || batch > ws->batch) {
@@ -539,12 +538,7 @@ int precond_prepare(hn_ctx* ctx, const char* who, const float* k_sq, const float
     }
     // hn_step's own refusals (a domain the network's depth does not divide) and its workspace now, with nothing enqueued: the call of the cycle with
     // zero iterations, which launches nothing
-    if (rho_grad != nullptr)
-        return step_named(ctx, who, hn_step_medium(ctx, ws->wf, ws->res, ws->states, k_sq, k_sq_im, rho_grad, ws->src, batch, batch, 0, nullptr, nullptr, nullptr,
-                                                   nullptr, s));
-    if (k_sq_im != nullptr)
-        return step_named(ctx, who, hn_step_lossy(ctx, ws->wf, ws->res, ws->states, k_sq, k_sq_im, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
-    return step_named(ctx, who, hn_step(ctx, ws->wf, ws->res, ws->states, k_sq, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
+    return step_named(ctx, who, step_entry(ctx, m.step_name(), ws->wf, ws->res, ws->states, m, ws->src, batch, batch, 0, nullptr, nullptr, nullptr, nullptr, s));
 }
 
 void adjoint_w_free(hn_ctx* ctx) {
@@ -625,8 +619,9 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
 // The restart cycle's launches, the workspace prepared.  tol_dev / pre_stopped: see SmallArgs (nullptr: hn_gmres_cycle, whose bits they leave alone --
 // the comparison est < tol is the same one on the same doubles); x, rhs and the outputs may lie in a workspace of the library's.  pc: the flexible
 // cycle's preconditioner (its workspace prepared when pc.iters > 0); the operator input then holds z_k while A is applied and v_{k+1} after k_scale.
-// op: Op::Adjoint runs the same cycle on A^H (and, with pc.iters > 0, needs ctx->adjw prepared); Op::Forward is every launch and argument of before.
-int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+// op: Op::Adjoint runs the same cycle on A^H (and, with pc.iters > 0, needs ctx->adjw prepared; a variable-density medium has none: spec_backward refuses
+// it before anything is enqueued); Op::Forward is every launch and argument of before.
+int launch_cycle(hn_ctx* ctx, Op op, float* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart, double tol,
                  const double* tol_dev, const int* pre_stopped, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
     const KrylovWs& ws = *ctx->kry;
     const long P = (long)ws.n * ws.n;
@@ -637,24 +632,12 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
     SmallArgs a{ws.part, ws.npart, ws.scale, ws.g, ws.cs, ws.R, ws.y, ws.stopped, hess, rmse, k_used, batch, restart, nchunk,
                 tol, 1.0 / sqrt(2.0 * (double)P), tol_dev, pre_stopped};
     const bool adj = op == Op::Adjoint;
-    const float* k_im = pc.k_sq_im;
-    const float* rho = pc.rho_grad;
-    if (rho != nullptr && adj) return fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator has no adjoint cycle", pc.who);
-    // w = A x - rhs = -r
-    if (rho != nullptr) {
-        if ((rc = spec_apply_medium(ctx, pc.who, x, ws.w, k_sq, k_im, rho, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
-        hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
-    } else if (k_im != nullptr && adj) {
-        if ((rc = spec_adjoint_lossy(ctx, pc.who, x, ws.w, k_sq, k_im, nullptr, batch, s)) != HN_OK) return rc;
-        hipLaunchKernelGGL(k_minus_rhs, grid, blk, 0, s, ws.w, rhs, rhs_batch == 1 ? 0L : 2 * P, ws.npart, P, nchunk);
-    } else if (k_im != nullptr) {
-        if ((rc = spec_apply_lossy(ctx, pc.who, x, ws.w, k_sq, k_im, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
-        hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
-    } else if (adj) {
-        if ((rc = spec_adjoint(ctx, x, ws.w, k_sq, nullptr, batch, s)) != HN_OK) return rc;
+    // w = A x - rhs = -r; A^H comes without a source operand
+    if (adj) {
+        if ((rc = spec_backward(ctx, pc.who, m, x, ws.w, nullptr, batch, s)) != HN_OK) return rc;
         hipLaunchKernelGGL(k_minus_rhs, grid, blk, 0, s, ws.w, rhs, rhs_batch == 1 ? 0L : 2 * P, ws.npart, P, nchunk);
     } else {
-        if ((rc = spec_apply(ctx, x, ws.w, k_sq, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
+        if ((rc = spec_forward(ctx, pc.who, m, x, ws.w, rhs, rhs_batch, batch, nullptr, s)) != HN_OK) return rc;
         hipLaunchKernelGGL(k_norm_part, grid, blk, 0, s, ws.w, ws.npart, P, nchunk);
     }
     hipLaunchKernelGGL(k_small_init, dim3(batch), dim3(64), 0, s, a);
@@ -665,20 +648,14 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* r
             if (adj) hipLaunchKernelGGL(k_seed_adj, grid, blk, 0, s, ws.vin, ctx->adjw->winv, pc.alpha, p.src, p.res, p.wf, P);
             else hipLaunchKernelGGL(k_seed, grid, blk, 0, s, ws.vin, pc.alpha, p.src, p.res, p.wf, P);
             if ((rc = zero_async(ctx, p.states, sizeof(float) * (size_t)batch * kState * (size_t)p.state_len, s)) != HN_OK) return rc;
-            rc = rho != nullptr  ? hn_step_medium(ctx, p.wf, p.res, p.states, k_sq, k_im, rho, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s)
-               : k_im != nullptr ? hn_step_lossy(ctx, p.wf, p.res, p.states, k_sq, k_im, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s)
-                                 : hn_step(ctx, p.wf, p.res, p.states, k_sq, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s);
+            rc = step_entry(ctx, m.step_name(), p.wf, p.res, p.states, m, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s);
             if (rc != HN_OK) return step_named(ctx, pc.who, rc);
             if (adj) hipLaunchKernelGGL(k_take_adj, grid, blk, 0, s, p.wf, ctx->adjw->w, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
             else hipLaunchKernelGGL(k_take, grid, blk, 0, s, p.wf, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
         } else if (pc.zbasis != nullptr) {
             hipLaunchKernelGGL(k_take_copy, grid, blk, 0, s, ws.vin, pc.zbasis, P, k, restart);
         }
-        rc = rho != nullptr         ? spec_apply_medium(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, rho, ws.zero, 1, batch, nullptr, s)
-             : k_im != nullptr && adj ? spec_adjoint_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, nullptr, batch, s)
-             : k_im != nullptr      ? spec_apply_lossy(ctx, pc.who, ws.vin, ws.w, k_sq, k_im, ws.zero, 1, batch, nullptr, s)
-             : adj                  ? spec_adjoint(ctx, ws.vin, ws.w, k_sq, nullptr, batch, s)
-                                    : spec_apply(ctx, ws.vin, ws.w, k_sq, ws.zero, 1, batch, nullptr, s);
+        rc = adj ? spec_backward(ctx, pc.who, m, ws.vin, ws.w, nullptr, batch, s) : spec_forward(ctx, pc.who, m, ws.vin, ws.w, ws.zero, 1, batch, nullptr, s);
         if (rc != HN_OK) return rc;
         hipLaunchKernelGGL(k_dots, grid, blk, 0, s, ws.w, basis, ws.part, P, k, restart, nchunk);
         hipLaunchKernelGGL(k_sub<0>, grid, blk, 0, s, ws.w, basis, ws.part, ws.npart, P, k, restart, nchunk);
@@ -794,13 +771,14 @@ int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s, bool lossy) {
     return HN_OK;
 }
 
-// What the four cycle entry points refuse alike, under the entry point's name: x fp32 and rmse64 NULL for the plain cycles, x float64 for the refinements;
-// zbasis NULL for the two without a preconditioner, required for the flexible ones.  Any two arguments that overlap are refused, read against read too
-// (every range counts as written).  hn_gmres_cycle reports a missing domain with HN_ERR_ARG, the other three with HN_ERR_STATE, and a caller may rely on
-// either: a known wart.
-int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, const void* x, const float* k_sq, const float* rhs, int rhs_batch, int batch,
+// What the cycle entry points refuse alike, under the entry point's name: x fp32 and rmse64 NULL for the plain cycles, x float64 for the refinements;
+// zbasis NULL for the two without a preconditioner, required for the flexible ones; the medium's k_sq_im and rho_grad where it has them.  Any two arguments
+// that overlap are refused, read against read too (every range counts as written); the medium's extra planes stand first in the table, so that they are
+// the ones named first ("k_sq_im overlaps basis").  hn_gmres_cycle reports a missing domain with HN_ERR_ARG, the others with HN_ERR_STATE, and a caller may
+// rely on either: a known wart.
+int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, const void* x, const Medium& m, const float* rhs, int rhs_batch, int batch,
                      int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64) {
-    if (!ctx || !x || !k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64) || (flexible && !zbasis))
+    if (!ctx || !x || !m.k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64) || (flexible && !zbasis))
         return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (ctx->rect) return rect_unsupported(ctx, who);
     if (ctx->tab.n == 0) return fail(ctx, refine || flexible ? HN_ERR_STATE : HN_ERR_ARG, "%s: hn_set_domain has not been called", who);
@@ -808,84 +786,62 @@ int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, c
     if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);
     if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: rhs batch %d must be 1 or equal to the batch %d", who, rhs_batch, batch);
     const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
-    const MemRange r[] = {{x, B * 2 * P * (refine ? 8 : 4), true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
+    const MemRange r[] = {{m.k_sq_im, B * P * 4, true, "k_sq_im"}, {m.rho_grad, B * 2 * P * 4, true, "rho_grad"},
+                          {x, B * 2 * P * (refine ? 8 : 4), true, "x"}, {m.k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
                           {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
                           {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"},
                           {rmse64, B * 8, true, "rmse64"}};
-    for (int i = 0; i < 5; ++i)   // the fields are read and written as float4 (x of the refinement: as double2); a NULL zbasis is aligned
+    for (int i = 0; i < 7; ++i)   // the fields are read and written as float4 (x of the refinement: as double2); a NULL one is aligned
         if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
     if (reinterpret_cast<uintptr_t>(rmse64) % 8 != 0) return fail(ctx, HN_ERR_ARG, "%s: rmse64 is not 8-byte aligned", who);
     const char *na, *nb;
-    if (first_overlap(r, 9, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    if (first_overlap(r, 11, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     return HN_OK;
 }
 
-// What the two flexible entry points refuse beyond check_cycle_args, and the preconditioner's workspace: nothing is enqueued before this has passed.
+// What the flexible entry points refuse beyond check_cycle_args, and the preconditioner's workspace: nothing is enqueued before this has passed.
 // Not capturable: hn_step's first call on a new stream probes its side stream and synchronises.
-int check_precond(hn_ctx* ctx, const char* who, int precond_iters, float precond_scale, const float* k_sq, int batch, hipStream_t s,
-                  const float* k_sq_im = nullptr, const float* rho_grad = nullptr) {
+int check_precond(hn_ctx* ctx, const char* who, int precond_iters, float precond_scale, const Medium& m, int batch, hipStream_t s) {
     if (precond_iters < 0) return fail(ctx, HN_ERR_ARG, "%s: precond_iters must be >= 0 (got %d)", who, precond_iters);
     if (!(precond_scale > 0.f) || !(precond_scale <= 3.402823466e38f))
         return fail(ctx, HN_ERR_ARG, "%s: precond_scale must be finite and > 0 (got %g)", who, (double)precond_scale);
     if (stream_capturing(s)) return fail(ctx, HN_ERR_STATE, "%s: not capturable (the preconditioner calls hn_step, whose first call on a stream synchronises)", who);
     if (precond_iters == 0) return HN_OK;
     if (!ctx->have_weights) return fail(ctx, HN_ERR_STATE, "%s: hn_load_weights has not been called (precond_iters %d needs the network)", who, precond_iters);
-    return precond_prepare(ctx, who, k_sq, k_sq_im, batch, s, rho_grad);
+    return precond_prepare(ctx, who, m, batch, s);
 }
 
-// A further read-only field of `planes` planes per sample (k_sq_im of the lossy cycles, rho_grad of the variable-density one) by k_sq's rules, after
-// check_cycle_args: 16-byte aligned, overlapping none of the other arguments
-int check_cycle_field(hn_ctx* ctx, const char* who, const char* name, int planes, const float* field, const float* x, const float* k_sq, const float* rhs,
-                      int rhs_batch, int batch, int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse,
-                      const int32_t* k_used) {
-    const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
-    if (reinterpret_cast<uintptr_t>(field) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, name);
-    const MemRange others[] = {{x, B * 2 * P * 4, true, "x"}, {k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
-                               {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
-                               {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"}};
-    for (const MemRange& o : others) {
-        const MemRange pair[] = {{field, B * (size_t)planes * P * 4, true, name}, o};
-        const char *na, *nb;
-        if (first_overlap(pair, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
-    }
-    return HN_OK;
-}
-int check_cycle_k_sq_im(hn_ctx* ctx, const char* who, const float* k_sq_im, const float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch,
-                        int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used) {
-    return check_cycle_field(ctx, who, "k_sq_im", 1, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used);
-}
-
-// hn_gmres_cycle and hn_fgmres_cycle, the arguments checked
-int run_cycle(hn_ctx* ctx, Op op, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol, const Precond& pc, float* basis,
+// the plain and the flexible cycles, the arguments checked
+int run_cycle(hn_ctx* ctx, Op op, float* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart, float tol, const Precond& pc, float* basis,
               float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
     if (const int rc = prepare(ctx, batch, restart, s); rc != HN_OK) return rc;
-    return launch_cycle(ctx, op, x, k_sq, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, pc, basis, hess, rmse, k_used, s);
+    return launch_cycle(ctx, op, x, m, rhs, rhs_batch, batch, restart, (double)tol, nullptr, nullptr, pc, basis, hess, rmse, k_used, s);
 }
 
-// hn_gmres_refine_cycle, hn_fgmres_refine_cycle and (pc.k_sq_im non-null: the lossy operator in the float64 residual, the cycle and the preconditioner)
-// hn_fgmres_refine_cycle_lossy, the arguments but tol and inner_floor checked
-int run_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+// the refinement steps, the arguments but tol and inner_floor checked; a lossy medium: the lossy operator in the float64 residual, the cycle and the
+// preconditioner
+int run_refine_cycle(hn_ctx* ctx, double* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart, double tol,
                      float inner_floor, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, hipStream_t s) {
     const long P = (long)ctx->tab.n * ctx->tab.n;
     // all three workspaces before the first launch: a call that has to build one under capture leaves nothing behind
     int rc = prepare(ctx, batch, restart, s);
-    const bool lossy = pc.k_sq_im != nullptr;
+    const bool lossy = m.k_sq_im != nullptr;
     if (rc == HN_OK) rc = refine_prepare(ctx, batch, s, lossy);
     if (rc == HN_OK) rc = lossy ? f64_lossy_reserve(ctx, batch, true, s) : f64_reserve(ctx, batch, true, s);
     if (rc != HN_OK) return rc;
     const RefineWs& ws = *ctx->rfn;
     const long nk4 = (long)batch * P / 4, nr4 = (long)rhs_batch * 2 * P / 4;   // (n is a multiple of 16)
     const dim3 grid(ctx->kry->nchunk, batch), blk(256);
-    hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + nr4 + 255) / 256)), blk, 0, s, k_sq, ws.ksq64, nk4, rhs, ws.rhs64, nr4);
+    hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + nr4 + 255) / 256)), blk, 0, s, m.k_sq, ws.ksq64, nk4, rhs, ws.rhs64, nr4);
     if (lossy) {
-        hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + 255) / 256)), blk, 0, s, pc.k_sq_im, ws.ksq_im64, nk4, nullptr, nullptr, 0L);
+        hipLaunchKernelGGL(k_refine_upcast, dim3((unsigned)((nk4 + 255) / 256)), blk, 0, s, m.k_sq_im, ws.ksq_im64, nk4, nullptr, nullptr, 0L);
         rc = f64_apply_lossy(ctx, x, ws.res64, ws.ksq64, ws.ksq_im64, ws.rhs64, rhs_batch, rmse64, batch, s);
     } else {
         rc = f64_apply(ctx, x, ws.res64, ws.ksq64, ws.rhs64, rhs_batch, rmse64, batch, s);
     }
     if (rc != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_rhs, grid, blk, 0, s, ws.res64, rmse64, tol, (double)inner_floor, ws.rhs32, ws.d32, ws.tol, ws.stop, P);
-    if ((rc = launch_cycle(ctx, Op::Forward, ws.d32, k_sq, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, pc, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
+    if ((rc = launch_cycle(ctx, Op::Forward, ws.d32, m, ws.rhs32, batch, batch, restart, 0.0, ws.tol, ws.stop, pc, basis, hess, rmse, k_used, s)) != HN_OK) return rc;
     hipLaunchKernelGGL(k_refine_update, grid, blk, 0, s, x, ws.d32, rmse64, k_used, P);
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
@@ -911,101 +867,65 @@ void precond_free(hn_ctx* ctx) { precond_ws_free(ctx); }
 
 using namespace hn;
 
-extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
-                              float* basis, float* hess, float* rmse, int32_t* k_used, void* stream) {
-    const int rc = check_cycle_args(ctx, "hn_gmres_cycle", false, false, x, k_sq, rhs, rhs_batch, batch, restart, basis, nullptr, hess, rmse, k_used, nullptr);
+// hn_gmres_cycle, hn_fgmres_cycle[_lossy|_medium] and hn_fgmres_adjoint_cycle[_lossy] behind their own NULL refusals
+static int cycle_entry(hn_ctx* ctx, const char* who, Op op, bool flexible, float* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart,
+                       float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used, void* stream) {
+    int rc = check_cycle_args(ctx, who, false, flexible, x, m, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
     if (rc != HN_OK) return rc;
     DeviceGuard guard(ctx);
-    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{}, basis, hess, rmse, k_used, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (!flexible) return run_cycle(ctx, op, x, m, rhs, rhs_batch, batch, restart, tol, Precond{}, basis, hess, rmse, k_used, s);
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, m, batch, s)) != HN_OK) return rc;
+    // (precond_iters 0 has not asked step_entry for the tables)
+    if (m.kind() != Medium::Kind::Lossless && (rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;
+    if (op == Op::Adjoint && precond_iters > 0 && (rc = adjoint_w_prepare(ctx, who)) != HN_OK) return rc;
+    return run_cycle(ctx, op, x, m, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse, k_used, s);
+}
+
+extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
+                              float* basis, float* hess, float* rmse, int32_t* k_used, void* stream) {
+    return cycle_entry(ctx, "hn_gmres_cycle", Op::Forward, false, x, Medium{k_sq}, rhs, rhs_batch, batch, restart, tol, 0, 1.f, basis, nullptr, hess, rmse, k_used,
+                       stream);
 }
 
 extern "C" int hn_fgmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
                                int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
                                void* stream) {
-    const char* who = "hn_fgmres_cycle";
-    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
-    if (rc != HN_OK) return rc;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
-    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse, k_used, s);
+    return cycle_entry(ctx, "hn_fgmres_cycle", Op::Forward, true, x, Medium{k_sq}, rhs, rhs_batch, batch, restart, tol, precond_iters, precond_scale, basis, zbasis,
+                       hess, rmse, k_used, stream);
 }
 
 extern "C" int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch, int restart,
                                      float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse,
                                      int32_t* k_used, void* stream) {
-    const char* who = "hn_fgmres_cycle_lossy";
-    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_fgmres_cycle)", who);
-    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
-    if (rc != HN_OK) return rc;
-    if ((rc = check_cycle_k_sq_im(ctx, who, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK) return rc;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im)) != HN_OK) return rc;
-    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (precond_iters 0 has not asked hn_step_lossy)
-    Precond pc{zbasis, precond_iters, precond_scale, who};
-    pc.k_sq_im = k_sq_im;
-    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_fgmres_cycle_lossy: k_sq_im is NULL (a lossless medium is hn_fgmres_cycle)");
+    return cycle_entry(ctx, "hn_fgmres_cycle_lossy", Op::Forward, true, x, Medium{k_sq, k_sq_im}, rhs, rhs_batch, batch, restart, tol, precond_iters, precond_scale,
+                       basis, zbasis, hess, rmse, k_used, stream);
 }
 
 extern "C" int hn_fgmres_cycle_medium(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* rhs, int rhs_batch,
                                       int batch, int restart, float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
                                       float* rmse, int32_t* k_used, void* stream) {
-    const char* who = "hn_fgmres_cycle_medium";
     if (ctx && !rho_grad)
-        return fail(ctx, HN_ERR_ARG, "%s: rho_grad is NULL (a medium of constant density is hn_fgmres_cycle_lossy, or hn_fgmres_cycle without absorption)", who);
-    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
-    if (rc != HN_OK) return rc;
-    if (k_sq_im != nullptr &&
-        (rc = check_cycle_k_sq_im(ctx, who, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK)
-        return rc;
-    if ((rc = check_cycle_field(ctx, who, "rho_grad", 2, rho_grad, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK) return rc;
-    {
-        const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
-        const MemRange pair[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, {rho_grad, B * 2 * P * 4, true, "rho_grad"}};
-        const char *na, *nb;
-        if (first_overlap(pair, 2, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
-    }
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im, rho_grad)) != HN_OK) return rc;
-    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (precond_iters 0 has not asked hn_step_medium)
-    Precond pc{zbasis, precond_iters, precond_scale, who};
-    pc.k_sq_im = k_sq_im;
-    pc.rho_grad = rho_grad;
-    return run_cycle(ctx, Op::Forward, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
+        return fail(ctx, HN_ERR_ARG, "hn_fgmres_cycle_medium: rho_grad is NULL (a medium of constant density is hn_fgmres_cycle_lossy, or hn_fgmres_cycle without "
+                    "absorption)");
+    return cycle_entry(ctx, "hn_fgmres_cycle_medium", Op::Forward, true, x, Medium{k_sq, k_sq_im, rho_grad}, rhs, rhs_batch, batch, restart, tol, precond_iters,
+                       precond_scale, basis, zbasis, hess, rmse, k_used, stream);
 }
 
 extern "C" int hn_fgmres_adjoint_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch,
                                              int restart, float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess,
                                              float* rmse, int32_t* k_used, void* stream) {
-    const char* who = "hn_fgmres_adjoint_cycle_lossy";
-    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_fgmres_adjoint_cycle)", who);
-    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
-    if (rc != HN_OK) return rc;
-    if ((rc = check_cycle_k_sq_im(ctx, who, k_sq_im, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used)) != HN_OK) return rc;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im)) != HN_OK) return rc;
-    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;
-    if (precond_iters > 0 && (rc = adjoint_w_prepare(ctx, who)) != HN_OK) return rc;
-    Precond pc{zbasis, precond_iters, precond_scale, who};
-    pc.k_sq_im = k_sq_im;
-    return run_cycle(ctx, Op::Adjoint, x, k_sq, rhs, rhs_batch, batch, restart, tol, pc, basis, hess, rmse, k_used, s);
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_fgmres_adjoint_cycle_lossy: k_sq_im is NULL (a lossless medium is hn_fgmres_adjoint_cycle)");
+    return cycle_entry(ctx, "hn_fgmres_adjoint_cycle_lossy", Op::Adjoint, true, x, Medium{k_sq, k_sq_im}, rhs, rhs_batch, batch, restart, tol, precond_iters,
+                       precond_scale, basis, zbasis, hess, rmse, k_used, stream);
 }
 
 extern "C" int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
                                        int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
                                        void* stream) {
-    const char* who = "hn_fgmres_adjoint_cycle";
-    int rc = check_cycle_args(ctx, who, false, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
-    if (rc != HN_OK) return rc;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
-    if (precond_iters > 0 && (rc = adjoint_w_prepare(ctx, who)) != HN_OK) return rc;
-    return run_cycle(ctx, Op::Adjoint, x, k_sq, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse,
-                     k_used, s);
+    return cycle_entry(ctx, "hn_fgmres_adjoint_cycle", Op::Adjoint, true, x, Medium{k_sq}, rhs, rhs_batch, batch, restart, tol, precond_iters, precond_scale, basis,
+                       zbasis, hess, rmse, k_used, stream);
 }
 
 // hn_adjoint_grad (g_k_sq_im nullptr, lossy false) and hn_adjoint_grad_lossy
@@ -1044,54 +964,40 @@ extern "C" int hn_adjoint_grad_lossy(hn_ctx* ctx, const float* lambda, const flo
     return adjoint_grad_entry(ctx, "hn_adjoint_grad_lossy", true, lambda, u, src_batch, batch, g_k_sq, g_k_sq_im, g_src, stream);
 }
 
-extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
-                                     float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
-    const char* who = "hn_gmres_refine_cycle";
-    int rc = check_cycle_args(ctx, who, true, false, x, k_sq, rhs, rhs_batch, batch, restart, basis, nullptr, hess, rmse, k_used, rmse64);
+// hn_gmres_refine_cycle and hn_fgmres_refine_cycle[_lossy] behind their own NULL refusals
+static int refine_entry(hn_ctx* ctx, const char* who, bool flexible, double* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart,
+                        double tol, float inner_floor, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse,
+                        int32_t* k_used, double* rmse64, void* stream) {
+    int rc = check_cycle_args(ctx, who, true, flexible, x, m, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, rmse64);
     if (rc == HN_OK) rc = check_refine_tols(ctx, who, tol, inner_floor);
     if (rc != HN_OK) return rc;
     DeviceGuard guard(ctx);
-    return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{}, basis, hess, rmse, k_used, rmse64,
-                            (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (!flexible) return run_refine_cycle(ctx, x, m, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{}, basis, hess, rmse, k_used, rmse64, s);
+    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, m, batch, s)) != HN_OK) return rc;
+    // (precond_iters 0 has not asked step_entry for the tables)
+    if (m.kind() != Medium::Kind::Lossless && (rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;
+    return run_refine_cycle(ctx, x, m, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse,
+                            k_used, rmse64, s);
+}
+
+extern "C" int hn_gmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
+                                     float inner_floor, float* basis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
+    return refine_entry(ctx, "hn_gmres_refine_cycle", false, x, Medium{k_sq}, rhs, rhs_batch, batch, restart, tol, inner_floor, 0, 1.f, basis, nullptr, hess, rmse,
+                        k_used, rmse64, stream);
 }
 
 extern "C" int hn_fgmres_refine_cycle(hn_ctx* ctx, double* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, double tol,
                                       float inner_floor, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse,
                                       int32_t* k_used, double* rmse64, void* stream) {
-    const char* who = "hn_fgmres_refine_cycle";
-    int rc = check_cycle_args(ctx, who, true, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, rmse64);
-    if (rc == HN_OK) rc = check_refine_tols(ctx, who, tol, inner_floor);
-    if (rc != HN_OK) return rc;
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s)) != HN_OK) return rc;
-    return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, Precond{zbasis, precond_iters, precond_scale, who}, basis,
-                            hess, rmse, k_used, rmse64, s);
+    return refine_entry(ctx, "hn_fgmres_refine_cycle", true, x, Medium{k_sq}, rhs, rhs_batch, batch, restart, tol, inner_floor, precond_iters, precond_scale, basis,
+                        zbasis, hess, rmse, k_used, rmse64, stream);
 }
 
 extern "C" int hn_fgmres_refine_cycle_lossy(hn_ctx* ctx, double* x, const float* k_sq, const float* k_sq_im, const float* rhs, int rhs_batch, int batch,
                                             int restart, double tol, float inner_floor, int precond_iters, float precond_scale, float* basis,
                                             float* zbasis, float* hess, float* rmse, int32_t* k_used, double* rmse64, void* stream) {
-    const char* who = "hn_fgmres_refine_cycle_lossy";
-    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "%s: k_sq_im is NULL (a lossless medium is hn_fgmres_refine_cycle)", who);
-    int rc = check_cycle_args(ctx, who, true, true, x, k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, rmse64);
-    if (rc == HN_OK) rc = check_refine_tols(ctx, who, tol, inner_floor);
-    if (rc != HN_OK) return rc;
-    // (x is float64 here: k_sq_im against its second half and against rmse64, which check_cycle_k_sq_im does not see)
-    if ((rc = check_cycle_k_sq_im(ctx, who, k_sq_im, reinterpret_cast<const float*>(x), k_sq, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse,
-                                  k_used)) != HN_OK)
-        return rc;
-    {
-        const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
-        const MemRange r[] = {{k_sq_im, B * P * 4, true, "k_sq_im"}, {x, B * 2 * P * 8, true, "x"}, {rmse64, B * 8, true, "rmse64"}};
-        const char *na, *nb;
-        if (first_overlap(r, 3, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
-    }
-    DeviceGuard guard(ctx);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_precond(ctx, who, precond_iters, precond_scale, k_sq, batch, s, k_sq_im)) != HN_OK) return rc;
-    if ((rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;   // (precond_iters 0 has not asked hn_step_lossy)
-    Precond pc{zbasis, precond_iters, precond_scale, who};
-    pc.k_sq_im = k_sq_im;
-    return run_refine_cycle(ctx, x, k_sq, rhs, rhs_batch, batch, restart, tol, inner_floor, pc, basis, hess, rmse, k_used, rmse64, s);
+    if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_fgmres_refine_cycle_lossy: k_sq_im is NULL (a lossless medium is hn_fgmres_refine_cycle)");
+    return refine_entry(ctx, "hn_fgmres_refine_cycle_lossy", true, x, Medium{k_sq, k_sq_im}, rhs, rhs_batch, batch, restart, tol, inner_floor, precond_iters,
+                        precond_scale, basis, zbasis, hess, rmse, k_used, rmse64, stream);
 }

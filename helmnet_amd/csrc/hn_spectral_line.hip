@@ -587,7 +587,7 @@ int spec_line_adjoint(hn_ctx* ctx, const float* g, float* out, const float* ksq,
     return rect_launch(ctx, d, g, out, ksq, nullptr, nullptr, 1, batch, nullptr, s, nullptr, 0, true, add);
 }
 
-// ---- the lossy operator: res = L(u) + (ksq + i ksq_im) u - src on either kind of domain ----
+// ---- the lossy operator, res = L(u) + (ksq + i ksq_im) u - src, and the variable-density one, which subtracts b_x q_x d_x u + b_y q_y d_y u: one set of tables ----
 // A rectangular domain has its tables, and so has a square one on the mixed route.  Any other square domain gets its axis here, at the first lossy call --
 // never under stream capture; ctx->rect stays null: the domain stays square.
 int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s) {
@@ -599,37 +599,33 @@ int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s) {
     return spec_sq_axis_build(ctx);
 }
 
-int spec_apply_lossy(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
-                     int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
-    if (ksq == nullptr || ksq_im == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
+// the operator of medium m (hn_internal.h): a lossless one is spec_apply's, with its own choice of route; the other two run here, on either kind of domain
+int spec_forward(hn_ctx* ctx, const char* who, const Medium& m, const float* wf, float* out, const float* src, int src_batch, int batch, float* sumsq,
+                 hipStream_t s, int* it_counter, int sumsq_stride) {
+    const Medium::Kind kind = m.kind();
+    if (kind == Medium::Kind::Lossless) return spec_apply(ctx, wf, out, m.k_sq, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
+    if (m.k_sq == nullptr)
+        return kind == Medium::Kind::Density ? fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator needs k_sq and rho_grad", who)
+                                             : fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
     if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
     if (batch <= 0) return HN_OK;
     LineDomain d;
     if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
-    return rect_launch(ctx, d, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride);
+    return rect_launch(ctx, d, wf, out, m.k_sq, m.k_sq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride, false, nullptr, m.rho_grad);
 }
 
-// ---- variable density: res = L(u) - b_x q_x d_x u - b_y q_y d_y u + (ksq [+ i ksq_im]) u - src on either kind of domain, on the lossy operator's tables ----
-int spec_apply_medium(hn_ctx* ctx, const char* who, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* rho_grad, const float* src,
-                      int src_batch, int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride) {
-    if (ksq == nullptr || rho_grad == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator needs k_sq and rho_grad", who);
-    if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
-    if (batch <= 0) return HN_OK;
-    LineDomain d;
-    if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
-    return rect_launch(ctx, d, wf, out, ksq, ksq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride, false, nullptr, rho_grad);
-}
-
-// out = A^H g = L^H(g) + (ksq - i ksq_im) g [+ add] on either kind of domain: the adjoint of the operator above, on the same tables
-int spec_adjoint_lossy(hn_ctx* ctx, const char* who, const float* g, float* out, const float* ksq, const float* ksq_im, const float* add, int batch,
-                       hipStream_t s) {
-    if (ksq == nullptr || ksq_im == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
+// out = A^H g [+ add]: spec_adjoint for a lossless medium; for a lossy one L^H(g) + (ksq - i ksq_im) g on the tables of spec_forward
+int spec_backward(hn_ctx* ctx, const char* who, const Medium& m, const float* g, float* out, const float* add, int batch, hipStream_t s) {
+    const Medium::Kind kind = m.kind();
+    if (kind == Medium::Kind::Density) return fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator has no adjoint cycle", who);
+    if (kind == Medium::Kind::Lossless) return spec_adjoint(ctx, g, out, m.k_sq, add, batch, s);
+    if (m.k_sq == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
     if (g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);
     if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
     if (batch <= 0) return HN_OK;
     LineDomain d;
     if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
-    return rect_launch(ctx, d, g, out, ksq, ksq_im, nullptr, 1, batch, nullptr, s, nullptr, 0, true, add);
+    return rect_launch(ctx, d, g, out, m.k_sq, m.k_sq_im, nullptr, 1, batch, nullptr, s, nullptr, 0, true, add);
 }
 
 int rect_unsupported(hn_ctx* ctx, const char* who) {

@@ -7,7 +7,7 @@ across the C ABI, and returns.  No arithmetic happens here.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -133,6 +133,30 @@ def _require_no_grad(what: str, *tensors):
     for t in tensors:
         if isinstance(t, torch.Tensor) and t.requires_grad:
             raise RuntimeError(f"{what} runs without gradients: pass detached tensors (the differentiable path is forward())")
+
+
+def _tensor(t, name: str) -> torch.Tensor:
+    """The plane a ``*_lossy`` / ``*_medium`` method cannot do without (None would name another kind of medium)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor")
+    return t
+
+
+class Medium(NamedTuple):
+    """What multiplies the wavefield beside the Laplacian: ``k_sq`` [B,1,h,w], for an absorbing medium its imaginary part ``k_sq_im`` [B,1,h,w], for a
+    heterogeneous density ``rho_grad`` [B,2,h,w] (and then ``k_sq_im`` or None).  A public method builds it, everything below passes it on."""
+    k_sq: torch.Tensor
+    k_sq_im: Optional[torch.Tensor] = None
+    rho_grad: Optional[torch.Tensor] = None
+
+    @property
+    def kind(self) -> str:
+        """The suffix of the library's entry points for this medium: ``hn_step`` + kind, ``hn_residual`` + kind, ..."""
+        return "_medium" if self.rho_grad is not None else "_lossy" if self.k_sq_im is not None else ""
+
+    def planes(self) -> tuple:
+        """The medium as the methods and entry points of its kind take it, in k_sq's place: their signatures differ only there."""
+        return {"": self[:1], "_lossy": self[:2], "_medium": self[:3]}[self.kind]
 
 
 class Engine:
@@ -278,24 +302,41 @@ class Engine:
         _lib.check(self.lib.hn_laplacian(self.ctx, _ptr(wf), _ptr(out), b, self._stream()), self.ctx, "hn_laplacian")
         return out
 
-    def residual(self, wf: torch.Tensor, k_sq: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    def _call(self, stem: str, m: Medium, before: list, after: list):
+        """The entry point ``stem`` + the medium's kind, the medium's pointers between ``before`` and ``after``."""
+        name = stem + m.kind
+        _lib.check(getattr(self.lib, name)(self.ctx, *before, *map(_ptr, m.planes()), *after, self._stream()), self.ctx, name)
+
+    def _chk_medium(self, m: Medium, b: int, dtype: torch.dtype = torch.float32) -> None:
+        self._chk(m.k_sq, (b, 1, *self.hw), "k_sq", dtype)
+        if m.k_sq_im is not None:
+            self._chk(m.k_sq_im, (b, 1, *self.hw), "k_sq_im", dtype)
+        if m.rho_grad is not None:
+            self._chk(m.rho_grad, (b, 2, *self.hw), "rho_grad", dtype)
+
+    def _residual(self, m: Medium, wf: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
         b = wf.shape[0]
         self._chk(wf, (b, 2, *self.hw), "wavefield")
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk_medium(m, b)
         self._chk(src, (src.shape[0], 2, *self.hw), "source")
         out = torch.empty_like(wf)
-        rc = self.lib.hn_residual(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), src.shape[0], _ptr(out), b, self._stream())
-        _lib.check(rc, self.ctx, "hn_residual")
+        self._call("hn_residual", m, [_ptr(wf)], [_ptr(src), src.shape[0], _ptr(out), b])
+        return out
+
+    def residual(self, wf: torch.Tensor, k_sq: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+        return self._residual(Medium(k_sq), wf, src)
+
+    def _residual_vjp(self, m: Medium, g: torch.Tensor) -> torch.Tensor:
+        b = g.shape[0]
+        self._chk(g, (b, 2, *self.hw), "cotangent")
+        self._chk_medium(m, b)
+        out = torch.empty_like(g)
+        self._call("hn_residual_vjp", m, [_ptr(g)], [_ptr(out), b])
         return out
 
     def residual_vjp(self, g: torch.Tensor, k_sq: torch.Tensor) -> torch.Tensor:
         """J^T g of ``residual`` with respect to the wavefield: L^H(g) + k_sq * g."""
-        b = g.shape[0]
-        self._chk(g, (b, 2, *self.hw), "cotangent")
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
-        out = torch.empty_like(g)
-        _lib.check(self.lib.hn_residual_vjp(self.ctx, _ptr(g), _ptr(k_sq), _ptr(out), b, self._stream()), self.ctx, "hn_residual_vjp")
-        return out
+        return self._residual_vjp(Medium(k_sq), g)
 
     def rmse(self, res: torch.Tensor) -> torch.Tensor:
         b = res.shape[0]
@@ -304,15 +345,15 @@ class Engine:
         _lib.check(self.lib.hn_rmse(self.ctx, _ptr(res), _ptr(out), b, self._stream()), self.ctx, "hn_rmse")
         return out
 
-    def _gmres_buffers(self, what: str, x, x_dtype, k_sq, rhs, restart: int, basis, hess):
-        """What the four cycle methods share: the grad refusal, the shape checks, ``basis`` / ``hess`` (allocated when not given) and the fresh ``rmse``
+    def _gmres_buffers(self, what: str, x, x_dtype, m: Medium, rhs, restart: int, basis, hess):
+        """What the cycle methods share: the grad refusal, the shape checks, ``basis`` / ``hess`` (allocated when not given) and the fresh ``rmse``
         [restart + 1, B] and ``k_used`` [B] int32 tables."""
         b, p2 = x.shape[0], 2 * self.hw[0] * self.hw[1]
-        for t, name in ((x, "x"), (k_sq, "k_sq"), (rhs, "rhs")):
+        for t, name in ((x, "x"), (m.k_sq, "k_sq"), (rhs, "rhs"), (m.k_sq_im, "k_sq_im"), (m.rho_grad, "rho_grad")):
             if isinstance(t, torch.Tensor) and t.requires_grad:
                 raise RuntimeError(f"{what}: {name} requires grad; the GMRES cycle is not differentiable")
         self._chk(x, (b, 2, *self.hw), "x", x_dtype)
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
+        self._chk_medium(m, b)
         self._chk(rhs, (rhs.shape[0], 2, *self.hw), "rhs")
         new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)  # noqa: E731
         basis = self._chk(new(b, restart + 1, p2) if basis is None else basis, (b, restart + 1, p2), "basis")
@@ -331,7 +372,7 @@ class Engine:
         iterations, ``k_used`` the inner iterations that entered each sample's update.  ``basis`` [B, restart + 1, 2 n^2] and ``hess``
         [B, restart + 1, restart, 2] receive the Arnoldi vectors and the Hessenberg matrix; they are allocated when not given."""
         restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("gmres_cycle", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("gmres_cycle", x, torch.float32, Medium(k_sq), rhs, restart, basis, hess)
         rc = self.lib.hn_gmres_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), _ptr(basis), _ptr(hess),
                                      _ptr(rmse), _ptr(k_used), self._stream())
         _lib.check(rc, self.ctx, "hn_gmres_cycle")
@@ -344,7 +385,7 @@ class Engine:
         problem.  Returns (rmse64 [B] float64: the true residual RMSE of ``x`` at the START of the call, rmse [restart + 1, B] and k_used [B] int32:
         the inner cycle's tables, as ``gmres_cycle`` returns them).  A sample with rmse64 < tol is not written and has k_used 0."""
         restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("gmres_refine_cycle", x, torch.float64, k_sq, rhs, restart, basis, hess)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("gmres_refine_cycle", x, torch.float64, Medium(k_sq), rhs, restart, basis, hess)
         rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
         rc = self.lib.hn_gmres_refine_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor),
                                             _ptr(basis), _ptr(hess), _ptr(rmse), _ptr(k_used), _ptr(rmse64), self._stream())
@@ -357,12 +398,15 @@ class Engine:
         ``precond_iters`` iterations of ``step`` on A z = precond_scale * v_k from rest, z_k = wf / precond_scale, w = A z_k, and the update over the
         z_j.  Returns (rmse, k_used) as ``gmres_cycle``; ``zbasis`` [B, restart, 2 n^2] (allocated when not given) receives the z_j.
         ``precond_iters`` 0: z = v, ``gmres_cycle`` bit for bit.  Not capturable."""
+        return self._fgmres_cycle("hn_fgmres_cycle", Medium(k_sq), x, rhs, restart, tol, precond_iters, precond_scale, basis, hess, zbasis)
+
+    def _fgmres_cycle(self, stem: str, m: Medium, x, rhs, restart, tol, precond_iters, precond_scale, basis, hess, zbasis):
+        """The flexible cycle on A (``stem`` hn_fgmres_cycle) or on A^H (hn_fgmres_adjoint_cycle) for the medium's kind."""
         restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_cycle", x, torch.float32, k_sq, rhs, restart, basis, hess)
+        b, basis, hess, rmse, k_used = self._gmres_buffers(stem[3:] + m.kind, x, torch.float32, m, rhs, restart, basis, hess)
         zbasis = self._zbasis(b, restart, zbasis)
-        rc = self.lib.hn_fgmres_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters),
-                                      float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used), self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_cycle")
+        self._call(stem, m, [_ptr(x)], [_ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters), float(precond_scale), _ptr(basis),
+                                       _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used)])
         return rmse, k_used
 
     def fgmres_refine_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float, precond_iters: int,
@@ -370,14 +414,16 @@ class Engine:
                             hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
         """One refinement step with the flexible cycle inside (hn_fgmres_refine_cycle): ``gmres_refine_cycle`` with the learned preconditioner of
         ``fgmres_cycle``.  Returns (rmse64, rmse, k_used) as ``gmres_refine_cycle``.  Not capturable."""
+        return self._fgmres_refine_cycle(Medium(k_sq), x, rhs, restart, tol, precond_iters, precond_scale, inner_floor, basis, hess, zbasis)
+
+    def _fgmres_refine_cycle(self, m: Medium, x, rhs, restart, tol, precond_iters, precond_scale, inner_floor, basis, hess, zbasis):
         restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_refine_cycle", x, torch.float64, k_sq, rhs, restart, basis, hess)
+        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_refine_cycle" + m.kind, x, torch.float64, m, rhs, restart, basis, hess)
         zbasis = self._zbasis(b, restart, zbasis)
         rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
-        rc = self.lib.hn_fgmres_refine_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor),
-                                             int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse),
-                                             _ptr(k_used), _ptr(rmse64), self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_refine_cycle")
+        self._call("hn_fgmres_refine_cycle", m, [_ptr(x)], [_ptr(rhs), rhs.shape[0], b, restart, float(tol), float(inner_floor), int(precond_iters),
+                                                            float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used),
+                                                            _ptr(rmse64)])
         return rmse64, rmse, k_used
 
     def fgmres_adjoint_cycle(self, x: torch.Tensor, k_sq: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float, precond_iters: int,
@@ -386,13 +432,7 @@ class Engine:
         """One flexible restart cycle on the ADJOINT system A^H x = rhs (hn_fgmres_adjoint_cycle), A^H the operator of ``residual_vjp``: arguments and
         returns as ``fgmres_cycle``.  ``precond_iters`` 0 is plain restarted GMRES on A^H; >= 1 preconditions with the learned iteration between the
         similarity weight of ``laplacian.adjoint_weight``: z_k = conj(W * M(conj(v_k) / W)).  Not capturable."""
-        restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_adjoint_cycle", x, torch.float32, k_sq, rhs, restart, basis, hess)
-        zbasis = self._zbasis(b, restart, zbasis)
-        rc = self.lib.hn_fgmres_adjoint_cycle(self.ctx, _ptr(x), _ptr(k_sq), _ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters),
-                                              float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used), self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_adjoint_cycle")
-        return rmse, k_used
+        return self._fgmres_cycle("hn_fgmres_adjoint_cycle", Medium(k_sq), x, rhs, restart, tol, precond_iters, precond_scale, basis, hess, zbasis)
 
     def adjoint_grad(self, lam: torch.Tensor, u: torch.Tensor, src_batch: Optional[int]):
         """The pointwise half of the adjoint-state gradient (hn_adjoint_grad): returns (g_k_sq [B,1,n,n] = -(lam_re u_re + lam_im u_im), g_src) with
@@ -416,14 +456,16 @@ class Engine:
 
     def residual64(self, wf: torch.Tensor, k_sq: torch.Tensor, src: torch.Tensor, want_res: bool = True, want_rmse: bool = True):
         """(res [B,2,n,n] or None, rmse [B] or None), both float64; the RMSE is summed in a fixed order (bit-reproducible)."""
+        return self._residual64(Medium(k_sq), wf, src, want_res, want_rmse)
+
+    def _residual64(self, m: Medium, wf, src, want_res: bool, want_rmse: bool):
         b = wf.shape[0]
         self._chk(wf, (b, 2, *self.hw), "wavefield", torch.float64)
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq", torch.float64)
+        self._chk_medium(m, b, torch.float64)
         self._chk(src, (src.shape[0], 2, *self.hw), "source", torch.float64)
         res = torch.empty_like(wf) if want_res else None
         rmse = torch.empty(b, device=self.device, dtype=torch.float64) if want_rmse else None
-        rc = self.lib.hn_residual_f64(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(src), src.shape[0], _ptr(res), _ptr(rmse), b, self._stream())
-        _lib.check(rc, self.ctx, "hn_residual_f64")
+        self._call("hn_residual_f64", m, [_ptr(wf)], [_ptr(src), src.shape[0], _ptr(res), _ptr(rmse), b])
         return res, rmse
 
     # ---- the UNet and the solver loop in float64: the trajectory the fp32 / fp16 / bf16 modes are measured against (hn_unet_f64.hip) ----
@@ -440,7 +482,7 @@ class Engine:
 
     def step64(self, wf, res, states, k_sq, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
         """n_iter solver iterations in float64; wf, res, states updated in place (``step`` with every tensor float64)."""
-        self._step(self.lib.hn_step_f64, "hn_step_f64", torch.float64, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
+        self._step("hn_step_f64", torch.float64, Medium(k_sq), wf, res, states, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
 
     def unet(self, in6: torch.Tensor, states_in: torch.Tensor):
         b = in6.shape[0]
@@ -500,13 +542,13 @@ class Engine:
         _lib.check(rc, self.ctx, "hn_out_conv")
         return out
 
-    def _step(self, entry, name: str, dtype, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist):
-        """``step`` / ``step64``: the checks and the one library call, for tensors of ``dtype``."""
+    def _step(self, stem: str, dtype, m: Medium, wf, res, states, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist):
+        """``step`` on any medium and ``step64``: the checks and the one library call, for tensors of ``dtype``."""
         b = wf.shape[0]
         self._chk(wf, (b, 2, *self.hw), "wavefield", dtype)
         self._chk(res, (b, 2, *self.hw), "residual", dtype)
         self._chk(states, (b, 2, self.state_len), "hidden state", dtype)
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq", dtype)
+        self._chk_medium(m, b, dtype)
         self._chk(src, (src.shape[0], 2, *self.hw), "source", dtype)
         if res_hist is not None:
             self._chk(res_hist, (n_iter, b, 2, *self.hw), "res_hist", dtype)
@@ -516,163 +558,76 @@ class Engine:
             self._chk(st_hist, (n_iter, b, 2, self.state_len), "st_hist", dtype)
         if rmse_hist is not None:
             self._chk(rmse_hist, (n_iter, b), "rmse_hist", dtype)
-        rc = entry(self.ctx, _ptr(wf), _ptr(res), _ptr(states), _ptr(k_sq), _ptr(src), src.shape[0], b,
-                   int(n_iter), _ptr(res_hist), _ptr(wf_hist), _ptr(st_hist), _ptr(rmse_hist), self._stream())
-        _lib.check(rc, self.ctx, name)
+        self._call(stem, m, [_ptr(wf), _ptr(res), _ptr(states)], [_ptr(src), src.shape[0], b, int(n_iter), _ptr(res_hist), _ptr(wf_hist), _ptr(st_hist),
+                                                                 _ptr(rmse_hist)])
 
     def step(self, wf, res, states, k_sq, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
         """n_iter solver iterations; wf, res, states updated in place."""
-        self._step(self.lib.hn_step, "hn_step", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
+        self._step("hn_step", torch.float32, Medium(k_sq), wf, res, states, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
 
-    # ---- absorbing media: complex k_sq = k_sq + i k_sq_im (hn_residual_lossy / hn_step_lossy / hn_fgmres_cycle_lossy) ----
+    # ---- absorbing media: complex k_sq = k_sq + i k_sq_im (the hn_*_lossy entry points) ----
     def residual_lossy(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
         """``residual`` with the complex pointwise term: L(wf) + (k_sq + i k_sq_im) wf - src; ``k_sq_im`` [B,1,h,w] fp32, any sign."""
-        b = wf.shape[0]
-        self._chk(wf, (b, 2, *self.hw), "wavefield")
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
-        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
-        self._chk(src, (src.shape[0], 2, *self.hw), "source")
-        out = torch.empty_like(wf)
-        rc = self.lib.hn_residual_lossy(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(k_sq_im), _ptr(src), src.shape[0], _ptr(out), b, self._stream())
-        _lib.check(rc, self.ctx, "hn_residual_lossy")
-        return out
+        return self._residual(Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), wf, src)
 
     def step_lossy(self, wf, res, states, k_sq, k_sq_im, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
         """``step`` on the lossy residual (hn_step_lossy): the same UNet launches, one lane, never a captured iteration."""
-        self._chk(k_sq_im, (wf.shape[0], 1, *self.hw), "k_sq_im")
-
-        def entry(ctx, wf_p, res_p, st_p, k_p, *rest):
-            return self.lib.hn_step_lossy(ctx, wf_p, res_p, st_p, k_p, _ptr(k_sq_im), *rest)
-
-        self._step(entry, "hn_step_lossy", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
+        self._step("hn_step", torch.float32, Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), wf, res, states, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
 
     def fgmres_cycle_lossy(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
                            precond_iters: int, precond_scale: float, basis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None,
                            zbasis: Optional[torch.Tensor] = None):
         """``fgmres_cycle`` on the lossy operator (hn_fgmres_cycle_lossy), preconditioned by ``precond_iters`` iterations of ``step_lossy``;
         ``precond_iters`` 0: plain restarted GMRES on the lossy operator.  Square domains.  Not capturable."""
-        restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_cycle_lossy", x, torch.float32, k_sq, rhs, restart, basis, hess)
-        if isinstance(k_sq_im, torch.Tensor) and k_sq_im.requires_grad:
-            raise RuntimeError("fgmres_cycle_lossy: k_sq_im requires grad; the GMRES cycle is not differentiable")
-        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
-        zbasis = self._zbasis(b, restart, zbasis)
-        rc = self.lib.hn_fgmres_cycle_lossy(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rhs), rhs.shape[0], b, restart, float(tol),
-                                            int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used),
-                                            self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_cycle_lossy")
-        return rmse, k_used
+        return self._fgmres_cycle("hn_fgmres_cycle", Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), x, rhs, restart, tol, precond_iters, precond_scale, basis,
+                                  hess, zbasis)
 
-    # ---- heterogeneous density: A_rho u = L(u) - b q . grad u + (k_sq [+ i k_sq_im]) u (hn_residual_medium / hn_step_medium / hn_fgmres_cycle_medium) ----
-    def _chk_medium(self, b: int, k_sq_im, rho_grad) -> None:
-        if k_sq_im is not None:
-            self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
-        self._chk(rho_grad, (b, 2, *self.hw), "rho_grad")
-
+    # ---- heterogeneous density: A_rho u = L(u) - b q . grad u + (k_sq [+ i k_sq_im]) u (the hn_*_medium entry points) ----
     def residual_medium(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor], rho_grad: torch.Tensor,
                         src: torch.Tensor) -> torch.Tensor:
         """``residual_lossy`` with the density term: ``rho_grad`` [B,2,h,w] fp32 holds d ln rho / dx (the last index) in plane 0 and d ln rho / dy in
         plane 1, per grid point (``helmnet_amd.density.log_density_gradient``).  ``k_sq_im`` may be None: a lossless medium."""
-        b = wf.shape[0]
-        self._chk(wf, (b, 2, *self.hw), "wavefield")
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
-        self._chk_medium(b, k_sq_im, rho_grad)
-        self._chk(src, (src.shape[0], 2, *self.hw), "source")
-        out = torch.empty_like(wf)
-        rc = self.lib.hn_residual_medium(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(k_sq_im), _ptr(rho_grad), _ptr(src), src.shape[0], _ptr(out), b,
-                                         self._stream())
-        _lib.check(rc, self.ctx, "hn_residual_medium")
-        return out
+        return self._residual(Medium(k_sq, k_sq_im, _tensor(rho_grad, "rho_grad")), wf, src)
 
     def step_medium(self, wf, res, states, k_sq, k_sq_im, rho_grad, src, n_iter: int, res_hist=None, wf_hist=None, st_hist=None, rmse_hist=None):
         """``step_lossy`` on the variable-density residual (hn_step_medium); ``k_sq_im`` may be None."""
-        self._chk_medium(wf.shape[0], k_sq_im, rho_grad)
-
-        def entry(ctx, wf_p, res_p, st_p, k_p, *rest):
-            return self.lib.hn_step_medium(ctx, wf_p, res_p, st_p, k_p, _ptr(k_sq_im), _ptr(rho_grad), *rest)
-
-        self._step(entry, "hn_step_medium", torch.float32, wf, res, states, k_sq, src, n_iter, res_hist, wf_hist, st_hist, rmse_hist)
+        self._step("hn_step", torch.float32, Medium(k_sq, k_sq_im, _tensor(rho_grad, "rho_grad")), wf, res, states, src, n_iter, res_hist, wf_hist, st_hist,
+                   rmse_hist)
 
     def fgmres_cycle_medium(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor], rho_grad: torch.Tensor, rhs: torch.Tensor,
                             restart: int, tol: float, precond_iters: int, precond_scale: float, basis: Optional[torch.Tensor] = None,
                             hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
         """``fgmres_cycle_lossy`` on the variable-density operator (hn_fgmres_cycle_medium), preconditioned by ``precond_iters`` iterations of
         ``step_medium``; ``precond_iters`` 0: plain restarted GMRES.  ``k_sq_im`` may be None.  Square domains.  Not capturable."""
-        restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_cycle_medium", x, torch.float32, k_sq, rhs, restart, basis, hess)
-        for name, t in (("k_sq_im", k_sq_im), ("rho_grad", rho_grad)):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise RuntimeError(f"fgmres_cycle_medium: {name} requires grad; the GMRES cycle is not differentiable")
-        self._chk_medium(b, k_sq_im, rho_grad)
-        zbasis = self._zbasis(b, restart, zbasis)
-        rc = self.lib.hn_fgmres_cycle_medium(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rho_grad), _ptr(rhs), rhs.shape[0], b, restart,
-                                             float(tol), int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse),
-                                             _ptr(k_used), self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_cycle_medium")
-        return rmse, k_used
+        return self._fgmres_cycle("hn_fgmres_cycle", Medium(k_sq, k_sq_im, _tensor(rho_grad, "rho_grad")), x, rhs, restart, tol, precond_iters,
+                                  precond_scale, basis, hess, zbasis)
 
     def residual64_lossy(self, wf: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, src: torch.Tensor, want_res: bool = True,
                          want_rmse: bool = True):
         """``residual64`` with the complex pointwise term (hn_residual_f64_lossy): (res [B,2,h,w] or None, rmse [B] or None), both float64, of
         L(wf) + (k_sq + i k_sq_im) wf - src.  Square and rectangular domains; always the float64 FFT route."""
-        b = wf.shape[0]
-        self._chk(wf, (b, 2, *self.hw), "wavefield", torch.float64)
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq", torch.float64)
-        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im", torch.float64)
-        self._chk(src, (src.shape[0], 2, *self.hw), "source", torch.float64)
-        res = torch.empty_like(wf) if want_res else None
-        rmse = torch.empty(b, device=self.device, dtype=torch.float64) if want_rmse else None
-        rc = self.lib.hn_residual_f64_lossy(self.ctx, _ptr(wf), _ptr(k_sq), _ptr(k_sq_im), _ptr(src), src.shape[0], _ptr(res), _ptr(rmse), b,
-                                            self._stream())
-        _lib.check(rc, self.ctx, "hn_residual_f64_lossy")
-        return res, rmse
+        return self._residual64(Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), wf, src, want_res, want_rmse)
 
     def fgmres_refine_cycle_lossy(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
                                   precond_iters: int, precond_scale: float, inner_floor: float = 1e-6, basis: Optional[torch.Tensor] = None,
                                   hess: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None):
         """``fgmres_refine_cycle`` on the lossy operator (hn_fgmres_refine_cycle_lossy): the float64 residual of ``residual64_lossy``, the fp32 cycle of
         ``fgmres_cycle_lossy``, the preconditioner ``step_lossy``.  Returns (rmse64, rmse, k_used).  Square domains.  Not capturable."""
-        restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_refine_cycle_lossy", x, torch.float64, k_sq, rhs, restart, basis, hess)
-        if isinstance(k_sq_im, torch.Tensor) and k_sq_im.requires_grad:
-            raise RuntimeError("fgmres_refine_cycle_lossy: k_sq_im requires grad; the GMRES cycle is not differentiable")
-        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
-        zbasis = self._zbasis(b, restart, zbasis)
-        rmse64 = torch.empty(b, device=self.device, dtype=torch.float64)
-        rc = self.lib.hn_fgmres_refine_cycle_lossy(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rhs), rhs.shape[0], b, restart, float(tol),
-                                                   float(inner_floor), int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess),
-                                                   _ptr(rmse), _ptr(k_used), _ptr(rmse64), self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_refine_cycle_lossy")
-        return rmse64, rmse, k_used
+        return self._fgmres_refine_cycle(Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), x, rhs, restart, tol, precond_iters, precond_scale, inner_floor, basis,
+                                         hess, zbasis)
 
     def residual_vjp_lossy(self, g: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor) -> torch.Tensor:
         """A^H g of the lossy operator (hn_residual_vjp_lossy): L^H(g) + (k_sq - i k_sq_im) g, the J^T g of ``residual_lossy`` with respect to the
         wavefield.  Square and rectangular domains."""
-        b = g.shape[0]
-        self._chk(g, (b, 2, *self.hw), "cotangent")
-        self._chk(k_sq, (b, 1, *self.hw), "k_sq")
-        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
-        out = torch.empty_like(g)
-        rc = self.lib.hn_residual_vjp_lossy(self.ctx, _ptr(g), _ptr(k_sq), _ptr(k_sq_im), _ptr(out), b, self._stream())
-        _lib.check(rc, self.ctx, "hn_residual_vjp_lossy")
-        return out
+        return self._residual_vjp(Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), g)
 
     def fgmres_adjoint_cycle_lossy(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: torch.Tensor, rhs: torch.Tensor, restart: int, tol: float,
                                    precond_iters: int, precond_scale: float, basis: Optional[torch.Tensor] = None,
                                    zbasis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
         """``fgmres_adjoint_cycle`` on the lossy system A^H x = rhs (hn_fgmres_adjoint_cycle_lossy), A^H the operator of ``residual_vjp_lossy``,
         preconditioned by ``precond_iters`` iterations of ``step_lossy`` between the similarity weight.  Square domains.  Not capturable."""
-        restart = int(restart)
-        b, basis, hess, rmse, k_used = self._gmres_buffers("fgmres_adjoint_cycle_lossy", x, torch.float32, k_sq, rhs, restart, basis, hess)
-        if isinstance(k_sq_im, torch.Tensor) and k_sq_im.requires_grad:
-            raise RuntimeError("fgmres_adjoint_cycle_lossy: k_sq_im requires grad; the GMRES cycle is not differentiable")
-        self._chk(k_sq_im, (b, 1, *self.hw), "k_sq_im")
-        zbasis = self._zbasis(b, restart, zbasis)
-        rc = self.lib.hn_fgmres_adjoint_cycle_lossy(self.ctx, _ptr(x), _ptr(k_sq), _ptr(k_sq_im), _ptr(rhs), rhs.shape[0], b, restart, float(tol),
-                                                    int(precond_iters), float(precond_scale), _ptr(basis), _ptr(zbasis), _ptr(hess), _ptr(rmse),
-                                                    _ptr(k_used), self._stream())
-        _lib.check(rc, self.ctx, "hn_fgmres_adjoint_cycle_lossy")
-        return rmse, k_used
+        return self._fgmres_cycle("hn_fgmres_adjoint_cycle", Medium(k_sq, _tensor(k_sq_im, "k_sq_im")), x, rhs, restart, tol, precond_iters,
+                                  precond_scale, basis, hess, zbasis)
 
     def adjoint_grad_lossy(self, lam: torch.Tensor, u: torch.Tensor, src_batch: Optional[int]):
         """``adjoint_grad`` for the lossy operator (hn_adjoint_grad_lossy): returns (g_k_sq, g_k_sq_im, g_src) with

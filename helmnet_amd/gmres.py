@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .engine import _require_no_grad
+from .engine import Medium, _require_no_grad
 
 
 def _hessenberg_least_squares(H: np.ndarray, beta: np.ndarray):
@@ -127,55 +127,58 @@ def default_precond_scale(source) -> float:
 
 
 def _hip_setup(solver, sos_maps, restart, x0, dtype, absorption=None, density=None):
-    """What both HIP drivers start from: (engine, k_sq, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess).
-    With ``absorption`` k_sq is the pair (k_sq, k_sq_im) of the lossy medium; with ``density`` the triple (k_sq, k_sq_im or None, rho_grad)."""
+    """What the HIP drivers start from: (engine, the Medium, rhs, the iterate x in ``dtype`` -- a copy of ``x0``, zeros without one --, basis, hess)."""
     _require_no_grad("gmres(backend='hip')", sos_maps, x0, absorption, density)
     eng = solver.engine()
-    rho_grad = None
-    if density is not None:
-        k_sq, k_sq_im, rho_grad, wf0 = solver._medium_initials("gmres", sos_maps, absorption, density)
-    elif absorption is not None:
-        k_sq, k_sq_im, wf0 = solver._lossy_initials("gmres", sos_maps, absorption)
+    if absorption is None and density is None:
+        k_sq, wf0 = solver.get_initials(sos_maps.float().contiguous())
+        m = Medium(k_sq.contiguous())
     else:
-        sos_maps = sos_maps.float().contiguous()
-        k_sq, wf0 = solver.get_initials(sos_maps)
+        m, wf0 = solver._initials("gmres", sos_maps, absorption, density)
     rhs = solver.source.detach().float().contiguous()
     bsz, n = sos_maps.shape[0], sos_maps.shape[-1]
     x = (wf0 if x0 is None else x0.detach()).to(rhs.device, dtype).contiguous().clone()
     basis = torch.empty(bsz, restart + 1, 2 * n * n, dtype=torch.float32, device=rhs.device)
     hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=rhs.device)
-    if density is not None:
-        return eng, (k_sq.contiguous(), None if k_sq_im is None else k_sq_im.contiguous(), rho_grad), rhs, x, basis, hess
-    if absorption is not None:
-        return eng, (k_sq.contiguous(), k_sq_im.contiguous()), rhs, x, basis, hess
-    return eng, k_sq.contiguous(), rhs, x, basis, hess
+    return eng, m, rhs, x, basis, hess
 
 
-def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor, precond=None):
-    """``gmres(backend="hip", refine=True)``: iterative refinement with the fp32 restart cycle as the inner solver (hn_gmres_refine_cycle).  The
-    iterate, its true residual and the update are float64; one host synchronisation per cycle.  ``precond`` (iterations, alpha): the flexible
-    cycle (hn_fgmres_refine_cycle)."""
-    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float64)
+def _zbasis(m: Medium, precond, basis):
+    """The flexible cycles' second basis; None where the plain cycle runs: a lossless medium without a preconditioner."""
+    if precond is None and not m.kind:
+        return None
+    return torch.empty(basis.shape[0], basis.shape[1] - 1, basis.shape[2], dtype=torch.float32, device=basis.device)
+
+
+def _gmres_refine(solver, sos_maps, restart, max_outer, tol, x0, inner_floor, precond=None, absorption=None):
+    """``gmres(backend="hip", refine=True)`` and ``gmres_refine_lossy``: iterative refinement with the fp32 restart cycle as the inner solver
+    (hn_gmres_refine_cycle).  The iterate, its true residual and the update are float64; one host synchronisation per cycle.  ``precond``
+    (iterations, alpha): the flexible cycle (hn_fgmres_refine_cycle).  ``absorption``: the lossy operator (hn_fgmres_refine_cycle_lossy, with zero
+    preconditioner iterations when ``precond`` is None)."""
+    eng, m, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float64, absorption)
     bsz, dev = x.shape[0], x.device
-    zbasis = None if precond is None else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
+    zbasis = _zbasis(m, precond, basis)
+    iters, alpha = (0, 1.0) if precond is None else precond
 
     def cycle():
-        if precond is None:
-            rmse64, rmse, k_used = eng.gmres_refine_cycle(x, k_sq, rhs, restart, tol, inner_floor, basis, hess)
+        if zbasis is None:
+            rmse64, rmse, k_used = eng.gmres_refine_cycle(x, m.k_sq, rhs, restart, tol, inner_floor, basis, hess)
         else:
-            rmse64, rmse, k_used = eng.fgmres_refine_cycle(x, k_sq, rhs, restart, tol, precond[0], precond[1], inner_floor, basis, hess, zbasis)
+            rmse64, rmse, k_used = getattr(eng, "fgmres_refine_cycle" + m.kind)(x, *m.planes(), rhs, restart, tol, iters, alpha, inner_floor, basis, hess,
+                                                                               zbasis)
         both = torch.cat([rmse64, rmse.reshape(-1).double(), k_used.double()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
-        m = (restart + 1) * bsz
-        return both[:bsz], both[bsz: bsz + m].reshape(restart + 1, bsz), both[bsz + m:].astype(np.int64)
+        n_tab = (restart + 1) * bsz
+        return both[:bsz], both[bsz: bsz + n_tab].reshape(restart + 1, bsz), both[bsz + n_tab:].astype(np.int64)
 
     out = drive_refinement(cycle, max_outer, tol)
     # converged: the last cycle checked the returned iterate and wrote nothing; else its last update is still unchecked
-    final = torch.from_numpy(out["history"][-1]).to(dev) if out["converged"] else eng.residual64(x, k_sq.double(), rhs.double(), False, True)[1]
+    final = (torch.from_numpy(out["history"][-1]).to(dev) if out["converged"]
+             else getattr(eng, "residual64" + m.kind)(x, *(p.double() for p in m.planes()), rhs.double(), False, True)[1])
     return {"wavefield": x, "residual_norm64": final, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
             "operator_applications": out["cycles"] * (restart + 1), "operator_applications64": out["cycles"], "converged": out["converged"],
             "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"],
-            "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
+            "unet_evaluations": unet_evaluations(out["cycles"], restart, iters)}
 
 
 def gmres_refine_lossy(solver, sos_maps: torch.Tensor, absorption, restart: int = 20, max_outer: int = 400, tol: float = 1e-10,
@@ -192,31 +195,12 @@ def gmres_refine_lossy(solver, sos_maps: torch.Tensor, absorption, restart: int 
         raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
     if precondition is not None and int(precond_iterations) < 0:
         raise ValueError(f"precond_iterations must be >= 0 (got {precond_iterations})")
-    restart, max_outer, tol, inner_floor = int(restart), int(max_outer), float(tol), float(inner_floor)
-    solver._refuse_lossy_grad("gmres64", sos_maps, absorption, x0)
+    solver._refuse_medium_grad("gmres64", False, sos_maps, absorption, x0)
     solver._require_square("gmres64 with absorption")
-    iters, alpha = 0, 1.0
+    precond = None
     if precondition is not None:
-        iters, alpha = int(precond_iterations), default_precond_scale(solver.source) if precond_scale is None else float(precond_scale)
-    eng, (k_sq, k_sq_im), rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float64, absorption)
-    bsz, dev = x.shape[0], x.device
-    zbasis = torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
-
-    def cycle():
-        rmse64, rmse, k_used = eng.fgmres_refine_cycle_lossy(x, k_sq, k_sq_im, rhs, restart, tol, iters, alpha, inner_floor, basis, hess, zbasis)
-        both = torch.cat([rmse64, rmse.reshape(-1).double(), k_used.double()]).cpu().numpy()          # the one synchronisation of the cycle
-        eng.check_async_errors()
-        m = (restart + 1) * bsz
-        return both[:bsz], both[bsz: bsz + m].reshape(restart + 1, bsz), both[bsz + m:].astype(np.int64)
-
-    out = drive_refinement(cycle, max_outer, tol)
-    # converged: the last cycle checked the returned iterate and wrote nothing; else its last update is still unchecked
-    final = (torch.from_numpy(out["history"][-1]).to(dev) if out["converged"]
-             else eng.residual64_lossy(x, k_sq.double(), k_sq_im.double(), rhs.double(), False, True)[1])
-    return {"wavefield": x, "residual_norm64": final, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
-            "operator_applications": out["cycles"] * (restart + 1), "operator_applications64": out["cycles"], "converged": out["converged"],
-            "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], "cycles": out["cycles"],
-            "unet_evaluations": unet_evaluations(out["cycles"], restart, iters)}
+        precond = (int(precond_iterations), default_precond_scale(solver.source) if precond_scale is None else float(precond_scale))
+    return _gmres_refine(solver, sos_maps, int(restart), int(max_outer), float(tol), x0, float(inner_floor), precond, absorption)
 
 
 def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, absorption=None, density=None):
@@ -224,40 +208,29 @@ def _gmres_hip(solver, sos_maps, restart, max_outer, tol, x0, precond=None, abso
     ``precond`` (iterations, alpha): the flexible cycle (hn_fgmres_cycle).  ``absorption``: the lossy operator (hn_fgmres_cycle_lossy, with zero
     preconditioner iterations when ``precond`` is None).  ``density``: the variable-density operator (hn_fgmres_cycle_medium, likewise), with or
     without ``absorption``."""
-    eng, k_sq, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32, absorption, density)
+    eng, m, rhs, x, basis, hess = _hip_setup(solver, sos_maps, restart, x0, torch.float32, absorption, density)
     bsz, dev = x.shape[0], x.device
-    medium = density is not None
-    lossy = absorption is not None or medium
-    zbasis = None if precond is None and not lossy else torch.empty(bsz, restart, basis.shape[-1], dtype=torch.float32, device=dev)
+    zbasis = _zbasis(m, precond, basis)
+    iters, alpha = (0, 1.0) if precond is None else precond
 
     def cycle():
-        if medium:
-            iters, alpha = (0, 1.0) if precond is None else precond
-            rmse, k_used = eng.fgmres_cycle_medium(x, k_sq[0], k_sq[1], k_sq[2], rhs, restart, tol, iters, alpha, basis, hess, zbasis)
-        elif lossy:
-            iters, alpha = (0, 1.0) if precond is None else precond
-            rmse, k_used = eng.fgmres_cycle_lossy(x, k_sq[0], k_sq[1], rhs, restart, tol, iters, alpha, basis, hess, zbasis)
-        elif precond is None:
-            rmse, k_used = eng.gmres_cycle(x, k_sq, rhs, restart, tol, basis, hess)
+        if zbasis is None:
+            rmse, k_used = eng.gmres_cycle(x, m.k_sq, rhs, restart, tol, basis, hess)
         else:
-            rmse, k_used = eng.fgmres_cycle(x, k_sq, rhs, restart, tol, precond[0], precond[1], basis, hess, zbasis)
+            rmse, k_used = getattr(eng, "fgmres_cycle" + m.kind)(x, *m.planes(), rhs, restart, tol, iters, alpha, basis, hess, zbasis)
         both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
 
     def true_rmse():
-        if medium:
-            return eng.rmse(eng.residual_medium(x, k_sq[0], k_sq[1], k_sq[2], rhs)).cpu().numpy()
-        if lossy:
-            return eng.rmse(eng.residual_lossy(x, k_sq[0], k_sq[1], rhs)).cpu().numpy()
-        return eng.rmse(eng.residual(x, k_sq, rhs)).cpu().numpy()
+        return eng.rmse(getattr(eng, "residual" + m.kind)(x, *m.planes(), rhs)).cpu().numpy()
 
     out = drive_cycles(cycle, true_rmse, max_outer, tol)
-    extra = {"cycles": out["cycles"]} if lossy else {}
+    extra = {"cycles": out["cycles"]} if m.kind else {}
     return {"wavefield": x, "residual_norms": [torch.from_numpy(h).to(dev) for h in out["history"]], "iterations": out["iterations"],
             "operator_applications": out["cycles"] * (restart + 1) + out["true_checks"], "converged": out["converged"],
             "iterations_per_sample": torch.from_numpy(out["iterations_per_sample"]), "cycle_tables": out["tables"], **extra,
-            "unet_evaluations": unet_evaluations(out["cycles"], restart, 0 if precond is None else precond[0])}
+            "unet_evaluations": unet_evaluations(out["cycles"], restart, iters)}
 
 
 def check_adjoint_rhs(solver, sos_maps, rhs):
@@ -309,14 +282,13 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
         alpha = default_precond_scale(solver.source) if precond_scale is None else float(precond_scale)
     eng = solver.engine()
     sos_maps = sos_maps.to(eng.device).float().contiguous()
-    lossy = absorption is not None
-    if lossy:
+    if absorption is not None:
         from .absorption import complex_k_sq
         if isinstance(absorption, torch.Tensor):
             absorption = absorption.detach().to(eng.device, torch.float32)
-        k_sq, k_sq_im = complex_k_sq(sos_maps, absorption, solver.hparams.omega)
+        m = Medium(*complex_k_sq(sos_maps, absorption, solver.hparams.omega))
     else:
-        k_sq = solver.get_initials(sos_maps)[0].contiguous()
+        m = Medium(solver.get_initials(sos_maps)[0].contiguous())
     rhs = rhs.detach().to(eng.device).float().contiguous()
     bsz, n, dev = sos_maps.shape[0], sos_maps.shape[-1], eng.device
     x = (torch.zeros(bsz, 2, n, n, device=dev) if x0 is None else x0.detach().to(dev, torch.float32)).contiguous().clone()
@@ -325,16 +297,13 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
     hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
 
     def cycle():
-        if lossy:
-            rmse, k_used = eng.fgmres_adjoint_cycle_lossy(x, k_sq, k_sq_im, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
-        else:
-            rmse, k_used = eng.fgmres_adjoint_cycle(x, k_sq, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
+        rmse, k_used = getattr(eng, "fgmres_adjoint_cycle" + m.kind)(x, *m.planes(), rhs, restart, tol, iters, alpha, basis, zbasis, hess)
         both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)
 
     def true_residual():
-        return eng.rmse(rhs - (eng.residual_vjp_lossy(x, k_sq, k_sq_im) if lossy else eng.residual_vjp(x, k_sq)))
+        return eng.rmse(rhs - getattr(eng, "residual_vjp" + m.kind)(x, *m.planes()))
 
     def true_rmse():
         return true_residual().cpu().numpy()
@@ -397,7 +366,7 @@ def gmres(solver, sos_maps: torch.Tensor, restart: int = 20, max_outer: int = 50
             raise ValueError("density needs backend='hip' (the torch backend has the constant-density operator only)")
         if refine:
             raise NotImplementedError("gmres(refine=True) is not implemented with density: the variable-density operator has no float64 residual")
-        solver._refuse_density_grad("gmres", sos_maps, x0, absorption, density)
+        solver._refuse_medium_grad("gmres", True, sos_maps, x0, absorption, density)
     if absorption is not None:
         if backend != "hip":
             raise ValueError("absorption needs backend='hip' (the torch backend has the lossless operator only)")

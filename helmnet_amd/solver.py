@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from .checkpoint import AttributeDict, read_lightning_checkpoint
-from .engine import Engine, _require_no_grad
+from .engine import Engine, Medium, _require_no_grad
 from .laplacian import FastLaplacianWithPML, domain_hw
 from .source import SourceModule
 from .unet import HybridNet
@@ -434,30 +434,14 @@ class IterativeSolver(nn.Module):
             return Laplacian.apply(self.engine(), x.float())
         return self.engine().laplacian(x.float().contiguous())
 
-    def _refuse_lossy_grad(self, what: str, *tensors):
-        """Absorbing media have one differentiable path, the adjoint-state gradients of ``solve_implicit`` (which detaches before it comes here);
-        the library has no derivative of the lossy solver LOOP: an input that requires grad -- or differentiable(True) under grad mode -- raises
-        before anything touches the device."""
+    def _refuse_medium_grad(self, what: str, density: bool, *tensors):
+        """Absorbing media have one differentiable path, the adjoint-state gradients of ``solve_implicit`` (which detaches before it comes here), and
+        variable density has none at all; the library has no derivative of either solver LOOP: an input that requires grad -- or
+        differentiable(True) under grad mode -- raises before anything touches the device.  ``density``: the medium has one, and is named for it."""
         if any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors) or (self._differentiable and torch.is_grad_enabled()):
-            raise RuntimeError(f"{what} with absorption runs without gradients (the library has no derivative of the lossy operator): pass detached "
+            name, operator = ("density", "variable-density") if density else ("absorption", "lossy")
+            raise RuntimeError(f"{what} with {name} runs without gradients (the library has no derivative of the {operator} operator): pass detached "
                                "tensors, or run under torch.no_grad() after differentiable(True)")
-
-    def _lossy_initials(self, what: str, sos_maps, absorption):
-        """(k_sq, k_sq_im, wf = 0) of ``get_initials`` for the medium (sos_maps, absorption): helmnet_amd.absorption.complex_k_sq."""
-        from .absorption import complex_k_sq
-        self._refuse_lossy_grad(what, sos_maps, absorption)
-        sos = sos_maps.float().contiguous()
-        if isinstance(absorption, torch.Tensor):
-            absorption = absorption.detach().to(sos.device, sos.dtype)
-        k_sq, k_sq_im = complex_k_sq(sos, absorption, self.hparams.omega)
-        return k_sq, k_sq_im, torch.zeros(sos.shape[0], 2, sos.shape[2], sos.shape[3], device=sos.device)
-
-    def _refuse_density_grad(self, what: str, *tensors):
-        """Variable density has no differentiable path at all: an input that requires grad -- or differentiable(True) under grad mode -- raises
-        before anything touches the device."""
-        if any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors) or (self._differentiable and torch.is_grad_enabled()):
-            raise RuntimeError(f"{what} with density runs without gradients (the library has no derivative of the variable-density operator): pass "
-                               "detached tensors, or run under torch.no_grad() after differentiable(True)")
 
     @staticmethod
     def _rho_grad(density, like: torch.Tensor) -> torch.Tensor:
@@ -472,28 +456,33 @@ class IterativeSolver(nn.Module):
             raise ValueError(f"density of shape {tuple(density.shape)} does not broadcast to {tuple(like.shape)}") from e
         return log_density_gradient(rho.contiguous())
 
-    def _medium_initials(self, what: str, sos_maps, absorption, density):
-        """(k_sq, k_sq_im or None, rho_grad, wf = 0) for the medium (sos_maps, absorption or None, density)."""
-        self._refuse_density_grad(what, sos_maps, absorption, density)
+    def _initials(self, what: str, sos_maps, absorption=None, density=None):
+        """(Medium, wf = 0) of a solve without gradients on (sos_maps, absorption or None, density or None): ``get_initials`` for the lossless medium
+        of constant density, else helmnet_amd.absorption.complex_k_sq and ``_rho_grad``."""
+        sos = sos_maps.float().contiguous()
+        if absorption is None and density is None:
+            k_sq, wf = self.get_initials(sos)
+            return Medium(k_sq.contiguous()), wf
+        self._refuse_medium_grad(what, density is not None, sos_maps, absorption, density)
         if absorption is not None:
-            k_sq, k_sq_im, wf = self._lossy_initials(what, sos_maps, absorption)
+            from .absorption import complex_k_sq
+            if isinstance(absorption, torch.Tensor):
+                absorption = absorption.detach().to(sos.device, sos.dtype)
+            k_sq, k_sq_im = complex_k_sq(sos, absorption, self.hparams.omega)
         else:
-            k_sq, wf = self.get_initials(sos_maps.float().contiguous())
-            k_sq, k_sq_im = k_sq.contiguous(), None
-        return k_sq, k_sq_im, self._rho_grad(density, k_sq), wf
+            k_sq, k_sq_im = self.get_initials(sos)[0].contiguous(), None
+        rho_grad = None if density is None else self._rho_grad(density, k_sq)
+        return Medium(k_sq, k_sq_im, rho_grad), torch.zeros(sos.shape[0], 2, sos.shape[2], sos.shape[3], device=sos.device)
 
     def get_residual(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor] = None, rho_grad: Optional[torch.Tensor] = None):
         """hybridnet.py:544-556.  ``k_sq_im`` (extension, [B,1,H,W]): the imaginary plane of an absorbing medium's squared wavenumber
         (helmnet_amd.absorption.complex_k_sq); the residual is then L(x) + (k_sq + i k_sq_im) x - source, without gradients.
         ``rho_grad`` (extension, [B,2,H,W]): the gradient of ln rho (helmnet_amd.density.log_density_gradient); the residual is then the
         variable-density operator's (hn_residual_medium), with or without ``k_sq_im``, without gradients."""
-        if rho_grad is not None:
-            self._refuse_density_grad("get_residual", x, k_sq, k_sq_im, rho_grad)
-            return self.engine().residual_medium(x.float().contiguous(), k_sq.float().contiguous(),
-                                                 None if k_sq_im is None else k_sq_im.float().contiguous(), rho_grad.float().contiguous(), self._src())
-        if k_sq_im is not None:
-            self._refuse_lossy_grad("get_residual", x, k_sq, k_sq_im)
-            return self.engine().residual_lossy(x.float().contiguous(), k_sq.float().contiguous(), k_sq_im.float().contiguous(), self._src())
+        if k_sq_im is not None or rho_grad is not None:
+            self._refuse_medium_grad("get_residual", rho_grad is not None, x, k_sq, k_sq_im, rho_grad)
+            m = Medium(*(None if t is None else t.float().contiguous() for t in (k_sq, k_sq_im, rho_grad)))
+            return getattr(self.engine(), "residual" + m.kind)(x.float().contiguous(), *m.planes(), self._src())
         if self._wants_grad(x, k_sq):
             from .autograd import Residual
             return Residual.apply(self.engine(), x.float(), k_sq.float(), self._src_graph())
@@ -551,9 +540,9 @@ class IterativeSolver(nn.Module):
             raise ValueError("absorption goes with sos_maps (with k_sq pass k_sq_im)")
         if k_sq_im is not None and k_sq is None:
             raise ValueError("k_sq_im goes with k_sq (with sos_maps pass absorption)")
-        self._refuse_lossy_grad("verify", wavefield, sos_maps, k_sq, absorption, k_sq_im)
+        self._refuse_medium_grad("verify", False, wavefield, sos_maps, k_sq, absorption, k_sq_im)
         if k_sq is None:
-            k_sq, k_sq_im, _ = self._lossy_initials("verify", sos_maps, absorption)
+            k_sq, k_sq_im, _ = self._initials("verify", sos_maps, absorption)[0]
         eng = self.engine()
         wf32, k32, ki32 = wavefield.float().contiguous(), k_sq.float().contiguous(), k_sq_im.float().contiguous()
         res32 = eng.residual_lossy(wf32, k32, ki32, self._src())
@@ -583,9 +572,9 @@ class IterativeSolver(nn.Module):
         return (wf, res) if get_residual else wf
 
     # ------------------------------------------------------------------ loops ------------
-    def _loop(self, wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals: str, k_sq_im=None, rho_grad=None):
-        """K iterations on wf / res / st, updated in place -- Engine.step for fp32 tensors, Engine.step64 for float64 ones, Engine.step_lossy with a
-        ``k_sq_im``, Engine.step_medium with a ``rho_grad`` -- with the histories asked for, in wf's dtype; the result dictionary of ``forward``."""
+    def _loop(self, wf, res, st, m: Medium, src, num_iterations, return_wavefields, return_states, residuals: str):
+        """K iterations on wf / res / st, updated in place -- Engine.step64 for float64 tensors, else Engine.step, step_lossy or step_medium by the
+        kind of the medium ``m`` -- with the histories asked for, in wf's dtype; the result dictionary of ``forward``."""
         eng = self.engine()
         b, hw, K = wf.shape[0], tuple(wf.shape[-2:]), int(num_iterations)
 
@@ -604,13 +593,8 @@ class IterativeSolver(nn.Module):
         rmse = torch.empty((K, b), device=wf.device, dtype=wf.dtype) if K > 0 else None
         if K > 0:
             keep = self.f.to_engine_states(st)      # levels without state: zeros in, the caller's values back out
-            if rho_grad is not None:
-                eng.step_medium(wf, res, st, k_sq, k_sq_im, rho_grad, src, K, res_hist, wf_hist, st_hist, rmse)
-            elif k_sq_im is not None:
-                eng.step_lossy(wf, res, st, k_sq, k_sq_im, src, K, res_hist, wf_hist, st_hist, rmse)
-            else:
-                step = eng.step64 if wf.dtype == torch.float64 else eng.step
-                step(wf, res, st, k_sq, src, K, res_hist, wf_hist, st_hist, rmse)
+            step = eng.step64 if wf.dtype == torch.float64 else getattr(eng, "step" + m.kind)
+            step(wf, res, st, *m.planes(), src, K, res_hist, wf_hist, st_hist, rmse)
             self.f.from_engine_states(keep, st, st_hist)
         out = {
             "wavefields": list(wf_hist.unbind(0)) if wf_hist is not None else [wf],
@@ -623,8 +607,8 @@ class IterativeSolver(nn.Module):
             out["last_residual"] = res
         return out
 
-    def _run(self, wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals: str, k_sq_im=None, rho_grad=None):
-        out = self._loop(wf, res, st, k_sq, self._src(), num_iterations, return_wavefields, return_states, residuals, k_sq_im, rho_grad)
+    def _run(self, wf, res, st, m: Medium, num_iterations, return_wavefields, return_states, residuals: str):
+        out = self._loop(wf, res, st, m, self._src(), num_iterations, return_wavefields, return_states, residuals)
         self.f.adopt_states(st)
         return out
 
@@ -651,29 +635,16 @@ class IterativeSolver(nn.Module):
             raise ValueError("residuals must be 'all', 'norms' or 'last'")
         if num_iterations is None:
             num_iterations = self.hparams.max_iterations
-        if density is not None:
-            k_sq, k_sq_im, rho_grad, wf = self._medium_initials("forward", sos_maps, absorption, density)
-            self.f.clear_states(wf)
-            res = self.get_residual(wf, k_sq, k_sq_im, rho_grad)
-            st = self.f.get_states(flatten=True).contiguous()
-            return self._run(wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals, k_sq_im, rho_grad)
-        if absorption is not None:
-            k_sq, k_sq_im, wf = self._lossy_initials("forward", sos_maps, absorption)
-            self.f.clear_states(wf)
-            res = self.get_residual(wf, k_sq, k_sq_im)
-            st = self.f.get_states(flatten=True).contiguous()
-            return self._run(wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals, k_sq_im)
-        if self._wants_grad(sos_maps):
+        if absorption is None and density is None and self._wants_grad(sos_maps):
             k_sq, wf = self.get_initials(sos_maps.float())
             self.f.clear_states(wf)
             res = self.get_residual(wf, k_sq)
             return self._run_autograd(wf, res, k_sq, num_iterations, return_wavefields, return_states, residuals, checkpoint_every)
-        sos_maps = sos_maps.float().contiguous()
-        k_sq, wf = self.get_initials(sos_maps)
+        m, wf = self._initials("forward", sos_maps, absorption, density)
         self.f.clear_states(wf)
-        res = self.get_residual(wf, k_sq)
+        res = self.get_residual(wf, *m)
         st = self.f.get_states(flatten=True).contiguous()
-        return self._run(wf, res, st, k_sq.contiguous(), num_iterations, return_wavefields, return_states, residuals)
+        return self._run(wf, res, st, m, num_iterations, return_wavefields, return_states, residuals)
 
     def n_steps(self, wavefield, k_sq, residual, num_iterations, return_wavefields=False, return_states=False,
                 residuals: str = "all", checkpoint_every: int = 1, absorption=None, density=None):
@@ -685,35 +656,23 @@ class IterativeSolver(nn.Module):
         2 sqrt(k_sq + alpha^2) alpha.  No gradients.
 
         ``density`` (extension; None: the code path and the bits of before): rho, as in ``forward``, broadcastable to ``k_sq``.  No gradients."""
-        if density is not None:
-            self._refuse_density_grad("n_steps", wavefield, k_sq, residual, absorption, density)
+        if absorption is not None or density is not None:
+            self._refuse_medium_grad("n_steps", density is not None, wavefield, k_sq, residual, absorption, density)
+        elif self._wants_grad(wavefield, k_sq, residual, states=True):
+            return self._run_autograd(wavefield, residual, k_sq, num_iterations, return_wavefields, return_states, residuals, checkpoint_every)
+        kq, k_sq_im = k_sq.float().contiguous(), None
         if absorption is not None:
-            self._refuse_lossy_grad("n_steps", wavefield, k_sq, residual, absorption)
-            kq = k_sq.float().contiguous()
             alpha = torch.as_tensor(absorption, dtype=kq.dtype, device=kq.device).expand_as(kq)
             k_sq_im = (2.0 * (kq + alpha * alpha).sqrt() * alpha).contiguous()
-            if density is not None:
-                return self._n_steps_lossy(wavefield, kq, k_sq_im, residual, num_iterations, return_wavefields, return_states, residuals,
-                                           self._rho_grad(density, kq))
-            return self._n_steps_lossy(wavefield, kq, k_sq_im, residual, num_iterations, return_wavefields, return_states, residuals)
-        if density is not None:
-            kq = k_sq.float().contiguous()
-            return self._n_steps_lossy(wavefield, kq, None, residual, num_iterations, return_wavefields, return_states, residuals,
-                                       self._rho_grad(density, kq))
-        if self._wants_grad(wavefield, k_sq, residual, states=True):
-            return self._run_autograd(wavefield, residual, k_sq, num_iterations, return_wavefields, return_states, residuals, checkpoint_every)
-        wf = wavefield.detach().float().clone().contiguous()
-        res = residual.detach().float().clone().contiguous()
-        st = self.f.get_states(flatten=True).float().contiguous().clone()
-        return self._run(wf, res, st, k_sq.float().contiguous(), num_iterations, return_wavefields, return_states, residuals)
+        m = Medium(kq, k_sq_im, None if density is None else self._rho_grad(density, kq))
+        return self._n_steps_no_grad(wavefield, m, residual, num_iterations, return_wavefields, return_states, residuals)
 
-    def _n_steps_lossy(self, wavefield, k_sq, k_sq_im, residual, num_iterations, return_wavefields=False, return_states=False, residuals: str = "all",
-                       rho_grad=None):
-        """``n_steps`` without gradients on the medium (k_sq, k_sq_im [, rho_grad: k_sq_im may then be None]): the inputs are not modified."""
+    def _n_steps_no_grad(self, wavefield, m: Medium, residual, num_iterations, return_wavefields=False, return_states=False, residuals: str = "all"):
+        """``n_steps`` without gradients on the medium ``m``: the inputs are not modified."""
         wf = wavefield.detach().float().clone().contiguous()
         res = residual.detach().float().clone().contiguous()
         st = self.f.get_states(flatten=True).float().contiguous().clone()
-        return self._run(wf, res, st, k_sq, num_iterations, return_wavefields, return_states, residuals, k_sq_im, rho_grad)
+        return self._run(wf, res, st, m, num_iterations, return_wavefields, return_states, residuals)
 
     # ------------------------------------------------------------------ forward mode ----
     def _jvp_setup(self, sos_maps):
@@ -774,7 +733,7 @@ class IterativeSolver(nn.Module):
         """``_run`` on hn_step_f64: wf / res / st (float64, owned by the caller of this helper) are updated in place; nothing held in f is touched."""
         if residuals not in ("all", "norms", "last"):
             raise ValueError("residuals must be 'all', 'norms' or 'last'")
-        return self._loop(wf, res, st, k_sq, src, num_iterations, return_wavefields, return_states, residuals)
+        return self._loop(wf, res, st, Medium(k_sq), src, num_iterations, return_wavefields, return_states, residuals)
 
     def _initials64(self, sos_maps, source):
         """(wf = 0, residual, zero flat states, k_sq, source), all float64: get_initials on a float64 input (hybridnet.py:522-538) and cleared states."""
@@ -858,25 +817,16 @@ class IterativeSolver(nn.Module):
                                       "absorption=...) on the result")
         if verify:
             self._require_square("solve_to_tolerance(verify=True)")
-        k_sq_im = rho_grad = None
-        if density is not None:
-            k_sq, k_sq_im, rho_grad, wf = self._medium_initials("solve_to_tolerance", sos_maps, absorption, density)
-        elif absorption is not None:
-            k_sq, k_sq_im, wf = self._lossy_initials("solve_to_tolerance", sos_maps, absorption)
-        else:
-            sos_maps = sos_maps.float().contiguous()
-            k_sq, wf = self.get_initials(sos_maps)
+        m, wf = self._initials("solve_to_tolerance", sos_maps, absorption, density)
+        k_sq = m.k_sq
         self.f.clear_states(wf)
-        res = self.get_residual(wf, k_sq, k_sq_im, rho_grad)
-        k_sq = k_sq.contiguous()
+        res = self.get_residual(wf, *m)
         done, traces, converged = 0, [], False
         while done < max_iterations:
             chunk = min(int(check_every), max_iterations - done)
-            if rho_grad is not None:
-                out = self._n_steps_lossy(wf, k_sq, k_sq_im, res, chunk, residuals="norms", rho_grad=rho_grad)
-            elif k_sq_im is not None:
-                out = self._n_steps_lossy(wf, k_sq, k_sq_im, res, chunk, residuals="norms")
-            else:
+            if m.kind:
+                out = self._n_steps_no_grad(wf, m, res, chunk, residuals="norms")
+            else:   # (differentiable where n_steps is)
                 out = self.n_steps(wf, k_sq, res, chunk, residuals="norms")
             wf, res = out["wavefields"][0], out["last_residual"]
             traces.append(out["residual_norms"])
@@ -922,7 +872,7 @@ class IterativeSolver(nn.Module):
         of before."""
         from .gmres import gmres, gmres_refine_lossy
         if absorption is not None:
-            self._refuse_lossy_grad("gmres64", sos_maps, absorption, x0)
+            self._refuse_medium_grad("gmres64", False, sos_maps, absorption, x0)
             self._require_square("gmres64")
             return gmres_refine_lossy(self, sos_maps, absorption, restart=restart, max_outer=max_cycles, tol=tol, x0=x0, precondition=precondition,
                                       precond_iterations=precond_iterations, precond_scale=precond_scale)
@@ -999,7 +949,7 @@ class IterativeSolver(nn.Module):
         residual RMSE of the reference: how good the ground truth is; below ``tol`` when ``converged``), ``reference`` (the float64 wavefield),
         ``converged`` and ``cycles``.  ``wavefield`` is not written.  ``absorption``: the lossy problem, as in ``gmres64``."""
         if absorption is not None:
-            self._refuse_lossy_grad("reference_error", wavefield, sos_maps, absorption)
+            self._refuse_medium_grad("reference_error", False, wavefield, sos_maps, absorption)
         _require_no_grad("reference_error", wavefield, sos_maps)
         self._require_square("reference_error")
         lossy = {} if absorption is None else {"absorption": absorption}
@@ -1110,7 +1060,7 @@ class IterativeSolver(nn.Module):
             if a in times:
                 self.set_source_maps(next(maps))
                 res = self.get_residual(wf, k_sq)
-            part = self._run(wf, res, st, k_sq, bnd - a, return_wavefields, return_states, residuals)
+            part = self._run(wf, res, st, Medium(k_sq), bnd - a, return_wavefields, return_states, residuals)
             if residuals == "all":
                 merged["residuals"] += part["residuals"]
             merged["states"] += part["states"]
