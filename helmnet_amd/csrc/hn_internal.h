@@ -330,6 +330,7 @@ struct hn_ctx {
     // domain
     hn::SpecTables tab;
     hn::F64Fft* f64fft = nullptr;     // built / grown by the first float64 call on the FFT route that needs it (beside tab.f64_tab, which stays); freed by hn_set_domain, hn_set_domain_rect, hn_destroy
+    int opt_mc_stage = 1;             // HN_OPT_MC_STAGE: 1 k_down_mfma_ring / k_up_mfma_ring / k_dc_mfma_s<8, 8, 0, 0, false, RING> (hn_mfma.hip) where k_down_mfma<., false> / k_up_mfma<., ., false> / k_dc_mfma_s<8, 8, 0, 0> ran, 0 those
     int opt_f64_fft = 0;              // HN_OPT_F64_FFT: 0 the dense kernel k_helm_f64, 1 the two line passes of hn_f64_fft.hip; read by every float64 call
     int f64_route = 0;                // HN_CNT_F64_ROUTE: 0 no float64 call on this domain yet, 1 the last one ran dense, 2 by FFT
     hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty

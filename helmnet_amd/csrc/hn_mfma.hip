@@ -45,6 +45,21 @@ __device__ __forceinline__ float div1000(float x) {
     const float e = fmaf(-qv, 1000.0f, x);
     return fmaf(e, r, qv);
 }
+// Timing ablations of the staging of k_dc_mfma_s, k_down_mfma and k_up_mfma (non-ALL instances; tools/build_variant.sh <name> hn_mfma.hip -DHN_MC_ABL=<bits>;
+// the results are WRONG, only the durations mean something -- profiles/mc_stage_ablation.txt).  Bits: 1 no global loads of the input after the first chunk
+// (k_down_mfma: after the first two channels, as HN_DN_ABL of r5), 2 no LDS commits after it, 4 no barriers after it, 8 the staging plan replaced by a
+// trivial one (no divisions, bounds tests or zero fill: every lane loads offset 0 and commits to its dummy slot), 16 no input loads, commits or barriers
+// at all (but the first chunk's commit, of zeros: LDS nobody writes would let the compiler drop the operand reads and the MFMAs with them): the weight loads,
+// the operand reads, the MFMAs and the epilogue remain.
+#ifndef HN_MC_ABL
+#ifdef HN_DN_ABL
+#define HN_MC_ABL HN_DN_ABL
+#else
+#define HN_MC_ABL 0
+#endif
+#endif
+constexpr int kMcAbl = HN_MC_ABL;
+
 // Scheduling hint for one pipelined step: N x (1 MFMA, then 1 LDS read issued in its shadow).
 template <int N>
 __device__ __forceinline__ void interleave_mfma_dsread() {
@@ -52,6 +67,18 @@ __device__ __forceinline__ void interleave_mfma_dsread() {
     for (int i = 0; i < N; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+    }
+}
+
+// Scheduling hint for one pipelined step of the ring kernels (HN_OPT_MC_STAGE): N x (1 MFMA, 1 LDS read in its shadow), the first NW of them
+// also followed by one LDS write (a share of the next chunk's commit).
+template <int N>
+__device__ __forceinline__ void interleave_mfma_ds_rw(int NW) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+        if (i < NW) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
     }
 }
 
@@ -359,7 +386,11 @@ struct ScCfg {
     static constexpr bool SCALED = CC > 0;         // only the 3-source input layer carries a staging scale (1e3 * residual)
 };
 
-template <int CA, int CB, int CC, int EPI, bool GEN = false>
+// RING (HN_OPT_MC_STAGE 1; launched for the 16-channel decoder, see launch_dc_mfma): conv1's input staging off the matrix pipe's critical path, as in
+// k_down_mfma_ring -- chunk g + 1 is committed to the other buffer behind the first channel's MFMAs of chunk g, its successor is loaded right behind
+// that, one barrier per chunk stands before the last 9 MFMAs, which cover the first operand reads of chunk g + 1; two named sets of weight
+// fragments, no copies.  The same MFMAs in the same order on every accumulator.
+template <int CA, int CB, int CC, int EPI, bool GEN = false, bool RING = false>
 __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, Src sc, Dst out, McW w, McEpi epi, int H, int W) {
     using C = ScCfg<CA, CB, CC>;
     __shared__ __attribute__((aligned(16))) float lds[C::LDS_FLOATS];
@@ -380,6 +411,7 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
     int lofw[C::NL];        // LDS float2 index inside a (padded) staged plane
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
+        if (kMcAbl & 8) { gofb[i] = 0u; lofw[i] = (C::PLANE + 2 * lane) >> 1; continue; }
         const int e = tid + i * 256;
         const int ir = e / (C::PI / 2), ic = 2 * (e - ir * (C::PI / 2));
         const int y = y0 - 2 + ir, x = x0 - 2 + ic;
@@ -412,7 +444,7 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
             const int c = 2 * g + j;
             const float* p0 = c < CA ? base_a + (long)c * sa.sc : c < CA + CB ? base_b + (long)(c - CA) * sb.sc : base_c + (long)(c - CA - CB) * sc.sc;
 #pragma unroll
-            for (int i = 0; i < C::NL; ++i) stage[j][i] = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(p0) + off[i]);
+            for (int i = 0; i < C::NL; ++i) stage[j][i] = (kMcAbl & 16) ? make_float2(0.f, 0.f) : *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(p0) + off[i]);
         }
 #pragma unroll
         for (int j = 0; j < 6; ++j) afrag_next[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(w.a1 + (g * 6 + j) * 64) + aoff);
@@ -449,16 +481,112 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
 #pragma unroll
     for (int r = 0; r < C::NR1; ++r) acc1[r] = (f32x4){bias0, bias0, bias1, bias1};
 
+    if constexpr (RING) {
+        static_assert(!C::SCALED && !GEN && 2 * C::NL <= C::NR1 + 2, "the commit rides on the reads of the second channel");
+        float afA[6], afB[6];
+        unsigned aoff = 4u * lane;
+        auto fetch_w = [&](int g, float (&af)[6]) {   // (offsets laundered in place: see k_down_mfma_ring)
+            asm("" : "+v"(aoff));
+#pragma unroll
+            for (int j = 0; j < 6; ++j) af[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(w.a1 + (g * 6 + j) * 64) + aoff);
+        };
+        auto fetch_s = [&](int g) {
+#pragma unroll
+            for (int i = 0; i < C::NL; ++i) asm("" : "+v"(gofb[i]));
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int c = 2 * g + j;
+                const float* p0 = c < CA ? base_a + (long)c * sa.sc : c < CA + CB ? base_b + (long)(c - CA) * sb.sc : base_c + (long)(c - CA - CB) * sc.sc;
+#pragma unroll
+                for (int i = 0; i < C::NL; ++i) stage[j][i] = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(p0) + gofb[i]);
+            }
+        };
+        fetch_w(0, afA);
+        fetch_s(0);
+        commit(0);
+        if (C::NG > 1) { fetch_w(1, afB); fetch_s(1); }
+        __syncthreads();
+        float br[2][C::NR1 + 2], bvv[3];
+#pragma unroll
+        for (int j = 0; j < C::NR1 + 2; ++j) br[0][j] = lds[bs1 + j * C::PI];
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) bvv[dy] = lds[vc * C::PLANE_P + bsv + dy * C::PI];
+        __builtin_amdgcn_sched_barrier(0);
+        // chunk g: its weights in af, its first channel's rows and its vertical operands already in br[0] / bvv; afn takes the weights of chunk g + 1
+        auto chunk = [&](int g, const float (&af)[6], float (&afn)[6]) {
+            const float* t = lds + (g & 1) * 2 * C::PLANE_P;
+            const int nbuf = (g + 1) & 1;
+            const float* tn = lds + nbuf * 2 * C::PLANE_P;
+            const bool more = g + 1 < C::NG;
+            if (g >= 1 && more) fetch_w(g + 1, afn);
+            // first channel: the second channel's rows are read, and chunk g + 1 is committed, behind its MFMAs (source order = the order of the hints)
+#pragma unroll
+            for (int j = 0; j < C::NR1 + 2; ++j) {
+                br[1][j] = t[C::PLANE_P + bs1 + j * C::PI];
+                if (more && j < 2 * C::NL) reinterpret_cast<float2*>(lds)[(nbuf * 2 + j / C::NL) * (C::PLANE_P / 2) + lofw[j % C::NL]] = stage[j / C::NL][j % C::NL];
+            }
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                for (int r = 0; r < C::NR1; ++r) acc1[r] = mfma4(af[dy], br[0][r + dy], acc1[r]);
+            interleave_mfma_ds_rw<C::NR1 + 2>(more ? 2 * C::NL : 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (vc == 0) {   // wave-uniform: this wave's channel of the vertical group
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) accv = mfma4(af[dy], bvv[dy], accv);
+            }
+            if (g + 2 < C::NG) fetch_s(g + 2);   // into the registers chunk g + 1 was just committed from
+            // second channel: two of its three row offsets, then the barrier, then the third one over the first operand reads of chunk g + 1
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int r = 0; r < C::NR1; ++r) acc1[r] = mfma4(af[3 + dy], br[1][r + dy], acc1[r]);
+            if (vc == 1) {
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) accv = mfma4(af[3 + dy], bvv[dy], accv);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) {   // the other buffer is complete, and this one has been read for the last time
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < C::NR1 + 2; ++j) br[0][j] = tn[bs1 + j * C::PI];
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) bvv[dy] = tn[vc * C::PLANE_P + bsv + dy * C::PI];
+            }
+#pragma unroll
+            for (int r = 0; r < C::NR1; ++r) acc1[r] = mfma4(af[5], br[1][r + 2], acc1[r]);
+            if (more) {
+#pragma unroll
+                for (int i = 0; i < C::NR1; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);           // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);           // DS reads: 14 behind 9 MFMAs
+                    if (i < 5) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+#pragma unroll
+        for (int g = 0; g < C::NG; g += 2) {
+            chunk(g, afA, afB);
+            if (g + 1 < C::NG) chunk(g + 1, afB, afA);
+        }
+    } else {
     fetch(0);
 #pragma unroll
     for (int g = 0; g < C::NG; ++g) {
         const int buf = g & 1;
-        commit(g);
+        if (!((kMcAbl & 18) && g >= 1)) commit(g);
         float afrag[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) afrag[j] = afrag_next[j];
-        __syncthreads();
-        if (g + 1 < C::NG) fetch(g + 1);
+        if (!((kMcAbl & 16) || ((kMcAbl & 4) && g >= 1))) __syncthreads();
+        if (g + 1 < C::NG) {
+            if (kMcAbl & 1) {   // the weight fragments only
+#pragma unroll
+                for (int j = 0; j < 6; ++j) afrag_next[j] = w.a1[((g + 1) * 6 + j) * 64 + lane];
+            } else fetch(g + 1);
+        }
         const float* t = lds + buf * 2 * C::PLANE_P;
         float br[2][C::NR1 + 2], bvv[3];
 #pragma unroll
@@ -483,6 +611,7 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
                 for (int dy = 0; dy < 3; ++dy) accv = mfma4(afrag[c * 3 + dy], bvv[dy], accv);
             }
         }
+    }
     }
     // partial sums of the vertical groups: producer waves (vc = 0) -> consumer's own corner of the (still unused) mid region
     float* const vx = lds + 7 * C::MPLANE + 9 * C::PM + 32 * vg;   // mid channel 7, row 9.., columns 32 vg ..: 32 floats per row
@@ -1893,6 +2022,7 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
     int lofw[C::NL];
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
+        if (!ALL && (kMcAbl & 8)) { gofb[i] = 0u; lofw[i] = C::PLANE + lane; continue; }
         const int e = tid + i * C::NT;
         const int ir = e / C::IC, ic = e - ir * C::IC;
         const int y = 2 * Y0 - 3 + ir, x = 2 * X0 - 3 + ic;
@@ -1917,7 +2047,7 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
         asm volatile("" : "+v"(aoff));
         const char* p0 = reinterpret_cast<const char*>(base + (long)ci * in.sc);
 #pragma unroll
-        for (int i = 0; i < C::NL; ++i) stage[i] = *reinterpret_cast<const float*>(p0 + off[i]);
+        for (int i = 0; i < C::NL; ++i) stage[i] = (kMcAbl & 16) ? 0.f : *reinterpret_cast<const float*>(p0 + off[i]);
 #pragma unroll
         for (int kx = 0; kx < 8; ++kx) afrag_next[kx] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(afr + (ci * 8 + kx) * 64) + aoff);
     };
@@ -1946,10 +2076,7 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
 #pragma unroll
     for (int ci = 0; ci < kFeat; ++ci) {
         float* t = lds + (ALL ? ci : (ci & 1)) * C::PLANE_P;
-#ifndef HN_DN_ABL   // timing ablations only (tools/exp_down.sh): 1 no global loads after the first two channels, 2 no LDS commits after them, 4 no barriers after them
-#define HN_DN_ABL 0
-#endif
-        if (!ALL && !((HN_DN_ABL & 2) && ci >= 2)) {
+        if (!ALL && !(((kMcAbl & 16) && ci >= 1) || ((kMcAbl & 2) && ci >= 2))) {   // (HN_MC_ABL: timing ablations only)
 #pragma unroll
             for (int i = 0; i < C::NL; ++i) t[lofw[i]] = stage[i];
         }
@@ -1957,8 +2084,13 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
 #pragma unroll
         for (int kx = 0; kx < 8; ++kx) afrag[kx] = afrag_next[kx];
         if (!ALL) {
-            if (!((HN_DN_ABL & 4) && ci >= 2)) __syncthreads();
-            if (ci + 1 < kFeat && !((HN_DN_ABL & 1) && ci >= 1)) fetch(ci + 1);
+            if (!((kMcAbl & 16) || ((kMcAbl & 4) && ci >= 2))) __syncthreads();
+            if (ci + 1 < kFeat) {
+                if ((kMcAbl & 1) && ci >= 1) {   // the weight fragments only
+#pragma unroll
+                    for (int kx = 0; kx < 8; ++kx) afrag_next[kx] = afr[((ci + 1) * 8 + kx) * 64 + lane];
+                } else fetch(ci + 1);
+            }
         } else if (ci + 1 < kFeat) {
 #pragma unroll
             for (int kx = 0; kx < 8; ++kx) afrag_next[kx] = afr[((ci + 1) * 8 + kx) * 64 + lane];
@@ -1978,6 +2110,149 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
             interleave_mfma_dsread<C::NWIN>();
             __builtin_amdgcn_sched_barrier(0);
         }
+    }
+    // D rows of lane (n, q): (co = 2q, h = 0), (2q, 1), (2q+1, 0), (2q+1, 1)
+    const int X = X0 + 16 * wx + n;
+    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
+    if (X < Wout) {
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) {
+            const int Y = Y0 + wy * C::R + r;
+            if (Y < Hout) {
+                float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)Y * Wout + X;
+                p[0] = acc[r][0] + acc[r + 2][1] + b0;
+                p[out.sc] = acc[r][2] + acc[r + 2][3] + b1;
+            }
+        }
+    }
+}
+
+// k_down_mfma<WX, false> with the input staging off the matrix pipe's critical path (HN_OPT_MC_STAGE 1).  Same tiles, same MFMAs in the same order
+// on every accumulator -- bit-identical --, but:
+//   * the commit runs one channel ahead: while the MFMAs of channel c read plane c & 1, channel c + 1 is committed to the other plane, a few LDS
+//     writes behind each of the taps 0 .. 6, from registers that were loaded one channel earlier (two register sets, named by the parity of the
+//     channel: the loop is unrolled and nothing is copied).  ONE barrier per channel, between taps 6 and 7: the operand reads of tap k + 1 are
+//     issued behind the MFMAs of tap k, so the last reads of plane c & 1 stand BEFORE that barrier (which waits for them), the writes of
+//     channel c + 2 into the same plane behind it, and the last tap's MFMAs cover the first operand reads of channel c + 1.  Two planes are
+//     therefore enough -- a third would buy nothing with the barrier in this place -- and the kernel keeps its 41.5 KB.
+//   * the prologue loads the first weight fragments, then every staged element as soon as its offset exists (row and column from a running counter:
+//     one division per thread instead of NL), then the second channel; the out-of-image zeros are written while those loads are in flight, and only by
+//     the threads of border tiles.
+template <int WX>
+__global__ __launch_bounds__(256, 2) void k_down_mfma_ring(Src in, Dst out, const float* __restrict__ afr /*[8][8][64]*/,
+                                                            const float* __restrict__ bias, int Hin, int Win, SyncHook hook) {
+    using C = DnCfg<WX>;
+    static_assert(C::NL <= 32, "zmask");
+    constexpr int WPT = cdiv_(C::NL, 7);   // LDS writes per tap: the commit is spread over taps 0 .. 6
+    sync_hook_begin(hook);
+    __shared__ float lds[2 * C::PLANE_P];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, q = lane >> 4;
+    const int wx = wave % WX, wy = wave / WX;
+    const TileId tl = xcd_tile();
+    const int b = tl.z;
+    const int X0 = tl.x * C::TW, Y0 = tl.y * C::TH;
+    const int Hout = Hin / 2, Wout = Win / 2;
+    const float* const base = in.p + (long)b * in.sb;
+
+    // two register sets, A for the even channels and B for the odd ones: the channel loop below is written out by pairs, so every name is static
+    float afA[8], afB[8], stA[C::NL], stB[C::NL];
+    unsigned aoff = 4u * lane;
+    // (laundering a 32-bit offset in place keeps its zero-extension out of the compiler's sight: SGPR-base + VGPR-offset loads, no 64-bit VALU adds, no copy)
+    auto fetch_w = [&](int ci, float (&af)[8]) {
+        asm("" : "+v"(aoff));
+#pragma unroll
+        for (int kx = 0; kx < 8; ++kx) af[kx] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(afr + (ci * 8 + kx) * 64) + aoff);
+    };
+    fetch_w(0, afA);
+    unsigned gofb[C::NL];
+    int lofw[C::NL];
+    unsigned zmask = 0;   // bit i: element i lies in the staged window but outside the image
+    const int ir0 = tid / C::IC, ic0 = tid - ir0 * C::IC;
+    {
+        const char* p0 = reinterpret_cast<const char*>(base);
+        int ir = ir0, ic = ic0;
+#pragma unroll
+        for (int i = 0; i < C::NL; ++i) {
+            const int y = 2 * Y0 - 3 + ir, x = 2 * X0 - 3 + ic;
+            const bool inr = tid + i * C::NT < C::IR * C::IC;
+            const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
+            gofb[i] = ok ? 4u * (unsigned)(y * Win + x) : 0u;
+            lofw[i] = ok ? ir * C::PI + ic : C::PLANE + lane;
+            zmask |= (inr && !ok) ? 1u << i : 0u;
+            stA[i] = *reinterpret_cast<const float*>(p0 + gofb[i]);
+            ic += C::NT % C::IC;
+            ir += C::NT / C::IC;
+            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+        }
+    }
+    auto fetch_s = [&](int ci, float (&st)[C::NL]) {
+        const char* p0 = reinterpret_cast<const char*>(base + (long)ci * in.sc);
+#pragma unroll
+        for (int i = 0; i < C::NL; ++i) {
+            asm("" : "+v"(gofb[i]));
+            st[i] = *reinterpret_cast<const float*>(p0 + gofb[i]);
+        }
+    };
+    fetch_w(1, afB);
+    fetch_s(1, stB);
+    if (zmask != 0) {
+        int ir = ir0, ic = ic0;
+#pragma unroll
+        for (int i = 0; i < C::NL; ++i) {
+            if ((zmask >> i) & 1) {
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
+            }
+            ic += C::NT % C::IC;
+            ir += C::NT / C::IC;
+            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+        }
+    }
+    // B operand of window row wr, tap kx: staged[(2*(wy*R + wr) + q) * PI + 2*(16*wx + n) + kx]
+    const int bbase = (2 * wy * C::R + q) * C::PI + 2 * (16 * wx + n);
+    f32x4 acc[C::NWIN];
+#pragma unroll
+    for (int i = 0; i < C::NWIN; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < C::NL; ++i) lds[lofw[i]] = stA[i];
+    __syncthreads();
+    float bv[2][C::NWIN];
+#pragma unroll
+    for (int wr = 0; wr < C::NWIN; ++wr) bv[0][wr] = lds[bbase + 2 * wr * C::PI];
+    __builtin_amdgcn_sched_barrier(0);
+    constexpr int last = kFeat - 1;
+    // channel ci: its weights in af, channel ci + 1 in (afn, stn); st is free (channel ci was committed from it) and takes channel ci + 2
+    auto channel = [&](int ci, const float (&af)[8], float (&afn)[8], float (&st)[C::NL], const float (&stn)[C::NL]) {
+        const float* t = lds + (ci & 1) * C::PLANE_P;
+        float* tn = lds + ((ci + 1) & 1) * C::PLANE_P;
+        if (ci >= 1 && ci < last) fetch_w(ci + 1, afn);
+        if (ci + 2 < kFeat) fetch_s(ci + 2, st);
+#pragma unroll
+        for (int kx = 0; kx < 8; ++kx) {
+            // (source order = the order the hints below ask for: one operand read, then one commit write, per MFMA)
+#pragma unroll
+            for (int wr = 0; wr < C::NWIN; ++wr) {
+                if (kx + 1 < 8) bv[(kx + 1) & 1][wr] = t[bbase + 2 * wr * C::PI + kx + 1];
+                else if (ci < last) bv[0][wr] = tn[bbase + 2 * wr * C::PI];
+                const int i = kx * WPT + wr;
+                if (ci < last && kx < 7 && wr < WPT && i < C::NL) tn[lofw[i]] = stn[i];
+            }
+#pragma unroll
+            for (int wr = 0; wr < C::NWIN; ++wr) acc[wr] = mfma4(af[kx], bv[kx & 1][wr], acc[wr]);
+            interleave_mfma_ds_rw<C::NWIN>(ci < last && kx < 7 ? WPT : 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (kx == 6 && ci < last) {   // the other plane is complete, and this one has been read for the last time
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+#pragma unroll
+    for (int ci = 0; ci < kFeat; ci += 2) {
+        channel(ci, afA, afB, stA, stB);
+        channel(ci + 1, afB, afA, stB, stA);
     }
     // D rows of lane (n, q): (co = 2q, h = 0), (2q, 1), (2q+1, 0), (2q+1, 1)
     const int X = X0 + 16 * wx + n;
@@ -2036,6 +2311,7 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
     int lofw[C::NL];
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
+        if (!ALL && (kMcAbl & 8)) { gofb[i] = 0u; lofw[i] = C::PLANE + lane; continue; }
         const int e = tid + i * C::NT;
         const int ir = e / C::IC, ic = e - ir * C::IC;
         const int y = Yb - 1 + ir, x = X0 - 2 + ic;
@@ -2062,8 +2338,8 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
         const char* p1 = reinterpret_cast<const char*>(base + (long)(2 * g + 1) * in.sc);
 #pragma unroll
         for (int i = 0; i < C::NL; ++i) {
-            stage[i][0] = *reinterpret_cast<const float*>(p0 + off[i]);
-            stage[i][1] = *reinterpret_cast<const float*>(p1 + off[i]);
+            stage[i][0] = (kMcAbl & 16) ? 0.f : *reinterpret_cast<const float*>(p0 + off[i]);
+            stage[i][1] = (kMcAbl & 16) ? 0.f : *reinterpret_cast<const float*>(p1 + off[i]);
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j) afrag_next[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(afr + (g * 16 + j) * 64) + aoff);
@@ -2093,7 +2369,7 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
 #pragma unroll
     for (int g = 0; g < kFeat / 2; ++g) {
         float* t = lds + (ALL ? 2 * g : (g & 1) * 2) * C::PLANE_P;
-        if (!ALL) {
+        if (!ALL && !((kMcAbl & 18) && g >= 1)) {   // (HN_MC_ABL: timing ablations only)
 #pragma unroll
             for (int i = 0; i < C::NL; ++i) {
                 t[lofw[i]] = stage[i][0];
@@ -2104,8 +2380,13 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
 #pragma unroll
         for (int j = 0; j < 16; ++j) afrag[j] = afrag_next[j];
         if (!ALL) {
-            __syncthreads();
-            if (g + 1 < kFeat / 2) fetch(g + 1);
+            if (!((kMcAbl & 16) || ((kMcAbl & 4) && g >= 1))) __syncthreads();
+            if (g + 1 < kFeat / 2) {
+                if (kMcAbl & 1) {   // the weight fragments only
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) afrag_next[j] = afr[((g + 1) * 16 + j) * 64 + lane];
+                } else fetch(g + 1);
+            }
         } else if (g + 1 < kFeat / 2) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) afrag_next[j] = afr[((g + 1) * 16 + j) * 64 + lane];
@@ -2129,6 +2410,161 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
             }
             interleave_mfma_dsread<C::R>();
             __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // D rows of lane (n, q): (co = 2q, py = 0), (2q, 1), (2q+1, 0), (2q+1, 1); acc[.][px]
+    const int X = X0 + 16 * wx + n;
+    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
+    if (X < Win) {
+#pragma unroll
+        for (int wr = 0; wr < C::R; ++wr) {
+            const int Y = Yb + wy * C::R + wr;
+#pragma unroll
+            for (int py = 0; py < 2; ++py) {
+                const int y = 2 * Y + 1 + py;
+                if (y >= 0 && y < Hout) {
+                    float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)y * Wout + 2 * X;
+                    float2 o0 = make_float2(acc[wr][0][py] + b0, acc[wr][1][py] + b0);
+                    float2 o1 = make_float2(acc[wr][0][2 + py] + b1, acc[wr][1][2 + py] + b1);
+                    if (ACC) {
+                        const float2 c0 = *reinterpret_cast<const float2*>(p), c1 = *reinterpret_cast<const float2*>(p + out.sc);
+                        o0.x += c0.x; o0.y += c0.y; o1.x += c1.x; o1.y += c1.y;
+                    }
+                    *reinterpret_cast<float2*>(p) = o0;
+                    *reinterpret_cast<float2*>(p + out.sc) = o1;
+                }
+            }
+        }
+    }
+    sync_hook_end(hook);
+}
+
+// k_up_mfma<WX, R_, false, ACC> with the input staging off the matrix pipe's critical path (HN_OPT_MC_STAGE 1; see k_down_mfma_ring): the same tiles and
+// the same MFMAs in the same order on every accumulator.  The channel pair g + 1 is committed to the other two planes behind the MFMAs of the first
+// steps of pair g, its successor is loaded into the same registers right behind that commit (more than half a pair ahead of its own commit), one barrier
+// per pair stands between steps 8 and 9, and step 9 covers the first operand reads of pair g + 1.  ONE set of 16 weight fragments: the first half is dead
+// after step 4 and takes the next pair's there, the second half follows at step 0 of that pair.
+template <int WX, int R_, bool ACC>
+__global__ __launch_bounds__(256, 3) void k_up_mfma_ring(Src in, Dst out, const float* __restrict__ afr /*[8][2][4][64]*/,
+                                                       const float* __restrict__ bias, int Hin, int Win, SyncHook hook) {
+    using C = UpCfg2<WX, R_>;
+    static_assert(C::NL <= 16, "zmask, and the commit fits steps 0 .. 7");
+    constexpr int NG = kFeat / 2;
+    constexpr int WSTEPS = 4, WPS = cdiv_(2 * C::NL, WSTEPS);   // the commit: WPS LDS writes behind each of the steps 0 .. WSTEPS - 1
+    __shared__ float lds[4 * C::PLANE_P];  // 2 buffers x 2 channels
+    sync_hook_begin(hook);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, q = lane >> 4;
+    const int wx = wave % WX, wy = wave / WX;
+    const TileId tl = xcd_tile();
+    const int b = tl.z;
+    const int X0 = tl.x * C::TW, Yb = tl.y * C::TH - 1;  // first window row of the block
+    const int Hout = 2 * Hin, Wout = 2 * Win;
+    const float* const base = in.p + (long)b * in.sb;
+
+    float afrag[16], stage[C::NL][2];
+    unsigned aoff = 4u * lane;
+    auto fetch_w = [&](int g, int half) {   // (offsets laundered in place: see k_down_mfma_ring)
+        asm("" : "+v"(aoff));
+#pragma unroll
+        for (int j = 8 * half; j < 8 * half + 8; ++j) afrag[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(afr + (g * 16 + j) * 64) + aoff);
+    };
+    fetch_w(0, 0);
+    fetch_w(0, 1);
+    unsigned gofb[C::NL];
+    int lofw[C::NL];
+    unsigned zmask = 0;   // bit i: element i lies in the staged window but outside the image
+    const int ir0 = tid / C::IC, ic0 = tid - ir0 * C::IC;
+    {
+        const char* p0 = reinterpret_cast<const char*>(base);
+        const char* p1 = reinterpret_cast<const char*>(base + in.sc);
+        int ir = ir0, ic = ic0;
+#pragma unroll
+        for (int i = 0; i < C::NL; ++i) {
+            const int y = Yb - 1 + ir, x = X0 - 2 + ic;
+            const bool inr = tid + i * C::NT < C::IR * C::IC;
+            const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
+            gofb[i] = ok ? 4u * (unsigned)(y * Win + x) : 0u;
+            lofw[i] = ok ? ir * C::PI + ic : C::PLANE + lane;
+            zmask |= (inr && !ok) ? 1u << i : 0u;
+            stage[i][0] = *reinterpret_cast<const float*>(p0 + gofb[i]);
+            stage[i][1] = *reinterpret_cast<const float*>(p1 + gofb[i]);
+            ic += C::NT % C::IC;
+            ir += C::NT / C::IC;
+            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+        }
+    }
+    auto fetch_s = [&](int g) {
+        const char* p0 = reinterpret_cast<const char*>(base + (long)(2 * g) * in.sc);
+        const char* p1 = reinterpret_cast<const char*>(base + (long)(2 * g + 1) * in.sc);
+#pragma unroll
+        for (int i = 0; i < C::NL; ++i) {
+            asm("" : "+v"(gofb[i]));
+            stage[i][0] = *reinterpret_cast<const float*>(p0 + gofb[i]);
+            stage[i][1] = *reinterpret_cast<const float*>(p1 + gofb[i]);
+        }
+    };
+    if (zmask != 0) {
+        int ir = ir0, ic = ic0;
+#pragma unroll
+        for (int i = 0; i < C::NL; ++i) {
+            if ((zmask >> i) & 1) {
+#pragma unroll
+                for (int pl = 0; pl < 4; ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
+            }
+            ic += C::NT % C::IC;
+            ir += C::NT / C::IC;
+            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+        }
+    }
+    // B operand for window row wr, column offset o (= ix - X + 2, 0..4): staged[(wy*R + wr + q) * PI + 16*wx + n + o]
+    const int bbase = (wy * C::R + q) * C::PI + 16 * wx + n;
+    f32x4 acc[C::R][2];
+#pragma unroll
+    for (int i = 0; i < C::R; ++i) acc[i][0] = acc[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < C::NL; ++i) {
+        lds[lofw[i]] = stage[i][0];
+        lds[C::PLANE_P + lofw[i]] = stage[i][1];
+    }
+    fetch_s(1);
+    __syncthreads();
+    float bv[2][C::R];
+#pragma unroll
+    for (int wr = 0; wr < C::R; ++wr) bv[0][wr] = lds[bbase + wr * C::PI];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const float* t = lds + (g & 1) * 2 * C::PLANE_P;
+        float* tn = lds + ((g + 1) & 1) * 2 * C::PLANE_P;
+        constexpr int last = NG - 1;
+        if (g >= 1) fetch_w(g, 1);
+#pragma unroll
+        for (int st = 0; st < 10; ++st) {
+            const int c = st / 5, o = st % 5;
+            const int c1 = (st + 1) / 5, o1 = (st + 1) % 5;
+            // (source order = the order the hints below ask for: one operand read, then one commit write, per MFMA)
+#pragma unroll
+            for (int wr = 0; wr < C::R; ++wr) {
+                if (st + 1 < 10) bv[(st + 1) & 1][wr] = t[c1 * C::PLANE_P + bbase + wr * C::PI + o1];
+                else if (g < last) bv[0][wr] = tn[bbase + wr * C::PI];
+                const int k = st * WPS + wr;   // element k >> 1, channel k & 1 of the pair
+                if (g < last && st < WSTEPS && wr < WPS && k < 2 * C::NL) tn[(k & 1) * C::PLANE_P + lofw[k >> 1]] = stage[k >> 1][k & 1];
+            }
+            if (g + 2 < NG && st == WSTEPS) fetch_s(g + 2);   // into the registers pair g + 1 was just committed from
+            if (g < last && st == 5) fetch_w(g + 1, 0);
+#pragma unroll
+            for (int wr = 0; wr < C::R; ++wr) {
+                if (o < 4) acc[wr][0] = mfma4(afrag[c * 8 + o], bv[st & 1][wr], acc[wr][0]);           // px = 0, bb = o
+                if (o > 0) acc[wr][1] = mfma4(afrag[c * 8 + 4 + (o - 1)], bv[st & 1][wr], acc[wr][1]);  // px = 1, bb = o - 1
+            }
+            interleave_mfma_ds_rw<C::R>(g < last && st < WSTEPS ? WPS : 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (st == 8 && g < last) {   // the other two planes are complete, and these two have been read for the last time
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
     // D rows of lane (n, q): (co = 2q, py = 0), (2q, 1), (2q+1, 0), (2q+1, 1); acc[.][px]
@@ -2363,7 +2799,7 @@ __global__ __launch_bounds__(256, 2) void k_up_x16(Src in, Dst out, const void* 
 }
 
 template <int CA, int CB, int CC, int EPI>
-void launch_dc_mfma(int x16, Src a, Src b, Src c, Dst out, const McW& w, const McEpi& e, int H, int W, int batch, hipStream_t s) {
+void launch_dc_mfma(int x16, Src a, Src b, Src c, Dst out, const McW& w, const McEpi& e, int H, int W, int batch, hipStream_t s, bool ring = false) {
     const bool even = (W & 1) == 0;
     const bool scaled = a.scale != 1.f || b.scale != 1.f || c.scale != 1.f;
     const bool off32 = 8.0 * (double)H * (double)W * 4.0 < 4.0e9;  // the strip kernel addresses a sample's planes with 32-bit byte offsets
@@ -2400,7 +2836,16 @@ void launch_dc_mfma(int x16, Src a, Src b, Src c, Dst out, const McW& w, const M
 #define HN_STRIP_MIN_W 128   // narrowest level on the strip kernel (experiment: tools/build_variant.sh ... -DHN_STRIP_MIN_W=256)
 #endif
     if (W >= HN_STRIP_MIN_W && even && off32 && (!scaled || ScCfg<CA, CB, CC>::SCALED)) {
-        hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI>), dim3(cdiv_(W, 64), cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
+        const dim3 g(cdiv_(W, 64), cdiv_(H, 16), batch);
+        // HN_OPT_MC_STAGE: conv1's staging behind the MFMAs, for the 16-channel decoder only ([measured, profiles/mc_stage_ablation.txt] 30.0 -> 28.7 us at
+        // 128^2 x 32; the 10-channel conv_signal instance built the same way measured 23.3 against 23.1 and stays on the kernel as it was)
+        if constexpr (!ScCfg<CA, CB, CC>::SCALED && EPI == 0 && CA == kFeat && CB == kFeat) {
+            if (ring) {
+                hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI, false, true>), g, dim3(256), 0, s, a, b, c, out, w, e, H, W);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI>), g, dim3(256), 0, s, a, b, c, out, w, e, H, W);
     } else if (even && W > 16) {
         // small levels are latency-bound: whole input tile staged at once (one barrier), small 8 x 32
         // tiles so that even a 32^2 image spreads over many CUs
@@ -2581,13 +3026,14 @@ void launch_dc8(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, co
     McEpi e{ctx->outc_w, ctx->outc_b, f.d_out, f.wf_out, ctx->f_dec0c, ctx->dec0c_b};
     e.wf_in = f.wf_in;
     const int x16 = (ctx->precision >= HN_PREC_BF16X3 && ctx->precision <= HN_PREC_BF16X2) ? ctx->precision : 0;
+    const bool ring = ctx->opt_mc_stage != 0;
     switch (kind) {
-        case DcKind::Inc: launch_dc_mfma<2, 2, 2, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;
-        case DcKind::Signal: launch_dc_mfma<kFeat, kState, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;
-        case DcKind::Bottleneck: launch_dc_mfma<kFeat, 0, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s); break;
+        case DcKind::Inc: launch_dc_mfma<2, 2, 2, 0>(x16, a, b, c, out, mw, e, H, W, batch, s, ring); break;
+        case DcKind::Signal: launch_dc_mfma<kFeat, kState, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s, ring); break;
+        case DcKind::Bottleneck: launch_dc_mfma<kFeat, 0, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s, ring); break;
         case DcKind::Decoder:
-            if (fin) launch_dc_mfma<kFeat, kFeat, 0, 1>(x16, a, b, c, out, mw, e, H, W, batch, s);
-            else launch_dc_mfma<kFeat, kFeat, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s);
+            if (fin) launch_dc_mfma<kFeat, kFeat, 0, 1>(x16, a, b, c, out, mw, e, H, W, batch, s, ring);
+            else launch_dc_mfma<kFeat, kFeat, 0, 0>(x16, a, b, c, out, mw, e, H, W, batch, s, ring);
             break;
     }
 }
@@ -2666,10 +3112,16 @@ void launch_down(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, i
     }
     // tile shape by level size: 64x16 outputs per block for the big levels, 32x16 at 64 < Wout... (more, shorter blocks
     // when there are few tiles: 17 us instead of 26 us at Wout = 64), all channels at once for the small ones
-    if (Wout > 64) hipLaunchKernelGGL((k_down_mfma<4, false>), dim3(cdiv_(Wout, 64), cdiv_(Hout, 16), batch), dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-    else if (Wout > 32) {
+    // (HN_OPT_MC_STAGE: the same tiles with the staging behind the MFMAs, k_down_mfma_ring)
+    const bool ring = ctx->opt_mc_stage != 0;
+    if (Wout > 64) {
+        const dim3 g(cdiv_(Wout, 64), cdiv_(Hout, 16), batch);
+        if (ring) hipLaunchKernelGGL((k_down_mfma_ring<4>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+        else hipLaunchKernelGGL((k_down_mfma<4, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+    } else if (Wout > 32) {
         const dim3 g(cdiv_(Wout, 32), cdiv_(Hout, 16), batch);
-        hipLaunchKernelGGL((k_down_mfma<2, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+        if (ring) hipLaunchKernelGGL((k_down_mfma_ring<2>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+        else hipLaunchKernelGGL((k_down_mfma<2, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
     }
     else {
         const dim3 g(cdiv_(Wout, 16), cdiv_(Hout, 16), batch);
@@ -2694,7 +3146,11 @@ void launch_up(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int
     // round of 3 resident blocks per CU at 256^2 x 32 (16-row blocks: 1152 = 1.5 rounds)
     if (Win > up_small) {
         const dim3 g(cdiv_(Win, 32), cdiv_(Hin + 1, 22), batch);
-        if (accumulate) hipLaunchKernelGGL((k_up_mfma<2, 11, false, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+        if (ctx->opt_mc_stage != 0) {   // HN_OPT_MC_STAGE: the same tiles with the staging behind the MFMAs
+            if (accumulate) hipLaunchKernelGGL((k_up_mfma_ring<2, 11, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            else hipLaunchKernelGGL((k_up_mfma_ring<2, 11, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+        }
+        else if (accumulate) hipLaunchKernelGGL((k_up_mfma<2, 11, false, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
         else hipLaunchKernelGGL((k_up_mfma<2, 11, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
     } else {
         const dim3 g(cdiv_(Win, 16), cdiv_(Hin + 1, 20), batch);

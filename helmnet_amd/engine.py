@@ -237,7 +237,8 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Library tuning knobs (enum hn_option of include/helmnet_hip.h): 'lanes' 1..8, 'side_stream' 0..3, 'deep' 0/1, 'spectral_pfa' 0/1,
-        'spectral_radix16' 0..2, 'dc_valu' 0..4, 'spectral_cols' 0..3, 'train_fused', 'train_overlap'; laboratory knobs (HN_EXP_*): 'graph' 0, 1 or an even
+        'spectral_radix16' 0..2, 'dc_valu' 0..4, 'spectral_cols' 0..3, 'train_fused', 'train_overlap', 'mc_stage' 0/1 (the matrix-core 8x8 / strip kernels with
+        the input staging behind the MFMAs; bit-identical); laboratory knobs (HN_EXP_*): 'graph' 0, 1 or an even
         number <= 64 of iterations per graph, 'train_lanes' 1/2 (hn_train_grad: the halves of the batch as two chains of launches on two streams).
         'spectral_pfa' and 'spectral_mixed' 0/1 (FFT for every other size P * 2^k, P odd; default 0) are read when the spectral tables are built:
         changing one re-builds them; counter('spectral_route') tells which kernels the domain runs on (1 power of two, 2 prime-factor, 3 dense,

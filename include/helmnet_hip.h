@@ -150,6 +150,12 @@ enum hn_option {
     HN_OPT_STATE_KERNEL = 14, /* 0/1 (default 1): the hidden-state DoubleConvs (10 -> 2 -> 2) of the levels at least 64 wide on the streaming kernel
                               * (hn_cs.hip: the tile's ten input planes through a ring of LDS-direct loads); 0: the general direct kernel.
                               * Bit-identical                                                                                          */
+    HN_OPT_MC_STAGE = 19,    /* 0/1 (default 1): the fp32 matrix-core 8x8 stride-2 convolutions of the levels more than 32 outputs (down) / 64 inputs (up) wide
+                              * and the 16-channel decoder DoubleConv of the levels at least 128 wide that run on the matrix core, with the input
+                              * staging off the matrix pipe's critical path (the next chunk is committed to LDS behind the MFMAs of the current one,
+                              * one barrier per chunk, no register copies, a prologue that loads before it plans; hn_mfma.hip: k_down_mfma_ring,
+                              * k_up_mfma_ring, k_dc_mfma_s<.., RING>); 0: the kernels as they were.  The same MFMAs in the same order on every
+                              * accumulator: bit-identical.  [measured, profiles/mc_stage_ab.txt] +2.1 % it/s at 256^2 x 32, +1.9 % at 512^2 x 16 */
     HN_OPT_HIST_COPY = 15,   /* 0 (default): hn_step's residual / wavefield histories are written in place of the copies (see hn_step); 1: every
                               * iteration works in the caller's wf / res and copies them into the history slots (A/B; bit-identical)       */
     HN_OPT_INC_SIGMA_MAP = 16, /* 0/1 (default 1): the sigma maps are constants of the domain and two of the six input channels of every UNet evaluation the solver
