@@ -21,11 +21,16 @@ _lib = None
 HN_ACT = {"prelu": 0, "relu": 1, "leakyrelu": 2, "celu": 3, "tanh": 4, "gelu": 5, "tanhshrink": 6, "softplus": 7}
 # enum hn_precision / hn_option / hn_counter of include/helmnet_hip.h
 HN_PRECISION = {"fp32": 0, "bf16x3": 1, "fp16": 2, "bf16x2": 3, "valu": 4}
-HN_OPTION = {"lanes": 0, "side_stream": 1, "deep": 3, "spectral_pfa": 4, "spectral_radix16": 5, "dc_valu": 6, "spectral_cols": 7, "train_fused": 10, "train_overlap": 11, "dc_pair": 12, "side_sync": 13, "state_kernel": 14, "hist_copy": 15, "inc_sigma_map": 16, "spectral_mixed": 17, "f64_fft": 18, "mc_stage": 19,
+HN_OPTION = {"lanes": 0, "side_stream": 1, "deep": 3, "spectral_pfa": 4, "spectral_radix16": 5, "dc_valu": 6, "spectral_cols": 7, "train_fused": 10, "train_overlap": 11, "dc_pair": 12, "side_sync": 13, "state_kernel": 14, "hist_copy": 15, "inc_sigma_map": 16, "spectral_mixed": 17, "f64_fft": 18, "mc_stage": 19, "module_mc": 20,
              "graph": 100, "train_lanes": 101, "spectral_plain": 102}   # 100 +: laboratory knobs (HN_EXP_*)
 HN_COUNTER = {"graph_replays": 0, "eager_iterations": 1, "graphs_captured": 2, "stream_probes": 3, "side_candidate": 4, "train_fwd_events": 5, "flag_sync_iterations": 6, "spectral_route": 7, "f64_route": 8}
 ABI_VERSION = 7
 HN_VJP = {"continue": 1, "defer": 2}   # enum hn_vjp_flags (hn_step_vjp)
+# enum hn_route (hn_module_route): the kernel instance a sub-module call takes with the option 'module_mc'
+HN_ROUTE = {"direct": 0, "dc_asm": 1, "dc_valu": 2, "k_dc_mfma_s": 3, "k_dc_mfma_s_gen": 4, "k_dc_mfma_s_ring": 5, "k_dc_mfma_p_32": 6, "k_dc_mfma_p_16": 7,
+            "k_dc_mfma_64": 8, "k_dc_mfma_32": 9, "k_dc_mfma_16": 10, "k_dc_x16_bf16x3": 11, "k_dc_x16_fp16": 12, "k_dc_x16_bf16x2": 13, "down_64": 14,
+            "down_32": 15, "down_16": 16, "down_ring_64": 17, "down_ring_32": 18, "down_x16": 19, "up_2_11": 20, "up_ring": 21, "up_1_5": 22, "up_x16": 23}
+HN_ROUTE_OP = {"double_conv": 0, "down": 1, "up": 2, "double_conv_smooth": 3}   # hn_module_route's `op`
 
 # name -> (restype, argtypes); every symbol include/helmnet_hip.h declares
 SYMBOLS = {
@@ -68,6 +73,7 @@ SYMBOLS = {
     "hn_double_conv": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_float), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hn_conv8x8": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hn_out_conv": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_void_p, c_int, c_int, c_int, c_void_p]),
+    "hn_module_route": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
     "hn_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # absorbing media: the siblings above with k_sq_im behind k_sq

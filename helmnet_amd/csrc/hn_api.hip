@@ -89,20 +89,76 @@ struct Arena {
     void resolve(const float* dev) const { for (const auto& sl : slots) *sl.first = dev + sl.second; }
 };
 
-// pack host weights (PyTorch layout) with `fill`, upload them, run `go` on the stream, wait, free
+// One layer's record as the network's launchers take it, from the raw blob `blob`: the fp32 weights re-packed into `packed` (to be uploaded to `dev`) and every
+// other packing appended to the arena.  hn_load_weights walks the blob with these; hn_double_conv / hn_conv8x8 (HN_OPT_MODULE_MC) build one temporary layer.
+void pack_dc_layer(const float* blob, float* packed, const float* dev, const RawDc& r, int act_kind, Arena& fr, DcLayer& l) {
+    auto frag3 = [&](const float* w, int cin, Frag& f) {   // matrix-core A fragments of a 3x3 convolution: fp32, split-bf16, fp16
+        pack_frag_3x3(w, cin, fr.at(fr.add((size_t)cin * 3 * 64, &f.f32)));
+        pack_frag_3x3_split(w, cin, fr.at(fr.add(frag_3x3_split_floats(cin), &f.bf16)));
+        pack_frag_3x3_half(w, cin, fr.at(fr.add(frag_3x3_half_floats(cin), &f.f16)));
+    };
+    l = DcLayer{};
+    l.w = pack_dc(blob, packed, dev, r, act_kind);
+    const float *w1 = blob + r.w1, *w2 = blob + r.w2;
+    if (r.cm != kFeat || r.co != kFeat) {   // conv_state: fp32 fragments with the two channels in rows 0..3 of M
+        pack_frag_3x3_c2(w1, r.cin, fr.at(fr.add((size_t)r.cin * 3 * 64, &l.f1.f32)));
+        pack_frag_3x3_c2(w2, r.cm, fr.at(fr.add((size_t)r.cm * 3 * 64, &l.f2.f32)));
+        return;
+    }
+    static const float inc_scale_a[kInCh] = {1.f, 1.f, 1000.f, 1000.f, 1.f, 1.f};
+    pack_valu_q(w1, r.cin, fr.at(fr.add((size_t)r.cin * 72, &l.w.w1q)));   // conv1 for hn_dcv.hip; conv1 and conv2 for hn_dca.hip
+    pack_dca(w1, r.cin, r.cin == kInCh ? inc_scale_a : nullptr, fr.at(fr.add((size_t)r.cin * 72, &l.w.wa)));
+    pack_dca(w2, kFeat, nullptr, fr.at(fr.add((size_t)kFeat * 72, &l.w.wa2)));
+    frag3(w1, r.cin, l.f1);
+    frag3(w2, kFeat, l.f2);
+}
+void pack_k8_layer(const float* blob, float* packed, const float* dev, const RawK8& r, bool up, Arena& fr, K8Layer& l) {
+    l = K8Layer{};
+    l.w = pack_k8(blob, packed, dev, r, up);
+    l.f.bias = l.w.b;
+    const float* w = blob + r.w;
+    (up ? pack_frag_up : pack_frag_down)(w, fr.at(fr.add((size_t)kFeat * kFeat * 64, &l.f.f32)));
+    const size_t split = fr.add(k8_split_floats(), &l.f.bf16), half = fr.add(k8_half_floats(), &l.f.f16);   // (mixed-precision modes)
+    (up ? pack_frag_up_x16 : pack_frag_down_x16)(w, fr.at(split), fr.at(half));
+    if (!up) pack_frag_down2(w, fr.at(fr.add((size_t)kFeat * 2 * 10 * 64, &l.f_pair)));
+}
+
+// pack host weights (PyTorch layout) with `fill`, upload them -- and the arena `fr`, if `fill` has put a layer's other packings there --, run `go` on the
+// stream, wait, free
 template <typename Fill, typename Go>
-int with_temp_weights(hn_ctx* ctx, size_t n_floats, hipStream_t s, Fill fill, Go go) {
+int with_temp_weights(hn_ctx* ctx, size_t n_floats, hipStream_t s, Fill fill, Go go, Arena* fr = nullptr) {
     DeviceGuard guard(ctx);
-    float* dev = nullptr;
+    float *dev = nullptr, *fragdev = nullptr;
     HN_HIP(ctx, hipMalloc((void**)&dev, n_floats * sizeof(float)));
     std::vector<float> packed(n_floats);
     fill(packed, dev);
     int rc = HN_OK;
     if (hipMemcpy(dev, packed.data(), n_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, HN_ERR_HIP, "weight upload failed");
+    if (rc == HN_OK && fr != nullptr && !fr->host.empty()) {
+        const size_t bytes = fr->host.size() * sizeof(float);
+        if (hipMalloc((void**)&fragdev, bytes) != hipSuccess || hipMemcpy(fragdev, fr->host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(ctx, HN_ERR_HIP, "weight upload failed");
+        else fr->resolve(fragdev);
+    }
     if (rc == HN_OK) rc = go();
     (void)hipStreamSynchronize(s);   // the temporary weights must outlive the kernels
+    (void)hipFree(fragdev);
     (void)hipFree(dev);
     return rc;
+}
+
+// HN_OPT_MODULE_MC: do the sub-module entry points take the network's launchers?  (HN_PREC_FP32_VALU is the direct kernels in the network too)
+bool module_mc(const hn_ctx* ctx) { return ctx->opt_module_mc != 0 && ctx->precision != HN_PREC_FP32_VALU; }
+// hn_double_conv's input as launch_dc8 takes it: the kind whose channel groups make up cin, with the channel views of module_double_conv, every scale 1
+struct ModuleDc { DcKind kind; Src a, b, c; };
+ModuleDc module_dc_views(const float* x, int cin, int H, int W) {
+    const long plane = (long)H * W;
+    const Src none{nullptr, 0, 0, 1.f};
+    auto view = [&](int c0) { return Src{x + c0 * plane, cin * plane, plane, 1.f}; };
+    if (cin == kInCh) return {DcKind::Inc, view(0), view(2), view(4)};
+    if (cin == kFeat) return {DcKind::Bottleneck, view(0), none, none};
+    if (cin == kFeat + kState) return {DcKind::Signal, view(0), view(kFeat), none};
+    return {DcKind::Decoder, view(0), view(kFeat), none};
 }
 
 int check_ready(hn_ctx* ctx, int batch) {
@@ -420,6 +476,10 @@ int hn_set_option(hn_ctx* ctx, int option, int value) {
             if (value != ctx->opt_mc_stage) clear_step_graphs(ctx);
             ctx->opt_mc_stage = value;
             break;
+        case HN_OPT_MODULE_MC:
+            if (value < 0 || value > 1) return fail(ctx, HN_ERR_ARG, "HN_OPT_MODULE_MC must be 0 or 1 (got %d)", value);
+            ctx->opt_module_mc = value;
+            break;
         case HN_OPT_INC_SIGMA_MAP:
             if (value < 0 || value > 1) return fail(ctx, HN_ERR_ARG, "HN_OPT_INC_SIGMA_MAP must be 0 or 1 (got %d)", value);
             ctx->opt_inc_sigma_map = value;
@@ -552,38 +612,9 @@ int hn_load_weights(hn_ctx* ctx, const float* blob, size_t n_floats, int feature
     // other packings, built from the original OIHW tensors.  Each block's pointer is a named member of its layer's record; nothing reads the arena by position.
     std::vector<float> packed(L.total);
     Arena fr;
-    auto frag3 = [&](const float* w, int cin, Frag& f) {   // matrix-core A fragments of a 3x3 convolution: fp32, split-bf16, fp16
-        pack_frag_3x3(w, cin, fr.at(fr.add((size_t)cin * 3 * 64, &f.f32)));
-        pack_frag_3x3_split(w, cin, fr.at(fr.add(frag_3x3_split_floats(cin), &f.bf16)));
-        pack_frag_3x3_half(w, cin, fr.at(fr.add(frag_3x3_half_floats(cin), &f.f16)));
-    };
     for_each_layer(depth,
-        [&](int, int, int, const RawDc& r, DcLayer& l) {
-            l = DcLayer{};
-            l.w = pack_dc(blob, packed.data(), ctx->wdev, r, act_kind);
-            const float *w1 = blob + r.w1, *w2 = blob + r.w2;
-            if (r.cm != kFeat || r.co != kFeat) {   // conv_state: fp32 fragments with the two channels in rows 0..3 of M
-                pack_frag_3x3_c2(w1, r.cin, fr.at(fr.add((size_t)r.cin * 3 * 64, &l.f1.f32)));
-                pack_frag_3x3_c2(w2, r.cm, fr.at(fr.add((size_t)r.cm * 3 * 64, &l.f2.f32)));
-                return;
-            }
-            static const float inc_scale_a[kInCh] = {1.f, 1.f, 1000.f, 1000.f, 1.f, 1.f};
-            pack_valu_q(w1, r.cin, fr.at(fr.add((size_t)r.cin * 72, &l.w.w1q)));   // conv1 for hn_dcv.hip; conv1 and conv2 for hn_dca.hip
-            pack_dca(w1, r.cin, r.cin == kInCh ? inc_scale_a : nullptr, fr.at(fr.add((size_t)r.cin * 72, &l.w.wa)));
-            pack_dca(w2, kFeat, nullptr, fr.at(fr.add((size_t)kFeat * 72, &l.w.wa2)));
-            frag3(w1, r.cin, l.f1);
-            frag3(w2, kFeat, l.f2);
-        },
-        [&](bool up, const RawK8& r, K8Layer& l) {
-            l = K8Layer{};
-            l.w = pack_k8(blob, packed.data(), ctx->wdev, r, up);
-            l.f.bias = l.w.b;
-            const float* w = blob + r.w;
-            (up ? pack_frag_up : pack_frag_down)(w, fr.at(fr.add((size_t)kFeat * kFeat * 64, &l.f.f32)));
-            const size_t split = fr.add(k8_split_floats(), &l.f.bf16), half = fr.add(k8_half_floats(), &l.f.f16);   // (mixed-precision modes)
-            (up ? pack_frag_up_x16 : pack_frag_down_x16)(w, fr.at(split), fr.at(half));
-            if (!up) pack_frag_down2(w, fr.at(fr.add((size_t)kFeat * 2 * 10 * 64, &l.f_pair)));
-        },
+        [&](int, int, int, const RawDc& r, DcLayer& l) { pack_dc_layer(blob, packed.data(), ctx->wdev, r, act_kind, fr, l); },
+        [&](bool up, const RawK8& r, K8Layer& l) { pack_k8_layer(blob, packed.data(), ctx->wdev, r, up, fr, l); },
         L, *ctx);
     repack_oihw(blob + L.outc_w, packed.data() + L.outc_w, 2, kFeat, 1);  // outc [2][8] -> [8][2]
     packed[L.outc_b] = blob[L.outc_b]; packed[L.outc_b + 1] = blob[L.outc_b + 1];
@@ -831,6 +862,18 @@ int hn_double_conv(hn_ctx* ctx, const float* x, int cin, int cout, const float* 
     DcW dw;
     size_t n_floats = 0;
     const RawDc r = raw_dc(n_floats, cin, cout, cout);
+    if (module_mc(ctx) && cout == kFeat) {   // HN_OPT_MODULE_MC: a temporary layer on the network's dispatch
+        DcLayer l;
+        Arena fr;
+        const ModuleDc v = module_dc_views(x, cin, h, w);
+        return with_temp_weights(ctx, n_floats, (hipStream_t)stream,
+            [&](std::vector<float>& packed, float* dev) { pack_dc_layer(weights_host, packed.data(), dev, r, act_kind, fr, l); },
+            [&]() {
+                launch_dc8(ctx, v.kind, v.a, v.b, v.c, Dst{out, (long)kFeat * h * w, (long)h * w}, l, nullptr, h, w, batch, (hipStream_t)stream);
+                HN_HIP(ctx, hipGetLastError());
+                return (int)HN_OK;
+            }, &fr);
+    }
     return with_temp_weights(ctx, n_floats, (hipStream_t)stream,
         [&](std::vector<float>& packed, float* dev) { dw = pack_dc(weights_host, packed.data(), dev, r, act_kind); },
         [&]() { return module_double_conv(ctx, x, cin, cout, dw, out, batch, h, w, (hipStream_t)stream); });
@@ -843,9 +886,46 @@ int hn_conv8x8(hn_ctx* ctx, const float* x, const float* weights_host, int trans
     K8W kw;
     size_t n_floats = 0;
     const RawK8 r = raw_k8(n_floats);
+    if (module_mc(ctx)) {   // HN_OPT_MODULE_MC: a temporary layer on the network's dispatch
+        K8Layer l;
+        Arena fr;
+        const long pin = (long)h * w, po = transposed ? 4 * pin : (long)(h / 2) * (w / 2);
+        const Src in{x, kFeat * pin, pin, 1.f};
+        const Dst o{out, kFeat * po, po};
+        return with_temp_weights(ctx, n_floats, (hipStream_t)stream,
+            [&](std::vector<float>& packed, float* dev) { pack_k8_layer(weights_host, packed.data(), dev, r, transposed != 0, fr, l); },
+            [&]() {
+                if (transposed) launch_up(ctx, in, o, l.f, h, w, batch, (hipStream_t)stream, false);
+                else launch_down(ctx, in, o, l.f, h, w, batch, (hipStream_t)stream);
+                HN_HIP(ctx, hipGetLastError());
+                return (int)HN_OK;
+            }, &fr);
+    }
     return with_temp_weights(ctx, n_floats, (hipStream_t)stream,
         [&](std::vector<float>& packed, float* dev) { kw = pack_k8(weights_host, packed.data(), dev, r, transposed != 0); },
         [&]() { return module_conv8x8(ctx, x, kw, transposed != 0, out, batch, h, w, (hipStream_t)stream); });
+}
+
+int hn_module_route(hn_ctx* ctx, int op, int cin, int h, int w) {
+    if (!ctx) return HN_ERR_ARG;
+    if (op < 0 || op > 3) return fail(ctx, HN_ERR_ARG, "hn_module_route: op must be 0 (double_conv), 1 (down), 2 (up) or 3 (double_conv, smooth activation) (got %d)", op);
+    if (h < 1 || w < 1) return fail(ctx, HN_ERR_ARG, "hn_module_route: h, w must be positive");
+    const bool dc = op == 0 || op == 3;
+    if (dc ? !(cin == kInCh || cin == kFeat || cin == kFeat + kState || cin == 2 * kFeat) : cin != kFeat)
+        return fail(ctx, HN_ERR_ARG, "hn_module_route: no such layer with %d input channels", cin);
+    if (op == 1 && ((h | w) & 1)) return fail(ctx, HN_ERR_ARG, "hn_module_route: the stride-2 convolution needs even h, w (got %d, %d)", h, w);
+    if (!module_mc(ctx)) return HN_ROUTE_DIRECT;
+    // what the route functions read of a layer and its tensors: the activation class, whether the 16-bit twins exist (always, here), scales, alignment
+    const float* present = reinterpret_cast<const float*>(uintptr_t{4096});
+    if (!dc) {
+        const K8Frag f{present, present, present, present};
+        return op == 1 ? down_route(ctx, f, h, w) : up_route(ctx, f, h, w);
+    }
+    DcLayer l{};
+    l.w.act = op == 3 ? HN_ACT_GELU : HN_ACT_PRELU;
+    l.f1 = l.f2 = Frag{present, present, present};
+    const ModuleDc v = module_dc_views(present, cin, h, w);
+    return dc8_route(ctx, v.kind, v.a, v.b, v.c, l, nullptr, h, w);
 }
 
 int hn_out_conv(hn_ctx* ctx, const float* x, const float* weights_host, float* out, int batch, int h, int w, void* stream) {

@@ -331,6 +331,7 @@ struct hn_ctx {
     hn::SpecTables tab;
     hn::F64Fft* f64fft = nullptr;     // built / grown by the first float64 call on the FFT route that needs it (beside tab.f64_tab, which stays); freed by hn_set_domain, hn_set_domain_rect, hn_destroy
     int opt_mc_stage = 1;             // HN_OPT_MC_STAGE: 1 k_down_mfma_ring / k_up_mfma_ring / k_dc_mfma_s<8, 8, 0, 0, false, RING> (hn_mfma.hip) where k_down_mfma<., false> / k_up_mfma<., ., false> / k_dc_mfma_s<8, 8, 0, 0> ran, 0 those
+    int opt_module_mc = 0;            // HN_OPT_MODULE_MC: 1 hn_double_conv (cout 8) / hn_conv8x8 through launch_dc8 / launch_down / launch_up on temporary fragments, 0 the direct kernels of hn_unet.hip
     int opt_f64_fft = 0;              // HN_OPT_F64_FFT: 0 the dense kernel k_helm_f64, 1 the two line passes of hn_f64_fft.hip; read by every float64 call
     int f64_route = 0;                // HN_CNT_F64_ROUTE: 0 no float64 call on this domain yet, 1 the last one ran dense, 2 by FFT
     hn::RectDomain* rect = nullptr;   // non-null: the domain is rectangular (hn_set_domain_rect, h != w) and tab is empty
@@ -652,6 +653,11 @@ enum class DcKind { Inc, Signal, Bottleneck, Decoder };
 // lds_pad: dynamic LDS of the launch on hn_dca.hip: 7168 (3 blocks per CU) while the side stream's gate kernel is resident, else 0
 struct FinalEpi { float* d_out; float* wf_out; const float* wf_in; int lds_pad; };
 void launch_dc8(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcLayer& l, const FinalEpi* fin, int H, int W, int batch, hipStream_t s);
+// The instance (enum hn_route) launch_dc8 / launch_down / launch_up would run: pure host functions of the context's precision mode and options, the layer's
+// activation and twins, the views' scales and alignment and the shape.  The launchers switch on them; hn_module_route reports them.
+int dc8_route(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, const DcLayer& l, const FinalEpi* fin, int H, int W);
+int down_route(const hn_ctx* ctx, const K8Frag& w, int Hin, int Win);
+int up_route(const hn_ctx* ctx, const K8Frag& w, int Hin, int Win);
 // training forward: the fused matrix-core DoubleConv with the pre-activation mid tensor stored to `z` ([B, 8, H, W]); fragments as pack_frag_3x3
 bool dc8_tape_applies(int H, int W);
 // Backward-data pass of an 8-channel DoubleConv (cin -> 8 -> 8) on the fp32 matrix core (hn_mfma.hip, k_dc_bwd_mfma_p): g_z = conv2^T(g) * act'(z),

@@ -2798,68 +2798,63 @@ __global__ __launch_bounds__(256, 2) void k_up_x16(Src in, Dst out, const void* 
     sync_hook_end(hook);
 }
 
-template <int CA, int CB, int CC, int EPI>
-void launch_dc_mfma(int x16, Src a, Src b, Src c, Dst out, const McW& w, const McEpi& e, int H, int W, int batch, hipStream_t s, bool ring = false) {
-    const bool even = (W & 1) == 0;
-    const bool scaled = a.scale != 1.f || b.scale != 1.f || c.scale != 1.f;
-    const bool off32 = 8.0 * (double)H * (double)W * 4.0 < 4.0e9;  // the strip kernel addresses a sample's planes with 32-bit byte offsets
-    if (w.act > HN_ACT_LEAKYRELU) {   // smooth activations: fp32 instances with the general epilogue (every precision mode)
-        if (W >= 128 && even && off32 && (!scaled || ScCfg<CA, CB, CC>::SCALED)) {
-            hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI, true>), dim3(cdiv_(W, 64), cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
-        } else if (even && W > 16) {
-            const int tx = cdiv_(W, 32), ty = cdiv_(H, 8), nt = tx * ty * batch;
-            hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 32, true>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt);
-        } else if (even) {
-            const int tx = cdiv_(W, 16), ty = cdiv_(H, 8), nt = tx * ty * batch;
-            hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 16, true>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt);
-        } else if (W > 32) {
-            hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 64, EPI, true>), dim3(cdiv_(W, 64), cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
-        } else if (W > 16) {
-            hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 32, EPI, true>), dim3(1, cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
-        } else {
-            hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 16, EPI, true>), dim3(1, cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
-        }
-        return;
-    }
-    if (x16 && W >= 128 && even && off32 && w.a1s != nullptr && (!scaled || B3Cfg<CA, CB, CC, 3>::SCALED)) {
-        if (x16 == 1) {   // the 3-part split in 8-row tiles (65 KB per 16-row tile -> 39 KB, 3 blocks per CU: +4 % it/s)
-            const dim3 g8(cdiv_(W, 64), cdiv_(H, 8), batch);
-            hipLaunchKernelGGL((k_dc_x16<SplitBf16, CA, CB, CC, EPI, 8>), g8, dim3(256), 0, s, a, b, c, out, w, e, H, W);
-            return;
-        }
-        const dim3 g(cdiv_(W, 64), cdiv_(H, 16), batch);
-        if (x16 == 2) hipLaunchKernelGGL((k_dc_x16<HalfF16, CA, CB, CC, EPI>), g, dim3(256), 0, s, a, b, c, out, w, e, H, W);
-        else hipLaunchKernelGGL((k_dc_x16<SplitBf16x2, CA, CB, CC, EPI>), g, dim3(256), 0, s, a, b, c, out, w, e, H, W);
-        return;
-    }
 #ifndef HN_STRIP_MIN_W
 #define HN_STRIP_MIN_W 128   // narrowest level on the strip kernel (experiment: tools/build_variant.sh ... -DHN_STRIP_MIN_W=256)
 #endif
-    if (W >= HN_STRIP_MIN_W && even && off32 && (!scaled || ScCfg<CA, CB, CC>::SCALED)) {
-        const dim3 g(cdiv_(W, 64), cdiv_(H, 16), batch);
-        // HN_OPT_MC_STAGE: conv1's staging behind the MFMAs, for the 16-channel decoder only ([measured, profiles/mc_stage_ablation.txt] 30.0 -> 28.7 us at
-        // 128^2 x 32; the 10-channel conv_signal instance built the same way measured 23.3 against 23.1 and stays on the kernel as it was)
-        if constexpr (!ScCfg<CA, CB, CC>::SCALED && EPI == 0 && CA == kFeat && CB == kFeat) {
-            if (ring) {
-                hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI, false, true>), g, dim3(256), 0, s, a, b, c, out, w, e, H, W);
-                return;
-            }
+// The instance (enum hn_route) launch_dc_mfma runs: a pure function of the mode, the activation, the input scales and the shape.
+//   smooth activations: fp32 instances with the general epilogue (every precision mode);
+//   the 16-bit modes' strips: the 3-part split in 8-row tiles (65 KB per 16-row tile -> 39 KB, 3 blocks per CU: +4 % it/s);
+//   HN_OPT_MC_STAGE (ring): conv1's staging behind the MFMAs, for the 16-channel decoder only ([measured, profiles/mc_stage_ablation.txt] 30.0 -> 28.7 us at
+//     128^2 x 32; the 10-channel conv_signal instance built the same way measured 23.3 against 23.1 and stays on the kernel as it was);
+//   small levels are latency-bound: whole input tile staged at once (one barrier), small 8 x 32 tiles so that even a 32^2 image spreads over many CUs;
+//   odd widths (e.g. the 3 x 3 bottleneck of a 48^2 domain): the any-shape kernel
+template <int CA, int CB, int CC, int EPI>
+int dc_mfma_route(int x16, Src a, Src b, Src c, const McW& w, int H, int W, bool ring) {
+    const bool even = (W & 1) == 0;
+    const bool scaled = a.scale != 1.f || b.scale != 1.f || c.scale != 1.f;
+    const bool off32 = 8.0 * (double)H * (double)W * 4.0 < 4.0e9;  // the strip kernel addresses a sample's planes with 32-bit byte offsets
+    const bool gen = w.act > HN_ACT_LEAKYRELU;
+    if (!gen && x16 && W >= 128 && even && off32 && w.a1s != nullptr && (!scaled || B3Cfg<CA, CB, CC, 3>::SCALED))
+        return x16 == 1 ? HN_ROUTE_K_DC_X16_BF16X3 : x16 == 2 ? HN_ROUTE_K_DC_X16_FP16 : HN_ROUTE_K_DC_X16_BF16X2;
+    if (W >= (gen ? 128 : HN_STRIP_MIN_W) && even && off32 && (!scaled || ScCfg<CA, CB, CC>::SCALED)) {
+        if (gen) return HN_ROUTE_K_DC_MFMA_S_GEN;
+        if (ring && !ScCfg<CA, CB, CC>::SCALED && EPI == 0 && CA == kFeat && CB == kFeat) return HN_ROUTE_K_DC_MFMA_S_RING;
+        return HN_ROUTE_K_DC_MFMA_S;
+    }
+    if (even) return W > 16 ? HN_ROUTE_K_DC_MFMA_P_32 : HN_ROUTE_K_DC_MFMA_P_16;
+    return W > 32 ? HN_ROUTE_K_DC_MFMA_64 : W > 16 ? HN_ROUTE_K_DC_MFMA_32 : HN_ROUTE_K_DC_MFMA_16;
+}
+
+template <int CA, int CB, int CC, int EPI>
+void launch_dc_mfma(int x16, Src a, Src b, Src c, Dst out, const McW& w, const McEpi& e, int H, int W, int batch, hipStream_t s, bool ring = false) {
+    const int route = dc_mfma_route<CA, CB, CC, EPI>(x16, a, b, c, w, H, W, ring);
+    const dim3 strip(cdiv_(W, 64), cdiv_(H, 16), batch), strip8(cdiv_(W, 64), cdiv_(H, 8), batch), rows(1, cdiv_(H, 16), batch);
+    const int tx = cdiv_(W, route == HN_ROUTE_K_DC_MFMA_P_16 ? 16 : 32), ty = cdiv_(H, 8), nt = tx * ty * batch;   // (k_dc_mfma_p)
+    if (w.act > HN_ACT_LEAKYRELU) {
+        switch (route) {
+            case HN_ROUTE_K_DC_MFMA_S_GEN: hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI, true>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+            case HN_ROUTE_K_DC_MFMA_P_32: hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 32, true>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt); break;
+            case HN_ROUTE_K_DC_MFMA_P_16: hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 16, true>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt); break;
+            case HN_ROUTE_K_DC_MFMA_64: hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 64, EPI, true>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+            case HN_ROUTE_K_DC_MFMA_32: hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 32, EPI, true>), rows, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+            default: hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 16, EPI, true>), rows, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
         }
-        hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI>), g, dim3(256), 0, s, a, b, c, out, w, e, H, W);
-    } else if (even && W > 16) {
-        // small levels are latency-bound: whole input tile staged at once (one barrier), small 8 x 32
-        // tiles so that even a 32^2 image spreads over many CUs
-        const int tx = cdiv_(W, 32), ty = cdiv_(H, 8), nt = tx * ty * batch;
-        hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 32>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt);
-    } else if (even) {
-        const int tx = cdiv_(W, 16), ty = cdiv_(H, 8), nt = tx * ty * batch;
-        hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 16>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt);
-    } else if (W > 32) {   // odd widths (e.g. the 3 x 3 bottleneck of a 48^2 domain): the any-shape kernel
-        hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 64, EPI>), dim3(cdiv_(W, 64), cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
-    } else if (W > 16) {
-        hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 32, EPI>), dim3(1, cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
-    } else {
-        hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 16, EPI>), dim3(1, cdiv_(H, 16), batch), dim3(256), 0, s, a, b, c, out, w, e, H, W);
+        return;
+    }
+    switch (route) {
+        case HN_ROUTE_K_DC_X16_BF16X3: hipLaunchKernelGGL((k_dc_x16<SplitBf16, CA, CB, CC, EPI, 8>), strip8, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+        case HN_ROUTE_K_DC_X16_FP16: hipLaunchKernelGGL((k_dc_x16<HalfF16, CA, CB, CC, EPI>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+        case HN_ROUTE_K_DC_X16_BF16X2: hipLaunchKernelGGL((k_dc_x16<SplitBf16x2, CA, CB, CC, EPI>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+        case HN_ROUTE_K_DC_MFMA_S_RING:
+            if constexpr (!ScCfg<CA, CB, CC>::SCALED && EPI == 0 && CA == kFeat && CB == kFeat)
+                hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI, false, true>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W);
+            break;
+        case HN_ROUTE_K_DC_MFMA_S: hipLaunchKernelGGL((k_dc_mfma_s<CA, CB, CC, EPI>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+        case HN_ROUTE_K_DC_MFMA_P_32: hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 32>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt); break;
+        case HN_ROUTE_K_DC_MFMA_P_16: hipLaunchKernelGGL((k_dc_mfma_p<CA, CB, CC, EPI, 8, 16>), dim3(nt), dim3(256), 0, s, a, b, c, out, w, e, H, W, tx, ty, nt); break;
+        case HN_ROUTE_K_DC_MFMA_64: hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 64, EPI>), strip, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+        case HN_ROUTE_K_DC_MFMA_32: hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 32, EPI>), rows, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
+        default: hipLaunchKernelGGL((k_dc_mfma<CA, CB, CC, 16, EPI>), rows, dim3(256), 0, s, a, b, c, out, w, e, H, W); break;
     }
 }
 
@@ -3017,15 +3012,40 @@ void pack_frag_up(const float* w, float* dst) {
                 }
 }
 
+static inline McW dc8_mcw(const DcLayer& l) {
+    const DcW& w = l.w;
+    return McW{l.f1.f32, w.b1, w.slope, l.f2.f32, w.b2, l.f1.bf16, l.f2.bf16, l.f1.f16, l.f2.f16, w.act};
+}
+static inline int dc8_x16(const hn_ctx* ctx) { return (ctx->precision >= HN_PREC_BF16X3 && ctx->precision <= HN_PREC_BF16X2) ? ctx->precision : 0; }
+
+// The instance launch_dc8 runs (enum hn_route): hn_dca.hip, hn_dcv.hip or what launch_dc_mfma picks for the kind's channel groups
+int dc8_route(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, const DcLayer& l, const FinalEpi* fin, int H, int W) {
+    if (dc_asm_applies(ctx, l.w.act, a, b, c, kind, H, W)) return HN_ROUTE_DC_ASM;
+    if (dc_valu_applies(ctx, l.w.act, a, b, c, kind, H, W)) return HN_ROUTE_DC_VALU;
+    const McW mw = dc8_mcw(l);
+    const int x16 = dc8_x16(ctx);
+    const bool ring = ctx->opt_mc_stage != 0;
+    switch (kind) {
+        case DcKind::Inc: return dc_mfma_route<2, 2, 2, 0>(x16, a, b, c, mw, H, W, ring);
+        case DcKind::Signal: return dc_mfma_route<kFeat, kState, 0, 0>(x16, a, b, c, mw, H, W, ring);
+        case DcKind::Bottleneck: return dc_mfma_route<kFeat, 0, 0, 0>(x16, a, b, c, mw, H, W, ring);
+        case DcKind::Decoder: break;
+    }
+    return fin ? dc_mfma_route<kFeat, kFeat, 0, 1>(x16, a, b, c, mw, H, W, ring) : dc_mfma_route<kFeat, kFeat, 0, 0>(x16, a, b, c, mw, H, W, ring);
+}
+
 void launch_dc8(const hn_ctx* ctx, DcKind kind, Src a, Src b, Src c, Dst out, const DcLayer& l, const FinalEpi* fin, int H, int W, int batch, hipStream_t s) {
     const DcW& w = l.w;
-    if (dc_asm_applies(ctx, w.act, a, b, c, kind, H, W)) return launch_dc_asm(ctx, kind, a, b, c, out, w, fin, H, W, batch, s);
-    if (dc_valu_applies(ctx, w.act, a, b, c, kind, H, W)) return launch_dc_valu(ctx, kind, a, b, c, out, w, fin, H, W, batch, s);
-    const McW mw{l.f1.f32, w.b1, w.slope, l.f2.f32, w.b2, l.f1.bf16, l.f2.bf16, l.f1.f16, l.f2.f16, w.act};
+    switch (dc8_route(ctx, kind, a, b, c, l, fin, H, W)) {
+        case HN_ROUTE_DC_ASM: return launch_dc_asm(ctx, kind, a, b, c, out, w, fin, H, W, batch, s);
+        case HN_ROUTE_DC_VALU: return launch_dc_valu(ctx, kind, a, b, c, out, w, fin, H, W, batch, s);
+        default: break;   // the matrix core: launch_dc_mfma switches on the same route
+    }
+    const McW mw = dc8_mcw(l);
     const FinalEpi f = fin ? *fin : FinalEpi{};
     McEpi e{ctx->outc_w, ctx->outc_b, f.d_out, f.wf_out, ctx->f_dec0c, ctx->dec0c_b};
     e.wf_in = f.wf_in;
-    const int x16 = (ctx->precision >= HN_PREC_BF16X3 && ctx->precision <= HN_PREC_BF16X2) ? ctx->precision : 0;
+    const int x16 = dc8_x16(ctx);
     const bool ring = ctx->opt_mc_stage != 0;
     switch (kind) {
         case DcKind::Inc: launch_dc_mfma<2, 2, 2, 0>(x16, a, b, c, out, mw, e, H, W, batch, s, ring); break;
@@ -3098,64 +3118,72 @@ int launch_dc8_bwd_aux(hn_ctx* ctx, const McBwd& a, const McBwdAux& x, int H, in
     return HN_OK;
 }
 
+// The instance launch_down runs (enum hn_route).  Mixed-precision modes: levels 0 and 1 on the 16-bit matrix core; the 3-part split stays on the fp32
+// kernel here (its 71 KB window and 288 MFMAs per wave measured 55 us against 48 us).  fp32: tile shape by level size, 64x16 outputs per block for
+// the big levels, 32x16 at 64 < Wout... (more, shorter blocks when there are few tiles: 17 us instead of 26 us at Wout = 64), all channels at once for
+// the small ones (HN_OPT_MC_STAGE: the same tiles with the staging behind the MFMAs, k_down_mfma_ring)
+int down_route(const hn_ctx* ctx, const K8Frag& w, int Hin, int Win) {
+    (void)Hin;
+    const int Wout = Win / 2;
+    const int mode = w.f16 != nullptr ? ctx->precision : HN_PREC_FP32;   // (no twins: the caller's own fp32 fragments, hn_train.hip)
+    if ((mode == HN_PREC_FP16 || mode == HN_PREC_BF16X2) && Wout >= 64) return HN_ROUTE_DOWN_X16;
+    const bool ring = ctx->opt_mc_stage != 0;
+    if (Wout > 64) return ring ? HN_ROUTE_DOWN_RING_64 : HN_ROUTE_DOWN_64;
+    if (Wout > 32) return ring ? HN_ROUTE_DOWN_RING_32 : HN_ROUTE_DOWN_32;
+    return HN_ROUTE_DOWN_16;
+}
+
 void launch_down(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s, SyncHook hook) {
     const int Wout = Win / 2, Hout = Hin / 2;
     const float *frag = w.f32, *bias = w.bias;
-    const int mode = w.f16 != nullptr ? ctx->precision : HN_PREC_FP32;   // (no twins: the caller's own fp32 fragments, hn_train.hip)
-    // mixed-precision modes: levels 0 and 1 on the 16-bit matrix core; the 3-part split stays on the fp32 kernel
-    // here (its 71 KB window and 288 MFMAs per wave measured 55 us against 48 us)
-    if ((mode == HN_PREC_FP16 || mode == HN_PREC_BF16X2) && Wout >= 64) {
-        const dim3 g(cdiv_(Wout, 16), cdiv_(Hout, 16), batch);
-        if (mode == 3) hipLaunchKernelGGL((k_down_x16<SplitBf16x2>), g, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win);
-        else hipLaunchKernelGGL((k_down_x16<HalfF16>), g, dim3(256), 0, s, in, out, w.f16, bias, Hin, Win);
-        return;
+    const dim3 g16(cdiv_(Wout, 16), cdiv_(Hout, 16), batch), g32(cdiv_(Wout, 32), cdiv_(Hout, 16), batch), g64(cdiv_(Wout, 64), cdiv_(Hout, 16), batch);
+    switch (down_route(ctx, w, Hin, Win)) {
+        case HN_ROUTE_DOWN_X16:
+            if (ctx->precision == HN_PREC_BF16X2) hipLaunchKernelGGL((k_down_x16<SplitBf16x2>), g16, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win);
+            else hipLaunchKernelGGL((k_down_x16<HalfF16>), g16, dim3(256), 0, s, in, out, w.f16, bias, Hin, Win);
+            break;
+        case HN_ROUTE_DOWN_RING_64: hipLaunchKernelGGL((k_down_mfma_ring<4>), g64, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook); break;
+        case HN_ROUTE_DOWN_64: hipLaunchKernelGGL((k_down_mfma<4, false>), g64, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook); break;
+        case HN_ROUTE_DOWN_RING_32: hipLaunchKernelGGL((k_down_mfma_ring<2>), g32, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook); break;
+        case HN_ROUTE_DOWN_32: hipLaunchKernelGGL((k_down_mfma<2, false>), g32, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook); break;
+        default: hipLaunchKernelGGL((k_down_mfma<1, true>), g16, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook); break;
     }
-    // tile shape by level size: 64x16 outputs per block for the big levels, 32x16 at 64 < Wout... (more, shorter blocks
-    // when there are few tiles: 17 us instead of 26 us at Wout = 64), all channels at once for the small ones
-    // (HN_OPT_MC_STAGE: the same tiles with the staging behind the MFMAs, k_down_mfma_ring)
-    const bool ring = ctx->opt_mc_stage != 0;
-    if (Wout > 64) {
-        const dim3 g(cdiv_(Wout, 64), cdiv_(Hout, 16), batch);
-        if (ring) hipLaunchKernelGGL((k_down_mfma_ring<4>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-        else hipLaunchKernelGGL((k_down_mfma<4, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-    } else if (Wout > 32) {
-        const dim3 g(cdiv_(Wout, 32), cdiv_(Hout, 16), batch);
-        if (ring) hipLaunchKernelGGL((k_down_mfma_ring<2>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-        else hipLaunchKernelGGL((k_down_mfma<2, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-    }
-    else {
-        const dim3 g(cdiv_(Wout, 16), cdiv_(Hout, 16), batch);
-        hipLaunchKernelGGL((k_down_mfma<1, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-    }
+}
+
+// The instance launch_up runs (enum hn_route).  Window rows -1 .. Hin-1.  At and below 64 input columns: the all-channels-at-once kernel (few tiles,
+// latency-bound).  Above: 22 window rows per block: the Hin + 1 = 129 (257) window rows of a 128^2 (256^2) input split into 6 (12)
+// row blocks with 2 % padding instead of 9 x 16 with 10 %, and 4 x 6 x 32 = 768 blocks are exactly one
+// round of 3 resident blocks per CU at 256^2 x 32 (16-row blocks: 1152 = 1.5 rounds); HN_OPT_MC_STAGE: the same tiles with the staging behind the MFMAs
+int up_route(const hn_ctx* ctx, const K8Frag& w, int Hin, int Win) {
+    (void)Hin;
+    const int mode = w.f16 != nullptr ? ctx->precision : HN_PREC_FP32;   // (as down_route)
+    if (mode >= HN_PREC_BF16X3 && mode <= HN_PREC_BF16X2 && Win >= 64) return HN_ROUTE_UP_X16;
+    constexpr int up_small = 64;
+    if (Win > up_small) return ctx->opt_mc_stage != 0 ? HN_ROUTE_UP_RING : HN_ROUTE_UP_2_11;
+    return HN_ROUTE_UP_1_5;
 }
 
 void launch_up(const hn_ctx* ctx, Src in, Dst out, const K8Frag& w, int Hin, int Win, int batch, hipStream_t s, bool accumulate, SyncHook hook) {
     const float *frag = w.f32, *bias = w.bias;
-    const int mode = w.f16 != nullptr ? ctx->precision : HN_PREC_FP32;   // (as launch_down)
-    // window rows -1 .. Hin-1
-    if (mode >= HN_PREC_BF16X3 && mode <= HN_PREC_BF16X2 && Win >= 64) {
-        const dim3 g(cdiv_(Win, 16), cdiv_(Hin + 1, 20), batch);
-        if (mode == 1) hipLaunchKernelGGL((k_up_x16<SplitBf16>), g, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win, hook);
-        else if (mode == 3) hipLaunchKernelGGL((k_up_x16<SplitBf16x2>), g, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win, hook);
-        else hipLaunchKernelGGL((k_up_x16<HalfF16>), g, dim3(256), 0, s, in, out, w.f16, bias, Hin, Win, hook);
-        return;
-    }
-    constexpr int up_small = 64;  // at and below: the all-channels-at-once kernel (few tiles, latency-bound)
-    // 22 window rows per block: the Hin + 1 = 129 (257) window rows of a 128^2 (256^2) input split into 6 (12)
-    // row blocks with 2 % padding instead of 9 x 16 with 10 %, and 4 x 6 x 32 = 768 blocks are exactly one
-    // round of 3 resident blocks per CU at 256^2 x 32 (16-row blocks: 1152 = 1.5 rounds)
-    if (Win > up_small) {
-        const dim3 g(cdiv_(Win, 32), cdiv_(Hin + 1, 22), batch);
-        if (ctx->opt_mc_stage != 0) {   // HN_OPT_MC_STAGE: the same tiles with the staging behind the MFMAs
-            if (accumulate) hipLaunchKernelGGL((k_up_mfma_ring<2, 11, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-            else hipLaunchKernelGGL((k_up_mfma_ring<2, 11, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-        }
-        else if (accumulate) hipLaunchKernelGGL((k_up_mfma<2, 11, false, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-        else hipLaunchKernelGGL((k_up_mfma<2, 11, false>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-    } else {
-        const dim3 g(cdiv_(Win, 16), cdiv_(Hin + 1, 20), batch);
-        if (accumulate) hipLaunchKernelGGL((k_up_mfma<1, 5, true, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
-        else hipLaunchKernelGGL((k_up_mfma<1, 5, true>), g, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+    const dim3 g16(cdiv_(Win, 16), cdiv_(Hin + 1, 20), batch), g32(cdiv_(Win, 32), cdiv_(Hin + 1, 22), batch);
+    switch (up_route(ctx, w, Hin, Win)) {
+        case HN_ROUTE_UP_X16:
+            if (ctx->precision == HN_PREC_BF16X3) hipLaunchKernelGGL((k_up_x16<SplitBf16>), g16, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win, hook);
+            else if (ctx->precision == HN_PREC_BF16X2) hipLaunchKernelGGL((k_up_x16<SplitBf16x2>), g16, dim3(256), 0, s, in, out, w.bf16, bias, Hin, Win, hook);
+            else hipLaunchKernelGGL((k_up_x16<HalfF16>), g16, dim3(256), 0, s, in, out, w.f16, bias, Hin, Win, hook);
+            break;
+        case HN_ROUTE_UP_RING:
+            if (accumulate) hipLaunchKernelGGL((k_up_mfma_ring<2, 11, true>), g32, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            else hipLaunchKernelGGL((k_up_mfma_ring<2, 11, false>), g32, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            break;
+        case HN_ROUTE_UP_2_11:
+            if (accumulate) hipLaunchKernelGGL((k_up_mfma<2, 11, false, true>), g32, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            else hipLaunchKernelGGL((k_up_mfma<2, 11, false>), g32, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            break;
+        default:
+            if (accumulate) hipLaunchKernelGGL((k_up_mfma<1, 5, true, true>), g16, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            else hipLaunchKernelGGL((k_up_mfma<1, 5, true>), g16, dim3(256), 0, s, in, out, frag, bias, Hin, Win, hook);
+            break;
     }
 }
 

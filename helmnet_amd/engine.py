@@ -238,7 +238,9 @@ class Engine:
     def set_option(self, name: str, value: int):
         """Library tuning knobs (enum hn_option of include/helmnet_hip.h): 'lanes' 1..8, 'side_stream' 0..3, 'deep' 0/1, 'spectral_pfa' 0/1,
         'spectral_radix16' 0..2, 'dc_valu' 0..4, 'spectral_cols' 0..3, 'train_fused', 'train_overlap', 'mc_stage' 0/1 (the matrix-core 8x8 / strip kernels with
-        the input staging behind the MFMAs; bit-identical); laboratory knobs (HN_EXP_*): 'graph' 0, 1 or an even
+        the input staging behind the MFMAs; bit-identical), 'module_mc' 0/1 (default 0; 1: double_conv with 8 output channels and conv8x8 run on the
+        network's own dispatch -- the matrix-core / vector-pipe kernels the precision mode, 'dc_valu' and 'mc_stage' select -- instead of the direct
+        kernels; module_route names the instance); laboratory knobs (HN_EXP_*): 'graph' 0, 1 or an even
         number <= 64 of iterations per graph, 'train_lanes' 1/2 (hn_train_grad: the halves of the batch as two chains of launches on two streams).
         'spectral_pfa' and 'spectral_mixed' 0/1 (FFT for every other size P * 2^k, P odd; default 0) are read when the spectral tables are built:
         changing one re-builds them; counter('spectral_route') tells which kernels the domain runs on (1 power of two, 2 prime-factor, 3 dense,
@@ -531,6 +533,13 @@ class Engine:
                                      b, h, w, self._stream())
         _lib.check(rc, self.ctx, "hn_conv8x8")
         return out
+
+    def module_route(self, op: str, cin: int, h: int, w: int) -> str:
+        """The kernel instance (enum hn_route, by its name in _lib.HN_ROUTE) a double_conv ('double_conv'; 'double_conv_smooth' for celu .. softplus) or
+        conv8x8 ('down', 'up') call on an h x w input would launch now: hn_module_route, a pure function of the precision mode, the options and the shape."""
+        code = int(self.lib.hn_module_route(self.ctx, _lib.HN_ROUTE_OP[op], int(cin), int(h), int(w)))
+        _lib.check(min(code, 0), self.ctx, "hn_module_route")
+        return {v: k for k, v in _lib.HN_ROUTE.items()}[code]
 
     def out_conv(self, x, weight, bias) -> torch.Tensor:
         """OutConv.forward (architectures.py:57-60): Conv2d(8, 2, 1)."""

@@ -156,6 +156,10 @@ enum hn_option {
                               * one barrier per chunk, no register copies, a prologue that loads before it plans; hn_mfma.hip: k_down_mfma_ring,
                               * k_up_mfma_ring, k_dc_mfma_s<.., RING>); 0: the kernels as they were.  The same MFMAs in the same order on every
                               * accumulator: bit-identical.  [measured, profiles/mc_stage_ab.txt] +2.1 % it/s at 256^2 x 32, +1.9 % at 512^2 x 16 */
+    HN_OPT_MODULE_MC = 20,   /* 0/1 (default 0): hn_double_conv for (6,8), (8,8), (10,8), (16,8) and hn_conv8x8 run on the NETWORK's dispatch -- launch_dc8 /
+                              * launch_down / launch_up with fragments packed from the call's weights as hn_load_weights packs a layer's -- instead of the direct
+                              * kernels, so the precision mode, HN_OPT_DC_VALU and HN_OPT_MC_STAGE pick the kernel as they do in the network, at any H x W
+                              * (see the sub-module entry points and hn_module_route).  0: every bit and every launch as before             */
     HN_OPT_HIST_COPY = 15,   /* 0 (default): hn_step's residual / wavefield histories are written in place of the copies (see hn_step); 1: every
                               * iteration works in the caller's wf / res and copies them into the history slots (A/B; bit-identical)       */
     HN_OPT_INC_SIGMA_MAP = 16, /* 0/1 (default 1): the sigma maps are constants of the domain and two of the six input channels of every UNet evaluation the solver
@@ -491,9 +495,47 @@ int hn_step_f64(hn_ctx* ctx, double* wf, double* res, double* states, const doub
  *                   weight [8,8,8,8] (out, in, kh, kw), bias [8];  transposed = 1: ConvTranspose2d(8, 8, 8, stride 2, padding 3),
  *                   x[B,8,H,W] -> out[B,8,2H,2W], weight [8,8,8,8] (in, out, kh, kw), bias [8]
  *   hn_out_conv     Conv2d(8, 2, 1): x[B,8,H,W] -> out[B,2,H,W], weights = weight [2,8], bias [2]
- * Always the direct fp32 kernels (those of HN_PREC_FP32_VALU), whatever the context's precision mode; any H, W >= 1.  Refusals enqueue nothing and leave
+ * By default (HN_OPT_MODULE_MC 0) always the direct fp32 kernels (those of HN_PREC_FP32_VALU), whatever the context's precision mode; any H, W >= 1.  Refusals enqueue nothing and leave
  * `out` untouched: HN_ERR_UNSUPPORTED for another (cin, cout), an act_kind outside enum hn_act and an odd H or W of the stride-2 form; HN_ERR_ARG for a
- * NULL pointer or a non-positive batch, H or W. */
+ * NULL pointer or a non-positive batch, H or W.
+ * HN_OPT_MODULE_MC 1: hn_double_conv with cout = 8 and hn_conv8x8 take the network's own dispatch instead, on temporary fragments packed from the call's
+ * weights exactly as hn_load_weights packs a layer's (they live until the stream has been synchronised, like the direct path's weights): launch_dc8 as
+ * the input layer (6), the bottleneck (8), conv_signal (10) or a decoder (16) with every input scale 1, launch_down / launch_up without accumulation.  The
+ * precision mode, HN_OPT_DC_VALU and HN_OPT_MC_STAGE then select the kernel as in the network (hn_module_route names it); HN_PREC_FP32_VALU and (10,2)
+ * keep the direct kernel (k_conv_state reads its weights as offsets into the loaded blob).  The input-layer instance of hn_dca.hip needs the
+ * 1e3 scale on the residual channels and is NOT reachable this way: with HN_OPT_DC_VALU 3 / 4 a (6,8) call runs on hn_dcv.hip.  hn_dca.hip also needs a
+ * context with weights loaded (its zero page).  Refusals and their messages are the same under either value. */
+/* Kernel instances of that dispatch (hn_mfma.hip unless named otherwise), as hn_module_route reports them */
+enum hn_route {
+    HN_ROUTE_DIRECT = 0,            /* the direct fp32 kernels of hn_unet.hip: HN_OPT_MODULE_MC 0, HN_PREC_FP32_VALU, (10,2) */
+    HN_ROUTE_DC_ASM = 1,            /* hn_dca.hip (HN_OPT_DC_VALU 3 / 4: W >= 256, W % 4 == 0, 16-byte aligned planes, piecewise-linear activation) */
+    HN_ROUTE_DC_VALU = 2,           /* hn_dcv.hip (HN_OPT_DC_VALU 1 .. 4: W >= 256, even W) */
+    HN_ROUTE_K_DC_MFMA_S = 3,       /* k_dc_mfma_s: 16 x 64 strips, even W >= 128 */
+    HN_ROUTE_K_DC_MFMA_S_GEN = 4,   /*   ... with the general epilogue (smooth activations, every precision mode) */
+    HN_ROUTE_K_DC_MFMA_S_RING = 5,  /*   ... the 16-channel decoder with HN_OPT_MC_STAGE 1 */
+    HN_ROUTE_K_DC_MFMA_P_32 = 6,    /* k_dc_mfma_p<8, 32>: even 16 < W < 128 (the smooth activations' GEN instance has the same code, as below) */
+    HN_ROUTE_K_DC_MFMA_P_16 = 7,    /* k_dc_mfma_p<8, 16>: even W <= 16 */
+    HN_ROUTE_K_DC_MFMA_64 = 8,      /* k_dc_mfma<64>: odd W > 32, 16-row tiles (the any-shape kernel) */
+    HN_ROUTE_K_DC_MFMA_32 = 9,      /* k_dc_mfma<32>: odd 16 < W <= 32 */
+    HN_ROUTE_K_DC_MFMA_16 = 10,     /* k_dc_mfma<16>: odd W <= 16 */
+    HN_ROUTE_K_DC_X16_BF16X3 = 11,  /* k_dc_x16<SplitBf16, .., 8>: 8 x 64 strips, even W >= 128, piecewise-linear activation (as the next two) */
+    HN_ROUTE_K_DC_X16_FP16 = 12,    /* k_dc_x16<HalfF16>: 16 x 64 strips */
+    HN_ROUTE_K_DC_X16_BF16X2 = 13,  /* k_dc_x16<SplitBf16x2> */
+    HN_ROUTE_DOWN_64 = 14,          /* k_down_mfma<4>: 16 rows x 64 outputs, Wout > 64 */
+    HN_ROUTE_DOWN_32 = 15,          /* k_down_mfma<2>: 32 < Wout <= 64 */
+    HN_ROUTE_DOWN_16 = 16,          /* k_down_mfma<1>: Wout <= 32 */
+    HN_ROUTE_DOWN_RING_64 = 17,     /* k_down_mfma_ring<4> (HN_OPT_MC_STAGE 1) */
+    HN_ROUTE_DOWN_RING_32 = 18,     /* k_down_mfma_ring<2> */
+    HN_ROUTE_DOWN_X16 = 19,         /* k_down_x16 (fp16, bf16x2): 16 x 16 outputs, Wout >= 64 */
+    HN_ROUTE_UP_2_11 = 20,          /* k_up_mfma<2, 11>: 22 window rows x 32 input columns, Win > 64 */
+    HN_ROUTE_UP_RING = 21,          /* k_up_mfma_ring<2, 11> (HN_OPT_MC_STAGE 1) */
+    HN_ROUTE_UP_1_5 = 22,           /* k_up_mfma<1, 5, true>: 20 window rows x 16 input columns, Win <= 64 */
+    HN_ROUTE_UP_X16 = 23            /* k_up_x16 (the three 16-bit modes): 20 window rows x 16 input columns, Win >= 64 */
+};
+/* The instance (enum hn_route) that hn_double_conv (op 0: a piecewise-linear activation, op 3: a smooth one; cin 6, 8, 10 or 16, cout 8) or hn_conv8x8
+ * (op 1: stride 2, op 2: transposed; cin 8) would launch NOW for an h x w input of 16-byte aligned, densely packed planes: a pure function of the
+ * context's precision mode and options and the shape.  Nothing is enqueued.  HN_ERR_ARG for another op, cin or a non-positive h, w (op 1: odd h, w). */
+int hn_module_route(hn_ctx* ctx, int op, int cin, int h, int w);
 int hn_double_conv(hn_ctx* ctx, const float* x, int cin, int cout, const float* weights_host, int act_kind, float* out,
                    int batch, int h, int w, void* stream);
 int hn_conv8x8(hn_ctx* ctx, const float* x, const float* weights_host, int transposed, float* out, int batch, int h, int w,
