@@ -282,7 +282,7 @@ struct hn_ctx {
     int opt_radix16 = 1;       // 256-point transforms as two register-resident radix-16 passes (0: the radix-4 Stockham kernels)
     int opt_cols_t = 1;        // 256-point column pass through an LDS transpose: 0 the r2 kernel (16-byte global accesses), 1: 16 columns per block, 2: 32, 3: 16 on the 8x4x8 transform (k_spec8_cols_t)
     bool cols_t_attr_set = false, cols512_attr_set = false;
-    int opt_spec_plain = 0;    // HN_EXP_SPECTRAL_PLAIN: 1 runs the 256- and 512-point register-resident kernels on the plain C++ complex helpers (plain::)
+    int opt_spec_plain = 0;    // HN_EXP_SPECTRAL_PLAIN: 1 runs the 256- and 512-point register-resident kernels on the plain C++ complex helpers (the PlainOps instances, k_spec*_plain)
     int opt_deep = 2;          // HN_OPT_DEEP: 1 deepest encoder level + bottleneck + deepest decoder level as one per-sample LDS kernel (hn_deep.hip, deepest level 32^2);
                                // 2 (default) the last one or two levels + bottleneck as ONE launch with eight workgroups per sample where it applies (hn_deepx.hip:
                                // a 64-wide level, with a 32-wide one below it or not), else as 1; 0 layer by layer

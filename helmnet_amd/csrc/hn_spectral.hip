@@ -387,9 +387,6 @@ __global__ __launch_bounds__(RowCfg<N>::T* RowCfg<N>::R) void k_spec_rows(
 // rounds per line instead of 8, a quarter of the LDS instructions and about half the instructions overall (these
 // kernels are issue-bound: ~150 instructions per element before).
 // ------------------------------------------------------------------------------------------
-// namespace plain: these kernels with the complex helpers in plain C++ and the residual flags read at run time.  They run with
-// HN_EXP_SPECTRAL_PLAIN 1 (k_spec16_rows and k_spec16_cols always) and are the bit-exact yardstick of the lean forms after it.
-namespace plain {
 // complex numbers as 2-vectors: hipcc maps the arithmetic below onto v_pk_add / v_pk_mul / v_pk_fma_f32 (one instruction
 // per complex add, two per complex multiply; swaps, broadcasts and sign flips ride on the op_sel / neg modifiers)
 typedef float v2 __attribute__((ext_vector_type(2)));
@@ -398,13 +395,107 @@ __device__ __forceinline__ v2 cmulv_conj(v2 a, v2 b) { return a.xx * (v2){b.x, -
 template <bool INV>
 __device__ __forceinline__ v2 rot(v2 a) { return INV ? (v2){-a.y, a.x} : (v2){a.y, -a.x}; }   // a * (+i | -i)
 
-template <bool INV>
+// ------------------------------------------------------------------------------------------
+// Every kernel body below exists once, over a policy Ops that holds the complex helpers whose spelling matters:
+//   cmulv, cmulv_conj       products with a twiddle or coefficient held in registers
+//   add_rot / sub_rot<INV>  a +- rot<INV>(r)
+//   mul / fma / fms_i_kx    the derivative spectrum i k u = (-u.y, u.x) * k.x, k = (k, -k^2) of the line's wavenumber, alone or
+//                           inside the first additions of the inverse transform that follows
+// PlainOps writes them in plain C++ and leaves instruction selection and contraction to hipcc.  Its instances run with
+// HN_EXP_SPECTRAL_PLAIN 1 (k_spec16_rows and k_spec16_cols always) and are the bit-exact yardstick of LeanOps.
+// LeanOps (default) is the same arithmetic, product for product and fused multiply-add for fused multiply-add, in fewer instructions.
+//  - hipcc builds the swapped, sign-flipped operand (-b.y, b.x) of a complex multiply or of a rotation by +-i with a v_xor
+//    and a v_mov -- two full-rate instructions beside the two packed ones that do the arithmetic.  The packed instructions
+//    can take both from their operand modifiers (op_sel picks the half each lane reads, neg_lo / neg_hi flip its sign), so
+//    LeanOps spells the instructions out.  Which product is rounded alone and which is fused follows what hipcc makes of
+//    PlainOps: cmulv rounds a.y * (-b.y, b.x) and fuses a.x * b; cmulv_conj rounds a.x * conj(b) and fuses a.y * (b.y, b.x); of
+//    the two inputs of an addition that takes i k u, the first stays unrounded inside a fused multiply-add, the second is rounded.
+//    Multiplications by CONSTANT twiddles stay on the plain cmulv above in both policies: their constants are folded, nothing is built.
+//  - Wait states: hipcc separates a packed instruction whose FIRST source has op_sel_hi 1 from a reader of its result in the
+//    next slot by s_nop 0, and none other (in the listing of the PlainOps kernels: every one of ~10 000 such pairs, and none of
+//    the ~5 000 back-to-back pairs whose first source has op_sel_hi 0).  Every instruction of LeanOps has op_sel_hi 0 on its first
+//    source -- the operands are ordered for it -- so neither the two instructions of one statement nor a reader after it
+//    fall under that rule.
+// The row kernels take the residual flags as a template parameter of their body and address global memory as a wave-uniform
+// base + one 32-bit lane offset + immediate offsets.
+// ------------------------------------------------------------------------------------------
+struct PlainOps {
+    static __device__ __forceinline__ v2 cmulv(v2 a, v2 b) { return hn::cmulv(a, b); }
+    static __device__ __forceinline__ v2 cmulv_conj(v2 a, v2 b) { return hn::cmulv_conj(a, b); }
+    template <bool INV>
+    static __device__ __forceinline__ v2 add_rot(v2 a, v2 r) { return a + rot<INV>(r); }
+    template <bool INV>
+    static __device__ __forceinline__ v2 sub_rot(v2 a, v2 r) { return a - rot<INV>(r); }
+    // a product feeding an addition, as when i k u is formed before the transform: hipcc contracts the same product into the same addition
+    static __device__ __forceinline__ v2 mul_i_kx(v2 u, v2 k) { return (v2){-u.y, u.x} * k.x; }
+    static __device__ __forceinline__ v2 fma_i_kx(v2 u, v2 k, v2 c) { return (v2){-u.y, u.x} * k.x + c; }
+    static __device__ __forceinline__ v2 fms_i_kx(v2 u, v2 k, v2 c) { return (v2){-u.y, u.x} * k.x - c; }
+};
+
+struct LeanOps {
+    static __device__ __forceinline__ v2 cmulv(v2 a, v2 b) {        // a * b = fma(a.xx, b, a.yy * (-b.y, b.x))
+        v2 r;
+        asm("v_pk_mul_f32 %0, %2, %1 op_sel:[1,1] op_sel_hi:[0,1] neg_lo:[1,0]\n\t"
+            "v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]"
+            : "=&v"(r) : "v"(a), "v"(b));
+        return r;
+    }
+    static __device__ __forceinline__ v2 cmulv_conj(v2 a, v2 b) {   // a * conj(b) = fma(a.yy, (b.y, b.x), a.xx * (b.x, -b.y))
+        v2 r;
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1] neg_hi:[0,1]\n\t"
+            "v_pk_fma_f32 %0, %2, %1, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1]"
+            : "=&v"(r) : "v"(a), "v"(b));
+        return r;
+    }
+    static __device__ __forceinline__ v2 add_i(v2 a, v2 r) {        // a + i r = (a.x - r.y, a.y + r.x)
+        v2 d;
+        asm("v_pk_add_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[1,0]" : "=v"(d) : "v"(a), "v"(r));
+        return d;
+    }
+    static __device__ __forceinline__ v2 sub_i(v2 a, v2 r) {        // a - i r = (a.x + r.y, a.y - r.x)
+        v2 d;
+        asm("v_pk_add_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_hi:[1,0]" : "=v"(d) : "v"(a), "v"(r));
+        return d;
+    }
+    template <bool INV>
+    static __device__ __forceinline__ v2 add_rot(v2 a, v2 r) { return INV ? add_i(a, r) : sub_i(a, r); }
+    template <bool INV>
+    static __device__ __forceinline__ v2 sub_rot(v2 a, v2 r) { return INV ? sub_i(a, r) : add_i(a, r); }
+    static __device__ __forceinline__ v2 mul_i_kx(v2 u, v2 k) {         // i k.x u
+        v2 d;
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,0] neg_lo:[1,0]" : "=v"(d) : "v"(u), "v"(k));
+        return d;
+    }
+    static __device__ __forceinline__ v2 fma_i_kx(v2 u, v2 k, v2 c) {   // i k.x u + c
+        v2 d;
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(u), "v"(k), "v"(c));
+        return d;
+    }
+    static __device__ __forceinline__ v2 fms_i_kx(v2 u, v2 k, v2 c) {   // i k.x u - c
+        v2 d;
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_lo:[1,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(u), "v"(k), "v"(c));
+        return d;
+    }
+};
+
+// ROT2: x2 stands for rot<INV>(x2) (the W^(N/4) twiddle of the enclosing transform, not applied beforehand)
+template <typename Ops, bool INV, bool ROT2 = false>
 __device__ __forceinline__ void bfly4(v2& x0, v2& x1, v2& x2, v2& x3) {
-    const v2 a0 = x0 + x2, a1 = x0 - x2, a2 = x1 + x3, r3 = rot<INV>(x1 - x3);
+    const v2 a0 = ROT2 ? Ops::template add_rot<INV>(x0, x2) : x0 + x2, a1 = ROT2 ? Ops::template sub_rot<INV>(x0, x2) : x0 - x2, a2 = x1 + x3, d3 = x1 - x3;
     x0 = a0 + a2;
-    x1 = a1 + r3;
+    x1 = Ops::template add_rot<INV>(a1, d3);
     x2 = a0 - a2;
-    x3 = a1 - r3;
+    x3 = Ops::template sub_rot<INV>(a1, d3);
+}
+// the butterfly of i k.x u: x holds u
+template <typename Ops, bool INV>
+__device__ __forceinline__ void bfly4_ik(v2& x0, v2& x1, v2& x2, v2& x3, v2 k0, v2 k1, v2 k2, v2 k3) {
+    const v2 p2 = Ops::mul_i_kx(x2, k2), p3 = Ops::mul_i_kx(x3, k3);
+    const v2 a0 = Ops::fma_i_kx(x0, k0, p2), a1 = Ops::fms_i_kx(x0, k0, p2), a2 = Ops::fma_i_kx(x1, k1, p3), d3 = Ops::fms_i_kx(x1, k1, p3);
+    x0 = a0 + a2;
+    x1 = Ops::template add_rot<INV>(a1, d3);
+    x2 = a0 - a2;
+    x3 = Ops::template sub_rot<INV>(a1, d3);
 }
 
 // The 1-D tables of a 256-point axis (twiddles, k, -k^2, PML a and b: 8 KB) copied into LDS at kernel start, together with the
@@ -436,19 +527,22 @@ __device__ __forceinline__ LdsTabs stage_tables_256(float* dst, const SpecPtrs& 
 }
 
 // in-register 16-point DFT, X[k] = sum_n x[n] W16^(+-n k): 4 + 4 radix-4 butterflies around the W16^(m q) twiddles
-template <bool INV>
-__device__ __forceinline__ void dft16(v2 (&x)[16]) {
+// IK: the transform of i k.x u, x holding u and kk the (k, -k^2) of its 16 points
+template <typename Ops, bool INV, bool IK = false>
+__device__ __forceinline__ void dft16(v2 (&x)[16], const v2* kk = nullptr) {
     constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, H = 0.70710678118654752f;
 #pragma unroll
-    for (int m = 0; m < 4; ++m) bfly4<INV>(x[m], x[m + 4], x[m + 8], x[m + 12]);   // y_q of column m now in x[m + 4 q]
+    for (int m = 0; m < 4; ++m) {   // y_q of column m now in x[m + 4 q]
+        if (IK) bfly4_ik<Ops, INV>(x[m], x[m + 4], x[m + 8], x[m + 12], kk[m], kk[m + 4], kk[m + 8], kk[m + 12]);
+        else bfly4<Ops, INV>(x[m], x[m + 4], x[m + 8], x[m + 12]);
+    }
     // x[m + 4 q] *= W16^(m q), W16^j = (cos, -+sin)(2 pi j / 16)
     auto tw = [](v2 v, float c, float sn) { return cmulv(v, (v2){c, INV ? sn : -sn}); };
     x[5] = tw(x[5], C1, S1);        // m q = 1
     x[9] = tw(x[9], H, H);          // 2
     x[13] = tw(x[13], S1, C1);      // 3
     x[6] = tw(x[6], H, H);          // 2
-    x[10] = rot<INV>(x[10]);        // 4
-    x[14] = tw(x[14], -H, H);       // 6
+    x[14] = tw(x[14], -H, H);       // 6; x[10] (m q = 4) takes its -+i inside the butterfly of q = 2
     x[7] = tw(x[7], S1, C1);        // 3
     x[11] = tw(x[11], -H, H);       // 6
     x[15] = tw(x[15], -C1, -S1);    // 9
@@ -456,7 +550,8 @@ __device__ __forceinline__ void dft16(v2 (&x)[16]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         v2 z0 = x[4 * q], z1 = x[4 * q + 1], z2 = x[4 * q + 2], z3 = x[4 * q + 3];
-        bfly4<INV>(z0, z1, z2, z3);
+        if (q == 2) bfly4<Ops, INV, true>(z0, z1, z2, z3);
+        else bfly4<Ops, INV>(z0, z1, z2, z3);
         o[q] = z0; o[q + 4] = z1; o[q + 8] = z2; o[q + 12] = z3;
     }
 #pragma unroll
@@ -482,7 +577,7 @@ __device__ __forceinline__ void xchg16(v2 (&v)[NB][16], v2* reg, int nbs, int t)
 
 // Forward transform of one line of 256 and the two derivative spectra: in u[k] = x[t + 16 k]; out d[0] = i k U, d[1] = -k^2 U
 // after the first inverse radix-16 pass and its twiddles, i.e. ready for the inverse exchange.
-template <typename Tab>
+template <typename Ops, typename Tab>
 __device__ __forceinline__ void axis_forward16(const v2 (&u)[16], v2 (&d)[2][16], v2* reg, int nbs, int t, const Tab& tab) {
     v2 w[16];   // W_256^(t q)
 #pragma unroll
@@ -490,36 +585,36 @@ __device__ __forceinline__ void axis_forward16(const v2 (&u)[16], v2 (&d)[2][16]
     v2 f[1][16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) f[0][k] = u[k];
-    dft16<false>(f[0]);
+    dft16<Ops, false>(f[0]);
 #pragma unroll
-    for (int q = 1; q < 16; ++q) f[0][q] = cmulv(f[0][q], w[q]);
+    for (int q = 1; q < 16; ++q) f[0][q] = Ops::cmulv(f[0][q], w[q]);
     xchg16<1>(f, reg, nbs, t);
-    dft16<false>(f[0]);
+    dft16<Ops, false>(f[0]);
+    v2 kk[16];
 #pragma unroll
     for (int p = 0; p < 16; ++p) {
-        const float k1 = tab.k1[t + 16 * p], k2 = tab.k2[t + 16 * p];
-        const v2 U = f[0][p];
-        d[0][p] = (v2){-U.y, U.x} * k1;   // (0, k) * U     (spectral.py:50, 281)
-        d[1][p] = U * k2;                 // (-k^2, 0) * U  (spectral.py:52, 283)
+        kk[p] = (v2){tab.k1[t + 16 * p], tab.k2[t + 16 * p]};
+        d[0][p] = f[0][p];               // (0, k) * U     (spectral.py:50, 281): inside the transform
+        d[1][p] = f[0][p] * kk[p].y;     // (-k^2, 0) * U  (spectral.py:52, 283)
     }
-    dft16<true>(d[0]);
-    dft16<true>(d[1]);
+    dft16<Ops, true, true>(d[0], kk);
+    dft16<Ops, true>(d[1]);
 #pragma unroll
     for (int q = 1; q < 16; ++q) {
-        d[0][q] = cmulv_conj(d[0][q], w[q]);
-        d[1][q] = cmulv_conj(d[1][q], w[q]);
+        d[0][q] = Ops::cmulv_conj(d[0][q], w[q]);
+        d[1][q] = Ops::cmulv_conj(d[1][q], w[q]);
     }
 }
 // ... and the rest: inverse exchange, second inverse pass, PML coefficients: acc[k] = (a du + b ddu)[t + 16 k]
-template <typename Tab>
+template <typename Ops, typename Tab>
 __device__ __forceinline__ void axis_finish16(v2 (&d)[2][16], v2 (&acc)[16], int t, const Tab& tab) {
-    dft16<true>(d[0]);
-    dft16<true>(d[1]);
+    dft16<Ops, true>(d[0]);
+    dft16<Ops, true>(d[1]);
     constexpr float inv_n = 1.0f / 256.0f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const float2 ca = tab.a[t + 16 * k], cb = tab.b[t + 16 * k];
-        acc[k] = (cmulv(d[0][k], (v2){ca.x, ca.y}) + cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n;
+        acc[k] = (Ops::cmulv(d[0][k], (v2){ca.x, ca.y}) + Ops::cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n;
     }
 }
 
@@ -530,17 +625,26 @@ __device__ __forceinline__ void axis_finish16(v2 (&d)[2][16], v2 (&acc)[16], int
 // DFT4 over b of A_(a + 8 b)[q] --> B_a[c][q] x W_32^(a c) --exchange--> thread u = q + 8 c: DFT8 over a --> X[u + 32 d]:
 // again the layout of the input.  Both exchanges stay inside the half-wavefront that owns the line.
 // ------------------------------------------------------------------------------------------
-template <bool INV>
-__device__ __forceinline__ void dft8(v2 (&x)[8]) {
+// IK: the transform of i k.x u, x holding u and kk the (k, -k^2) of its 8 points
+template <typename Ops, bool INV, bool IK = false>
+__device__ __forceinline__ void dft8(v2 (&x)[8], const v2* kk = nullptr) {
     constexpr float H = 0.70710678118654752f;
     v2 a[4], b[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { a[j] = x[j] + x[j + 4]; b[j] = x[j] - x[j + 4]; }
+    for (int j = 0; j < 4; ++j) {
+        if (IK) {
+            const v2 p = Ops::mul_i_kx(x[j + 4], kk[j + 4]);
+            a[j] = Ops::fma_i_kx(x[j], kk[j], p);
+            b[j] = Ops::fms_i_kx(x[j], kk[j], p);
+        } else {
+            a[j] = x[j] + x[j + 4];
+            b[j] = x[j] - x[j + 4];
+        }
+    }
     b[1] = cmulv(b[1], (v2){H, INV ? H : -H});      // W8^1
-    b[2] = rot<INV>(b[2]);                           // W8^2 = -+i
-    b[3] = cmulv(b[3], (v2){-H, INV ? H : -H});     // W8^3
-    bfly4<INV>(a[0], a[1], a[2], a[3]);
-    bfly4<INV>(b[0], b[1], b[2], b[3]);
+    b[3] = cmulv(b[3], (v2){-H, INV ? H : -H});     // W8^3; b[2] takes its W8^2 = -+i inside the butterfly
+    bfly4<Ops, INV>(a[0], a[1], a[2], a[3]);
+    bfly4<Ops, INV, true>(b[0], b[1], b[2], b[3]);
 #pragma unroll
     for (int p = 0; p < 4; ++p) { x[2 * p] = a[p]; x[2 * p + 1] = b[p]; }
 }
@@ -556,688 +660,6 @@ constexpr int kE1 = 36;            // exchange 1: slot q * 36 + t (reads a + 8 b
 constexpr int kE2 = 9;
 constexpr int kReg8 = 8 * kE1;     // float2 per transform region (= 32 * kE2)
 
-struct Tw8 {
-    v2 w256[8], w32[4];
-    __device__ __forceinline__ void load(int t, const float2* __restrict__ tw) {
-#pragma unroll
-        for (int q = 1; q < 8; ++q) { const float2 f = tw[t * q]; w256[q] = (v2){f.x, f.y}; }
-#pragma unroll
-        for (int c = 1; c < 4; ++c) { const float2 f = tw[8 * (t & 7) * c]; w32[c] = (v2){f.x, f.y}; }
-    }
-};
-
-// NB lock-step transforms of one line held by 32 threads x 8 elements; v[nb][k] = x[t + 32 k] in, X[t + 32 k] out
-template <bool INV, int NB>
-__device__ __forceinline__ void fft256_t32(v2 (&v)[NB][8], v2* reg, int nbs, int t, const Tw8& tw) {
-    const int a = t & 7, qp = t >> 3;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        dft8<INV>(v[nb]);
-#pragma unroll
-        for (int q = 1; q < 8; ++q) v[nb][q] = INV ? cmulv_conj(v[nb][q], tw.w256[q]) : cmulv(v[nb][q], tw.w256[q]);
-    }
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) reg[nb * nbs + q * kE1 + t] = v[nb][q];
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) v[nb][4 * s2 + b] = reg[nb * nbs + (2 * qp + s2) * kE1 + a + 8 * b];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            bfly4<INV>(v[nb][4 * s2], v[nb][4 * s2 + 1], v[nb][4 * s2 + 2], v[nb][4 * s2 + 3]);   // index b -> c
-#pragma unroll
-            for (int c = 1; c < 4; ++c) v[nb][4 * s2 + c] = INV ? cmulv_conj(v[nb][4 * s2 + c], tw.w32[c]) : cmulv(v[nb][4 * s2 + c], tw.w32[c]);
-        }
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) reg[nb * nbs + (2 * qp + s2 + 8 * c) * kE2 + a] = v[nb][4 * s2 + c];
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[nb][k] = reg[nb * nbs + t * kE2 + k];   // thread t = q + 8 c reads a = 0 .. 7
-        dft8<INV>(v[nb]);
-    }
-}
-
-// row pass at N = 256: workgroup = 8 rows (4 wavefronts x 2 rows), lane = 32 r + t
-__global__ __launch_bounds__(256, 4) void k_spec8_rows(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
-                                                    const float* __restrict__ src, long src_sb, SpecPtrs tab, int flags,
-                                                    float* __restrict__ sumsq, const int* __restrict__ it_counter, int sumsq_stride) {
-    constexpr int N = 256;
-    __shared__ v2 buf[4 * 2 * 2 * kReg8];
-    __shared__ float red[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = lane & 31, r = lane >> 5;
-    const TileId tl = xcd_tile();
-    const int row = tl.x * 8 + wave * 2 + r, b = tl.y;
-    const long plane = (long)N * N, ro = (long)row * N;
-    const float* pre = wf + (long)b * 2 * plane + ro;
-    float* po = out + (long)b * 2 * plane + ro;
-    v2 u[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) u[k] = (v2){pre[t + 32 * k], pre[plane + t + 32 * k]};
-    Tw8 tw;
-    tw.load(t, tab.tw);
-    v2* reg = buf + (wave * 2 + r) * 2 * kReg8;
-    v2 f[1][8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) f[0][k] = u[k];
-    fft256_t32<false, 1>(f, reg, kReg8, t, tw);
-    v2 d[2][8];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const float k1 = tab.k1[t + 32 * p], k2 = tab.k2[t + 32 * p];
-        const v2 U = f[0][p];
-        d[0][p] = (v2){-U.y, U.x} * k1;   // (0, k) * U     (spectral.py:50, 281)
-        d[1][p] = U * k2;                 // (-k^2, 0) * U  (spectral.py:52, 283)
-    }
-    fft256_t32<true, 2>(d, reg, kReg8, t, tw);
-    // the other operands of the row: requested after the transforms (registers: 4 wavefronts per SIMD cover the round trip)
-    v2 part[8], sv[8];
-    float kq[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int x = t + 32 * k;
-        part[k] = (flags & 1) ? (v2){po[x], po[plane + x]} : (v2){0.f, 0.f};
-        kq[k] = 0.f;
-        sv[k] = (v2){0.f, 0.f};
-        if (flags & 2) {
-            kq[k] = ksq[(long)b * plane + ro + x];
-            const float* ps = src + (long)b * src_sb + ro + x;
-            sv[k] = (v2){ps[0], ps[plane]};
-        }
-    }
-    constexpr float inv_n = 1.0f / 256.0f;
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int x = t + 32 * k;
-        const float2 ca = tab.a[x], cb = tab.b[x];
-        v2 o = (cmulv(d[0][k], (v2){ca.x, ca.y}) + cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n + part[k];
-        if (flags & 2) o = o + u[k] * kq[k] - sv[k];
-        po[x] = o.x;
-        po[plane + x] = o.y;
-        ss += o.x * o.x + o.y * o.y;
-    }
-    if (sumsq != nullptr) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
-        if (lane == 0) red[wave] = ss;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const long hist_row = it_counter != nullptr ? (long)(*it_counter - 1) * sumsq_stride : 0;
-            atomicAdd(&sumsq[hist_row + b], red[0] + red[1] + red[2] + red[3]);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// N = 512 = 8 x 8 x 8 on 64 threads x 8 elements per line (r3): the 256-point scheme above with one more factor of 2 in the
-// middle stage, one wavefront per line.  x[t + 64 k] --DFT8 over k--> A_t[q] x W_512^(t q) --exchange--> thread (a = t % 8, q):
-// DFT8 over b of A_(a + 8 b)[q] --> B_a[c][q] x W_64^(a c) --exchange--> thread u = q + 8 c: DFT8 over a --> X[u + 64 d]: the
-// layout of the input.  Both exchanges stay inside the wavefront that owns the line (wave-level fences, no workgroup barrier).
-// The radix-4 Stockham kernels this replaces at 512^2 run 5 exchange rounds per transform on 128 threads per line and address
-// global memory in 32-byte pieces in the column pass.
-// ------------------------------------------------------------------------------------------
-constexpr int kF1 = 72;            // exchange 1: slot q * 72 + t; reads a + 8 b of row q: the two rows of a 16-lane group sit 144 = 16 (mod 64) dwords apart
-constexpr int kF2 = 9;             // exchange 2: slot (q + 8 c) * 9 + a (stride 18 dwords: conflict-free)
-constexpr int kReg512 = 8 * kF1;   // float2 per transform region (= 64 * kF2)
-
-struct Tw512 {
-    v2 w512[8], w64[8];
-    __device__ __forceinline__ void load(int t, const float2* __restrict__ tw) {
-#pragma unroll
-        for (int q = 1; q < 8; ++q) { const float2 f = tw[t * q]; w512[q] = (v2){f.x, f.y}; }
-#pragma unroll
-        for (int c = 1; c < 8; ++c) { const float2 f = tw[8 * (t & 7) * c]; w64[c] = (v2){f.x, f.y}; }
-    }
-};
-
-// NB lock-step transforms of one line held by 64 threads x 8 elements; v[nb][k] = x[t + 64 k] in, X[t + 64 k] out
-template <bool INV, int NB>
-__device__ __forceinline__ void fft512_t64(v2 (&v)[NB][8], v2* reg, int nbs, int t, const Tw512& tw) {
-    const int a = t & 7, q = t >> 3;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        dft8<INV>(v[nb]);
-#pragma unroll
-        for (int i = 1; i < 8; ++i) v[nb][i] = INV ? cmulv_conj(v[nb][i], tw.w512[i]) : cmulv(v[nb][i], tw.w512[i]);
-    }
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) reg[nb * nbs + i * kF1 + t] = v[nb][i];
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) v[nb][b] = reg[nb * nbs + q * kF1 + a + 8 * b];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        dft8<INV>(v[nb]);   // index b -> c
-#pragma unroll
-        for (int c = 1; c < 8; ++c) v[nb][c] = INV ? cmulv_conj(v[nb][c], tw.w64[c]) : cmulv(v[nb][c], tw.w64[c]);
-    }
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) reg[nb * nbs + (q + 8 * c) * kF2 + a] = v[nb][c];
-    exchange_sync<true>();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[nb][k] = reg[nb * nbs + t * kF2 + k];   // thread t = q + 8 c reads a = 0 .. 7
-        dft8<INV>(v[nb]);
-    }
-}
-
-// forward transform, derivative multipliers, two inverse transforms, PML coefficients of one 512-point line: u[k] = x[t + 64 k] in,
-// acc[k] = (a du + b ddu)[t + 64 k] out
-__device__ __forceinline__ void axis512(const v2 (&u)[8], v2 (&acc)[8], v2* reg, int t, const Tw512& tw, const SpecPtrs& tab) {
-    v2 f[1][8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) f[0][k] = u[k];
-    fft512_t64<false, 1>(f, reg, kReg512, t, tw);
-    v2 d[2][8];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const float k1 = tab.k1[t + 64 * p], k2 = tab.k2[t + 64 * p];
-        const v2 U = f[0][p];
-        d[0][p] = (v2){-U.y, U.x} * k1;   // (0, k) * U     (spectral.py:50, 281)
-        d[1][p] = U * k2;                 // (-k^2, 0) * U  (spectral.py:52, 283)
-    }
-    fft512_t64<true, 2>(d, reg, kReg512, t, tw);
-    constexpr float inv_n = 1.0f / 512.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float2 ca = tab.a[t + 64 * k], cb = tab.b[t + 64 * k];
-        acc[k] = (cmulv(d[0][k], (v2){ca.x, ca.y}) + cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n;
-    }
-}
-
-// row pass at N = 512: workgroup = 8 rows, one wavefront per row.  (With 4 rows per workgroup the 128 workgroups of a sample each add their sum
-// of squares to ONE address: same-address float atomics are serialised at the memory side, and in the solver loop -- where the RMSE
-// history is on -- the kernel took 55 us instead of the 35 us it takes alone.  64 per sample, as the radix-4 kernel has, are hidden.)
-__global__ __launch_bounds__(512, 2) void k_spec512_rows(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
-                                                       const float* __restrict__ src, long src_sb, SpecPtrs tab, int flags,
-                                                       float* __restrict__ sumsq, const int* __restrict__ it_counter, int sumsq_stride) {
-    constexpr int N = 512;
-    __shared__ v2 buf[8 * 2 * kReg512];
-    __shared__ float red[8];
-    const int t = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const TileId tl = xcd_tile();
-    const int row = tl.x * 8 + wave, b = tl.y;
-    const long plane = (long)N * N, ro = (long)row * N;
-    const float* pre = wf + (long)b * 2 * plane + ro;
-    float* po = out + (long)b * 2 * plane + ro;
-    v2 acc[8];
-    {
-        v2 u[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) u[k] = (v2){pre[t + 64 * k], pre[plane + t + 64 * k]};
-        Tw512 tw;
-        tw.load(t, tab.tw);
-        axis512(u, acc, buf + wave * 2 * kReg512, t, tw, tab);
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int x = t + 64 * k;
-        v2 o = acc[k];
-        if (flags & 1) o = o + (v2){po[x], po[plane + x]};
-        if (flags & 2) {
-            // the line itself is read again here (an L2 hit) instead of being held through the transforms: 16 registers, which at
-            // 128 VGPRs (four wavefronts per SIMD) would otherwise be spilled
-            const v2 uk = (v2){pre[x], pre[plane + x]};
-            const float kq = ksq[(long)b * plane + ro + x];
-            o = o + uk * kq;
-            if (src != nullptr) {
-                const float* ps = src + (long)b * src_sb + ro + x;
-                o = o - (v2){ps[0], ps[plane]};
-            }
-        }
-        po[x] = o.x;
-        po[plane + x] = o.y;
-        ss += o.x * o.x + o.y * o.y;
-    }
-    if (sumsq != nullptr) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
-        if (t == 0) red[wave] = ss;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const long hist_row = it_counter != nullptr ? (long)(*it_counter - 1) * sumsq_stride : 0;
-            atomicAdd(&sumsq[hist_row + b], ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7])));
-        }
-    }
-}
-
-// column pass at N = 512, coalesced through an LDS transpose like k_spec16_cols_t: a workgroup owns 16 columns x all 512 rows of a
-// sample (16 wavefronts, one per column); column c lives at cbuf + c * kCols512P: its 512 inputs first, then the 2 x 576 float2 of
-// the lock-step inverse exchange, finally its 512 outputs.  8 * 1153 = 8 (mod 64) dwords: the four float4 segments of a row land
-// on disjoint banks in the transposed writes and reads.
-constexpr int kCols512P = 1153;
-
-__global__ __launch_bounds__(1024) void k_spec512_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
-                                                        int* __restrict__ it_counter) {
-    constexpr int N = 512, COLS = 16, NT = 1024, P = kCols512P, SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
-    extern __shared__ v2 cbuf512[];   // [COLS][P]
-    const int tid = threadIdx.x, t = tid & 63, wave = tid >> 6;
-    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
-    const TileId tl = xcd_tile();
-    const long plane = (long)N * N;
-    const int seg = tid % SEG, rr = tid / SEG;
-    const float* pre = wf + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-    Tw512 tw;
-    tw.load(t, tab.tw);
-    {
-        float4 re[NP], im[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const long o = (long)(rr + RPP * i) * N;
-            re[i] = *reinterpret_cast<const float4*>(pre + o);
-            im[i] = *reinterpret_cast<const float4*>(pre + o + plane);
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            v2* q = cbuf512 + (4 * seg) * P + rr + RPP * i;
-            q[0] = (v2){re[i].x, im[i].x};
-            q[P] = (v2){re[i].y, im[i].y};
-            q[2 * P] = (v2){re[i].z, im[i].z};
-            q[3 * P] = (v2){re[i].w, im[i].w};
-        }
-    }
-    __syncthreads();
-    {
-        v2* reg = cbuf512 + wave * P;
-        v2 u[8], acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) u[k] = reg[t + 64 * k];
-        axis512(u, acc, reg, t, tw, tab);   // the first exchange overwrites the column's region: every lane of the wavefront has read its inputs
-        exchange_sync<true>();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) reg[t + 64 * k] = acc[k];
-    }
-    __syncthreads();
-    float* po = out + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const v2* q = cbuf512 + (4 * seg) * P + rr + RPP * i;
-        const v2 a = q[0], b = q[P], c = q[2 * P], d4 = q[3 * P];
-        const long o = (long)(rr + RPP * i) * N;
-        *reinterpret_cast<float4*>(po + o) = make_float4(a.x, b.x, c.x, d4.x);
-        *reinterpret_cast<float4*>(po + o + plane) = make_float4(a.y, b.y, c.y, d4.y);
-    }
-}
-
-constexpr int kReg16Rows = 272;   // float2 per transform region: 16 x 17; 544 dwords = 32 (mod 64): the two transforms of a 32-lane group on disjoint banks
-constexpr int kReg16Cols = 280;   // 560 dwords = 48 (mod 64): the four transforms of a 32-lane group (lane = 4 t + c) on disjoint quarters
-
-// column pass at N = 256: workgroup = 16 columns (4 wavefronts x 4 columns), lane = 4 t + c
-__global__ __launch_bounds__(256) void k_spec16_cols(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
-                                                     int* __restrict__ it_counter) {
-    constexpr int N = 256;
-    __shared__ v2 buf[4 * 4 * 2 * kReg16Cols];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = lane >> 2, c = lane & 3;
-    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) atomicAdd(it_counter, 1);
-    const TileId tl = xcd_tile();   // sample -> XCD as in the UNet kernels: the wavefield decode0 just wrote and the partial the row pass reads next stay in one L2
-    const int col = tl.x * 16 + wave * 4 + c;
-    const long plane = (long)N * N;
-    const float* pre = wf + (long)tl.y * 2 * plane + col;
-    v2 u[16], d[2][16], acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const long o = (long)(t + 16 * k) * N;
-        u[k] = (v2){pre[o], pre[o + plane]};
-    }
-    v2* reg = buf + (wave * 4 + c) * 2 * kReg16Cols;
-    axis_forward16(u, d, reg, kReg16Cols, t, tab);
-    xchg16<2>(d, reg, kReg16Cols, t);
-    axis_finish16(d, acc, t, tab);
-    float* po = out + (long)tl.y * 2 * plane + col;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const long o = (long)(t + 16 * k) * N;
-        po[o] = acc[k].x;
-        po[o + plane] = acc[k].y;
-    }
-}
-
-// column pass at N = 256, coalesced through an LDS transpose (r3).  k_spec16_cols above addresses global memory as 16 rows x 16
-// bytes per wave instruction.  Here a block owns COLS columns x all 256 rows of one sample: it loads row segments of COLS * 4
-// bytes as float4 (a wave instruction covers 64 / (COLS / 4) rows x COLS * 4 contiguous bytes), writes them TRANSPOSED into LDS
-// (column c at buf + c * P, (re, im) interleaved), runs the two radix-16 passes per column out of LDS with the 16 threads of a
-// transform on consecutive lanes (lane = 16 c' + t: the exchange pattern of the row kernel, whose conflicts are 1.6 cycles per
-// LDS instruction against 24 for lane = 4 t + c), writes the result back into the column's region and stores it the way it
-// was loaded.  P = 545 float2: a column region holds the 2 x 272 float2 of the lock-step inverse exchange, and 8 P = 8 (mod 64)
-// dwords puts the COLS / 4 float4 segments of a row on disjoint banks for the transposed writes and reads.
-constexpr int kColsP = 545;
-
-template <int COLS>
-__global__ __launch_bounds__(COLS * 16) void k_spec16_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
-                                                           int* __restrict__ it_counter) {
-    constexpr int N = 256, NT = COLS * 16, P = kColsP, SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
-    extern __shared__ v2 cbuf[];   // [COLS][P], then the tables
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
-    const TileId tl = xcd_tile();
-    const long plane = (long)N * N;
-    const int seg = tid % SEG, rr = tid / SEG;
-    const LdsTabs ltab = stage_tables_256<NT>(reinterpret_cast<float*>(cbuf + COLS * P), tab, tid);
-    const float* pre = wf + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-    {
-        float4 re[NP], im[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const long o = (long)(rr + RPP * i) * N;
-            re[i] = *reinterpret_cast<const float4*>(pre + o);
-            im[i] = *reinterpret_cast<const float4*>(pre + o + plane);
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            v2* q = cbuf + (4 * seg) * P + rr + RPP * i;
-            q[0] = (v2){re[i].x, im[i].x};
-            q[P] = (v2){re[i].y, im[i].y};
-            q[2 * P] = (v2){re[i].z, im[i].z};
-            q[3 * P] = (v2){re[i].w, im[i].w};
-        }
-    }
-    __syncthreads();
-    {
-        const int t = lane & 15, cl = wave * 4 + (lane >> 4);
-        v2* reg = cbuf + cl * P;
-        v2 u[16], d[2][16], acc[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) u[k] = reg[t + 16 * k];
-        axis_forward16(u, d, reg, kReg16Rows, t, ltab);   // the first exchange overwrites the column's region: every lane of the wave has read its inputs
-        xchg16<2>(d, reg, kReg16Rows, t);
-        axis_finish16(d, acc, t, ltab);
-        exchange_sync<true>();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) reg[t + 16 * k] = acc[k];
-    }
-    __syncthreads();
-    float* po = out + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const v2* q = cbuf + (4 * seg) * P + rr + RPP * i;
-        const v2 a = q[0], b = q[P], c = q[2 * P], d4 = q[3 * P];
-        const long o = (long)(rr + RPP * i) * N;
-        *reinterpret_cast<float4*>(po + o) = make_float4(a.x, b.x, c.x, d4.x);
-        *reinterpret_cast<float4*>(po + o + plane) = make_float4(a.y, b.y, c.y, d4.y);
-    }
-}
-
-// row pass at N = 256: workgroup = 16 rows (4 wavefronts x 4 rows), lane = 16 r + t
-__global__ __launch_bounds__(256) void k_spec16_rows(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
-                                                     const float* __restrict__ src, long src_sb, SpecPtrs tab, int flags,
-                                                     float* __restrict__ sumsq, const int* __restrict__ it_counter, int sumsq_stride) {
-    constexpr int N = 256;
-    __shared__ v2 buf[4 * 4 * 2 * kReg16Rows];
-    __shared__ float red[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = lane & 15, r = lane >> 4;
-    const TileId tl = xcd_tile();
-    const int row = tl.x * 16 + wave * 4 + r, b = tl.y;
-    const long plane = (long)N * N, ro = (long)row * N;
-    const float* pre = wf + (long)b * 2 * plane + ro;
-    float* po = out + (long)b * 2 * plane + ro;
-    v2 u[16], d[2][16], acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) u[k] = (v2){pre[t + 16 * k], pre[plane + t + 16 * k]};
-    v2* reg = buf + (wave * 4 + r) * 2 * kReg16Rows;
-    axis_forward16(u, d, reg, kReg16Rows, t, tab);
-    xchg16<2>(d, reg, kReg16Rows, t);
-    // the other operands of the row are requested now (the twiddles are dead: registers are free) and arrive while the last
-    // radix-16 pass runs
-    v2 part[16], sv[16];
-    float kq[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int x = t + 16 * k;
-        part[k] = (flags & 1) ? (v2){po[x], po[plane + x]} : (v2){0.f, 0.f};
-        kq[k] = 0.f;
-        sv[k] = (v2){0.f, 0.f};
-        if (flags & 2) {
-            kq[k] = ksq[(long)b * plane + ro + x];
-            const float* ps = src + (long)b * src_sb + ro + x;
-            sv[k] = (v2){ps[0], ps[plane]};
-        }
-    }
-    axis_finish16(d, acc, t, tab);
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int x = t + 16 * k;
-        v2 o = acc[k] + part[k];
-        if (flags & 2) o = o + u[k] * kq[k] - sv[k];
-        po[x] = o.x;
-        po[plane + x] = o.y;
-        ss += o.x * o.x + o.y * o.y;
-    }
-    if (sumsq != nullptr) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
-        if (lane == 0) red[wave] = ss;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const long hist_row = it_counter != nullptr ? (long)(*it_counter - 1) * sumsq_stride : 0;
-            atomicAdd(&sumsq[hist_row + b], red[0] + red[1] + red[2] + red[3]);
-        }
-    }
-}
-}  // namespace plain
-
-// ------------------------------------------------------------------------------------------
-// The lean forms (default) of k_spec8_rows, k_spec16_cols_t, k_spec512_rows and k_spec512_cols_t: the arithmetic of namespace
-// plain, product for product and fused multiply-add for fused multiply-add, in fewer instructions.
-//  - hipcc builds the swapped, sign-flipped operand (-b.y, b.x) of a complex multiply or of a rotation by +-i with a v_xor
-//    and a v_mov -- two full-rate instructions beside the two packed ones that do the arithmetic.  The packed instructions
-//    can take both from their operand modifiers (op_sel picks the half each lane reads, neg_lo / neg_hi flip its sign), so
-//    the helpers below spell the instructions out.  Which product is rounded alone and which is fused follows what hipcc
-//    makes of the plain helpers: cmulv rounds a.y * (-b.y, b.x) and fuses a.x * b; cmulv_conj rounds a.x * conj(b) and fuses
-//    a.y * (b.y, b.x).  Multiplications by CONSTANT twiddles stay plain::cmulv: their constants are folded, nothing is built.
-//  - Wait states: hipcc separates a packed instruction whose FIRST source has op_sel_hi 1 from a reader of its result in the
-//    next slot by s_nop 0, and none other (in the listing of namespace plain: every one of ~10 000 such pairs, and none of
-//    the ~5 000 back-to-back pairs whose first source has op_sel_hi 0).  Every instruction below has op_sel_hi 0 on its first
-//    source -- the operands are ordered for it -- so neither the two instructions of one statement nor a reader after it
-//    fall under that rule.
-//  - The row kernels take the residual flags as a template parameter of their body and address global memory as a
-//    wave-uniform base + one 32-bit lane offset + immediate offsets.
-// ------------------------------------------------------------------------------------------
-using plain::v2;
-using plain::LdsTabs;
-using plain::stage_tables_256;
-using plain::kLdsTabFloats;
-using plain::xchg16;
-using plain::kE1;
-using plain::kE2;
-using plain::kReg8;
-using plain::kF1;
-using plain::kF2;
-using plain::kReg512;
-using plain::kCols512P;
-using plain::kColsP;
-using plain::kReg16Rows;
-
-__device__ __forceinline__ v2 cmulv(v2 a, v2 b) {        // a * b = fma(a.xx, b, a.yy * (-b.y, b.x))
-    v2 r;
-    asm("v_pk_mul_f32 %0, %2, %1 op_sel:[1,1] op_sel_hi:[0,1] neg_lo:[1,0]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]"
-        : "=&v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ v2 cmulv_conj(v2 a, v2 b) {   // a * conj(b) = fma(a.yy, (b.y, b.x), a.xx * (b.x, -b.y))
-    v2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_fma_f32 %0, %2, %1, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1]"
-        : "=&v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ v2 add_i(v2 a, v2 r) {        // a + i r = (a.x - r.y, a.y + r.x)
-    v2 d;
-    asm("v_pk_add_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[1,0]" : "=v"(d) : "v"(a), "v"(r));
-    return d;
-}
-__device__ __forceinline__ v2 sub_i(v2 a, v2 r) {        // a - i r = (a.x + r.y, a.y - r.x)
-    v2 d;
-    asm("v_pk_add_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_hi:[1,0]" : "=v"(d) : "v"(a), "v"(r));
-    return d;
-}
-// a +- rot<INV>(r) of namespace plain, rot = multiplication by +i (INV) or -i
-template <bool INV>
-__device__ __forceinline__ v2 add_rot(v2 a, v2 r) { return INV ? add_i(a, r) : sub_i(a, r); }
-template <bool INV>
-__device__ __forceinline__ v2 sub_rot(v2 a, v2 r) { return INV ? sub_i(a, r) : add_i(a, r); }
-// The derivative spectrum i k u = (-u.y, u.x) * k.x, k = (k, -k^2) of the line's wavenumber.  hipcc contracts plain's product with the first
-// additions of the inverse transform that follows: of the two inputs of such an addition the first stays unrounded inside a fused
-// multiply-add, the second is rounded.  The three forms:
-__device__ __forceinline__ v2 mul_i_kx(v2 u, v2 k) {         // i k.x u
-    v2 d;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,0] neg_lo:[1,0]" : "=v"(d) : "v"(u), "v"(k));
-    return d;
-}
-__device__ __forceinline__ v2 fma_i_kx(v2 u, v2 k, v2 c) {   // i k.x u + c
-    v2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(u), "v"(k), "v"(c));
-    return d;
-}
-__device__ __forceinline__ v2 fms_i_kx(v2 u, v2 k, v2 c) {   // i k.x u - c
-    v2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_lo:[1,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(u), "v"(k), "v"(c));
-    return d;
-}
-
-// ROT2: x2 stands for rot<INV>(x2) (the W^(N/4) twiddle of the enclosing transform, not applied beforehand)
-template <bool INV, bool ROT2 = false>
-__device__ __forceinline__ void bfly4(v2& x0, v2& x1, v2& x2, v2& x3) {
-    const v2 a0 = ROT2 ? add_rot<INV>(x0, x2) : x0 + x2, a1 = ROT2 ? sub_rot<INV>(x0, x2) : x0 - x2, a2 = x1 + x3, d3 = x1 - x3;
-    x0 = a0 + a2;
-    x1 = add_rot<INV>(a1, d3);
-    x2 = a0 - a2;
-    x3 = sub_rot<INV>(a1, d3);
-}
-// the butterfly of i k.x u: x holds u
-template <bool INV>
-__device__ __forceinline__ void bfly4_ik(v2& x0, v2& x1, v2& x2, v2& x3, v2 k0, v2 k1, v2 k2, v2 k3) {
-    const v2 p2 = mul_i_kx(x2, k2), p3 = mul_i_kx(x3, k3);
-    const v2 a0 = fma_i_kx(x0, k0, p2), a1 = fms_i_kx(x0, k0, p2), a2 = fma_i_kx(x1, k1, p3), d3 = fms_i_kx(x1, k1, p3);
-    x0 = a0 + a2;
-    x1 = add_rot<INV>(a1, d3);
-    x2 = a0 - a2;
-    x3 = sub_rot<INV>(a1, d3);
-}
-
-// IK: the transform of i k.x u, x holding u and kk the (k, -k^2) of its 16 points
-template <bool INV, bool IK = false>
-__device__ __forceinline__ void dft16(v2 (&x)[16], const v2* kk = nullptr) {
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, H = 0.70710678118654752f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        if (IK) bfly4_ik<INV>(x[m], x[m + 4], x[m + 8], x[m + 12], kk[m], kk[m + 4], kk[m + 8], kk[m + 12]);
-        else bfly4<INV>(x[m], x[m + 4], x[m + 8], x[m + 12]);
-    }
-    auto tw = [](v2 v, float c, float sn) { return plain::cmulv(v, (v2){c, INV ? sn : -sn}); };
-    x[5] = tw(x[5], C1, S1);
-    x[9] = tw(x[9], H, H);
-    x[13] = tw(x[13], S1, C1);
-    x[6] = tw(x[6], H, H);
-    x[14] = tw(x[14], -H, H);       // x[10] takes its -+i inside the butterfly of q = 2
-    x[7] = tw(x[7], S1, C1);
-    x[11] = tw(x[11], -H, H);
-    x[15] = tw(x[15], -C1, -S1);
-    v2 o[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        v2 z0 = x[4 * q], z1 = x[4 * q + 1], z2 = x[4 * q + 2], z3 = x[4 * q + 3];
-        if (q == 2) bfly4<INV, true>(z0, z1, z2, z3);
-        else bfly4<INV>(z0, z1, z2, z3);
-        o[q] = z0; o[q + 4] = z1; o[q + 8] = z2; o[q + 12] = z3;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = o[k];
-}
-
-template <typename Tab>
-__device__ __forceinline__ void axis_forward16(const v2 (&u)[16], v2 (&d)[2][16], v2* reg, int nbs, int t, const Tab& tab) {
-    v2 w[16];   // W_256^(t q)
-#pragma unroll
-    for (int q = 1; q < 16; ++q) { const float2 f = tab.tw[t * q]; w[q] = (v2){f.x, f.y}; }
-    v2 f[1][16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) f[0][k] = u[k];
-    dft16<false>(f[0]);
-#pragma unroll
-    for (int q = 1; q < 16; ++q) f[0][q] = cmulv(f[0][q], w[q]);
-    xchg16<1>(f, reg, nbs, t);
-    dft16<false>(f[0]);
-    v2 kk[16];
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-        kk[p] = (v2){tab.k1[t + 16 * p], tab.k2[t + 16 * p]};
-        d[0][p] = f[0][p];               // (0, k) * U     (spectral.py:50, 281): inside the transform
-        d[1][p] = f[0][p] * kk[p].y;     // (-k^2, 0) * U  (spectral.py:52, 283)
-    }
-    dft16<true, true>(d[0], kk);
-    dft16<true>(d[1]);
-#pragma unroll
-    for (int q = 1; q < 16; ++q) {
-        d[0][q] = cmulv_conj(d[0][q], w[q]);
-        d[1][q] = cmulv_conj(d[1][q], w[q]);
-    }
-}
-template <typename Tab>
-__device__ __forceinline__ void axis_finish16(v2 (&d)[2][16], v2 (&acc)[16], int t, const Tab& tab) {
-    dft16<true>(d[0]);
-    dft16<true>(d[1]);
-    constexpr float inv_n = 1.0f / 256.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const float2 ca = tab.a[t + 16 * k], cb = tab.b[t + 16 * k];
-        acc[k] = (cmulv(d[0][k], (v2){ca.x, ca.y}) + cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n;
-    }
-}
-
-// IK: the transform of i k.x u, x holding u and kk the (k, -k^2) of its 8 points
-template <bool INV, bool IK = false>
-__device__ __forceinline__ void dft8(v2 (&x)[8], const v2* kk = nullptr) {
-    constexpr float H = 0.70710678118654752f;
-    v2 a[4], b[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (IK) {
-            const v2 p = mul_i_kx(x[j + 4], kk[j + 4]);
-            a[j] = fma_i_kx(x[j], kk[j], p);
-            b[j] = fms_i_kx(x[j], kk[j], p);
-        } else {
-            a[j] = x[j] + x[j + 4];
-            b[j] = x[j] - x[j + 4];
-        }
-    }
-    b[1] = plain::cmulv(b[1], (v2){H, INV ? H : -H});      // W8^1
-    b[3] = plain::cmulv(b[3], (v2){-H, INV ? H : -H});     // W8^3; b[2] takes its W8^2 = -+i inside the butterfly
-    bfly4<INV>(a[0], a[1], a[2], a[3]);
-    bfly4<INV, true>(b[0], b[1], b[2], b[3]);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) { x[2 * p] = a[p]; x[2 * p + 1] = b[p]; }
-}
-
 // the twiddles of a thread, read with one 32-bit offset each from the (wave-uniform) table pointer
 struct Tw8 {
     v2 w256[8], w32[4];
@@ -1249,16 +671,17 @@ struct Tw8 {
     }
 };
 
-// IK0: v[0] holds u and is transformed as i k.x u (dft8<INV, true>)
-template <bool INV, int NB, bool IK0 = false>
+// NB lock-step transforms of one line held by 32 threads x 8 elements; v[nb][k] = x[t + 32 k] in, X[t + 32 k] out
+// IK0: v[0] holds u and is transformed as i k.x u (dft8<Ops, INV, true>)
+template <typename Ops, bool INV, int NB, bool IK0 = false>
 __device__ __forceinline__ void fft256_t32(v2 (&v)[NB][8], v2* reg, int nbs, int t, const Tw8& tw, const v2* kk = nullptr) {
     const int a = t & 7, qp = t >> 3;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        if (IK0 && nb == 0) dft8<INV, true>(v[nb], kk);
-        else dft8<INV>(v[nb]);
+        if (IK0 && nb == 0) dft8<Ops, INV, true>(v[nb], kk);
+        else dft8<Ops, INV>(v[nb]);
 #pragma unroll
-        for (int q = 1; q < 8; ++q) v[nb][q] = INV ? cmulv_conj(v[nb][q], tw.w256[q]) : cmulv(v[nb][q], tw.w256[q]);
+        for (int q = 1; q < 8; ++q) v[nb][q] = INV ? Ops::cmulv_conj(v[nb][q], tw.w256[q]) : Ops::cmulv(v[nb][q], tw.w256[q]);
     }
     exchange_sync<true>();
 #pragma unroll
@@ -1276,9 +699,9 @@ __device__ __forceinline__ void fft256_t32(v2 (&v)[NB][8], v2* reg, int nbs, int
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            bfly4<INV>(v[nb][4 * s2], v[nb][4 * s2 + 1], v[nb][4 * s2 + 2], v[nb][4 * s2 + 3]);   // index b -> c
+            bfly4<Ops, INV>(v[nb][4 * s2], v[nb][4 * s2 + 1], v[nb][4 * s2 + 2], v[nb][4 * s2 + 3]);   // index b -> c
 #pragma unroll
-            for (int c = 1; c < 4; ++c) v[nb][4 * s2 + c] = INV ? cmulv_conj(v[nb][4 * s2 + c], tw.w32[c]) : cmulv(v[nb][4 * s2 + c], tw.w32[c]);
+            for (int c = 1; c < 4; ++c) v[nb][4 * s2 + c] = INV ? Ops::cmulv_conj(v[nb][4 * s2 + c], tw.w32[c]) : Ops::cmulv(v[nb][4 * s2 + c], tw.w32[c]);
         }
     exchange_sync<true>();
 #pragma unroll
@@ -1292,11 +715,11 @@ __device__ __forceinline__ void fft256_t32(v2 (&v)[NB][8], v2* reg, int nbs, int
     for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[nb][k] = reg[nb * nbs + t * kE2 + k];   // thread t = q + 8 c reads a = 0 .. 7
-        dft8<INV>(v[nb]);
+        dft8<Ops, INV>(v[nb]);
     }
 }
 
-// the sum of squares of a workgroup's rows into the RMSE history (NW wavefronts; the order of the sum is the plain kernels')
+// the sum of squares of a workgroup's rows into the RMSE history (NW wavefronts)
 template <int NW>
 __device__ __forceinline__ void rows_sumsq(float ss, float* red, int lane, int wave, int b, float* __restrict__ sumsq,
                                            const int* __restrict__ it_counter, int sumsq_stride) {
@@ -1312,7 +735,7 @@ __device__ __forceinline__ void rows_sumsq(float ss, float* red, int lane, int w
 }
 
 // row pass at N = 256 (workgroup = 8 rows: 4 wavefronts x 2 rows, lane = 32 r + t); FLAGS: 1 add the column pass's partial, 2 the residual
-template <int FLAGS>
+template <typename Ops, int FLAGS>
 __device__ __forceinline__ void spec8_rows_body(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
                                                 const float* __restrict__ src, long src_sb, const SpecPtrs& tab, float* __restrict__ sumsq,
                                                 const int* __restrict__ it_counter, int sumsq_stride, v2* buf, float* red) {
@@ -1337,7 +760,7 @@ __device__ __forceinline__ void spec8_rows_body(const float* __restrict__ wf, fl
     v2 f[1][8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[0][k] = u[k];
-    fft256_t32<false, 1>(f, reg, kReg8, t, tw);
+    fft256_t32<Ops, false, 1>(f, reg, kReg8, t, tw);
     v2 d[2][8];
     v2 kk[8];
 #pragma unroll
@@ -1346,7 +769,7 @@ __device__ __forceinline__ void spec8_rows_body(const float* __restrict__ wf, fl
         d[0][p] = f[0][p];               // (0, k) * U     (spectral.py:50, 281): inside the transform
         d[1][p] = f[0][p] * kk[p].y;     // (-k^2, 0) * U  (spectral.py:52, 283)
     }
-    fft256_t32<true, 2, true>(d, reg, kReg8, t, tw, kk);
+    fft256_t32<Ops, true, 2, true>(d, reg, kReg8, t, tw, kk);
     // the other operands of the row: requested after the transforms (registers: 4 wavefronts per SIMD cover the round trip)
     v2 part[8], sv[8];
     float kq[8];
@@ -1367,7 +790,7 @@ __device__ __forceinline__ void spec8_rows_body(const float* __restrict__ wf, fl
 #pragma unroll
     for (unsigned k = 0; k < 8; ++k) {
         const float2 ca = tab.a[t + 32 * k], cb = tab.b[t + 32 * k];
-        v2 o = (cmulv(d[0][k], (v2){ca.x, ca.y}) + cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n + part[k];
+        v2 o = (Ops::cmulv(d[0][k], (v2){ca.x, ca.y}) + Ops::cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n + part[k];
         if (FLAGS & 2) o = o + u[k] * kq[k] - sv[k];
         po[lo + 32 * k] = o.x;
         poi[lo + 32 * k] = o.y;
@@ -1382,9 +805,29 @@ __global__ __launch_bounds__(256, 4) void k_spec8_rows(const float* __restrict__
     __shared__ v2 buf[4 * 2 * 2 * kReg8];
     __shared__ float red[4];
     // uniform; spec_apply passes 1 (Laplacian) or 3 (residual) and nothing else
-    if (flags & 2) spec8_rows_body<3>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
-    else spec8_rows_body<1>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+    if (flags & 2) spec8_rows_body<LeanOps, 3>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+    else spec8_rows_body<LeanOps, 1>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
 }
+__global__ __launch_bounds__(256, 4) void k_spec8_rows_plain(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
+                                                          const float* __restrict__ src, long src_sb, SpecPtrs tab, int flags,
+                                                          float* __restrict__ sumsq, const int* __restrict__ it_counter, int sumsq_stride) {
+    __shared__ v2 buf[4 * 2 * 2 * kReg8];
+    __shared__ float red[4];
+    if (flags & 2) spec8_rows_body<PlainOps, 3>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+    else spec8_rows_body<PlainOps, 1>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+}
+
+// ------------------------------------------------------------------------------------------
+// N = 512 = 8 x 8 x 8 on 64 threads x 8 elements per line (r3): the 256-point scheme above with one more factor of 2 in the
+// middle stage, one wavefront per line.  x[t + 64 k] --DFT8 over k--> A_t[q] x W_512^(t q) --exchange--> thread (a = t % 8, q):
+// DFT8 over b of A_(a + 8 b)[q] --> B_a[c][q] x W_64^(a c) --exchange--> thread u = q + 8 c: DFT8 over a --> X[u + 64 d]: the
+// layout of the input.  Both exchanges stay inside the wavefront that owns the line (wave-level fences, no workgroup barrier).
+// The radix-4 Stockham kernels this replaces at 512^2 run 5 exchange rounds per transform on 128 threads per line and address
+// global memory in 32-byte pieces in the column pass.
+// ------------------------------------------------------------------------------------------
+constexpr int kF1 = 72;            // exchange 1: slot q * 72 + t; reads a + 8 b of row q: the two rows of a 16-lane group sit 144 = 16 (mod 64) dwords apart
+constexpr int kF2 = 9;             // exchange 2: slot (q + 8 c) * 9 + a (stride 18 dwords: conflict-free)
+constexpr int kReg512 = 8 * kF1;   // float2 per transform region (= 64 * kF2)
 
 struct Tw512 {
     v2 w512[8], w64[8];
@@ -1396,15 +839,16 @@ struct Tw512 {
     }
 };
 
-template <bool INV, int NB, bool IK0 = false>
+// NB lock-step transforms of one line held by 64 threads x 8 elements; v[nb][k] = x[t + 64 k] in, X[t + 64 k] out
+template <typename Ops, bool INV, int NB, bool IK0 = false>
 __device__ __forceinline__ void fft512_t64(v2 (&v)[NB][8], v2* reg, int nbs, int t, const Tw512& tw, const v2* kk = nullptr) {
     const int a = t & 7, q = t >> 3;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        if (IK0 && nb == 0) dft8<INV, true>(v[nb], kk);
-        else dft8<INV>(v[nb]);
+        if (IK0 && nb == 0) dft8<Ops, INV, true>(v[nb], kk);
+        else dft8<Ops, INV>(v[nb]);
 #pragma unroll
-        for (int i = 1; i < 8; ++i) v[nb][i] = INV ? cmulv_conj(v[nb][i], tw.w512[i]) : cmulv(v[nb][i], tw.w512[i]);
+        for (int i = 1; i < 8; ++i) v[nb][i] = INV ? Ops::cmulv_conj(v[nb][i], tw.w512[i]) : Ops::cmulv(v[nb][i], tw.w512[i]);
     }
     exchange_sync<true>();
 #pragma unroll
@@ -1418,9 +862,9 @@ __device__ __forceinline__ void fft512_t64(v2 (&v)[NB][8], v2* reg, int nbs, int
         for (int b = 0; b < 8; ++b) v[nb][b] = reg[nb * nbs + q * kF1 + a + 8 * b];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        dft8<INV>(v[nb]);   // index b -> c
+        dft8<Ops, INV>(v[nb]);   // index b -> c
 #pragma unroll
-        for (int c = 1; c < 8; ++c) v[nb][c] = INV ? cmulv_conj(v[nb][c], tw.w64[c]) : cmulv(v[nb][c], tw.w64[c]);
+        for (int c = 1; c < 8; ++c) v[nb][c] = INV ? Ops::cmulv_conj(v[nb][c], tw.w64[c]) : Ops::cmulv(v[nb][c], tw.w64[c]);
     }
     exchange_sync<true>();
 #pragma unroll
@@ -1432,15 +876,18 @@ __device__ __forceinline__ void fft512_t64(v2 (&v)[NB][8], v2* reg, int nbs, int
     for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[nb][k] = reg[nb * nbs + t * kF2 + k];   // thread t = q + 8 c reads a = 0 .. 7
-        dft8<INV>(v[nb]);
+        dft8<Ops, INV>(v[nb]);
     }
 }
 
+// forward transform, derivative multipliers, two inverse transforms, PML coefficients of one 512-point line: u[k] = x[t + 64 k] in,
+// acc[k] = (a du + b ddu)[t + 64 k] out
+template <typename Ops>
 __device__ __forceinline__ void axis512(const v2 (&u)[8], v2 (&acc)[8], v2* reg, unsigned t, const Tw512& tw, const SpecPtrs& tab) {
     v2 f[1][8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[0][k] = u[k];
-    fft512_t64<false, 1>(f, reg, kReg512, t, tw);
+    fft512_t64<Ops, false, 1>(f, reg, kReg512, t, tw);
     v2 d[2][8];
     v2 kk[8];
 #pragma unroll
@@ -1449,17 +896,19 @@ __device__ __forceinline__ void axis512(const v2 (&u)[8], v2 (&acc)[8], v2* reg,
         d[0][p] = f[0][p];               // (0, k) * U     (spectral.py:50, 281): inside the transform
         d[1][p] = f[0][p] * kk[p].y;     // (-k^2, 0) * U  (spectral.py:52, 283)
     }
-    fft512_t64<true, 2, true>(d, reg, kReg512, t, tw, kk);
+    fft512_t64<Ops, true, 2, true>(d, reg, kReg512, t, tw, kk);
     constexpr float inv_n = 1.0f / 512.0f;
 #pragma unroll
     for (unsigned k = 0; k < 8; ++k) {
         const float2 ca = tab.a[t + 64 * k], cb = tab.b[t + 64 * k];
-        acc[k] = (cmulv(d[0][k], (v2){ca.x, ca.y}) + cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n;
+        acc[k] = (Ops::cmulv(d[0][k], (v2){ca.x, ca.y}) + Ops::cmulv(d[1][k], (v2){cb.x, cb.y})) * inv_n;
     }
 }
 
-// row pass at N = 512: workgroup = 8 rows, one wavefront per row (see plain::k_spec512_rows for the choice of 8)
-template <int FLAGS>
+// row pass at N = 512: workgroup = 8 rows, one wavefront per row.  (With 4 rows per workgroup the 128 workgroups of a sample each add their sum
+// of squares to ONE address: same-address float atomics are serialised at the memory side, and in the solver loop -- where the RMSE
+// history is on -- the kernel took 55 us instead of the 35 us it takes alone.  64 per sample, as the radix-4 kernel has, are hidden.)
+template <typename Ops, int FLAGS>
 __device__ __forceinline__ void spec512_rows_body(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
                                                   const float* __restrict__ src, long src_sb, const SpecPtrs& tab, float* __restrict__ sumsq,
                                                   const int* __restrict__ it_counter, int sumsq_stride, v2* buf, float* red) {
@@ -1481,7 +930,7 @@ __device__ __forceinline__ void spec512_rows_body(const float* __restrict__ wf, 
         for (unsigned k = 0; k < 8; ++k) u[k] = (v2){pre[t + 64 * k], pim[t + 64 * k]};
         Tw512 tw;
         tw.load(t, tab.tw);
-        axis512(u, acc, buf + wave * 2 * kReg512, t, tw, tab);
+        axis512<Ops>(u, acc, buf + wave * 2 * kReg512, t, tw, tab);
     }
     const float* pk = ksq + (long)b * plane + ro;
     const float* ps = src + (long)b * src_sb + ro;
@@ -1513,110 +962,51 @@ __global__ __launch_bounds__(512, 2) void k_spec512_rows(const float* __restrict
     __shared__ v2 buf[8 * 2 * kReg512];
     __shared__ float red[8];
     // uniform; spec_apply passes 1 (Laplacian) or 3 (residual) and nothing else
-    if (flags & 2) spec512_rows_body<3>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
-    else spec512_rows_body<1>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+    if (flags & 2) spec512_rows_body<LeanOps, 3>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+    else spec512_rows_body<LeanOps, 1>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+}
+__global__ __launch_bounds__(512, 2) void k_spec512_rows_plain(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
+                                                             const float* __restrict__ src, long src_sb, SpecPtrs tab, int flags,
+                                                             float* __restrict__ sumsq, const int* __restrict__ it_counter, int sumsq_stride) {
+    __shared__ v2 buf[8 * 2 * kReg512];
+    __shared__ float red[8];
+    if (flags & 2) spec512_rows_body<PlainOps, 3>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
+    else spec512_rows_body<PlainOps, 1>(wf, out, ksq, src, src_sb, tab, sumsq, it_counter, sumsq_stride, buf, red);
 }
 
-// column pass at N = 512 (plain::k_spec512_cols_t has the layout)
-__global__ __launch_bounds__(1024) void k_spec512_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
-                                                        int* __restrict__ it_counter) {
-    constexpr int N = 512, COLS = 16, NT = 1024, P = kCols512P, SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
-    extern __shared__ v2 cbuf512[];   // [COLS][P]
-    const int tid = threadIdx.x, t = tid & 63, wave = tid >> 6;
-    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
-    const TileId tl = xcd_tile();
+// The transposed column passes move global memory as float4 row segments: a workgroup of NT threads owns COLS columns x all N rows
+// of one sample, a wave instruction covers 64 / (COLS / 4) rows x COLS * 4 contiguous bytes.  cols_stage_in loads the N / (NT / (COLS / 4))
+// segments of a thread and writes them TRANSPOSED into LDS (column c at cbuf + c * P, (re, im) interleaved); cols_stage_out stores the
+// columns' results the way they were loaded.  g: the sample's plane at the workgroup's first column.  8 P = 8 (mod 64) dwords puts the
+// COLS / 4 float4 segments of a row on disjoint banks for the transposed writes and reads.
+template <int N, int COLS, int NT, int P>
+__device__ __forceinline__ void cols_stage_in(v2* cbuf, const float* g, int tid) {
+    constexpr int SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
     const long plane = (long)N * N;
     const int seg = tid % SEG, rr = tid / SEG;
-    const float* pre = wf + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-    Tw512 tw;
-    tw.load(t, tab.tw);
-    {
-        float4 re[NP], im[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const long o = (long)(rr + RPP * i) * N;
-            re[i] = *reinterpret_cast<const float4*>(pre + o);
-            im[i] = *reinterpret_cast<const float4*>(pre + o + plane);
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            v2* q = cbuf512 + (4 * seg) * P + rr + RPP * i;
-            q[0] = (v2){re[i].x, im[i].x};
-            q[P] = (v2){re[i].y, im[i].y};
-            q[2 * P] = (v2){re[i].z, im[i].z};
-            q[3 * P] = (v2){re[i].w, im[i].w};
-        }
-    }
-    __syncthreads();
-    {
-        v2* reg = cbuf512 + wave * P;
-        v2 u[8], acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) u[k] = reg[t + 64 * k];
-        axis512(u, acc, reg, t, tw, tab);   // the first exchange overwrites the column's region: every lane of the wavefront has read its inputs
-        exchange_sync<true>();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) reg[t + 64 * k] = acc[k];
-    }
-    __syncthreads();
-    float* po = out + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
+    const float* pre = g + 4 * seg;
+    float4 re[NP], im[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const v2* q = cbuf512 + (4 * seg) * P + rr + RPP * i;
-        const v2 a = q[0], b = q[P], c = q[2 * P], d4 = q[3 * P];
         const long o = (long)(rr + RPP * i) * N;
-        *reinterpret_cast<float4*>(po + o) = make_float4(a.x, b.x, c.x, d4.x);
-        *reinterpret_cast<float4*>(po + o + plane) = make_float4(a.y, b.y, c.y, d4.y);
+        re[i] = *reinterpret_cast<const float4*>(pre + o);
+        im[i] = *reinterpret_cast<const float4*>(pre + o + plane);
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        v2* q = cbuf + (4 * seg) * P + rr + RPP * i;
+        q[0] = (v2){re[i].x, im[i].x};
+        q[P] = (v2){re[i].y, im[i].y};
+        q[2 * P] = (v2){re[i].z, im[i].z};
+        q[3 * P] = (v2){re[i].w, im[i].w};
     }
 }
-
-// column pass at N = 256, coalesced through an LDS transpose (plain::k_spec16_cols_t has the layout)
-template <int COLS>
-__global__ __launch_bounds__(COLS * 16) void k_spec16_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
-                                                           int* __restrict__ it_counter) {
-    constexpr int N = 256, NT = COLS * 16, P = kColsP, SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
-    extern __shared__ v2 cbuf[];   // [COLS][P], then the tables
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
-    const TileId tl = xcd_tile();
+template <int N, int COLS, int NT, int P>
+__device__ __forceinline__ void cols_stage_out(float* g, const v2* cbuf, int tid) {
+    constexpr int SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
     const long plane = (long)N * N;
     const int seg = tid % SEG, rr = tid / SEG;
-    const LdsTabs ltab = stage_tables_256<NT>(reinterpret_cast<float*>(cbuf + COLS * P), tab, tid);
-    const float* pre = wf + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-    {
-        float4 re[NP], im[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const long o = (long)(rr + RPP * i) * N;
-            re[i] = *reinterpret_cast<const float4*>(pre + o);
-            im[i] = *reinterpret_cast<const float4*>(pre + o + plane);
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            v2* q = cbuf + (4 * seg) * P + rr + RPP * i;
-            q[0] = (v2){re[i].x, im[i].x};
-            q[P] = (v2){re[i].y, im[i].y};
-            q[2 * P] = (v2){re[i].z, im[i].z};
-            q[3 * P] = (v2){re[i].w, im[i].w};
-        }
-    }
-    __syncthreads();
-    {
-        const int t = lane & 15, cl = wave * 4 + (lane >> 4);
-        v2* reg = cbuf + cl * P;
-        v2 u[16], d[2][16], acc[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) u[k] = reg[t + 16 * k];
-        // (parenthesised: the argument type plain::LdsTabs would otherwise bring plain's functions of the same names in)
-        (axis_forward16)(u, d, reg, kReg16Rows, t, ltab);   // the first exchange overwrites the column's region: every lane of the wave has read its inputs
-        xchg16<2>(d, reg, kReg16Rows, t);
-        (axis_finish16)(d, acc, t, ltab);
-        exchange_sync<true>();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) reg[t + 16 * k] = acc[k];
-    }
-    __syncthreads();
-    float* po = out + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
+    float* po = g + 4 * seg;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const v2* q = cbuf + (4 * seg) * P + rr + RPP * i;
@@ -1627,44 +1017,200 @@ __global__ __launch_bounds__(COLS * 16) void k_spec16_cols_t(const float* __rest
     }
 }
 
+// column pass at N = 512, coalesced through the LDS transpose: a workgroup owns 16 columns x all 512 rows of a sample (16 wavefronts,
+// one per column); column c lives at cbuf + c * kCols512P: its 512 inputs first, then the 2 x 576 float2 of the lock-step inverse
+// exchange, finally its 512 outputs.
+constexpr int kCols512P = 1153;
+
+template <typename Ops>
+__device__ __forceinline__ void spec512_cols_body(const float* wf, float* out, const SpecPtrs& tab, int* it_counter, v2* cbuf) {   // cbuf: [COLS][P]
+    constexpr int N = 512, COLS = 16, NT = 1024, P = kCols512P;
+    const int tid = threadIdx.x, t = tid & 63, wave = tid >> 6;
+    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
+    const TileId tl = xcd_tile();
+    const long plane = (long)N * N;
+    Tw512 tw;
+    tw.load(t, tab.tw);
+    cols_stage_in<N, COLS, NT, P>(cbuf, wf + (long)tl.y * 2 * plane + tl.x * COLS, tid);
+    __syncthreads();
+    {
+        v2* reg = cbuf + wave * P;
+        v2 u[8], acc[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) u[k] = reg[t + 64 * k];
+        axis512<Ops>(u, acc, reg, t, tw, tab);   // the first exchange overwrites the column's region: every lane of the wavefront has read its inputs
+        exchange_sync<true>();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) reg[t + 64 * k] = acc[k];
+    }
+    __syncthreads();
+    cols_stage_out<N, COLS, NT, P>(out + (long)tl.y * 2 * plane + tl.x * COLS, cbuf, tid);
+}
+
+__global__ __launch_bounds__(1024) void k_spec512_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
+                                                        int* __restrict__ it_counter) {
+    extern __shared__ v2 cbuf512[];
+    spec512_cols_body<LeanOps>(wf, out, tab, it_counter, cbuf512);
+}
+__global__ __launch_bounds__(1024) void k_spec512_cols_t_plain(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
+                                                              int* __restrict__ it_counter) {
+    extern __shared__ v2 cbuf512[];
+    spec512_cols_body<PlainOps>(wf, out, tab, it_counter, cbuf512);
+}
+
+constexpr int kReg16Rows = 272;   // float2 per transform region: 16 x 17; 544 dwords = 32 (mod 64): the two transforms of a 32-lane group on disjoint banks
+constexpr int kReg16Cols = 280;   // 560 dwords = 48 (mod 64): the four transforms of a 32-lane group (lane = 4 t + c) on disjoint quarters
+
+// column pass at N = 256: workgroup = 16 columns (4 wavefronts x 4 columns), lane = 4 t + c
+__global__ __launch_bounds__(256) void k_spec16_cols(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
+                                                     int* __restrict__ it_counter) {
+    constexpr int N = 256;
+    __shared__ v2 buf[4 * 4 * 2 * kReg16Cols];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = lane >> 2, c = lane & 3;
+    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) atomicAdd(it_counter, 1);
+    const TileId tl = xcd_tile();   // sample -> XCD as in the UNet kernels: the wavefield decode0 just wrote and the partial the row pass reads next stay in one L2
+    const int col = tl.x * 16 + wave * 4 + c;
+    const long plane = (long)N * N;
+    const float* pre = wf + (long)tl.y * 2 * plane + col;
+    v2 u[16], d[2][16], acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const long o = (long)(t + 16 * k) * N;
+        u[k] = (v2){pre[o], pre[o + plane]};
+    }
+    v2* reg = buf + (wave * 4 + c) * 2 * kReg16Cols;
+    axis_forward16<PlainOps>(u, d, reg, kReg16Cols, t, tab);
+    xchg16<2>(d, reg, kReg16Cols, t);
+    axis_finish16<PlainOps>(d, acc, t, tab);
+    float* po = out + (long)tl.y * 2 * plane + col;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const long o = (long)(t + 16 * k) * N;
+        po[o] = acc[k].x;
+        po[o + plane] = acc[k].y;
+    }
+}
+
+// column pass at N = 256, coalesced through the LDS transpose (r3).  k_spec16_cols above addresses global memory as 16 rows x 16
+// bytes per wave instruction.  Here a block owns COLS columns x all 256 rows of one sample: it stages them through cols_stage_in,
+// runs the two radix-16 passes per column out of LDS with the 16 threads of a transform on consecutive lanes (lane = 16 c' + t: the
+// exchange pattern of the row kernel, whose conflicts are 1.6 cycles per LDS instruction against 24 for lane = 4 t + c), writes the
+// result back into the column's region and stores it the way it was loaded.  P = 545 float2: a column region holds the 2 x 272
+// float2 of the lock-step inverse exchange.
+constexpr int kColsP = 545;
+
+template <typename Ops, int COLS>
+__device__ __forceinline__ void spec16_cols_body(const float* wf, float* out, const SpecPtrs& tab, int* it_counter, v2* cbuf) {   // cbuf: [COLS][P], then the tables
+    constexpr int N = 256, NT = COLS * 16, P = kColsP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
+    const TileId tl = xcd_tile();
+    const long plane = (long)N * N;
+    const LdsTabs ltab = stage_tables_256<NT>(reinterpret_cast<float*>(cbuf + COLS * P), tab, tid);
+    cols_stage_in<N, COLS, NT, P>(cbuf, wf + (long)tl.y * 2 * plane + tl.x * COLS, tid);
+    __syncthreads();
+    {
+        const int t = lane & 15, cl = wave * 4 + (lane >> 4);
+        v2* reg = cbuf + cl * P;
+        v2 u[16], d[2][16], acc[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) u[k] = reg[t + 16 * k];
+        axis_forward16<Ops>(u, d, reg, kReg16Rows, t, ltab);   // the first exchange overwrites the column's region: every lane of the wave has read its inputs
+        xchg16<2>(d, reg, kReg16Rows, t);
+        axis_finish16<Ops>(d, acc, t, ltab);
+        exchange_sync<true>();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) reg[t + 16 * k] = acc[k];
+    }
+    __syncthreads();
+    cols_stage_out<N, COLS, NT, P>(out + (long)tl.y * 2 * plane + tl.x * COLS, cbuf, tid);
+}
+
+template <int COLS>
+__global__ __launch_bounds__(COLS * 16) void k_spec16_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
+                                                           int* __restrict__ it_counter) {
+    extern __shared__ v2 cbuf[];
+    spec16_cols_body<LeanOps, COLS>(wf, out, tab, it_counter, cbuf);
+}
+template <int COLS>
+__global__ __launch_bounds__(COLS * 16) void k_spec16_cols_t_plain(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
+                                                                 int* __restrict__ it_counter) {
+    extern __shared__ v2 cbuf[];
+    spec16_cols_body<PlainOps, COLS>(wf, out, tab, it_counter, cbuf);
+}
+
+// row pass at N = 256: workgroup = 16 rows (4 wavefronts x 4 rows), lane = 16 r + t
+__global__ __launch_bounds__(256) void k_spec16_rows(const float* __restrict__ wf, float* __restrict__ out, const float* __restrict__ ksq,
+                                                     const float* __restrict__ src, long src_sb, SpecPtrs tab, int flags,
+                                                     float* __restrict__ sumsq, const int* __restrict__ it_counter, int sumsq_stride) {
+    constexpr int N = 256;
+    __shared__ v2 buf[4 * 4 * 2 * kReg16Rows];
+    __shared__ float red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = lane & 15, r = lane >> 4;
+    const TileId tl = xcd_tile();
+    const int row = tl.x * 16 + wave * 4 + r, b = tl.y;
+    const long plane = (long)N * N, ro = (long)row * N;
+    const float* pre = wf + (long)b * 2 * plane + ro;
+    float* po = out + (long)b * 2 * plane + ro;
+    v2 u[16], d[2][16], acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) u[k] = (v2){pre[t + 16 * k], pre[plane + t + 16 * k]};
+    v2* reg = buf + (wave * 4 + r) * 2 * kReg16Rows;
+    axis_forward16<PlainOps>(u, d, reg, kReg16Rows, t, tab);
+    xchg16<2>(d, reg, kReg16Rows, t);
+    // the other operands of the row are requested now (the twiddles are dead: registers are free) and arrive while the last
+    // radix-16 pass runs
+    v2 part[16], sv[16];
+    float kq[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int x = t + 16 * k;
+        part[k] = (flags & 1) ? (v2){po[x], po[plane + x]} : (v2){0.f, 0.f};
+        kq[k] = 0.f;
+        sv[k] = (v2){0.f, 0.f};
+        if (flags & 2) {
+            kq[k] = ksq[(long)b * plane + ro + x];
+            const float* ps = src + (long)b * src_sb + ro + x;
+            sv[k] = (v2){ps[0], ps[plane]};
+        }
+    }
+    axis_finish16<PlainOps>(d, acc, t, tab);
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int x = t + 16 * k;
+        v2 o = acc[k] + part[k];
+        if (flags & 2) o = o + u[k] * kq[k] - sv[k];
+        po[x] = o.x;
+        po[plane + x] = o.y;
+        ss += o.x * o.x + o.y * o.y;
+    }
+    if (sumsq != nullptr) rows_sumsq<4>(ss, red, lane, wave, b, sumsq, it_counter, sumsq_stride);
+}
+
 // column pass at N = 256 on the 8 x 4 x 8 transform of the row pass (HN_OPT_SPECTRAL_COLS 3): k_spec16_cols_t's coalesced float4
 // staging through the LDS transpose, then 32 threads x 8 elements per column, two columns per wavefront: 512 threads for 16 columns
 // at <= 128 registers, two workgroups per CU = four wavefronts per SIMD where k_spec16_cols_t<16> (206 registers) has two.  A
 // column's region is its 256 inputs, then the 288 float2 of ONE transform's exchanges -- the two inverse transforms run one after
 // the other in it (in lock step they would need 2 x 288: 82 KB per workgroup with the tables, and two of those do not fit a CU)
 // -- finally its 256 outputs.  8 * 289 = 8 (mod 64) dwords: the four float4 segments of a row on disjoint banks, as with kColsP.
-// Another factorisation than the radix-16 column kernels: the same result to fp32 rounding, not the same bits.
+// Another factorisation than the radix-16 column kernels: the same result to fp32 rounding, not the same bits.  LeanOps only.
 constexpr int kCols8P = 289;
 static_assert(kCols8P >= kReg8, "a column region holds one transform's exchanges");
 
 __global__ __launch_bounds__(512, 2) void k_spec8_cols_t(const float* __restrict__ wf, float* __restrict__ out, SpecPtrs tab,
                                                        int* __restrict__ it_counter) {
-    constexpr int N = 256, COLS = 16, NT = 512, P = kCols8P, SEG = COLS / 4, RPP = NT / SEG, NP = N / RPP;
+    using Ops = LeanOps;
+    constexpr int N = 256, COLS = 16, NT = 512, P = kCols8P;
     extern __shared__ v2 cbuf8[];   // [COLS][P], then the tables
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (it_counter != nullptr && (blockIdx.x | blockIdx.y | tid) == 0) atomicAdd(it_counter, 1);
     const TileId tl = xcd_tile();
     const long plane = (long)N * N;
-    const int seg = tid % SEG, rr = tid / SEG;
     const LdsTabs ltab = stage_tables_256<NT>(reinterpret_cast<float*>(cbuf8 + COLS * P), tab, tid);
-    const float* pre = wf + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-    {
-        float4 re[NP], im[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const long o = (long)(rr + RPP * i) * N;
-            re[i] = *reinterpret_cast<const float4*>(pre + o);
-            im[i] = *reinterpret_cast<const float4*>(pre + o + plane);
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            v2* q = cbuf8 + (4 * seg) * P + rr + RPP * i;
-            q[0] = (v2){re[i].x, im[i].x};
-            q[P] = (v2){re[i].y, im[i].y};
-            q[2 * P] = (v2){re[i].z, im[i].z};
-            q[3 * P] = (v2){re[i].w, im[i].w};
-        }
-    }
+    cols_stage_in<N, COLS, NT, P>(cbuf8, wf + (long)tl.y * 2 * plane + tl.x * COLS, tid);
     __syncthreads();
     {
         const int t = lane & 31, cl = wave * 2 + (lane >> 5);
@@ -1674,7 +1220,7 @@ __global__ __launch_bounds__(512, 2) void k_spec8_cols_t(const float* __restrict
         v2 f[1][8], d0[1][8], d1[1][8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[0][k] = reg[t + 32 * k];
-        fft256_t32<false, 1>(f, reg, 0, t, tw);   // the first exchange overwrites the column's region: every lane of the wavefront has read its inputs
+        fft256_t32<Ops, false, 1>(f, reg, 0, t, tw);   // the first exchange overwrites the column's region: every lane of the wavefront has read its inputs
         v2 kk[8];
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
@@ -1682,29 +1228,21 @@ __global__ __launch_bounds__(512, 2) void k_spec8_cols_t(const float* __restrict
             d0[0][p] = f[0][p];               // (0, k) * U     (spectral.py:50, 281): inside the transform
             d1[0][p] = f[0][p] * kk[p].y;     // (-k^2, 0) * U  (spectral.py:52, 283)
         }
-        fft256_t32<true, 1, true>(d0, reg, 0, t, tw, kk);
-        fft256_t32<true, 1>(d1, reg, 0, t, tw);
+        fft256_t32<Ops, true, 1, true>(d0, reg, 0, t, tw, kk);
+        fft256_t32<Ops, true, 1>(d1, reg, 0, t, tw);
         constexpr float inv_n = 1.0f / 256.0f;
         v2 acc[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const float2 ca = ltab.a[t + 32 * k], cb = ltab.b[t + 32 * k];
-            acc[k] = (cmulv(d0[0][k], (v2){ca.x, ca.y}) + cmulv(d1[0][k], (v2){cb.x, cb.y})) * inv_n;
+            acc[k] = (Ops::cmulv(d0[0][k], (v2){ca.x, ca.y}) + Ops::cmulv(d1[0][k], (v2){cb.x, cb.y})) * inv_n;
         }
         exchange_sync<true>();
 #pragma unroll
         for (int k = 0; k < 8; ++k) reg[t + 32 * k] = acc[k];
     }
     __syncthreads();
-    float* po = out + (long)tl.y * 2 * plane + tl.x * COLS + 4 * seg;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const v2* q = cbuf8 + (4 * seg) * P + rr + RPP * i;
-        const v2 a = q[0], b = q[P], c = q[2 * P], d4 = q[3 * P];
-        const long o = (long)(rr + RPP * i) * N;
-        *reinterpret_cast<float4*>(po + o) = make_float4(a.x, b.x, c.x, d4.x);
-        *reinterpret_cast<float4*>(po + o + plane) = make_float4(a.y, b.y, c.y, d4.y);
-    }
+    cols_stage_out<N, COLS, NT, P>(out + (long)tl.y * 2 * plane + tl.x * COLS, cbuf8, tid);
 }
 
 __global__ void k_bump(int* counter) { atomicAdd(counter, 1); }
@@ -2170,29 +1708,29 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
                     const bool pl = ctx->opt_spec_plain != 0;
                     {
                         ProfScope ps(ctx, KID_SPEC_COLS, s);
-                        if (ctx->opt_cols_t == 0) hipLaunchKernelGGL(plain::k_spec16_cols, dim3(16, batch), dim3(256), 0, s, wf, out, p, it_counter);
+                        if (ctx->opt_cols_t == 0) hipLaunchKernelGGL(k_spec16_cols, dim3(16, batch), dim3(256), 0, s, wf, out, p, it_counter);
                         else if (ctx->opt_cols_t == 3)   // 45 KB of dynamic LDS: below the limit that needs the attribute
                             hipLaunchKernelGGL(k_spec8_cols_t, dim3(16, batch), dim3(512), 16 * kCols8P * 8 + kLdsTabFloats * 4, s, wf, out, p, it_counter);
                         else {
                             if (!ctx->cols_t_attr_set) {
-                                for (auto* k : {k_spec16_cols_t<16>, plain::k_spec16_cols_t<16>})
+                                for (auto* k : {k_spec16_cols_t<16>, k_spec16_cols_t_plain<16>})
                                     HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kColsP * 8 + kLdsTabFloats * 4));
-                                for (auto* k : {k_spec16_cols_t<32>, plain::k_spec16_cols_t<32>})
+                                for (auto* k : {k_spec16_cols_t<32>, k_spec16_cols_t_plain<32>})
                                     HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * kColsP * 8 + kLdsTabFloats * 4));
                                 ctx->cols_t_attr_set = true;
                             }
                             if (ctx->opt_cols_t == 1)
-                                hipLaunchKernelGGL((pl ? plain::k_spec16_cols_t<16> : k_spec16_cols_t<16>), dim3(16, batch), dim3(256), 16 * kColsP * 8 + kLdsTabFloats * 4, s, wf, out, p, it_counter);
+                                hipLaunchKernelGGL((pl ? k_spec16_cols_t_plain<16> : k_spec16_cols_t<16>), dim3(16, batch), dim3(256), 16 * kColsP * 8 + kLdsTabFloats * 4, s, wf, out, p, it_counter);
                             else
-                                hipLaunchKernelGGL((pl ? plain::k_spec16_cols_t<32> : k_spec16_cols_t<32>), dim3(8, batch), dim3(512), 32 * kColsP * 8 + kLdsTabFloats * 4, s, wf, out, p, it_counter);
+                                hipLaunchKernelGGL((pl ? k_spec16_cols_t_plain<32> : k_spec16_cols_t<32>), dim3(8, batch), dim3(512), 32 * kColsP * 8 + kLdsTabFloats * 4, s, wf, out, p, it_counter);
                         }
                     }
                     ProfScope ps(ctx, KID_SPEC_ROWS, s);
                     if (ctx->opt_radix16 == 2)
-                        hipLaunchKernelGGL(plain::k_spec16_rows, dim3(16, batch), dim3(256), 0, s, wf, out, ksq, src, src_sb, p, 1 | (resid ? 2 : 0),
+                        hipLaunchKernelGGL(k_spec16_rows, dim3(16, batch), dim3(256), 0, s, wf, out, ksq, src, src_sb, p, 1 | (resid ? 2 : 0),
                                            accum_sumsq, it_counter, sumsq_stride);
                     else
-                        hipLaunchKernelGGL((pl ? plain::k_spec8_rows : k_spec8_rows), dim3(32, batch), dim3(256), 0, s, wf, out, ksq, src, src_sb, p, 1 | (resid ? 2 : 0),
+                        hipLaunchKernelGGL((pl ? k_spec8_rows_plain : k_spec8_rows), dim3(32, batch), dim3(256), 0, s, wf, out, ksq, src, src_sb, p, 1 | (resid ? 2 : 0),
                                            accum_sumsq, it_counter, sumsq_stride);
                 } else {
                     launch_pow2<256>(ctx, wf, out, ksq, src, src_sb, batch, p, resid, accum_sumsq, s, it_counter, sumsq_stride);
@@ -2202,16 +1740,16 @@ int spec_apply(hn_ctx* ctx, const float* wf, float* out, const float* ksq, const
                 if (ctx->opt_radix16) {   // 8 x 8 x 8 register-resident passes, column pass through an LDS transpose (r3)
                     const bool pl = ctx->opt_spec_plain != 0;
                     if (!ctx->cols512_attr_set) {
-                        for (auto* k : {k_spec512_cols_t, plain::k_spec512_cols_t})
+                        for (auto* k : {k_spec512_cols_t, k_spec512_cols_t_plain})
                             HN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kCols512P * 8));
                         ctx->cols512_attr_set = true;
                     }
                     {
                         ProfScope ps(ctx, KID_SPEC_COLS, s);
-                        hipLaunchKernelGGL((pl ? plain::k_spec512_cols_t : k_spec512_cols_t), dim3(32, batch), dim3(1024), 16 * kCols512P * 8, s, wf, out, p, it_counter);
+                        hipLaunchKernelGGL((pl ? k_spec512_cols_t_plain : k_spec512_cols_t), dim3(32, batch), dim3(1024), 16 * kCols512P * 8, s, wf, out, p, it_counter);
                     }
                     ProfScope ps(ctx, KID_SPEC_ROWS, s);
-                    hipLaunchKernelGGL((pl ? plain::k_spec512_rows : k_spec512_rows), dim3(64, batch), dim3(512), 0, s, wf, out, ksq, src, src_sb, p, 1 | (resid ? 2 : 0), accum_sumsq,
+                    hipLaunchKernelGGL((pl ? k_spec512_rows_plain : k_spec512_rows), dim3(64, batch), dim3(512), 0, s, wf, out, ksq, src, src_sb, p, 1 | (resid ? 2 : 0), accum_sumsq,
                                        it_counter, sumsq_stride);
                 } else {
                     launch_pow2<512>(ctx, wf, out, ksq, src, src_sb, batch, p, resid, accum_sumsq, s, it_counter, sumsq_stride);

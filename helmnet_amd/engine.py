@@ -246,8 +246,8 @@ class Engine:
         changing one re-builds them; counter('spectral_route') tells which kernels the domain runs on (1 power of two, 2 prime-factor, 3 dense,
         4 mixed, 5 rectangular).
         'spectral_cols' 0..2 is bit-exact: for a fixed 'spectral_radix16' these three column kernels give the same bits (with 'spectral_radix16' 0 it
-        is not read); 3 is another factorisation (fp32 rounding).  'spectral_plain' (laboratory knob) 1: the 256- / 512-point kernels on plain C++
-        complex helpers, bit-identical to 0.  'spectral_radix16' and 'spectral_pfa' select other kernels for the same fp32 arithmetic: results agree to fp32 rounding (every
+        is not read); 3 is another factorisation (fp32 rounding).  'spectral_plain' (laboratory knob) 1: the 256- / 512-point kernel bodies instantiated on
+        plain C++ complex helpers (k_spec*_plain), bit-identical to 0.  'spectral_radix16' and 'spectral_pfa' select other kernels for the same fp32 arithmetic: results agree to fp32 rounding (every
         combination is within 1e-6 of the operator's scale of the float64 oracle, the dense operator within 7e-6), not bit for bit.  Neither makes a
         sample's result depend on what shares its batch (tests/test_spectral_gpu.py).
         'f64_fft' 0/1 (default 0) picks the route of the float64 operator (laplacian64, residual64, step64, the refine cycles): 0 the dense kernel, 1 two

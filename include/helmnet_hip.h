@@ -202,8 +202,8 @@ enum hn_option {
     HN_EXP_TRAIN_LANES = 101, /* hn_train_grad: 1 (default) the whole batch as one chain of launches; 2: the two halves of the batch as
                               * two chains on two streams.  Same gradient up to the order of the final sum over the halves; measured equal to 1 */
     HN_EXP_SPECTRAL_PLAIN = 102 /* 0 (default): the 256-point 8x4x8 row pass, the 256-point transposed column pass and both 512-point passes multiply and
-                              * rotate complex numbers with the swap and the sign in the operand modifiers of the packed instructions, and take the
-                              * residual flags at compile time; 1: the same kernels on plain C++ helpers with run-time flags, as before.  Bit-identical
+                              * rotate complex numbers with the swap and the sign in the operand modifiers of the packed instructions; 1: the same
+                              * kernel bodies instantiated on plain C++ helpers (kernel names with the suffix _plain).  Bit-identical
                               * (same products, same fused multiply-adds); for the bit-identity test and in-process A/B runs                 */
 };
 /* Diagnostics counters (hn_get_counter). */

@@ -1,6 +1,6 @@
 """The lean forms of the 256- and 512-point spectral kernels (hn_spectral.hip: complex multiplies and +-i rotations with the swap and the sign in
-the operand modifiers of the packed instructions, residual flags at compile time) against the same kernels on the plain C++ helpers
-(HN_EXP_SPECTRAL_PLAIN 1, namespace plain).  The lean forms claim the SAME products and the SAME fused multiply-adds: every comparison here is
+the operand modifiers of the packed instructions: the LeanOps policy) against the same kernel bodies instantiated on the plain C++ helpers
+(HN_EXP_SPECTRAL_PLAIN 1: the PlainOps policy, kernels k_spec*_plain).  The lean forms claim the SAME products and the SAME fused multiply-adds: every comparison here is
 torch.equal, on the probes of spectral_probes.py (noise, single modes along x and y, impulses) and on one solver iteration."""
 import pytest
 import torch
