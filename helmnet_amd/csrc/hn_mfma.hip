@@ -45,21 +45,6 @@ __device__ __forceinline__ float div1000(float x) {
     const float e = fmaf(-qv, 1000.0f, x);
     return fmaf(e, r, qv);
 }
-// Timing ablations of the staging of k_dc_mfma_s, k_down_mfma and k_up_mfma (non-ALL instances; tools/build_variant.sh <name> hn_mfma.hip -DHN_MC_ABL=<bits>;
-// the results are WRONG, only the durations mean something -- profiles/mc_stage_ablation.txt).  Bits: 1 no global loads of the input after the first chunk
-// (k_down_mfma: after the first two channels, as HN_DN_ABL of r5), 2 no LDS commits after it, 4 no barriers after it, 8 the staging plan replaced by a
-// trivial one (no divisions, bounds tests or zero fill: every lane loads offset 0 and commits to its dummy slot), 16 no input loads, commits or barriers
-// at all (but the first chunk's commit, of zeros: LDS nobody writes would let the compiler drop the operand reads and the MFMAs with them): the weight loads,
-// the operand reads, the MFMAs and the epilogue remain.
-#ifndef HN_MC_ABL
-#ifdef HN_DN_ABL
-#define HN_MC_ABL HN_DN_ABL
-#else
-#define HN_MC_ABL 0
-#endif
-#endif
-constexpr int kMcAbl = HN_MC_ABL;
-
 // Scheduling hint for one pipelined step: N x (1 MFMA, then 1 LDS read issued in its shadow).
 template <int N>
 __device__ __forceinline__ void interleave_mfma_dsread() {
@@ -133,6 +118,22 @@ struct McEpi {
     long z_sb = 0, z_sc = 0;
     const float* wf_in = nullptr;   // the wavefield the update starts from: wf itself (in place), or another buffer (hn_step's zero-copy wavefield history)
 };
+
+// The final layer's stores for two adjacent pixels of one row, re and im planes: d itself (where asked for), then wf <- d / 1e3 + wf_old
+// (hybridnet.py:570; `old` was read from epi.wf_in up front, so the update exposes no global round trip).  The address inside the
+// [b][2][H][W] tensors is (float offset rowf, wave-uniform where the caller can keep it so) + (32-bit byte offset offb).
+__device__ __forceinline__ void wf_update(const McEpi& epi, long rowf, unsigned offb, long plane, float2 re, float2 im, const float2 (&old)[2]) {
+    if (epi.d_out) {
+        char* row = reinterpret_cast<char*>(epi.d_out + rowf);
+        *reinterpret_cast<float2*>(row + offb) = re;
+        *reinterpret_cast<float2*>(row + 4 * plane + offb) = im;
+    }
+    if (epi.wf) {
+        char* row = reinterpret_cast<char*>(epi.wf + rowf);
+        *reinterpret_cast<float2*>(row + offb) = make_float2(div1000(re.x) + old[0].x, div1000(re.y) + old[0].y);
+        *reinterpret_cast<float2*>(row + 4 * plane + offb) = make_float2(div1000(im.x) + old[1].x, div1000(im.y) + old[1].y);
+    }
+}
 
 template <int CA, int CB, int CC, int TW, int EPI, bool GEN = false>
 __global__ __launch_bounds__(256) void k_dc_mfma(Src sa, Src sb, Src sc, Dst out, McW w, McEpi epi, int H, int W) {
@@ -411,7 +412,6 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
     int lofw[C::NL];        // LDS float2 index inside a (padded) staged plane
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
-        if (kMcAbl & 8) { gofb[i] = 0u; lofw[i] = (C::PLANE + 2 * lane) >> 1; continue; }
         const int e = tid + i * 256;
         const int ir = e / (C::PI / 2), ic = 2 * (e - ir * (C::PI / 2));
         const int y = y0 - 2 + ir, x = x0 - 2 + ic;
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
             const int c = 2 * g + j;
             const float* p0 = c < CA ? base_a + (long)c * sa.sc : c < CA + CB ? base_b + (long)(c - CA) * sb.sc : base_c + (long)(c - CA - CB) * sc.sc;
 #pragma unroll
-            for (int i = 0; i < C::NL; ++i) stage[j][i] = (kMcAbl & 16) ? make_float2(0.f, 0.f) : *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(p0) + off[i]);
+            for (int i = 0; i < C::NL; ++i) stage[j][i] = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(p0) + off[i]);
         }
 #pragma unroll
         for (int j = 0; j < 6; ++j) afrag_next[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(w.a1 + (g * 6 + j) * 64) + aoff);
@@ -576,17 +576,12 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
 #pragma unroll
     for (int g = 0; g < C::NG; ++g) {
         const int buf = g & 1;
-        if (!((kMcAbl & 18) && g >= 1)) commit(g);
+        commit(g);
         float afrag[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) afrag[j] = afrag_next[j];
-        if (!((kMcAbl & 16) || ((kMcAbl & 4) && g >= 1))) __syncthreads();
-        if (g + 1 < C::NG) {
-            if (kMcAbl & 1) {   // the weight fragments only
-#pragma unroll
-                for (int j = 0; j < 6; ++j) afrag_next[j] = w.a1[((g + 1) * 6 + j) * 64 + lane];
-            } else fetch(g + 1);
-        }
+        __syncthreads();
+        if (g + 1 < C::NG) fetch(g + 1);
         const float* t = lds + buf * 2 * C::PLANE_P;
         float br[2][C::NR1 + 2], bvv[3];
 #pragma unroll
@@ -624,15 +619,13 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
             for (int r = 0; r < 4; ++r) vx[((n - 14) * 4 + q) * 4 + r] = accv[r];
         }
     }
-    float a2[EPI == 1 ? 1 : kFeat * 3];
-    float a2c[EPI == 1 ? kFeat * 5 : 1];
-    if (EPI == 1) {
+    // conv2's A fragments, issued here so that they land while the mid tensor is written: the plain ones [8 cm][3 dy], or the final layer's
+    // row-triple ones [8 cm][5] (conv2 composed with the out-conv, see below)
+    constexpr int NA2 = kFeat * (EPI == 1 ? 5 : 3);
+    const float* const a2src = EPI == 1 ? epi.a2c : w.a2;
+    float a2[NA2];
 #pragma unroll
-        for (int j = 0; j < kFeat * 5; ++j) a2c[EPI == 1 ? j : 0] = epi.a2c[j * 64 + lane];
-    } else {
-#pragma unroll
-        for (int j = 0; j < kFeat * 3; ++j) a2[EPI == 1 ? 0 : j] = w.a2[j * 64 + lane];
-    }
+    for (int j = 0; j < NA2; ++j) a2[j] = a2src[j * 64 + lane];
     __syncthreads();  // staged input is dead: the mid tensor takes its place
     if (vc == 1) {   // the producer's share of the vertical group, before this wave's own mid rows overwrite those words
         if (vg == 0) {
@@ -738,62 +731,24 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
 #pragma unroll
                 for (int T = 0; T < 3; ++T) {
                     const int j = 3 * T + jj + 1;   // staged row index of local input row 3T + jj
-                    if (j <= C::NR2 + 1) acc[T] = mfma4(a2c[cm * 5 + jj + 1], br[cm & 1][j], acc[T]);
+                    if (j <= C::NR2 + 1) acc[T] = mfma4(a2[cm * 5 + jj + 1], br[cm & 1][j], acc[T]);
                 }
             if (cm + 1 < kFeat) interleave_mfma_dsread<C::NR2 + 2>();
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int T = 0; T < 3; ++T) {
-            if (rok[T]) {
-                const float re0 = acc[T][0], re1 = acc[T][1], im0 = acc[T][2], im1 = acc[T][3];
-                if (epi.d_out) {
-                    char* base = reinterpret_cast<char*>(epi.d_out + (long)b * 2 * plane);
-                    *reinterpret_cast<float2*>(base + roff[T]) = make_float2(re0, re1);
-                    *reinterpret_cast<float2*>(base + 4 * plane + roff[T]) = make_float2(im0, im1);
-                }
-                if (epi.wf) {  // wf <- d / 1e3 + wf (hybridnet.py:570)
-                    char* base = reinterpret_cast<char*>(epi.wf + (long)b * 2 * plane);
-                    *reinterpret_cast<float2*>(base + roff[T]) = make_float2(div1000(re0) + wf_old[T][0].x, div1000(re1) + wf_old[T][0].y);
-                    *reinterpret_cast<float2*>(base + 4 * plane + roff[T]) = make_float2(div1000(im0) + wf_old[T][1].x, div1000(im1) + wf_old[T][1].y);
-                }
-            }
+            if (rok[T]) wf_update(epi, (long)b * 2 * plane, roff[T], plane, make_float2(acc[T][0], acc[T][1]), make_float2(acc[T][2], acc[T][3]), wf_old[T]);
         }
         return;
     }
+    // intermediate layer (EPI == 0): the 8 output channels go to `out`
     const float bo0 = w.b2[2 * q], bo1 = w.b2[2 * q + 1];
     f32x4 acc2[C::NR2];
 #pragma unroll
     for (int r = 0; r < C::NR2; ++r) acc2[r] = (f32x4){bo0, bo0, bo1, bo1};  // start at the bias
     const int ox = x0 + 2 * (16 * strip + n);
     const int yb = y0 + rb2;                       // first output row of this wave (wave-uniform)
-    const bool xin = ox < W;
-    // all global addresses of the epilogue are (wave-uniform 64-bit base) + (32-bit per-lane byte offset):
-    // rows advance the scalar base, so the row loop carries no vector address arithmetic
-    const long plane = (long)H * W;
-    const unsigned wvoff = xin ? 4u * (unsigned)ox : 0u;
-    float aoc0 = 0.f, aoc1 = 0.f, ob_re = 0.f, ob_im = 0.f;
-    float2 wf_old[EPI == 1 ? C::NR2 : 1][2];
-    if (EPI == 1) {  // out-conv fragments A_j[m][k = q] = ow[2q + j][m] (m < 2); old wavefield values
-        const int m = lane & 15;
-        if (m < 2) {
-            aoc0 = epi.ow[(2 * q) * 2 + m];
-            aoc1 = epi.ow[(2 * q + 1) * 2 + m];
-        }
-        ob_re = epi.ob[0];
-        ob_im = epi.ob[1];
-        if (epi.wf != nullptr && q == 0) {
-            unsigned off = wvoff;
-            asm volatile("" : "+v"(off));
-#pragma unroll
-            for (int r = 0; r < C::NR2; ++r) {
-                const int y = yb + r < H ? yb + r : 0;
-                const char* row = reinterpret_cast<const char*>(epi.wf_in + (long)b * 2 * plane + (long)y * W);
-                wf_old[r][0] = *reinterpret_cast<const float2*>(row + off);
-                wf_old[r][1] = *reinterpret_cast<const float2*>(row + 4 * plane + off);
-            }
-        }
-    }
     {
         float br[2][C::NR2 + 2];
 #pragma unroll
@@ -813,56 +768,17 @@ __global__ __launch_bounds__(256, GEN ? 2 : 4) void k_dc_mfma_s(Src sa, Src sb, 
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // acc2[r] = {channel 2q: pixels ox, ox+1; channel 2q+1: pixels ox, ox+1}
-    if (EPI == 0) {
-        if (xin) {
-            unsigned off = 4u * (unsigned)((2 * q) * (int)out.sc + ox);
-            asm volatile("" : "+v"(off));
-#pragma unroll
-            for (int r = 0; r < C::NR2; ++r) {
-                if (yb + r < H) {
-                    char* row = reinterpret_cast<char*>(out.p + (long)b * out.sb + (long)(yb + r) * W);
-                    *reinterpret_cast<float2*>(row + off) = make_float2(acc2[r][0], acc2[r][1]);
-                    *reinterpret_cast<float2*>(row + 4 * out.sc + off) = make_float2(acc2[r][2], acc2[r][3]);
-                }
-            }
-        }
-    } else {
-        // 1x1 out-conv (architectures.py:47-60) as two rounds of independent MFMAs (no back-to-back
-        // dependent pair); C starts at the out-conv bias: D rows 0 / 1 (lanes q = 0) = re / im
-        unsigned off = wvoff;
+    // acc2[r] = {channel 2q: pixels ox, ox+1; channel 2q+1: pixels ox, ox+1}.  Every global address is (wave-uniform 64-bit base) +
+    // (32-bit per-lane byte offset): rows advance the scalar base, so the row loop carries no vector address arithmetic
+    if (ox < W) {
+        unsigned off = 4u * (unsigned)((2 * q) * (int)out.sc + ox);
         asm volatile("" : "+v"(off));
 #pragma unroll
-        for (int h = 0; h < C::NR2; h += 4) {  // four rows at a time: 16 more live registers, not 64
-            f32x4 dA[4], dB[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                dA[r] = mfma4(aoc0, acc2[h + r][0], (f32x4){ob_re, ob_im, 0.f, 0.f});  // pixel ox
-                dB[r] = mfma4(aoc0, acc2[h + r][1], (f32x4){ob_re, ob_im, 0.f, 0.f});  // pixel ox + 1
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                dA[r] = mfma4(aoc1, acc2[h + r][2], dA[r]);
-                dB[r] = mfma4(aoc1, acc2[h + r][3], dB[r]);
-            }
-            if (q == 0 && xin) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (yb + h + r < H) {
-                        const long ro = (long)b * 2 * plane + (long)(yb + h + r) * W;
-                        const float re0 = dA[r][0], im0 = dA[r][1], re1 = dB[r][0], im1 = dB[r][1];
-                        if (epi.d_out) {
-                            char* row = reinterpret_cast<char*>(epi.d_out + ro);
-                            *reinterpret_cast<float2*>(row + off) = make_float2(re0, re1);
-                            *reinterpret_cast<float2*>(row + 4 * plane + off) = make_float2(im0, im1);
-                        }
-                        if (epi.wf) {  // wf <- d / 1e3 + wf (hybridnet.py:570)
-                            char* row = reinterpret_cast<char*>(epi.wf + ro);
-                            *reinterpret_cast<float2*>(row + off) = make_float2(div1000(re0) + wf_old[h + r][0].x, div1000(re1) + wf_old[h + r][0].y);
-                            *reinterpret_cast<float2*>(row + 4 * plane + off) = make_float2(div1000(im0) + wf_old[h + r][1].x, div1000(im1) + wf_old[h + r][1].y);
-                        }
-                    }
-                }
+        for (int r = 0; r < C::NR2; ++r) {
+            if (yb + r < H) {
+                char* row = reinterpret_cast<char*>(out.p + (long)b * out.sb + (long)(yb + r) * W);
+                *reinterpret_cast<float2*>(row + off) = make_float2(acc2[r][0], acc2[r][1]);
+                *reinterpret_cast<float2*>(row + 4 * out.sc + off) = make_float2(acc2[r][2], acc2[r][3]);
             }
         }
     }
@@ -1216,17 +1132,7 @@ __global__ __launch_bounds__(256, TH == 16 ? 2 : 3) void k_dc_x16(Src sa, Src sb
                 for (int r = 0; r < 4; ++r) {
                     if (yb + h + r < H) {
                         const long ro = (long)b * 2 * plane + (long)(yb + h + r) * W;
-                        const float re0 = dA[r][0], im0 = dA[r][1], re1 = dB[r][0], im1 = dB[r][1];
-                        if (epi.d_out) {
-                            char* row = reinterpret_cast<char*>(epi.d_out + ro);
-                            *reinterpret_cast<float2*>(row + off) = make_float2(re0, re1);
-                            *reinterpret_cast<float2*>(row + 4 * plane + off) = make_float2(im0, im1);
-                        }
-                        if (epi.wf) {
-                            char* row = reinterpret_cast<char*>(epi.wf + ro);
-                            *reinterpret_cast<float2*>(row + off) = make_float2(div1000(re0) + wf_old[h + r][0].x, div1000(re1) + wf_old[h + r][0].y);
-                            *reinterpret_cast<float2*>(row + 4 * plane + off) = make_float2(div1000(im0) + wf_old[h + r][1].x, div1000(im1) + wf_old[h + r][1].y);
-                        }
+                        wf_update(epi, ro, off, plane, make_float2(dA[r][0], dB[r][0]), make_float2(dA[r][1], dB[r][1]), wf_old[h + r]);
                     }
                 }
             }
@@ -1504,7 +1410,7 @@ __global__ __launch_bounds__(256) void k_dc_mfma_p(Src sa, Src sb, Src sc, Dst o
                         *reinterpret_cast<float2*>(epi.d_out + o) = make_float2(re0, re1);
                         *reinterpret_cast<float2*>(epi.d_out + o + plane) = make_float2(im0, im1);
                     }
-                    if (epi.wf) {  // wf <- d / 1e3 + wf (hybridnet.py:570)
+                    if (epi.wf) {  // wf <- d / 1e3 + wf (hybridnet.py:570); per-lane 64-bit addresses here, not wf_update's uniform row + byte offset
                         const float2 o0 = wf_old[EPI == 1 ? gi : 0][0], o1 = wf_old[EPI == 1 ? gi : 0][1];
                         *reinterpret_cast<float2*>(epi.wf + o) = make_float2(div1000(re0) + o0.x, div1000(re1) + o0.y);
                         *reinterpret_cast<float2*>(epi.wf + o + plane) = make_float2(div1000(im0) + o1.x, div1000(im1) + o1.y);
@@ -1975,6 +1881,111 @@ __global__ __launch_bounds__(256) void k_dc_bwd_mfma_aux(McBwd a, McBwdAux x, in
 }
 
 // ------------------------------------------------------------------------------------------
+// What the 8x8 stride-2 kernels below share (k_down_mfma / _ring / k_down_x16 and k_up_mfma / _ring / k_up_x16): who a thread is,
+// the staging map of the fp32 kernels, and the two stores.  C is the kernel's config struct (DnCfg, UpCfg2, DnX, UpX).
+// ------------------------------------------------------------------------------------------
+// Lane (n, q) of wavefront (wx, wy) of the block that owns tile (X0, Y0) of sample b.  A block is WX x WY wavefronts of 16 columns each
+// (C::TW = 16 WX); Y0 counts output rows in `down` and window rows in `up`, whose first window row is Y0 - 1.
+struct Pos8 {
+    int tid, lane, wave, n, q, wx, wy, b, X0, Y0;
+};
+template <class C>
+__device__ __forceinline__ Pos8 pos8() {
+    constexpr int WX = C::TW / 16;
+    Pos8 me;
+    me.tid = threadIdx.x, me.lane = me.tid & 63;
+    me.wave = __builtin_amdgcn_readfirstlane(me.tid >> 6);   // wave-uniform: branches on it are scalar
+    me.n = me.lane & 15, me.q = me.lane >> 4;
+    me.wx = me.wave % WX, me.wy = me.wave / WX;
+    const TileId tl = xcd_tile();
+    me.b = tl.z;
+    me.X0 = tl.x * C::TW, me.Y0 = tl.y * C::TH;
+    return me;
+}
+
+// Staging map of the fp32 kernels.  As in k_dc_mfma_s the channel loop carries no predicate or vector address arithmetic (they are paid in
+// matrix-pipe time): a thread stages the elements tid, tid + NT, ... of the IR x IC window, and for each of them stage_slot gives the byte
+// offset inside a channel plane to load from and the LDS index inside a staged plane to commit to.  A position outside the image -- or
+// past the end of the window, !inr -- loads offset 0 and commits to the lane's dummy slot behind the plane; stage_slot returns true where
+// such a position lies inside the window, and the kernel then zeroes it ONCE, in all its NPL planes, with stage_zero.
+// (oy, ox) is the input pixel in the window's corner.
+template <class C>
+__device__ __forceinline__ bool stage_slot(int ir, int ic, bool inr, int oy, int ox, int Hin, int Win, int lane, unsigned& gofb, int& lofw) {
+    const int y = oy + ir, x = ox + ic;
+    const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
+    gofb = ok ? 4u * (unsigned)(y * Win + x) : 0u;
+    lofw = ok ? ir * C::PI + ic : C::PLANE + lane;
+    return inr && !ok;
+}
+template <class C, int NPL>
+__device__ __forceinline__ void stage_zero(float* lds, int ir, int ic) {
+#pragma unroll
+    for (int pl = 0; pl < NPL; ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
+}
+// (row, column) of a thread's elements, one after the other, without a division per element (the ring kernels' prologue)
+template <class C>
+struct StageWalk {
+    int ir, ic;
+    __device__ __forceinline__ explicit StageWalk(int tid) : ir(tid / C::IC), ic(tid - ir * C::IC) {}
+    __device__ __forceinline__ void next() {
+        ic += C::NT % C::IC;
+        ir += C::NT / C::IC;
+        if (ic >= C::IC) { ic -= C::IC; ++ir; }
+    }
+};
+
+// down: D rows of lane (n, q) are (co = 2q, h = 0), (2q, 1), (2q+1, 0), (2q+1, 1) of the window rows acc[0 .. R + 1];
+// out[Y] = P0[Y] + P1[Y + 2] + bias
+template <class C>
+__device__ __forceinline__ void down_store(const Pos8& me, const f32x4 (&acc)[C::NWIN], Dst out, const float* bias, int Hin, int Win) {
+    const int Hout = Hin / 2, Wout = Win / 2;
+    const int X = me.X0 + 16 * me.wx + me.n;
+    const float b0 = bias[2 * me.q], b1 = bias[2 * me.q + 1];
+    if (X < Wout) {
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) {
+            const int Y = me.Y0 + me.wy * C::R + r;
+            if (Y < Hout) {
+                float* p = out.p + (long)me.b * out.sb + (long)(2 * me.q) * out.sc + (long)Y * Wout + X;
+                p[0] = acc[r][0] + acc[r + 2][1] + b0;
+                p[out.sc] = acc[r][2] + acc[r + 2][3] + b1;
+            }
+        }
+    }
+}
+
+// up: D rows of lane (n, q) are (co = 2q, py = 0), (2q, 1), (2q+1, 0), (2q+1, 1) of acc[window row][px]; window row Y gives the output rows
+// 2 Y + 1 + py, a lane's two px are one float2.  ACC: out += (the training step's backward pass adds `down`'s input gradient to the skip gradient)
+template <class C, bool ACC>
+__device__ __forceinline__ void up_store(const Pos8& me, const f32x4 (&acc)[C::R][2], Dst out, const float* bias, int Hin, int Win) {
+    const int Hout = 2 * Hin, Wout = 2 * Win;
+    const int X = me.X0 + 16 * me.wx + me.n;
+    const float b0 = bias[2 * me.q], b1 = bias[2 * me.q + 1];
+    if (X < Win) {
+        float* const col = out.p + (long)me.b * out.sb + (long)(2 * me.q) * out.sc + 2 * X;   // per lane; the rows below add a wave-uniform offset
+#pragma unroll
+        for (int wr = 0; wr < C::R; ++wr) {
+            const int Y = me.Y0 - 1 + me.wy * C::R + wr;
+#pragma unroll
+            for (int py = 0; py < 2; ++py) {
+                const int y = 2 * Y + 1 + py;
+                if (y >= 0 && y < Hout) {
+                    float* p = col + (long)y * Wout;
+                    float2 o0 = make_float2(acc[wr][0][py] + b0, acc[wr][1][py] + b0);
+                    float2 o1 = make_float2(acc[wr][0][2 + py] + b1, acc[wr][1][2 + py] + b1);
+                    if (ACC) {
+                        const float2 c0 = *reinterpret_cast<const float2*>(p), c1 = *reinterpret_cast<const float2*>(p + out.sc);
+                        o0.x += c0.x; o0.y += c0.y; o1.x += c1.x; o1.y += c1.y;
+                    }
+                    *reinterpret_cast<float2*>(p) = o0;
+                    *reinterpret_cast<float2*>(p + out.sc) = o1;
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // 8x8 stride-2 down convolution (architectures.py:209-211)
 //   P_h[Yw][X] = sum_ci sum_kx sum_{k<4} w[co][ci][4h + k][kx] * in[ci][2 Yw - 3 + k][2 X - 3 + kx]
 //   out[Y][X]  = b + P_0[Y][X] + P_1[Y + 2][X]
@@ -1998,44 +2009,29 @@ struct DnCfg {
 
 // ALL = true (small, latency-bound levels): all 8 input channels are staged at once behind a single
 // barrier instead of one channel per double-buffered chunk.
-// As in k_dc_mfma_s the channel loop carries no predicate or vector address arithmetic (they are paid in
-// matrix-pipe time): out-of-image positions are zeroed once, masked lanes load offset 0 and commit to a
-// dummy slot, the loop is fully unrolled and loads use SGPR-base + 32-bit VGPR-offset addressing.
+// The staging map (stage_slot) is built before the first load; the channel loop is fully unrolled and
+// loads use SGPR-base + 32-bit VGPR-offset addressing.
 // Two blocks per CU (<= 256 registers): the second block's MFMAs fill the first one's staging /
 // barrier gaps (56 -> 49 us at 256^2 x 32; one wavefront per SIMD cannot hide them by itself).
 template <int WX, bool ALL>
 __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const float* __restrict__ afr /*[8][8][64]*/,
                                                        const float* __restrict__ bias, int Hin, int Win, SyncHook hook) {
     using C = DnCfg<WX>;
+    constexpr int NPL = ALL ? kFeat : 2;   // staged planes
     sync_hook_begin(hook);   // (flag sync of the training step: releases the hidden-state launch of the iteration on the side stream, hn_train.hip)
-    __shared__ float lds[(ALL ? kFeat : 2) * C::PLANE_P];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const int wx = wave % WX, wy = wave / WX;
-    const TileId tl = xcd_tile();
-    const int b = tl.z;
-    const int X0 = tl.x * C::TW, Y0 = tl.y * C::TH;
-    const int Hout = Hin / 2, Wout = Win / 2;
+    __shared__ float lds[NPL * C::PLANE_P];
+    const Pos8 me = pos8<C>();
+    const int lane = me.lane;
 
     unsigned gofb[C::NL];
     int lofw[C::NL];
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
-        if (!ALL && (kMcAbl & 8)) { gofb[i] = 0u; lofw[i] = C::PLANE + lane; continue; }
-        const int e = tid + i * C::NT;
+        const int e = me.tid + i * C::NT;
         const int ir = e / C::IC, ic = e - ir * C::IC;
-        const int y = 2 * Y0 - 3 + ir, x = 2 * X0 - 3 + ic;
-        const bool inr = e < C::IR * C::IC;
-        const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
-        gofb[i] = ok ? 4u * (unsigned)(y * Win + x) : 0u;
-        lofw[i] = ok ? ir * C::PI + ic : C::PLANE + lane;
-        if (inr && !ok) {
-#pragma unroll
-            for (int pl = 0; pl < (ALL ? kFeat : 2); ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
-        }
+        if (stage_slot<C>(ir, ic, e < C::IR * C::IC, 2 * me.Y0 - 3, 2 * me.X0 - 3, Hin, Win, lane, gofb[i], lofw[i])) stage_zero<C, NPL>(lds, ir, ic);
     }
-    const float* const base = in.p + (long)b * in.sb;
+    const float* const base = in.p + (long)me.b * in.sb;
     float stage[C::NL], afrag_next[8];
     auto fetch = [&](int ci) {
         unsigned off[C::NL], aoff = 4u * lane;
@@ -2047,12 +2043,12 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
         asm volatile("" : "+v"(aoff));
         const char* p0 = reinterpret_cast<const char*>(base + (long)ci * in.sc);
 #pragma unroll
-        for (int i = 0; i < C::NL; ++i) stage[i] = (kMcAbl & 16) ? 0.f : *reinterpret_cast<const float*>(p0 + off[i]);
+        for (int i = 0; i < C::NL; ++i) stage[i] = *reinterpret_cast<const float*>(p0 + off[i]);
 #pragma unroll
         for (int kx = 0; kx < 8; ++kx) afrag_next[kx] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(afr + (ci * 8 + kx) * 64) + aoff);
     };
     // B operand of window row wr, tap kx: staged[(2*(wy*R + wr) + q) * PI + 2*(16*wx + n) + kx]
-    const int bbase = (2 * wy * C::R + q) * C::PI + 2 * (16 * wx + n);
+    const int bbase = (2 * me.wy * C::R + me.q) * C::PI + 2 * (16 * me.wx + me.n);
     f32x4 acc[C::NWIN];
 #pragma unroll
     for (int i = 0; i < C::NWIN; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2076,7 +2072,7 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
 #pragma unroll
     for (int ci = 0; ci < kFeat; ++ci) {
         float* t = lds + (ALL ? ci : (ci & 1)) * C::PLANE_P;
-        if (!ALL && !(((kMcAbl & 16) && ci >= 1) || ((kMcAbl & 2) && ci >= 2))) {   // (HN_MC_ABL: timing ablations only)
+        if (!ALL) {
 #pragma unroll
             for (int i = 0; i < C::NL; ++i) t[lofw[i]] = stage[i];
         }
@@ -2084,13 +2080,8 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
 #pragma unroll
         for (int kx = 0; kx < 8; ++kx) afrag[kx] = afrag_next[kx];
         if (!ALL) {
-            if (!((kMcAbl & 16) || ((kMcAbl & 4) && ci >= 2))) __syncthreads();
-            if (ci + 1 < kFeat) {
-                if ((kMcAbl & 1) && ci >= 1) {   // the weight fragments only
-#pragma unroll
-                    for (int kx = 0; kx < 8; ++kx) afrag_next[kx] = afr[((ci + 1) * 8 + kx) * 64 + lane];
-                } else fetch(ci + 1);
-            }
+            __syncthreads();
+            if (ci + 1 < kFeat) fetch(ci + 1);
         } else if (ci + 1 < kFeat) {
 #pragma unroll
             for (int kx = 0; kx < 8; ++kx) afrag_next[kx] = afr[((ci + 1) * 8 + kx) * 64 + lane];
@@ -2111,20 +2102,7 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // D rows of lane (n, q): (co = 2q, h = 0), (2q, 1), (2q+1, 0), (2q+1, 1)
-    const int X = X0 + 16 * wx + n;
-    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
-    if (X < Wout) {
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) {
-            const int Y = Y0 + wy * C::R + r;
-            if (Y < Hout) {
-                float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)Y * Wout + X;
-                p[0] = acc[r][0] + acc[r + 2][1] + b0;
-                p[out.sc] = acc[r][2] + acc[r + 2][3] + b1;
-            }
-        }
-    }
+    down_store<C>(me, acc, out, bias, Hin, Win);
 }
 
 // k_down_mfma<WX, false> with the input staging off the matrix pipe's critical path (HN_OPT_MC_STAGE 1).  Same tiles, same MFMAs in the same order
@@ -2135,9 +2113,9 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma(Src in, Dst out, const flo
 //     issued behind the MFMAs of tap k, so the last reads of plane c & 1 stand BEFORE that barrier (which waits for them), the writes of
 //     channel c + 2 into the same plane behind it, and the last tap's MFMAs cover the first operand reads of channel c + 1.  Two planes are
 //     therefore enough -- a third would buy nothing with the barrier in this place -- and the kernel keeps its 41.5 KB.
-//   * the prologue loads the first weight fragments, then every staged element as soon as its offset exists (row and column from a running counter:
-//     one division per thread instead of NL), then the second channel; the out-of-image zeros are written while those loads are in flight, and only by
-//     the threads of border tiles.
+//   * the prologue loads the first weight fragments, then every staged element as soon as stage_slot has given its offset (row and column from a
+//     running counter, StageWalk: one division per thread instead of NL), then the second channel; the out-of-image zeros (zmask) are written while
+//     those loads are in flight, and only by the threads of border tiles.
 template <int WX>
 __global__ __launch_bounds__(256, 2) void k_down_mfma_ring(Src in, Dst out, const float* __restrict__ afr /*[8][8][64]*/,
                                                             const float* __restrict__ bias, int Hin, int Win, SyncHook hook) {
@@ -2146,15 +2124,9 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma_ring(Src in, Dst out, cons
     constexpr int WPT = cdiv_(C::NL, 7);   // LDS writes per tap: the commit is spread over taps 0 .. 6
     sync_hook_begin(hook);
     __shared__ float lds[2 * C::PLANE_P];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const int wx = wave % WX, wy = wave / WX;
-    const TileId tl = xcd_tile();
-    const int b = tl.z;
-    const int X0 = tl.x * C::TW, Y0 = tl.y * C::TH;
-    const int Hout = Hin / 2, Wout = Win / 2;
-    const float* const base = in.p + (long)b * in.sb;
+    const Pos8 me = pos8<C>();
+    const int lane = me.lane;
+    const float* const base = in.p + (long)me.b * in.sb;
 
     // two register sets, A for the even channels and B for the odd ones: the channel loop below is written out by pairs, so every name is static
     float afA[8], afB[8], stA[C::NL], stB[C::NL];
@@ -2169,22 +2141,16 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma_ring(Src in, Dst out, cons
     unsigned gofb[C::NL];
     int lofw[C::NL];
     unsigned zmask = 0;   // bit i: element i lies in the staged window but outside the image
-    const int ir0 = tid / C::IC, ic0 = tid - ir0 * C::IC;
+    const StageWalk<C> first(me.tid);
     {
         const char* p0 = reinterpret_cast<const char*>(base);
-        int ir = ir0, ic = ic0;
+        StageWalk<C> at = first;
 #pragma unroll
         for (int i = 0; i < C::NL; ++i) {
-            const int y = 2 * Y0 - 3 + ir, x = 2 * X0 - 3 + ic;
-            const bool inr = tid + i * C::NT < C::IR * C::IC;
-            const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
-            gofb[i] = ok ? 4u * (unsigned)(y * Win + x) : 0u;
-            lofw[i] = ok ? ir * C::PI + ic : C::PLANE + lane;
-            zmask |= (inr && !ok) ? 1u << i : 0u;
+            const bool z = stage_slot<C>(at.ir, at.ic, me.tid + i * C::NT < C::IR * C::IC, 2 * me.Y0 - 3, 2 * me.X0 - 3, Hin, Win, lane, gofb[i], lofw[i]);
+            zmask |= z ? 1u << i : 0u;
             stA[i] = *reinterpret_cast<const float*>(p0 + gofb[i]);
-            ic += C::NT % C::IC;
-            ir += C::NT / C::IC;
-            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+            at.next();
         }
     }
     auto fetch_s = [&](int ci, float (&st)[C::NL]) {
@@ -2198,20 +2164,15 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma_ring(Src in, Dst out, cons
     fetch_w(1, afB);
     fetch_s(1, stB);
     if (zmask != 0) {
-        int ir = ir0, ic = ic0;
+        StageWalk<C> at = first;
 #pragma unroll
         for (int i = 0; i < C::NL; ++i) {
-            if ((zmask >> i) & 1) {
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
-            }
-            ic += C::NT % C::IC;
-            ir += C::NT / C::IC;
-            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+            if ((zmask >> i) & 1) stage_zero<C, 2>(lds, at.ir, at.ic);
+            at.next();
         }
     }
     // B operand of window row wr, tap kx: staged[(2*(wy*R + wr) + q) * PI + 2*(16*wx + n) + kx]
-    const int bbase = (2 * wy * C::R + q) * C::PI + 2 * (16 * wx + n);
+    const int bbase = (2 * me.wy * C::R + me.q) * C::PI + 2 * (16 * me.wx + me.n);
     f32x4 acc[C::NWIN];
 #pragma unroll
     for (int i = 0; i < C::NWIN; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2254,20 +2215,7 @@ __global__ __launch_bounds__(256, 2) void k_down_mfma_ring(Src in, Dst out, cons
         channel(ci, afA, afB, stA, stB);
         channel(ci + 1, afB, afA, stB, stA);
     }
-    // D rows of lane (n, q): (co = 2q, h = 0), (2q, 1), (2q+1, 0), (2q+1, 1)
-    const int X = X0 + 16 * wx + n;
-    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
-    if (X < Wout) {
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) {
-            const int Y = Y0 + wy * C::R + r;
-            if (Y < Hout) {
-                float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)Y * Wout + X;
-                p[0] = acc[r][0] + acc[r + 2][1] + b0;
-                p[out.sc] = acc[r][2] + acc[r + 2][3] + b1;
-            }
-        }
-    }
+    down_store<C>(me, acc, out, bias, Hin, Win);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2291,40 +2239,26 @@ struct UpCfg2 {
     static constexpr int NL = cdiv_(IR * IC, NT);
 };
 
-// Staging follows k_down_mfma: zero the out-of-image positions once, no predicates in the (unrolled) loop.
-template <int WX, int R_, bool ALL, bool ACC = false>   // ACC: out += (the training step's backward pass adds `down`'s input gradient to the skip gradient)
+// Staged like k_down_mfma: the map (stage_slot) before the first load, no predicates in the (unrolled) loop.
+template <int WX, int R_, bool ALL, bool ACC = false>   // ACC: out += (up_store)
 __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float* __restrict__ afr /*[8][2][4][64]*/,
                                                   const float* __restrict__ bias, int Hin, int Win, SyncHook hook) {
     using C = UpCfg2<WX, R_>;
-    __shared__ float lds[(ALL ? kFeat : 4) * C::PLANE_P];  // ALL: every channel at once; else 2 buffers x 2 channels
+    constexpr int NPL = ALL ? kFeat : 4;   // staged planes.  ALL: every channel at once; else 2 buffers x 2 channels
+    __shared__ float lds[NPL * C::PLANE_P];
     sync_hook_begin(hook);   // (flag sync: the side stream's hand-overs ride on this kernel, hn_internal.h)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const int wx = wave % WX, wy = wave / WX;
-    const TileId tl = xcd_tile();
-    const int b = tl.z;
-    const int X0 = tl.x * C::TW, Yb = tl.y * C::TH - 1;  // first window row of the block
-    const int Hout = 2 * Hin, Wout = 2 * Win;
+    const Pos8 me = pos8<C>();
+    const int lane = me.lane;
 
     unsigned gofb[C::NL];
     int lofw[C::NL];
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
-        if (!ALL && (kMcAbl & 8)) { gofb[i] = 0u; lofw[i] = C::PLANE + lane; continue; }
-        const int e = tid + i * C::NT;
+        const int e = me.tid + i * C::NT;
         const int ir = e / C::IC, ic = e - ir * C::IC;
-        const int y = Yb - 1 + ir, x = X0 - 2 + ic;
-        const bool inr = e < C::IR * C::IC;
-        const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
-        gofb[i] = ok ? 4u * (unsigned)(y * Win + x) : 0u;
-        lofw[i] = ok ? ir * C::PI + ic : C::PLANE + lane;
-        if (inr && !ok) {
-#pragma unroll
-            for (int pl = 0; pl < (ALL ? kFeat : 4); ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
-        }
+        if (stage_slot<C>(ir, ic, e < C::IR * C::IC, me.Y0 - 2, me.X0 - 2, Hin, Win, lane, gofb[i], lofw[i])) stage_zero<C, NPL>(lds, ir, ic);
     }
-    const float* const base = in.p + (long)b * in.sb;
+    const float* const base = in.p + (long)me.b * in.sb;
     float stage[C::NL][2], afrag_next[16];
     auto fetch = [&](int g) {
         unsigned off[C::NL], aoff = 4u * lane;
@@ -2338,14 +2272,14 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
         const char* p1 = reinterpret_cast<const char*>(base + (long)(2 * g + 1) * in.sc);
 #pragma unroll
         for (int i = 0; i < C::NL; ++i) {
-            stage[i][0] = (kMcAbl & 16) ? 0.f : *reinterpret_cast<const float*>(p0 + off[i]);
-            stage[i][1] = (kMcAbl & 16) ? 0.f : *reinterpret_cast<const float*>(p1 + off[i]);
+            stage[i][0] = *reinterpret_cast<const float*>(p0 + off[i]);
+            stage[i][1] = *reinterpret_cast<const float*>(p1 + off[i]);
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j) afrag_next[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(afr + (g * 16 + j) * 64) + aoff);
     };
     // B operand for window row wr, column offset o (= ix - X + 2, 0..4): staged[(wy*R + wr + q) * PI + 16*wx + n + o]
-    const int bbase = (wy * C::R + q) * C::PI + 16 * wx + n;
+    const int bbase = (me.wy * C::R + me.q) * C::PI + 16 * me.wx + me.n;
     f32x4 acc[C::R][2];
 #pragma unroll
     for (int i = 0; i < C::R; ++i) acc[i][0] = acc[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2369,7 +2303,7 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
 #pragma unroll
     for (int g = 0; g < kFeat / 2; ++g) {
         float* t = lds + (ALL ? 2 * g : (g & 1) * 2) * C::PLANE_P;
-        if (!ALL && !((kMcAbl & 18) && g >= 1)) {   // (HN_MC_ABL: timing ablations only)
+        if (!ALL) {
 #pragma unroll
             for (int i = 0; i < C::NL; ++i) {
                 t[lofw[i]] = stage[i][0];
@@ -2380,13 +2314,8 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
 #pragma unroll
         for (int j = 0; j < 16; ++j) afrag[j] = afrag_next[j];
         if (!ALL) {
-            if (!((kMcAbl & 16) || ((kMcAbl & 4) && g >= 1))) __syncthreads();
-            if (g + 1 < kFeat / 2) {
-                if (kMcAbl & 1) {   // the weight fragments only
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) afrag_next[j] = afr[((g + 1) * 16 + j) * 64 + lane];
-                } else fetch(g + 1);
-            }
+            __syncthreads();
+            if (g + 1 < kFeat / 2) fetch(g + 1);
         } else if (g + 1 < kFeat / 2) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) afrag_next[j] = afr[((g + 1) * 16 + j) * 64 + lane];
@@ -2412,30 +2341,7 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma(Src in, Dst out, const float
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // D rows of lane (n, q): (co = 2q, py = 0), (2q, 1), (2q+1, 0), (2q+1, 1); acc[.][px]
-    const int X = X0 + 16 * wx + n;
-    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
-    if (X < Win) {
-#pragma unroll
-        for (int wr = 0; wr < C::R; ++wr) {
-            const int Y = Yb + wy * C::R + wr;
-#pragma unroll
-            for (int py = 0; py < 2; ++py) {
-                const int y = 2 * Y + 1 + py;
-                if (y >= 0 && y < Hout) {
-                    float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)y * Wout + 2 * X;
-                    float2 o0 = make_float2(acc[wr][0][py] + b0, acc[wr][1][py] + b0);
-                    float2 o1 = make_float2(acc[wr][0][2 + py] + b1, acc[wr][1][2 + py] + b1);
-                    if (ACC) {
-                        const float2 c0 = *reinterpret_cast<const float2*>(p), c1 = *reinterpret_cast<const float2*>(p + out.sc);
-                        o0.x += c0.x; o0.y += c0.y; o1.x += c1.x; o1.y += c1.y;
-                    }
-                    *reinterpret_cast<float2*>(p) = o0;
-                    *reinterpret_cast<float2*>(p + out.sc) = o1;
-                }
-            }
-        }
-    }
+    up_store<C, ACC>(me, acc, out, bias, Hin, Win);
     sync_hook_end(hook);
 }
 
@@ -2453,15 +2359,9 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma_ring(Src in, Dst out, const 
     constexpr int WSTEPS = 4, WPS = cdiv_(2 * C::NL, WSTEPS);   // the commit: WPS LDS writes behind each of the steps 0 .. WSTEPS - 1
     __shared__ float lds[4 * C::PLANE_P];  // 2 buffers x 2 channels
     sync_hook_begin(hook);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const int wx = wave % WX, wy = wave / WX;
-    const TileId tl = xcd_tile();
-    const int b = tl.z;
-    const int X0 = tl.x * C::TW, Yb = tl.y * C::TH - 1;  // first window row of the block
-    const int Hout = 2 * Hin, Wout = 2 * Win;
-    const float* const base = in.p + (long)b * in.sb;
+    const Pos8 me = pos8<C>();
+    const int lane = me.lane;
+    const float* const base = in.p + (long)me.b * in.sb;
 
     float afrag[16], stage[C::NL][2];
     unsigned aoff = 4u * lane;
@@ -2475,24 +2375,18 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma_ring(Src in, Dst out, const 
     unsigned gofb[C::NL];
     int lofw[C::NL];
     unsigned zmask = 0;   // bit i: element i lies in the staged window but outside the image
-    const int ir0 = tid / C::IC, ic0 = tid - ir0 * C::IC;
+    const StageWalk<C> first(me.tid);
     {
         const char* p0 = reinterpret_cast<const char*>(base);
         const char* p1 = reinterpret_cast<const char*>(base + in.sc);
-        int ir = ir0, ic = ic0;
+        StageWalk<C> at = first;
 #pragma unroll
         for (int i = 0; i < C::NL; ++i) {
-            const int y = Yb - 1 + ir, x = X0 - 2 + ic;
-            const bool inr = tid + i * C::NT < C::IR * C::IC;
-            const bool ok = inr && y >= 0 && y < Hin && x >= 0 && x < Win;
-            gofb[i] = ok ? 4u * (unsigned)(y * Win + x) : 0u;
-            lofw[i] = ok ? ir * C::PI + ic : C::PLANE + lane;
-            zmask |= (inr && !ok) ? 1u << i : 0u;
+            const bool z = stage_slot<C>(at.ir, at.ic, me.tid + i * C::NT < C::IR * C::IC, me.Y0 - 2, me.X0 - 2, Hin, Win, lane, gofb[i], lofw[i]);
+            zmask |= z ? 1u << i : 0u;
             stage[i][0] = *reinterpret_cast<const float*>(p0 + gofb[i]);
             stage[i][1] = *reinterpret_cast<const float*>(p1 + gofb[i]);
-            ic += C::NT % C::IC;
-            ir += C::NT / C::IC;
-            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+            at.next();
         }
     }
     auto fetch_s = [&](int g) {
@@ -2506,20 +2400,15 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma_ring(Src in, Dst out, const 
         }
     };
     if (zmask != 0) {
-        int ir = ir0, ic = ic0;
+        StageWalk<C> at = first;
 #pragma unroll
         for (int i = 0; i < C::NL; ++i) {
-            if ((zmask >> i) & 1) {
-#pragma unroll
-                for (int pl = 0; pl < 4; ++pl) lds[pl * C::PLANE_P + ir * C::PI + ic] = 0.f;
-            }
-            ic += C::NT % C::IC;
-            ir += C::NT / C::IC;
-            if (ic >= C::IC) { ic -= C::IC; ++ir; }
+            if ((zmask >> i) & 1) stage_zero<C, 4>(lds, at.ir, at.ic);
+            at.next();
         }
     }
     // B operand for window row wr, column offset o (= ix - X + 2, 0..4): staged[(wy*R + wr + q) * PI + 16*wx + n + o]
-    const int bbase = (wy * C::R + q) * C::PI + 16 * wx + n;
+    const int bbase = (me.wy * C::R + me.q) * C::PI + 16 * me.wx + me.n;
     f32x4 acc[C::R][2];
 #pragma unroll
     for (int i = 0; i < C::R; ++i) acc[i][0] = acc[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2567,30 +2456,7 @@ __global__ __launch_bounds__(256, 3) void k_up_mfma_ring(Src in, Dst out, const 
             }
         }
     }
-    // D rows of lane (n, q): (co = 2q, py = 0), (2q, 1), (2q+1, 0), (2q+1, 1); acc[.][px]
-    const int X = X0 + 16 * wx + n;
-    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
-    if (X < Win) {
-#pragma unroll
-        for (int wr = 0; wr < C::R; ++wr) {
-            const int Y = Yb + wy * C::R + wr;
-#pragma unroll
-            for (int py = 0; py < 2; ++py) {
-                const int y = 2 * Y + 1 + py;
-                if (y >= 0 && y < Hout) {
-                    float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)y * Wout + 2 * X;
-                    float2 o0 = make_float2(acc[wr][0][py] + b0, acc[wr][1][py] + b0);
-                    float2 o1 = make_float2(acc[wr][0][2 + py] + b1, acc[wr][1][2 + py] + b1);
-                    if (ACC) {
-                        const float2 c0 = *reinterpret_cast<const float2*>(p), c1 = *reinterpret_cast<const float2*>(p + out.sc);
-                        o0.x += c0.x; o0.y += c0.y; o1.x += c1.x; o1.y += c1.y;
-                    }
-                    *reinterpret_cast<float2*>(p) = o0;
-                    *reinterpret_cast<float2*>(p + out.sc) = o1;
-                }
-            }
-        }
-    }
+    up_store<C, ACC>(me, acc, out, bias, Hin, Win);
     sync_hook_end(hook);
 }
 
@@ -2616,14 +2482,9 @@ __global__ __launch_bounds__(256, 2) void k_down_x16(Src in, Dst out, const void
     typedef typename M::V8 V8;
     typedef typename M::T T;
     __shared__ __attribute__((aligned(16))) unsigned char lds[C::LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wy = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const TileId tl = xcd_tile();
-    const int b = tl.z;
-    const int X0 = tl.x * C::TW, Y0 = tl.y * C::TH;
-    const int Hout = Hin / 2, Wout = Win / 2;
-    const float* const base = in.p + (long)b * in.sb;
+    const Pos8 me = pos8<C>();   // (one wavefront per row of the block: wx = 0, wy = wave)
+    const int tid = me.tid, lane = me.lane, wy = me.wy, n = me.n, q = me.q, X0 = me.X0, Y0 = me.Y0;
+    const float* const base = in.p + (long)me.b * in.sb;
     // ---- stage the whole 38 x 38 x 8 input window: one pixel (8 channel loads) per thread and step ----
     float v[C::NL][kFeat];
 #pragma unroll
@@ -2677,20 +2538,7 @@ __global__ __launch_bounds__(256, 2) void k_down_x16(Src in, Dst out, const void
             for (int t = 0; t < M::NT; ++t) acc[wr] = M::mma(a[M::ap(t)], bv[M::bp(t)], acc[wr]);
         }
     }
-    // D rows of lane (n, q): (co = 2q, h = 0), (2q, 1), (2q+1, 0), (2q+1, 1); out[Y] = P0[Y] + P1[Y + 2]
-    const int X = X0 + n;
-    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
-    if (X < Wout) {
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) {
-            const int Y = Y0 + wy * C::R + r;
-            if (Y < Hout) {
-                float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)Y * Wout + X;
-                p[0] = acc[r][0] + acc[r + 2][1] + b0;
-                p[out.sc] = acc[r][2] + acc[r + 2][3] + b1;
-            }
-        }
-    }
+    down_store<C>(me, acc, out, bias, Hin, Win);
 }
 
 template <typename M>
@@ -2711,14 +2559,9 @@ __global__ __launch_bounds__(256, 2) void k_up_x16(Src in, Dst out, const void* 
     typedef typename M::V8 V8;
     typedef typename M::T T;
     __shared__ __attribute__((aligned(16))) unsigned char lds[C::LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wy = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const TileId tl = xcd_tile();
-    const int b = tl.z;
-    const int X0 = tl.x * C::TW, Yb = tl.y * C::TH - 1;  // first window row of the block
-    const int Hout = 2 * Hin, Wout = 2 * Win;
-    const float* const base = in.p + (long)b * in.sb;
+    const Pos8 me = pos8<C>();   // (wx = 0, wy = wave)
+    const int tid = me.tid, lane = me.lane, wy = me.wy, n = me.n, q = me.q, X0 = me.X0, Yb = me.Y0 - 1;   // Yb: first window row of the block
+    const float* const base = in.p + (long)me.b * in.sb;
     float v[C::NL][kFeat];
 #pragma unroll
     for (int i = 0; i < C::NL; ++i) {
@@ -2777,24 +2620,7 @@ __global__ __launch_bounds__(256, 2) void k_up_x16(Src in, Dst out, const void* 
             }
         }
     }
-    // D rows of lane (n, q): (co = 2q, py = 0), (2q, 1), (2q+1, 0), (2q+1, 1); acc[.][px]
-    const int X = X0 + n;
-    const float b0 = bias[2 * q], b1 = bias[2 * q + 1];
-    if (X < Win) {
-#pragma unroll
-        for (int wr = 0; wr < C::R; ++wr) {
-            const int Y = Yb + wy * C::R + wr;
-#pragma unroll
-            for (int py = 0; py < 2; ++py) {
-                const int y = 2 * Y + 1 + py;
-                if (y >= 0 && y < Hout) {
-                    float* p = out.p + (long)b * out.sb + (long)(2 * q) * out.sc + (long)y * Wout + 2 * X;
-                    *reinterpret_cast<float2*>(p) = make_float2(acc[wr][0][py] + b0, acc[wr][1][py] + b0);
-                    *reinterpret_cast<float2*>(p + out.sc) = make_float2(acc[wr][0][2 + py] + b1, acc[wr][1][2 + py] + b1);
-                }
-            }
-        }
-    }
+    up_store<C, false>(me, acc, out, bias, Hin, Win);
     sync_hook_end(hook);
 }
 
