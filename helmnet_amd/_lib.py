@@ -92,6 +92,11 @@ SYMBOLS = {
     "hn_fgmres_adjoint_cycle_lossy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_float, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hn_adjoint_grad_lossy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # heterogeneous density, the adjoint side: rho_grad behind k_sq_im (the cycle: rho behind rho_grad), g_rho_grad behind g_k_sq_im
+    "hn_residual_vjp_medium": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "hn_fgmres_adjoint_cycle_medium": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                               c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hn_adjoint_grad_medium": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hn_residual_f64_lossy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "hn_fgmres_refine_cycle_lossy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_float, c_int, c_float,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -387,3 +387,45 @@ class SolveImplicitLossy(torch.autograd.Function):
         ctx.adjoint_info.update({"cycles": adj["cycles"], "rmse": adj["residual_norm"], "converged": adj["converged"], "iterations": adj["iterations"],
                                  "unet_evaluations": adj["unet_evaluations"]})
         return None, g_sos, g_alpha, g_src
+
+
+class SolveImplicitMedium(torch.autograd.Function):
+    """``SolveImplicitLossy`` for a medium of heterogeneous density, with absorption (``spec["lossy"]``) or without (``alpha`` is then a placeholder
+    and gets no gradient): (sos, alpha, rho, src) -> the converged wavefield of A_rho u = src.  backward solves A_rho^H lam = g (gmres_adjoint with
+    ``density``), forms dJ/dk_sq, dJ/dk_sq_im, dJ/dq and dJ/dsrc in one call (hn_adjoint_grad_medium) and chains: to ``sos`` and ``alpha`` through
+    ``absorption.complex_k_sq_grads`` (without absorption: the lossless chain of ``adjoint_state_grads``), to ``rho`` through
+    ``density.log_density_gradient_vjp`` -- q does not enter its own gradient, dJ/dq = Re(conj(lam) b D u) per axis -- summed to rho's own shape."""
+
+    @staticmethod
+    def forward(ctx, spec, sos, alpha, rho, src):
+        ctx.spec, ctx.src_batch, ctx.adjoint_info = spec, src.shape[0], spec["info"]
+        ctx.save_for_backward(sos.detach(), alpha.detach(), rho.detach())
+        return spec["wavefield"].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        _no_double_backward()
+        from .absorption import complex_k_sq_grads
+        from .density import log_density_gradient_vjp
+        from .gmres import gmres_adjoint
+        spec = ctx.spec
+        sos, alpha, rho = ctx.saved_tensors
+        solver, u, lossy = spec["solver"], spec["wavefield"], spec["lossy"]
+        need = ctx.needs_input_grad
+        with torch.no_grad():
+            medium = {"absorption": alpha, "density": rho} if lossy else {"density": rho}
+            adj = gmres_adjoint(solver, sos, g.detach().float().contiguous(), **medium, **spec["adjoint_kwargs"])
+            lam = adj["wavefield"]
+            g_k_sq, g_k_sq_im, g_q, g_src = solver.engine().adjoint_grad_medium(lam, u, ctx.src_batch if need[4] else None, lossy)
+            g_sos = g_alpha = g_rho = None
+            if lossy and (need[1] or need[2]):
+                g_sos, g_alpha = complex_k_sq_grads(g_k_sq, g_k_sq_im, sos, alpha, float(solver.hparams.omega))
+                g_sos = g_sos if need[1] else None
+                g_alpha = (g_alpha.sum_to_size(alpha.shape) if alpha.dim() else g_alpha.sum()) if need[2] else None
+            elif need[1]:
+                g_sos = adjoint_state_grads(lam, u, sos, float(solver.hparams.omega), g_k_sq)[0]
+            if need[3]:
+                g_rho = log_density_gradient_vjp(g_q, rho.expand(g_q.shape[0], 1, *g_q.shape[2:])).sum_to_size(rho.shape)
+        ctx.adjoint_info.update({"cycles": adj["cycles"], "rmse": adj["residual_norm"], "converged": adj["converged"], "iterations": adj["iterations"],
+                                 "unet_evaluations": adj["unet_evaluations"]})
+        return None, g_sos, g_alpha, g_rho, g_src

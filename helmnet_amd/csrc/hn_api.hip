@@ -790,16 +790,19 @@ int hn_residual_medium(hn_ctx* ctx, const float* wf, const float* k_sq, const fl
     return residual_entry(ctx, "hn_residual_medium", Medium{k_sq, k_sq_im, rho_grad}, wf, src, src_batch, res, batch, stream);
 }
 
-// hn_residual_vjp (rect_ok false: its adjoint kernels are a square domain's) and hn_residual_vjp_lossy (the LDS-line kernels, either kind of domain)
+// hn_residual_vjp (rect_ok false: its adjoint kernels are a square domain's), hn_residual_vjp_lossy and hn_residual_vjp_medium (the LDS-line kernels,
+// either kind of domain)
 static int residual_vjp_entry(hn_ctx* ctx, const char* who, bool rect_ok, const Medium& m, const float* g, float* out, int batch, void* stream) {
     if (!ctx || !g || !m.k_sq || !out) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (ctx->rect && !rect_ok) return rect_unsupported(ctx, who);
     if (batch <= 0) return fail(ctx, HN_ERR_ARG, "batch must be positive (got %d)", batch);
-    if (m.k_sq_im != nullptr && g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);   // (ahead of the overlap below)
+    if (m.kind() != Medium::Kind::Lossless && g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);   // (ahead of the overlap below)
     const size_t plane = (size_t)ctx->geo.plane();
-    const MemRange r[] = {{m.k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"}, {out, sizeof(float) * (size_t)batch * 2 * plane, true, "out"}};
+    const MemRange r[] = {{m.k_sq_im, sizeof(float) * (size_t)batch * plane, false, "k_sq_im"},
+                          {m.rho_grad, sizeof(float) * (size_t)batch * 2 * plane, false, "rho_grad"},
+                          {out, sizeof(float) * (size_t)batch * 2 * plane, true, "out"}};
     const char *a, *b;
-    if (first_overlap(r, 2, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
+    if (first_overlap(r, 3, &a, &b)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, a, b);
     DeviceGuard guard(ctx);
     return spec_backward(ctx, who, m, g, out, nullptr, batch, (hipStream_t)stream);
 }
@@ -811,6 +814,14 @@ int hn_residual_vjp(hn_ctx* ctx, const float* g, const float* k_sq, float* out, 
 int hn_residual_vjp_lossy(hn_ctx* ctx, const float* g, const float* k_sq, const float* k_sq_im, float* out, int batch, void* stream) {
     if (ctx && !k_sq_im) return fail(ctx, HN_ERR_ARG, "hn_residual_vjp_lossy: k_sq_im is NULL (a lossless medium is hn_residual_vjp)");
     return residual_vjp_entry(ctx, "hn_residual_vjp_lossy", true, Medium{k_sq, k_sq_im}, g, out, batch, stream);
+}
+
+int hn_residual_vjp_medium(hn_ctx* ctx, const float* g, const float* k_sq, const float* k_sq_im, const float* rho_grad, float* out, int batch,
+                           void* stream) {
+    if (ctx && !rho_grad)
+        return fail(ctx, HN_ERR_ARG, "hn_residual_vjp_medium: rho_grad is NULL (a medium of constant density is hn_residual_vjp_lossy, or hn_residual_vjp "
+                    "without absorption)");
+    return residual_vjp_entry(ctx, "hn_residual_vjp_medium", true, Medium{k_sq, k_sq_im, rho_grad}, g, out, batch, stream);
 }
 
 int hn_rmse(hn_ctx* ctx, const float* res, float* rmse, int batch, void* stream) {

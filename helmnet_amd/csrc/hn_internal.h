@@ -585,8 +585,11 @@ int spec_lossy_reserve(hn_ctx* ctx, const char* who, hipStream_t s);
 int spec_forward(hn_ctx* ctx, const char* who, const Medium& m, const float* wf, float* out, const float* src, int src_batch, int batch, float* sumsq,
                  hipStream_t s, int* it_counter = nullptr, int sumsq_stride = 0);
 // Its adjoint: out = A^H g [+ add].  Lossless: spec_adjoint itself; Lossy: L^H(g) + (ksq - i ksq_im) g on the LDS-line kernels (g != out; `add` may alias
-// out); Density: refused, the variable-density operator has no adjoint
+// out); Density: that minus D_x^H(conj(b_x) q_x g) + D_y^H(conj(b_y) q_y g) on the same kernels, k_sq_im nullable
 int spec_backward(hn_ctx* ctx, const char* who, const Medium& m, const float* g, float* out, const float* add, int batch, hipStream_t s);
+// g_rho_grad[b][0] = Re(conj(lam) b_x D_x u), [b][1] = Re(conj(lam) b_y D_y u) (real [B][2][h][w]): dJ/dq of the variable-density operator, on the tables
+// of spec_forward, which the caller has asked spec_lossy_reserve for before its first launch
+int spec_density_grad(hn_ctx* ctx, const char* who, const float* lam, const float* u, float* g_rho_grad, int batch, hipStream_t s);
 // HN_ERR_UNSUPPORTED "<who>: not implemented on a rectangular domain ..." (every entry point that reads the domain and has no rectangular path)
 int rect_unsupported(hn_ctx* ctx, const char* who);
 // ---- float64 residual check (hn_f64.hip) ----

@@ -31,6 +31,7 @@
 // also leaves the partial sums of |w|^2 that k_norm_part leaves for the forward operator).  The learned network approximates A^-1, not A^-H; the PML
 // operator is complex-symmetric up to the diagonal similarity W = gamma_y[i] gamma_x[j] (A^T ~ W A W^-1), so A^-H v ~ conj(W A^-1 (conj(v) / W)): the
 // preconditioner is the SAME hn_step problem between two streaming kernels (k_seed_adj, k_take_adj) that conjugate and scale by 1 / W and W.
+// hn_fgmres_adjoint_cycle_medium is that cycle on A_rho^H; its similarity weight is W / rho (k_seed_adj_rho, k_take_adj_rho read the caller's rho plane).
 // hn_adjoint_grad (at the end) is the pointwise product that turns the adjoint solution into the gradients with respect to k_sq and the source.
 #include "hn_internal.h"
 
@@ -465,6 +466,53 @@ __global__ __launch_bounds__(256) void k_take_adj(const float* __restrict__ wf, 
     *reinterpret_cast<float4*>(pz) = zr; *reinterpret_cast<float4*>(pz + P) = zi;
 }
 
+// ---- the variable-density adjoint cycle's twins of the two above: the weight is W / rho, rho [B][n^2] per sample (A_rho = rho * a W-symmetric operator) ----
+// The same expressions with ONE more operation per component, a multiply resp. a true division by rho / rho[b][0], in front of alpha's: with rho == 1
+// the bits are k_seed_adj's and k_take_adj's.  Same traffic plus the one plane.  The sample's first pixel (a corner of the PML: the background) normalises
+// the plane, so that only ratios of rho enter and the network's right-hand side keeps the magnitude precond_scale gives it whatever the units of rho.
+
+// src = alpha * ((conj(v) * winv) * (rho / rho[b][0])); res = 0 - src, wf = 0
+__global__ __launch_bounds__(256) void k_seed_adj_rho(const float* __restrict__ vin, const float* __restrict__ winv, const float* __restrict__ rho, float alpha,
+                                                      float* __restrict__ src, float* __restrict__ res, float* __restrict__ wf, long P) {
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)blockIdx.y * 2 * P + off;
+    const float4 vr = *reinterpret_cast<const float4*>(vin + at), vi = *reinterpret_cast<const float4*>(vin + at + P);
+    const float4 ir = *reinterpret_cast<const float4*>(winv + off), ii = *reinterpret_cast<const float4*>(winv + P + off);
+    const float r0 = rho[(long)blockIdx.y * P];
+    const float4 rw = *reinterpret_cast<const float4*>(rho + (long)blockIdx.y * P + off);
+    const float4 rh = make_float4(rw.x / r0, rw.y / r0, rw.z / r0, rw.w / r0);
+    const float4 pr = make_float4(vr.x * ir.x + vi.x * ii.x, vr.y * ir.y + vi.y * ii.y, vr.z * ir.z + vi.z * ii.z, vr.w * ir.w + vi.w * ii.w);
+    const float4 pi = make_float4(vr.x * ii.x - vi.x * ir.x, vr.y * ii.y - vi.y * ir.y, vr.z * ii.z - vi.z * ir.z, vr.w * ii.w - vi.w * ir.w);
+    const float4 sr = mul4(make_float4(pr.x * rh.x, pr.y * rh.y, pr.z * rh.z, pr.w * rh.w), alpha);
+    const float4 si = mul4(make_float4(pi.x * rh.x, pi.y * rh.y, pi.z * rh.z, pi.w * rh.w), alpha);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(src + at) = sr; *reinterpret_cast<float4*>(src + at + P) = si;
+    *reinterpret_cast<float4*>(res + at) = zero_minus4(sr); *reinterpret_cast<float4*>(res + at + P) = zero_minus4(si);
+    *reinterpret_cast<float4*>(wf + at) = z; *reinterpret_cast<float4*>(wf + at + P) = z;
+}
+
+// z = conj(w * wf) / (rho / rho[b][0]) / alpha, into slot `slot` of zbasis and into the dense operator input
+__global__ __launch_bounds__(256) void k_take_adj_rho(const float* __restrict__ wf, const float* __restrict__ w, const float* __restrict__ rho, float alpha,
+                                                      float* __restrict__ vin, float* __restrict__ zbasis, long P, int slot, int restart) {
+    const int b = blockIdx.y;
+    const long off = (long)blockIdx.x * kKryChunk + threadIdx.x * 4;
+    if (off >= P) return;
+    const long at = (long)b * 2 * P + off;
+    const float4 fr = *reinterpret_cast<const float4*>(wf + at), fi = *reinterpret_cast<const float4*>(wf + at + P);
+    const float4 wr = *reinterpret_cast<const float4*>(w + off), wi = *reinterpret_cast<const float4*>(w + P + off);
+    const float r0 = rho[(long)b * P];
+    const float4 rw = *reinterpret_cast<const float4*>(rho + (long)b * P + off);
+    const float4 rh = make_float4(rw.x / r0, rw.y / r0, rw.z / r0, rw.w / r0);
+    const float4 pr = make_float4(wr.x * fr.x - wi.x * fi.x, wr.y * fr.y - wi.y * fi.y, wr.z * fr.z - wi.z * fi.z, wr.w * fr.w - wi.w * fi.w);
+    const float4 pi = zero_minus4(make_float4(wr.x * fi.x + wi.x * fr.x, wr.y * fi.y + wi.y * fr.y, wr.z * fi.z + wi.z * fr.z, wr.w * fi.w + wi.w * fr.w));
+    const float4 zr = div4(make_float4(pr.x / rh.x, pr.y / rh.y, pr.z / rh.z, pr.w / rh.w), alpha);
+    const float4 zi = div4(make_float4(pi.x / rh.x, pi.y / rh.y, pi.z / rh.z, pi.w / rh.w), alpha);
+    float* pz = zbasis + ((long)b * restart + slot) * 2 * P + off;
+    *reinterpret_cast<float4*>(vin + at) = zr; *reinterpret_cast<float4*>(vin + at + P) = zi;
+    *reinterpret_cast<float4*>(pz) = zr; *reinterpret_cast<float4*>(pz + P) = zi;
+}
+
 // g_k_sq[b] = -(l_re u_re + l_im u_im); g_src (nullable): lambda per sample (per == 1), or its sum over the `per` samples of the batch in sample order
 // GIm: empty (hn_adjoint_grad), or one float* (hn_adjoint_grad_lossy): g_k_sq_im[b] = l_re u_im - l_im u_re from the same loads; the pack stands last, so
 // the lossless kernel keeps its arguments, and the other two outputs their expressions and bits
@@ -504,6 +552,7 @@ struct Precond {
     int iters = 0;             // hn_step iterations per inner step; 0: z = v
     float alpha = 1.f;         // the learned solve sees alpha v
     const char* who = "";      // the entry point, for what the operator and hn_step report from inside the cycle
+    const float* rho = nullptr;   // [B][n^2], the adjoint cycle of a variable-density medium: the similarity weight is W / rho (k_seed_adj_rho, k_take_adj_rho)
 };
 
 // what hn_step reported, under the name of the entry point that called it
@@ -619,8 +668,8 @@ int prepare(hn_ctx* ctx, int batch, int restart, hipStream_t s) {
 // The restart cycle's launches, the workspace prepared.  tol_dev / pre_stopped: see SmallArgs (nullptr: hn_gmres_cycle, whose bits they leave alone --
 // the comparison est < tol is the same one on the same doubles); x, rhs and the outputs may lie in a workspace of the library's.  pc: the flexible
 // cycle's preconditioner (its workspace prepared when pc.iters > 0); the operator input then holds z_k while A is applied and v_{k+1} after k_scale.
-// op: Op::Adjoint runs the same cycle on A^H (and, with pc.iters > 0, needs ctx->adjw prepared; a variable-density medium has none: spec_backward refuses
-// it before anything is enqueued); Op::Forward is every launch and argument of before.
+// op: Op::Adjoint runs the same cycle on A^H (and, with pc.iters > 0, needs ctx->adjw prepared and, for a variable-density medium, pc.rho);
+// Op::Forward is every launch and argument of before.
 int launch_cycle(hn_ctx* ctx, Op op, float* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart, double tol,
                  const double* tol_dev, const int* pre_stopped, const Precond& pc, float* basis, float* hess, float* rmse, int32_t* k_used, hipStream_t s) {
     const KrylovWs& ws = *ctx->kry;
@@ -645,12 +694,15 @@ int launch_cycle(hn_ctx* ctx, Op op, float* x, const Medium& m, const float* rhs
     for (int k = 0; k < restart; ++k) {
         if (pc.zbasis != nullptr && pc.iters > 0) {
             const PrecondWs& p = *ctx->pcw;
-            if (adj) hipLaunchKernelGGL(k_seed_adj, grid, blk, 0, s, ws.vin, ctx->adjw->winv, pc.alpha, p.src, p.res, p.wf, P);
+            if (adj && pc.rho != nullptr) hipLaunchKernelGGL(k_seed_adj_rho, grid, blk, 0, s, ws.vin, ctx->adjw->winv, pc.rho, pc.alpha, p.src, p.res, p.wf, P);
+            else if (adj) hipLaunchKernelGGL(k_seed_adj, grid, blk, 0, s, ws.vin, ctx->adjw->winv, pc.alpha, p.src, p.res, p.wf, P);
             else hipLaunchKernelGGL(k_seed, grid, blk, 0, s, ws.vin, pc.alpha, p.src, p.res, p.wf, P);
             if ((rc = zero_async(ctx, p.states, sizeof(float) * (size_t)batch * kState * (size_t)p.state_len, s)) != HN_OK) return rc;
             rc = step_entry(ctx, m.step_name(), p.wf, p.res, p.states, m, p.src, batch, batch, pc.iters, nullptr, nullptr, nullptr, nullptr, s);
             if (rc != HN_OK) return step_named(ctx, pc.who, rc);
-            if (adj) hipLaunchKernelGGL(k_take_adj, grid, blk, 0, s, p.wf, ctx->adjw->w, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
+            if (adj && pc.rho != nullptr)
+                hipLaunchKernelGGL(k_take_adj_rho, grid, blk, 0, s, p.wf, ctx->adjw->w, pc.rho, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
+            else if (adj) hipLaunchKernelGGL(k_take_adj, grid, blk, 0, s, p.wf, ctx->adjw->w, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
             else hipLaunchKernelGGL(k_take, grid, blk, 0, s, p.wf, pc.alpha, ws.vin, pc.zbasis, P, k, restart);
         } else if (pc.zbasis != nullptr) {
             hipLaunchKernelGGL(k_take_copy, grid, blk, 0, s, ws.vin, pc.zbasis, P, k, restart);
@@ -777,7 +829,8 @@ int refine_prepare(hn_ctx* ctx, int batch, hipStream_t s, bool lossy) {
 // the ones named first ("k_sq_im overlaps basis").  hn_gmres_cycle reports a missing domain with HN_ERR_ARG, the others with HN_ERR_STATE, and a caller may
 // rely on either: a known wart.
 int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, const void* x, const Medium& m, const float* rhs, int rhs_batch, int batch,
-                     int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64) {
+                     int restart, const float* basis, const float* zbasis, const float* hess, const float* rmse, const int32_t* k_used, const double* rmse64,
+                     const float* rho = nullptr) {
     if (!ctx || !x || !m.k_sq || !rhs || !basis || !hess || !rmse || !k_used || (refine && !rmse64) || (flexible && !zbasis))
         return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (ctx->rect) return rect_unsupported(ctx, who);
@@ -786,16 +839,16 @@ int check_cycle_args(hn_ctx* ctx, const char* who, bool refine, bool flexible, c
     if (restart < 1 || restart > kKryMaxRestart) return fail(ctx, HN_ERR_ARG, "%s: restart %d outside [1, %d]", who, restart, kKryMaxRestart);
     if (rhs_batch != 1 && rhs_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: rhs batch %d must be 1 or equal to the batch %d", who, rhs_batch, batch);
     const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch, R = (size_t)restart;
-    const MemRange r[] = {{m.k_sq_im, B * P * 4, true, "k_sq_im"}, {m.rho_grad, B * 2 * P * 4, true, "rho_grad"},
+    const MemRange r[] = {{m.k_sq_im, B * P * 4, true, "k_sq_im"}, {m.rho_grad, B * 2 * P * 4, true, "rho_grad"}, {rho, B * P * 4, true, "rho"},
                           {x, B * 2 * P * (refine ? 8 : 4), true, "x"}, {m.k_sq, B * P * 4, true, "k_sq"}, {rhs, (size_t)rhs_batch * 2 * P * 4, true, "rhs"},
                           {basis, B * (R + 1) * 2 * P * 4, true, "basis"}, {zbasis, B * R * 2 * P * 4, true, "zbasis"},
                           {hess, B * (R + 1) * R * 2 * 4, true, "hess"}, {rmse, (R + 1) * B * 4, true, "rmse"}, {k_used, B * 4, true, "k_used"},
                           {rmse64, B * 8, true, "rmse64"}};
-    for (int i = 0; i < 7; ++i)   // the fields are read and written as float4 (x of the refinement: as double2); a NULL one is aligned
+    for (int i = 0; i < 8; ++i)   // the fields are read and written as float4 (x of the refinement: as double2); a NULL one is aligned
         if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
     if (reinterpret_cast<uintptr_t>(rmse64) % 8 != 0) return fail(ctx, HN_ERR_ARG, "%s: rmse64 is not 8-byte aligned", who);
     const char *na, *nb;
-    if (first_overlap(r, 11, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
+    if (first_overlap(r, 12, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     return HN_OK;
 }
 
@@ -867,11 +920,15 @@ void precond_free(hn_ctx* ctx) { precond_ws_free(ctx); }
 
 using namespace hn;
 
-// hn_gmres_cycle, hn_fgmres_cycle[_lossy|_medium] and hn_fgmres_adjoint_cycle[_lossy] behind their own NULL refusals
+// hn_gmres_cycle, hn_fgmres_cycle[_lossy|_medium] and hn_fgmres_adjoint_cycle[_lossy|_medium] behind their own NULL refusals; rho: the last one's
 static int cycle_entry(hn_ctx* ctx, const char* who, Op op, bool flexible, float* x, const Medium& m, const float* rhs, int rhs_batch, int batch, int restart,
-                       float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used, void* stream) {
-    int rc = check_cycle_args(ctx, who, false, flexible, x, m, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr);
+                       float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used, void* stream,
+                       const float* rho = nullptr) {
+    int rc = check_cycle_args(ctx, who, false, flexible, x, m, rhs, rhs_batch, batch, restart, basis, zbasis, hess, rmse, k_used, nullptr, rho);
     if (rc != HN_OK) return rc;
+    if (op == Op::Adjoint && m.kind() == Medium::Kind::Density && precond_iters > 0 && rho == nullptr)
+        return fail(ctx, HN_ERR_ARG, "%s: rho is NULL (precond_iters %d: the preconditioner's similarity weight is W / rho; only precond_iters 0 runs without)", who,
+                    precond_iters);
     DeviceGuard guard(ctx);
     hipStream_t s = (hipStream_t)stream;
     if (!flexible) return run_cycle(ctx, op, x, m, rhs, rhs_batch, batch, restart, tol, Precond{}, basis, hess, rmse, k_used, s);
@@ -879,7 +936,8 @@ static int cycle_entry(hn_ctx* ctx, const char* who, Op op, bool flexible, float
     // (precond_iters 0 has not asked step_entry for the tables)
     if (m.kind() != Medium::Kind::Lossless && (rc = spec_lossy_reserve(ctx, who, s)) != HN_OK) return rc;
     if (op == Op::Adjoint && precond_iters > 0 && (rc = adjoint_w_prepare(ctx, who)) != HN_OK) return rc;
-    return run_cycle(ctx, op, x, m, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who}, basis, hess, rmse, k_used, s);
+    return run_cycle(ctx, op, x, m, rhs, rhs_batch, batch, restart, tol, Precond{zbasis, precond_iters, precond_scale, who, precond_iters > 0 ? rho : nullptr},
+                     basis, hess, rmse, k_used, s);
 }
 
 extern "C" int hn_gmres_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
@@ -921,6 +979,16 @@ extern "C" int hn_fgmres_adjoint_cycle_lossy(hn_ctx* ctx, float* x, const float*
                        precond_scale, basis, zbasis, hess, rmse, k_used, stream);
 }
 
+extern "C" int hn_fgmres_adjoint_cycle_medium(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im, const float* rho_grad, const float* rho,
+                                              const float* rhs, int rhs_batch, int batch, int restart, float tol, int precond_iters, float precond_scale,
+                                              float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used, void* stream) {
+    if (ctx && !rho_grad)
+        return fail(ctx, HN_ERR_ARG, "hn_fgmres_adjoint_cycle_medium: rho_grad is NULL (a medium of constant density is hn_fgmres_adjoint_cycle_lossy, or "
+                    "hn_fgmres_adjoint_cycle without absorption)");
+    return cycle_entry(ctx, "hn_fgmres_adjoint_cycle_medium", Op::Adjoint, true, x, Medium{k_sq, k_sq_im, rho_grad}, rhs, rhs_batch, batch, restart, tol,
+                       precond_iters, precond_scale, basis, zbasis, hess, rmse, k_used, stream, rho);
+}
+
 extern "C" int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq, const float* rhs, int rhs_batch, int batch, int restart, float tol,
                                        int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse, int32_t* k_used,
                                        void* stream) {
@@ -928,23 +996,27 @@ extern "C" int hn_fgmres_adjoint_cycle(hn_ctx* ctx, float* x, const float* k_sq,
                        zbasis, hess, rmse, k_used, stream);
 }
 
-// hn_adjoint_grad (g_k_sq_im nullptr, lossy false) and hn_adjoint_grad_lossy
+// hn_adjoint_grad (g_k_sq_im nullptr, lossy false), hn_adjoint_grad_lossy and hn_adjoint_grad_medium (medium: g_rho_grad required, lossy = g_k_sq_im given)
 static int adjoint_grad_entry(hn_ctx* ctx, const char* who, bool lossy, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq,
-                              float* g_k_sq_im, float* g_src, void* stream) {
-    if (!ctx || !lambda || !u || !g_k_sq || (lossy && !g_k_sq_im)) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
+                              float* g_k_sq_im, float* g_src, void* stream, bool medium = false, float* g_rho_grad = nullptr) {
+    if (!ctx || !lambda || !u || !g_k_sq || (lossy && !g_k_sq_im) || (medium && !g_rho_grad)) return fail(ctx, HN_ERR_ARG, "%s: NULL argument", who);
     if (ctx->rect) return rect_unsupported(ctx, who);
     if (ctx->tab.n == 0) return fail(ctx, HN_ERR_STATE, "%s: hn_set_domain has not been called", who);
     if (batch < 1) return fail(ctx, HN_ERR_ARG, "%s: batch must be positive (got %d)", who, batch);
     if (src_batch != 1 && src_batch != batch) return fail(ctx, HN_ERR_ARG, "%s: src batch %d must be 1 or equal to the batch %d", who, src_batch, batch);
     const size_t P = (size_t)ctx->tab.n * ctx->tab.n, B = (size_t)batch;
     const MemRange r[] = {{lambda, B * 2 * P * 4, false, "lambda"}, {u, B * 2 * P * 4, false, "u"}, {g_k_sq, B * P * 4, true, "g_k_sq"},
-                          {g_src, (size_t)src_batch * 2 * P * 4, true, "g_src"}, {g_k_sq_im, B * P * 4, true, "g_k_sq_im"}};
-    const int nr = lossy ? 5 : 4;
+                          {g_src, (size_t)src_batch * 2 * P * 4, true, "g_src"}, {g_k_sq_im, B * P * 4, true, "g_k_sq_im"},
+                          {g_rho_grad, B * 2 * P * 4, true, "g_rho_grad"}};
+    const int nr = medium ? 6 : lossy ? 5 : 4;   // (a NULL g_k_sq_im of the medium call is aligned and overlaps nothing)
     for (int i = 0; i < nr; ++i)   // read and written as float4; a NULL g_src is aligned
         if (reinterpret_cast<uintptr_t>(r[i].p) % 16 != 0) return fail(ctx, HN_ERR_ARG, "%s: %s is not 16-byte aligned", who, r[i].name);
     const char *na, *nb;
     if (first_overlap(r, nr, &na, &nb)) return fail(ctx, HN_ERR_ARG, "%s: %s overlaps %s", who, na, nb);
     DeviceGuard guard(ctx);
+    // the line tables before the first launch: a first call under stream capture that has them to build enqueues nothing
+    if (medium)
+        if (const int rc = spec_lossy_reserve(ctx, who, (hipStream_t)stream); rc != HN_OK) return rc;
     const int per = (g_src != nullptr && src_batch == 1) ? batch : 1;
     const dim3 grid((unsigned)((P + kKryChunk - 1) / kKryChunk), batch / per);
     if (lossy)
@@ -952,7 +1024,14 @@ static int adjoint_grad_entry(hn_ctx* ctx, const char* who, bool lossy, const fl
     else
         hipLaunchKernelGGL((k_adjoint_grad<>), grid, dim3(256), 0, (hipStream_t)stream, lambda, u, g_k_sq, g_src, (long)P, per);
     HN_HIP(ctx, hipGetLastError());
+    if (medium) return spec_density_grad(ctx, who, lambda, u, g_rho_grad, batch, (hipStream_t)stream);
     return HN_OK;
+}
+
+extern "C" int hn_adjoint_grad_medium(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_k_sq_im,
+                                      float* g_rho_grad, float* g_src, void* stream) {
+    return adjoint_grad_entry(ctx, "hn_adjoint_grad_medium", g_k_sq_im != nullptr, lambda, u, src_batch, batch, g_k_sq, g_k_sq_im, g_src, stream, true,
+                              g_rho_grad);
 }
 
 extern "C" int hn_adjoint_grad(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_src, void* stream) {

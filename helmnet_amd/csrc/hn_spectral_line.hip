@@ -4,7 +4,8 @@
 //       k_spec_pfa<Q, P> (P = 3, 5, 7 held in registers) of hn_spectral.hip take, and that otherwise run the dense n x n operator; forward and adjoint
 //   a rectangular h x w domain (hn_set_domain_rect, h != w): each axis factored on its own, with its own tables; the lossless operator forward only
 //   the lossy operator (complex k_sq) on either kind of domain; forward and adjoint
-//       and on its tables the variable-density operator (rho_grad: a - q b on the first derivative in step 6, one more plane read per pass); forward only
+//       and on its tables the variable-density operator (rho_grad: a - q b on the first derivative, one more plane read per pass) -- forward in step 6,
+//       adjoint at the load -- and k_spec_line_d1, the first-derivative pass of hn_adjoint_grad_medium (behind k_spec_line)
 // Line length, line count and row pitch are three arguments:
 //   column pass   lines of length h, w of them, element stride w:   out  = ay d/dy + by d2/dy2
 //   row pass      lines of length w, h of them:                      out += ax d/dx + bx d2/dx2 [+ k_sq u - src], per-sample sum of squares
@@ -165,6 +166,9 @@ struct LineTabs {
 // element it stores, and step 6 multiplies the first derivative with a[i] - q b[i] instead of a[i]: rho (1/gamma) d((1/rho)(1/gamma) du) in expanded
 // form is a du + b d2u - b q du.  ksq_im may then be null (a lossless medium: the plane is not read, the pointwise term is the lossless kernels');
 // the column pass is handed null.  Nothing else differs: no further LDS, no further transform.
+// The same two pointers with ADJ: the adjoint of that operator (hn_residual_vjp_medium / hn_fgmres_adjoint_cycle_medium),
+// L^H g - D^H(conj(b) q g) per axis: the first of the two loads is conj(a - q b) g, q from plane AXIS at the element LOADED (the multiplication stands in
+// front of the transposed derivative), the pointwise term conj(ksq + i ksq_im) g or, ksq_im null, ksq g.  LDS and lines per block are the adjoint pass's.
 template <int AXIS, bool ADJ, typename... KsqIm>
 __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restrict__ wf, float* out, const float* __restrict__ ksq,
                                                             const float* __restrict__ src, long src_sb, LineTabs t, int len, int count, int pitch, int P,
@@ -172,7 +176,7 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
                                                             const int* __restrict__ it_counter, int sumsq_stride, KsqIm... ksq_im, const float* add) {
     constexpr int NF = ADJ ? 2 : 1;       // buffers through the forward transforms
     constexpr bool RHO = sizeof...(KsqIm) == 2;
-    static_assert(sizeof...(KsqIm) <= 2 && !(RHO && ADJ), "k_spec_line: (ksq_im) or, forward only, (ksq_im, rho_grad)");
+    static_assert(sizeof...(KsqIm) <= 2, "k_spec_line: (ksq_im) or (ksq_im, rho_grad)");
     extern __shared__ float2 lbuf[];
     __shared__ float red[kLineThreads / 64];
     const int tid = threadIdx.x, b = blockIdx.y;
@@ -195,13 +199,22 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
         const int i = AXIS == 0 ? e - l * len : e >> logl;
         const int line = line0 + l;
         float2 u = make_float2(0.f, 0.f);       // a block's lines past the last one carry zeros and are not stored
+        [[maybe_unused]] float q = 0.f;         // (ADJ && RHO) q of this axis at the element loaded
         if (line < count) {
             const long o = AXIS == 0 ? (long)line * pitch + i : (long)i * pitch + line;
             u = make_float2(pre[o], pre[o + plane]);
+            if constexpr (ADJ && RHO) {
+                const float* const kr[] = {ksq_im...};
+                q = kr[1][((long)b * 2 + AXIS) * plane + o];
+            }
         }
         const int sl = l * len + t.slot[i];
         if constexpr (!ADJ) {
             B0[sl] = u;
+        } else if constexpr (RHO) {             // conj(a - q b) g: the forward pass's step-6 coefficient, conjugated
+            const float2 ca = t.a[i], cb = t.b[i];
+            B0[sl] = cmulc(u, make_float2(ca.x - q * cb.x, ca.y - q * cb.y));
+            B1[sl] = cmulc(u, cb);
         } else {
             B0[sl] = cmulc(u, t.a[i]);
             B1[sl] = cmulc(u, t.b[i]);
@@ -352,6 +365,93 @@ __global__ __launch_bounds__(kLineThreads) void k_spec_line(const float* __restr
     }
 }
 
+// The first-derivative pass of the density gradient (hn_adjoint_grad_medium): per line D u = F^-1 (i k) F u on k_spec_line's maps, tables, transforms
+// and row-segment addressing, and at the store out[b][AXIS] = Re(conj(lam) * b[i] * D u / len) = dJ/dq of this axis, `lam` read at the element stored;
+// `out` is the real [B][2][h][w] field, plane 0 written by the row pass (x), plane 1 by the column pass (y).  A sibling of k_spec_line and not a mode of it:
+// there is no second-derivative spectrum, so a line needs ONE buffer at P = 1 (the multiplier goes on in place between the two in-place transforms) and
+// two otherwise (the P-point DFTs go from one to the other and back).  Dynamic LDS: (P == 1 ? 1 : 2) buffers of L * len float2, then the Q and P twiddles.
+template <int AXIS>
+__global__ __launch_bounds__(kLineThreads) void k_spec_line_d1(const float* __restrict__ u, const float* __restrict__ lam, float* __restrict__ out, LineTabs t,
+                                                               int len, int count, int pitch, int P, int logq, int logl) {
+    extern __shared__ float2 lbuf[];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int Q = 1 << logq, L = 1 << logl, PH = (P + 1) >> 1;
+    const int ln = L * len;
+    float2* const B0 = lbuf;
+    float2* const B1 = lbuf + ln;             // (P > 1 only)
+    float2* const twq = lbuf + (P == 1 ? 1 : 2) * ln;
+    float2* const wp = twq + Q;
+    const long plane = AXIS == 0 ? (long)count * pitch : (long)len * pitch;
+    const int line0 = blockIdx.x * L;
+    for (int i = tid; i < Q; i += kLineThreads) twq[i] = t.tw_q[i];
+    for (int i = tid; i < P; i += kLineThreads) wp[i] = t.wp[i];
+    const float* pre = u + (long)b * 2 * plane;
+    for (int e = tid; e < ln; e += kLineThreads) {
+        const int l = AXIS == 0 ? e / len : e & (L - 1);
+        const int i = AXIS == 0 ? e - l * len : e >> logl;
+        const int line = line0 + l;
+        float2 v = make_float2(0.f, 0.f);
+        if (line < count) {
+            const long o = AXIS == 0 ? (long)line * pitch + i : (long)i * pitch + line;
+            v = make_float2(pre[o], pre[o + plane]);
+        }
+        B0[l * len + t.slot[i]] = v;
+    }
+    __syncthreads();
+    fft_inplace<false>(B0, B0, 1, L * P, logq, twq, tid);
+    if (P == 1) {
+        for (int e = tid; e < ln; e += kLineThreads) {
+            const float kk1 = t.k1m[e & (Q - 1)];
+            const float2 Y = B0[e];
+            B0[e] = make_float2(-Y.y * kk1, Y.x * kk1);       // (0, k) * U, in place: the element is this thread's alone
+        }
+        __syncthreads();
+    } else {
+        for (int item = tid; item < (L * PH) << logq; item += kLineThreads) {
+            const int r = item & (Q - 1), lk = item >> logq;
+            const int l = lk / PH, k1 = lk - l * PH;
+            const int base = l * len + r;
+            float2 A[1], Bv[1];
+            pdft_sums<1>(B0 + base, B0 + base, Q, P, k1, wp, A, Bv);
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                if (m == 1 && k1 == 0) break;
+                const int kk = m == 0 ? k1 : P - k1;
+                const float kk1 = t.k1m[(kk << logq) + r];
+                const float2 Y = m == 0 ? plus_i(A[0], Bv[0]) : minus_i(A[0], Bv[0]);
+                B1[base + (kk << logq)] = make_float2(-Y.y * kk1, Y.x * kk1);
+            }
+        }
+        __syncthreads();
+        for (int item = tid; item < (L * PH) << logq; item += kLineThreads) {
+            const int r = item & (Q - 1), lk = item >> logq;
+            const int l = lk / PH, s = lk - l * PH;
+            const int base = l * len + r;
+            float2 A[1], Bv[1];
+            pdft_sums<1>(B1 + base, B1 + base, Q, P, s, wp, A, Bv);
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                if (m == 1 && s == 0) break;
+                B0[base + ((m == 0 ? s : P - s) << logq)] = m == 0 ? minus_i(A[0], Bv[0]) : plus_i(A[0], Bv[0]);
+            }
+        }
+        __syncthreads();
+    }
+    fft_inplace<true>(B0, B0, 1, L * P, logq, twq, tid);
+    const float inv_n = 1.0f / (float)len;
+    const float* pl = lam + (long)b * 2 * plane;
+    float* po = out + ((long)b * 2 + AXIS) * plane;
+    for (int e = tid; e < ln; e += kLineThreads) {
+        const int l = AXIS == 0 ? e / len : e & (L - 1);
+        const int i = AXIS == 0 ? e - l * len : e >> logl;
+        const int line = line0 + l;
+        if (line >= count) continue;
+        const float2 z = cmul(t.b[i], B0[l * len + t.slot[i]]);
+        const long o = AXIS == 0 ? (long)line * pitch + i : (long)i * pitch + line;
+        po[o] = pl[o] * (z.x * inv_n) + pl[o + plane] * (z.y * inv_n);
+    }
+}
+
 __global__ void k_line_bump(int* counter) { atomicAdd(counter, 1); }
 
 int ilog2(int v) {
@@ -376,7 +476,10 @@ int line_kernels_lds_attr(hn_ctx* ctx) {
                           reinterpret_cast<const void*>(k_spec_line<0, false, const float*>), reinterpret_cast<const void*>(k_spec_line<1, true>),
                           reinterpret_cast<const void*>(k_spec_line<0, true>), reinterpret_cast<const void*>(k_spec_line<0, true, const float*>),
                           reinterpret_cast<const void*>(k_spec_line<1, false, const float*, const float*>),
-                          reinterpret_cast<const void*>(k_spec_line<0, false, const float*, const float*>)})
+                          reinterpret_cast<const void*>(k_spec_line<0, false, const float*, const float*>),
+                          reinterpret_cast<const void*>(k_spec_line<1, true, const float*, const float*>),
+                          reinterpret_cast<const void*>(k_spec_line<0, true, const float*, const float*>),
+                          reinterpret_cast<const void*>(k_spec_line_d1<1>), reinterpret_cast<const void*>(k_spec_line_d1<0>)})
         HN_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLineLdsAttr));
     return HN_OK;
 }
@@ -438,7 +541,7 @@ bool line_domain(const hn_ctx* ctx, LineDomain* d) {
 //   forward           ksq nullptr: the Laplacian alone; ksq_im non-null (ksq too): the row pass with the complex pointwise term
 //   adj               out = L^H(wf) + ksq wf [+ add]: three buffers, `add` on the column pass, no sum of squares; ksq_im non-null: the row pass with the
 //                     conjugate pointwise term, conj(ksq + i ksq_im) wf
-//   rho_grad          non-null (forward, with ksq; ksq_im may be null): both passes of the variable-density operator
+//   rho_grad          non-null (with ksq; ksq_im may be null): both passes of the variable-density operator, or with adj of its adjoint
 int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, const float* ksq, const float* ksq_im, const float* src, int src_batch,
                 int batch, float* sumsq, hipStream_t s, int* it_counter, int sumsq_stride, bool adj = false, const float* add = nullptr,
                 const float* rho_grad = nullptr) {
@@ -446,8 +549,8 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
     const int h = d.h, w = d.w;
     if (adj && (ksq == nullptr || src != nullptr || sumsq != nullptr || it_counter != nullptr))
         return fail(ctx, HN_ERR_ARG, "internal: the adjoint LDS-line kernels (%d x %d) take k_sq and neither a source, a sum of squares nor a counter", h, w);
-    if (rho_grad != nullptr && (adj || ksq == nullptr))
-        return fail(ctx, HN_ERR_ARG, "internal: the variable-density LDS-line kernels (%d x %d) are forward only and take k_sq", h, w);
+    if (rho_grad != nullptr && ksq == nullptr)
+        return fail(ctx, HN_ERR_ARG, "internal: the variable-density LDS-line kernels (%d x %d) take k_sq", h, w);
     const bool resid = ksq != nullptr;
     const long src_sb = src_batch == 1 ? 0 : 2L * h * w;
     const int nbuf_c = adj || cols.P == 1 ? 3 : 4, nbuf_r = adj || rows.P == 1 ? 3 : 4;
@@ -464,7 +567,10 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
     if (it_counter != nullptr) hipLaunchKernelGGL(k_line_bump, dim3(1), dim3(1), 0, s, it_counter);
     {
         ProfScope ps(ctx, KID_SPEC_COLS, s);
-        if (adj)
+        if (adj && rho_grad != nullptr)
+            hipLaunchKernelGGL((k_spec_line<1, true, const float*, const float*>), grid_c, block, lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, cols.P,
+                               logq_c, logl_c, 0, nullptr, nullptr, 0, nullptr, rho_grad, add);
+        else if (adj)
             hipLaunchKernelGGL((k_spec_line<1, true>), grid_c, block, lds_c, s, wf, out, nullptr, nullptr, 0L, tc, h, w, w, cols.P, logq_c, logl_c, 0, nullptr,
                                nullptr, 0, add);
         else if (rho_grad != nullptr)
@@ -476,7 +582,10 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
     }
     {
         ProfScope ps(ctx, KID_SPEC_ROWS, s);
-        if (adj && ksq_im != nullptr)
+        if (adj && rho_grad != nullptr)
+            hipLaunchKernelGGL((k_spec_line<0, true, const float*, const float*>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P,
+                               logq_r, logl_r, rflags, sumsq, it_counter, sumsq_stride, ksq_im, rho_grad, nullptr);
+        else if (adj && ksq_im != nullptr)
             hipLaunchKernelGGL((k_spec_line<0, true, const float*>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P, logq_r, logl_r,
                                rflags, sumsq, it_counter, sumsq_stride, ksq_im, nullptr);
         else if (rho_grad != nullptr)
@@ -492,6 +601,24 @@ int rect_launch(hn_ctx* ctx, const LineDomain& d, const float* wf, float* out, c
             hipLaunchKernelGGL((k_spec_line<0, false>), grid_r, block, lds_r, s, wf, out, ksq, src, src_sb, tr, w, h, w, rows.P, logq_r, logl_r, rflags, sumsq,
                                it_counter, sumsq_stride, nullptr);
     }
+    HN_HIP(ctx, hipGetLastError());
+    return HN_OK;
+}
+
+// dJ/dq of both axes (k_spec_line_d1): the column pass writes plane 1 of `out`, the row pass plane 0; the two are independent
+int rect_launch_d1(hn_ctx* ctx, const LineDomain& d, const float* u, const float* lam, float* out, int batch, hipStream_t s) {
+    const LineAxis &cols = *d.cols, &rows = *d.rows;
+    const int h = d.h, w = d.w;
+    const int nbuf_c = cols.P == 1 ? 1 : 2, nbuf_r = rows.P == 1 ? 1 : 2;
+    const int Lc = rect_lines(h, w, nbuf_c, batch), Lr = rect_lines(w, h, nbuf_r, batch);
+    const size_t lds_c = ((size_t)Lc * nbuf_c * h + cols.Q + cols.P) * sizeof(float2), lds_r = ((size_t)Lr * nbuf_r * w + rows.Q + rows.P) * sizeof(float2);
+    if (lds_c > (size_t)kLineLdsAttr || lds_r > (size_t)kLineLdsAttr)
+        return fail(ctx, HN_ERR_ARG, "internal: LDS-line first-derivative kernel needs %zu / %zu bytes of LDS at %d x %d", lds_c, lds_r, h, w);
+    const LineTabs tc{cols.tw_q, cols.wp, cols.k1m, cols.k2m, cols.a, cols.b, cols.slot};
+    const LineTabs tr{rows.tw_q, rows.wp, rows.k1m, rows.k2m, rows.a, rows.b, rows.slot};
+    const dim3 grid_c((w + Lc - 1) / Lc, batch), grid_r((h + Lr - 1) / Lr, batch), block(kLineThreads);
+    hipLaunchKernelGGL((k_spec_line_d1<1>), grid_c, block, lds_c, s, u, lam, out, tc, h, w, w, cols.P, ilog2(cols.Q), ilog2(Lc));
+    hipLaunchKernelGGL((k_spec_line_d1<0>), grid_r, block, lds_r, s, u, lam, out, tr, w, h, w, rows.P, ilog2(rows.Q), ilog2(Lr));
     HN_HIP(ctx, hipGetLastError());
     return HN_OK;
 }
@@ -614,18 +741,27 @@ int spec_forward(hn_ctx* ctx, const char* who, const Medium& m, const float* wf,
     return rect_launch(ctx, d, wf, out, m.k_sq, m.k_sq_im, src, src_batch, batch, sumsq, s, it_counter, sumsq_stride, false, nullptr, m.rho_grad);
 }
 
-// out = A^H g [+ add]: spec_adjoint for a lossless medium; for a lossy one L^H(g) + (ksq - i ksq_im) g on the tables of spec_forward
+// out = A^H g [+ add]: spec_adjoint for a lossless medium; for a lossy one L^H(g) + (ksq - i ksq_im) g on the tables of spec_forward, and for a
+// variable-density one that minus D_x^H(conj(b_x) q_x g) + D_y^H(conj(b_y) q_y g) (k_sq_im may be null)
 int spec_backward(hn_ctx* ctx, const char* who, const Medium& m, const float* g, float* out, const float* add, int batch, hipStream_t s) {
     const Medium::Kind kind = m.kind();
-    if (kind == Medium::Kind::Density) return fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator has no adjoint cycle", who);
     if (kind == Medium::Kind::Lossless) return spec_adjoint(ctx, g, out, m.k_sq, add, batch, s);
-    if (m.k_sq == nullptr) return fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
+    if (m.k_sq == nullptr)
+        return kind == Medium::Kind::Density ? fail(ctx, HN_ERR_ARG, "internal: %s: the variable-density operator needs k_sq and rho_grad", who)
+                                             : fail(ctx, HN_ERR_ARG, "internal: %s: the lossy operator needs both planes of k_sq", who);
     if (g == out) return fail(ctx, HN_ERR_ARG, "%s: input and output must not alias", who);
     if (const int rc = spec_lossy_reserve(ctx, who, s); rc != HN_OK) return rc;
     if (batch <= 0) return HN_OK;
     LineDomain d;
     if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "hn_set_domain_rect has not been called");
-    return rect_launch(ctx, d, g, out, m.k_sq, m.k_sq_im, nullptr, 1, batch, nullptr, s, nullptr, 0, true, add);
+    return rect_launch(ctx, d, g, out, m.k_sq, m.k_sq_im, nullptr, 1, batch, nullptr, s, nullptr, 0, true, add, m.rho_grad);
+}
+
+int spec_density_grad(hn_ctx* ctx, const char* who, const float* lam, const float* u, float* g_rho_grad, int batch, hipStream_t s) {
+    if (batch <= 0) return HN_OK;
+    LineDomain d;
+    if (!line_domain(ctx, &d)) return fail(ctx, HN_ERR_STATE, "%s: the line tables have not been built (spec_lossy_reserve)", who);
+    return rect_launch_d1(ctx, d, u, lam, g_rho_grad, batch, s);
 }
 
 int rect_unsupported(hn_ctx* ctx, const char* who) {

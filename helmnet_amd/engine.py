@@ -403,12 +403,18 @@ class Engine:
         ``precond_iters`` 0: z = v, ``gmres_cycle`` bit for bit.  Not capturable."""
         return self._fgmres_cycle("hn_fgmres_cycle", Medium(k_sq), x, rhs, restart, tol, precond_iters, precond_scale, basis, hess, zbasis)
 
-    def _fgmres_cycle(self, stem: str, m: Medium, x, rhs, restart, tol, precond_iters, precond_scale, basis, hess, zbasis):
-        """The flexible cycle on A (``stem`` hn_fgmres_cycle) or on A^H (hn_fgmres_adjoint_cycle) for the medium's kind."""
+    def _fgmres_cycle(self, stem: str, m: Medium, x, rhs, restart, tol, precond_iters, precond_scale, basis, hess, zbasis, rho: tuple = ()):
+        """The flexible cycle on A (``stem`` hn_fgmres_cycle) or on A^H (hn_fgmres_adjoint_cycle) for the medium's kind.  ``rho``: empty, or the one
+        plane (or None) that hn_fgmres_adjoint_cycle_medium takes behind the medium."""
         restart = int(restart)
         b, basis, hess, rmse, k_used = self._gmres_buffers(stem[3:] + m.kind, x, torch.float32, m, rhs, restart, basis, hess)
         zbasis = self._zbasis(b, restart, zbasis)
-        self._call(stem, m, [_ptr(x)], [_ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters), float(precond_scale), _ptr(basis),
+        for t in rho:
+            if t is not None:
+                if t.requires_grad:
+                    raise RuntimeError(f"{stem[3:] + m.kind}: rho requires grad; the GMRES cycle is not differentiable")
+                self._chk(t, (b, 1, *self.hw), "rho")
+        self._call(stem, m, [_ptr(x)], [*map(_ptr, rho), _ptr(rhs), rhs.shape[0], b, restart, float(tol), int(precond_iters), float(precond_scale), _ptr(basis),
                                        _ptr(zbasis), _ptr(hess), _ptr(rmse), _ptr(k_used)])
         return rmse, k_used
 
@@ -652,6 +658,37 @@ class Engine:
                                             _ptr(g_src), self._stream())
         _lib.check(rc, self.ctx, "hn_adjoint_grad_lossy")
         return g_k_sq, g_k_sq_im, g_src
+
+    # ---- heterogeneous density: the adjoint operator and adjoint-state gradients ----
+    def residual_vjp_medium(self, g: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor], rho_grad: torch.Tensor) -> torch.Tensor:
+        """A_rho^H g (hn_residual_vjp_medium): L^H g - D_x^H(conj(b_x) q_x g) - D_y^H(conj(b_y) q_y g) + (k_sq - i k_sq_im) g, the J^T g of
+        ``residual_medium`` with respect to the wavefield.  ``k_sq_im`` may be None.  Square and rectangular domains."""
+        return self._residual_vjp(Medium(k_sq, k_sq_im, _tensor(rho_grad, "rho_grad")), g)
+
+    def fgmres_adjoint_cycle_medium(self, x: torch.Tensor, k_sq: torch.Tensor, k_sq_im: Optional[torch.Tensor], rho_grad: torch.Tensor,
+                                    rho: Optional[torch.Tensor], rhs: torch.Tensor, restart: int, tol: float, precond_iters: int, precond_scale: float,
+                                    basis: Optional[torch.Tensor] = None, zbasis: Optional[torch.Tensor] = None, hess: Optional[torch.Tensor] = None):
+        """``fgmres_adjoint_cycle_lossy`` on A_rho^H x = rhs (hn_fgmres_adjoint_cycle_medium), preconditioned by ``precond_iters`` iterations of
+        ``step_medium`` between the similarity weight W / rho: ``rho`` [B,1,n,n] fp32, positive (only its ratios matter); None is allowed with
+        ``precond_iters`` 0 alone, which is plain restarted GMRES on A_rho^H.  ``k_sq_im`` may be None.  Square domains.  Not capturable."""
+        return self._fgmres_cycle("hn_fgmres_adjoint_cycle", Medium(k_sq, k_sq_im, _tensor(rho_grad, "rho_grad")), x, rhs, restart, tol, precond_iters,
+                                  precond_scale, basis, hess, zbasis, rho=(rho,))
+
+    def adjoint_grad_medium(self, lam: torch.Tensor, u: torch.Tensor, src_batch: Optional[int], lossy: bool = True):
+        """``adjoint_grad_lossy`` for the variable-density operator (hn_adjoint_grad_medium): returns (g_k_sq, g_k_sq_im, g_rho_grad, g_src) with
+        g_rho_grad [B,2,n,n] = dJ/dq: plane 0 Re(conj(lam) b_x D_x u), plane 1 Re(conj(lam) b_y D_y u); the others as ``adjoint_grad_lossy`` returns
+        them, bit for bit.  ``lossy`` False (a medium without absorption): g_k_sq_im is None and is not computed."""
+        b = lam.shape[0]
+        self._chk(lam, (b, 2, *self.hw), "lam")
+        self._chk(u, (b, 2, *self.hw), "u")
+        g_k_sq = torch.empty(b, 1, *self.hw, device=self.device, dtype=torch.float32)
+        g_k_sq_im = torch.empty_like(g_k_sq) if lossy else None
+        g_rho_grad = torch.empty(b, 2, *self.hw, device=self.device, dtype=torch.float32)
+        g_src = None if src_batch is None else torch.empty(int(src_batch), 2, *self.hw, device=self.device, dtype=torch.float32)
+        rc = self.lib.hn_adjoint_grad_medium(self.ctx, _ptr(lam), _ptr(u), 1 if src_batch is None else int(src_batch), b, _ptr(g_k_sq), _ptr(g_k_sq_im),
+                                             _ptr(g_rho_grad), _ptr(g_src), self._stream())
+        _lib.check(rc, self.ctx, "hn_adjoint_grad_medium")
+        return g_k_sq, g_k_sq_im, g_rho_grad, g_src
 
     # ---- training step (hn_train_grad / hn_adam_step; SURVEY.md 8 f4) -------------------------------------------------
     def train_reserve(self, batch: int, n_unroll: int):

@@ -246,7 +246,7 @@ def check_adjoint_rhs(solver, sos_maps, rhs):
 
 def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: int = 20, max_outer: int = 50, tol: float = 1e-4,
                   x0: Optional[torch.Tensor] = None, precondition: Optional[str] = None, precond_iterations: int = 10,
-                  precond_scale: Optional[float] = None, backend: str = "hip", absorption=None):
+                  precond_scale: Optional[float] = None, backend: str = "hip", absorption=None, density=None):
     """Solve the ADJOINT system A^H lam = rhs for every map of ``sos_maps`` [B,1,n,n]: A u = L(u) + k_sq * u is the operator of ``gmres``, A^H its
     conjugate transpose (``hn_residual_vjp``), ``rhs`` [B or 1,2,n,n] a cotangent dJ/du as two real planes.  Restarted GMRES with the cycle fused
     on the device (hn_fgmres_adjoint_cycle), on the host loop of ``gmres(backend="hip")`` (``drive_cycles``): one synchronisation per cycle, every
@@ -261,9 +261,17 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
     ``absorption`` (alpha, as in ``gmres``): the medium is lossy, A u = L(u) + (k_sq + i k_sq_im) u with both planes from
     ``helmnet_amd.absorption.complex_k_sq``, and A^H g = L^H(g) + (k_sq - i k_sq_im) g.  The cycles run on hn_fgmres_adjoint_cycle_lossy (the learned
     preconditioner is the lossy iteration between the same W) and the true-residual check on hn_residual_vjp_lossy.  None: the code path and the bits
-    of before."""
+    of before.
+
+    ``density`` (rho, a tensor broadcastable to ``sos_maps``, as in ``gmres``): the operator is the variable-density one, with or without
+    ``absorption``, A_rho^H g = L^H g - D_x^H(conj(b_x) q_x g) - D_y^H(conj(b_y) q_y g) + (k_sq - i k_sq_im) g with q = grad ln rho
+    (``density.log_density_gradient``).  The cycles run on hn_fgmres_adjoint_cycle_medium -- the learned preconditioner is the variable-density
+    iteration between the weight W / rho, which is why rho itself goes down and not only q -- and the true-residual check on hn_residual_vjp_medium.
+    None: the code path and the bits of before."""
     if absorption is not None and backend != "hip":
         raise ValueError("absorption needs backend='hip' (gmres_adjoint has no other backend)")
+    if density is not None and backend != "hip":
+        raise ValueError("density needs backend='hip' (gmres_adjoint has no other backend)")
     if precondition not in (None, "learned"):
         raise ValueError(f"unknown precondition {precondition!r} (choose None or 'learned')")
     if precondition is not None and backend != "hip":
@@ -274,7 +282,7 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
         raise ValueError(f"precond_iterations must be >= 0 (got {precond_iterations})")
     solver._require_square("gmres_adjoint")
     check_adjoint_rhs(solver, sos_maps, rhs)
-    _require_no_grad("gmres_adjoint", sos_maps, rhs, x0, absorption)
+    _require_no_grad("gmres_adjoint", sos_maps, rhs, x0, absorption, density)
     restart, max_outer, tol = int(restart), int(max_outer), float(tol)
     iters = 0 if precondition is None else int(precond_iterations)
     alpha = 1.0
@@ -289,6 +297,16 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
         m = Medium(*complex_k_sq(sos_maps, absorption, solver.hparams.omega))
     else:
         m = Medium(solver.get_initials(sos_maps)[0].contiguous())
+    rho = ()
+    if density is not None:
+        if not isinstance(density, torch.Tensor):
+            raise TypeError("density must be a tensor broadcastable to the sound-speed maps")
+        try:
+            plane = density.detach().to(eng.device, torch.float32).expand_as(m.k_sq).contiguous()
+        except RuntimeError as e:
+            raise ValueError(f"density of shape {tuple(density.shape)} does not broadcast to {tuple(m.k_sq.shape)}") from e
+        m = Medium(m.k_sq, m.k_sq_im, solver._rho_grad(plane, m.k_sq))
+        rho = (plane,)        # the cycle's one argument behind the medium: the preconditioner's weight is W / rho
     rhs = rhs.detach().to(eng.device).float().contiguous()
     bsz, n, dev = sos_maps.shape[0], sos_maps.shape[-1], eng.device
     x = (torch.zeros(bsz, 2, n, n, device=dev) if x0 is None else x0.detach().to(dev, torch.float32)).contiguous().clone()
@@ -297,7 +315,7 @@ def gmres_adjoint(solver, sos_maps: torch.Tensor, rhs: torch.Tensor, restart: in
     hess = torch.empty(bsz, restart + 1, restart, 2, dtype=torch.float32, device=dev)
 
     def cycle():
-        rmse, k_used = getattr(eng, "fgmres_adjoint_cycle" + m.kind)(x, *m.planes(), rhs, restart, tol, iters, alpha, basis, zbasis, hess)
+        rmse, k_used = getattr(eng, "fgmres_adjoint_cycle" + m.kind)(x, *m.planes(), *rho, rhs, restart, tol, iters, alpha, basis, zbasis, hess)
         both = torch.cat([rmse.reshape(-1), k_used.float()]).cpu().numpy()          # the one synchronisation of the cycle
         eng.check_async_errors()
         return both[: (restart + 1) * bsz].reshape(restart + 1, bsz), both[(restart + 1) * bsz:].astype(np.int64)

@@ -435,8 +435,8 @@ class IterativeSolver(nn.Module):
         return self.engine().laplacian(x.float().contiguous())
 
     def _refuse_medium_grad(self, what: str, density: bool, *tensors):
-        """Absorbing media have one differentiable path, the adjoint-state gradients of ``solve_implicit`` (which detaches before it comes here), and
-        variable density has none at all; the library has no derivative of either solver LOOP: an input that requires grad -- or
+        """Absorbing media and variable density have one differentiable path, the adjoint-state gradients of ``solve_implicit`` (which detaches
+        before it comes here); the library has no derivative of either solver LOOP: an input that requires grad -- or
         differentiable(True) under grad mode -- raises before anything touches the device.  ``density``: the medium has one, and is named for it."""
         if any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors) or (self._differentiable and torch.is_grad_enabled()):
             name, operator = ("density", "variable-density") if density else ("absorption", "lossy")
@@ -885,13 +885,14 @@ class IterativeSolver(nn.Module):
         the conjugate transpose of ``gmres``'s operator (``helmnet_amd.gmres.gmres_adjoint``, whose keyword arguments pass through).
         ``precondition="learned"`` (the default here: measured faster than the plain cycle at 96^2 and at 256^2): the flexible cycle
         with this solver's network between the similarity weight W; None: plain restarted GMRES.  ``out["wavefield"]`` is lam.  No gradients.
-        ``absorption=alpha`` among the keyword arguments: the adjoint of the lossy operator (hn_fgmres_adjoint_cycle_lossy)."""
+        ``absorption=alpha`` among the keyword arguments: the adjoint of the lossy operator (hn_fgmres_adjoint_cycle_lossy); ``density=rho``: the
+        adjoint of the variable-density operator (hn_fgmres_adjoint_cycle_medium), with or without absorption."""
         from .gmres import gmres_adjoint
         self._require_square("adjoint_solve")
         return gmres_adjoint(self, sos, cotangent, precondition=precondition, **kwargs)
 
     def solve_implicit(self, sos, tol: float = 1e-4, adjoint_tol: Optional[float] = None, restart: int = 20, max_cycles: int = 50,
-                       precondition: Optional[str] = "learned", precond_iterations: int = 10, x0=None, absorption=None) -> dict:
+                       precondition: Optional[str] = "learned", precond_iterations: int = 10, x0=None, absorption=None, density=None) -> dict:
         """The solution of A u = source to ``tol`` with the gradient of the SOLUTION, by the adjoint-state method: the forward solve is ``gmres`` (fused
         cycles on the device, under no_grad on detached inputs, nothing taped), and ``out["wavefield"]`` carries one autograd node whose backward solves
         A^H lam = dJ/du to ``adjoint_tol`` (default ``tol``; ``adjoint_solve`` with the same restart, max_cycles, precondition and precond_iterations),
@@ -904,8 +905,13 @@ class IterativeSolver(nn.Module):
         one autograd node solves the lossy adjoint system (hn_fgmres_adjoint_cycle_lossy), forms dJ/dk_sq, dJ/dk_sq_im and dJ/dsource
         (hn_adjoint_grad_lossy) and chains through ``absorption.complex_k_sq`` to ``sos``, to ``absorption`` when it is a tensor that requires grad
         (summed over the dimensions it broadcasts along) and to ``self.source``.  A number gets no gradient.  None: the code path and the bits of
-        before."""
-        from .autograd import SolveImplicit, SolveImplicitLossy
+        before.
+        ``density`` (rho, a tensor broadcastable to ``sos``, as in ``gmres``): the medium has a heterogeneous density, with or without ``absorption``.
+        The forward solve is ``gmres(..., density=...)`` on detached inputs; the one autograd node solves A_rho^H lam = dJ/du
+        (hn_fgmres_adjoint_cycle_medium), forms dJ/dk_sq, dJ/dk_sq_im, dJ/dq and dJ/dsource in one call (hn_adjoint_grad_medium) and chains to
+        ``sos``, to ``absorption``, to ``density`` when it requires grad (``density.log_density_gradient_vjp``, summed to its own shape) and to
+        ``self.source``.  None: the code path and the bits of before."""
+        from .autograd import SolveImplicit, SolveImplicitLossy, SolveImplicitMedium
         from .gmres import gmres
         self._require_square("solve_implicit")
         n = int(self.hparams.domain_size)
@@ -926,15 +932,31 @@ class IterativeSolver(nn.Module):
                 fits = False
             if not fits:
                 raise ValueError(f"absorption of shape {tuple(alpha.shape)} does not broadcast to sos {tuple(sos.shape)}")
+        if density is not None:
+            if not isinstance(density, torch.Tensor):
+                raise TypeError("density must be a tensor broadcastable to the sound-speed maps")
+            try:
+                fits = density.dim() == 4 and tuple(torch.broadcast_shapes(tuple(density.shape), tuple(sos.shape))) == tuple(sos.shape)
+            except RuntimeError:
+                fits = False
+            if not fits:
+                raise ValueError(f"density of shape {tuple(density.shape)} does not broadcast to sos {tuple(sos.shape)}")
         common = dict(restart=int(restart), precondition=precondition, precond_iterations=int(precond_iterations))
         lossy = {} if alpha is None else {"absorption": alpha.detach()}
+        if density is not None:
+            lossy["density"] = density.detach()
         with torch.no_grad():
             out = gmres(self, sos.detach(), max_outer=int(max_cycles), tol=float(tol), x0=None if x0 is None else x0.detach(), backend="hip", **common,
                         **lossy)
         info: dict = {}
         spec = {"solver": self, "wavefield": out["wavefield"], "info": info,
                 "adjoint_kwargs": dict(common, max_outer=int(max_cycles), tol=float(tol if adjoint_tol is None else adjoint_tol))}
-        if alpha is None:
+        if density is not None:
+            dev = out["wavefield"].device
+            spec["lossy"] = alpha is not None
+            a = torch.zeros((), device=dev) if alpha is None else alpha.to(dev).float()
+            out["wavefield"] = SolveImplicitMedium.apply(spec, sos.to(dev).float(), a, density.to(dev).float(), self._src_graph())
+        elif alpha is None:
             out["wavefield"] = SolveImplicit.apply(spec, sos.float(), self._src_graph())
         else:
             dev = out["wavefield"].device

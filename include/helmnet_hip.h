@@ -624,7 +624,9 @@ int hn_fgmres_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, const float*
  * [measured, MI355X, profiles/density_bench.txt] hn_residual_medium / hn_residual_lossy, alternating in one process: 1.060 at 256^2 x 32, 1.108 at
  * 512^2 x 16, 1.070 at 400^2 x 16 (from the traffic alone, 8 more bytes on about 56 per pixel: at most 1.14); one hn_step_medium iteration /
  * one hn_step_lossy iteration 1.023, 1.018, 1.019.
- * No entry point exists for: the adjoint of A_rho and adjoint-state gradients, anything float64, gradients through the loop, training, the stream of maps (hn_stream_swap). */
+ * The adjoint of A_rho and the adjoint-state gradients of a converged solve are further down: hn_residual_vjp_medium (A_rho^H g),
+ * hn_fgmres_adjoint_cycle_medium (A_rho^H lambda = g) and hn_adjoint_grad_medium (dJ/dk_sq, dJ/dk_sq_im, dJ/dq, dJ/dsrc).
+ * No entry point exists for: anything float64, gradients through the loop, training, the stream of maps (hn_stream_swap). */
 
 /* hn_residual_lossy with the density term; every legal square size and every rectangular domain.  rho_grad and k_sq_im may overlap nothing written
  * ("hn_residual_medium: rho_grad overlaps res"); 4-byte alignment suffices. */
@@ -671,6 +673,60 @@ int hn_fgmres_adjoint_cycle_lossy(hn_ctx* ctx, float* x, const float* k_sq, cons
  * (HN_ERR_UNSUPPORTED on a rectangular domain).  A refused call leaves the outputs alone. */
 int hn_adjoint_grad_lossy(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_k_sq_im, float* g_src,
                           void* stream);
+
+/* ---- heterogeneous density: the adjoint operator and adjoint-state gradients (added within ABI v7: new entry points, nothing existing changes) ----
+ * With D the Fourier first derivative of an axis and q = grad ln rho (real):
+ *     A_rho u   = L(u) - b_x q_x D_x u - b_y q_y D_y u + (k_sq + i k_sq_im) u
+ *     A_rho^H g = L^H g - D_x^H(conj(b_x) q_x g) - D_y^H(conj(b_y) q_y g) + (k_sq - i k_sq_im) g.
+ * Per axis the lossy adjoint pass loads conj(a) g and conj(b) g; here the first of the two loads is conj(a - q b) g, q read from plane AXIS of rho_grad at
+ * the element loaded.  Nothing else differs: no further buffer, no further transform; LDS and lines per block are the lossy adjoint pass's.
+ * For A_rho u = src, a real loss J, g = dJ/du and A_rho^H lambda = g:
+ *     dJ/dk_sq, dJ/dk_sq_im, dJ/dsrc    hn_adjoint_grad_lossy's formulas and bits
+ *     dJ/dq_x = Re(conj(lambda) b_x D_x u),   dJ/dq_y = Re(conj(lambda) b_y D_y u)      (no dependence on q itself)
+ *     dJ/dln rho = -(G_x dJ/dq_x + G_y dJ/dq_y),   dJ/drho = dJ/dln rho / rho
+ * with G the real, antisymmetric map q = G ln rho of the axis (helmnet_amd.density.log_density_gradient; its transpose is -G, the Nyquist mode drops out).
+ * The library computes dJ/dq; the last two lines belong to whoever made q (helmnet_amd.density.log_density_gradient_vjp for the spectral one).
+ * The learned preconditioner of the adjoint cycle uses A^-H ~ conj(X A^-1 X^-1 conj(.)).  For the constant-density operators X = W = gamma_y[i] gamma_x[j];
+ * here X = W / rho, because in the continuous problem A_rho = rho * (a W-symmetric operator).  Dense float64 A_rho of the ring medium (tests/
+ * density_common.ring_medium), defect = ||A^T - X A X^-1||_F / ||A||_F, 2-norm = ||A^H M - I||_2 with M built from the exact inverse:
+ *        n   max|q|   defect W   W/rho   W rho     2-norm W   W/rho   W rho
+ *       32    0.21     0.056     0.034   0.107       2.40      0.19    5.75
+ *       48    0.28     0.061     0.031   0.124       6.41      0.28   16.5
+ * With W alone the exact inverse is not even a contraction; with W / rho it is.  So the cycle takes rho itself (only its ratios matter).
+ * [measured, MI355X, profiles/density_bench.txt, third table] hn_residual_vjp_medium / hn_residual_vjp_lossy, alternating in one process: 1.113 at
+ * 256^2 x 32, 1.133 at 512^2 x 16, 1.030 at 400^2 x 16; hn_adjoint_grad_medium 0.065 / 0.130 / 0.140 ms, about three quarters of one
+ * hn_residual_vjp_medium (hn_adjoint_grad_lossy, a single pointwise launch: 0.011 / 0.015 / 0.011 ms).
+ * [measured, profiles/adjoint_bench_density.txt] the adjoint solve to 1e-4, batch 4, restart 20, alpha 0.1 with density: plain 22 cycles / 0.034 s at
+ * 96^2 and 26 / 0.062 s at 256^2; learned between W / rho 1 cycle (200 UNet evaluations) / 0.040 s and 1 / 0.049 s; learned between W alone (ones in
+ * rho's place) the same within one inner step -- with the learned inverse the two weights cannot be told apart on this medium.
+ *
+ * hn_residual_vjp_medium: out = A_rho^H g; every legal square size and every rectangular domain.  Arguments as hn_residual_vjp_lossy, rho_grad
+ * [B,2,h,w] behind k_sq_im, which MAY be NULL (a lossless medium).  HN_ERR_ARG: a NULL pointer (a NULL rho_grad with a message that names
+ * hn_residual_vjp_lossy / hn_residual_vjp), batch < 1, g == out, k_sq_im or rho_grad overlapping out.  The tables and the capture rule are the lossy call's. */
+int hn_residual_vjp_medium(hn_ctx* ctx, const float* g, const float* k_sq, const float* k_sq_im /* NULL: lossless */, const float* rho_grad,
+                           float* out, int batch, void* stream);
+
+/* hn_fgmres_adjoint_cycle_lossy on A_rho^H x = rhs.  rho: fp32 [B,1,n,n], > 0, read only, 16-byte aligned, overlapping nothing (as k_sq); it is read by
+ * the preconditioner alone, normalised per sample by its first pixel rho[b,0,0,0] (a corner of the PML: the background), so that only ratios of rho
+ * enter and the network sees the magnitude precond_scale sets, whatever the units of rho.  CALLER'S OBLIGATION: that pixel must hold the density
+ * of the background medium (water in a skull map; helmnet_amd and the tests keep the PML in the background) -- a map whose corner is not the
+ * reference density changes the magnitude the network sees, which costs cycles, not correctness (any positive weight leaves flexible GMRES exact): src = precond_scale * conj(v) * rho / W goes into precond_iters iterations of the hn_step_medium problem (zero start, zero
+ * hidden states), and z = conj((W / rho) * wf) / precond_scale comes out (two streaming kernels, the lossy cycle's traffic plus the one plane; with
+ * rho == 1 their bits are the lossy cycle's kernels').  precond_iters == 0 is plain restarted GMRES on A_rho^H: zbasis[:, j] == basis[:, j] bit for bit,
+ * rho is not read and may be NULL.  precond_iters >= 1 with rho == NULL returns HN_ERR_ARG with a message that names rho.  Square domains only
+ * (HN_ERR_UNSUPPORTED on a rectangular one); not capturable; every other rule is hn_fgmres_adjoint_cycle_lossy's, k_sq_im may be NULL. */
+int hn_fgmres_adjoint_cycle_medium(hn_ctx* ctx, float* x, const float* k_sq, const float* k_sq_im /* NULL ok */, const float* rho_grad,
+                           const float* rho /* [B,1,n,n], > 0; NULL allowed only with precond_iters == 0 */, const float* rhs, int rhs_batch, int batch,
+                           int restart, float tol, int precond_iters, float precond_scale, float* basis, float* zbasis, float* hess, float* rmse,
+                           int* k_used, void* stream);
+
+/* hn_adjoint_grad_lossy with one more output, g_rho_grad [B,2,n,n] = dJ/dq (plane 0: x, plane 1: y), per sample.  g_k_sq, g_k_sq_im and g_src are
+ * hn_adjoint_grad_lossy's bit for bit (the same launch); with g_k_sq_im == NULL they are hn_adjoint_grad's.  g_rho_grad comes from two line passes
+ * that transform u, multiply by i k alone, transform back and store Re(conj(lambda) b D u): one LDS buffer per line on a power-of-two size, two
+ * otherwise.  g_rho_grad is required, 16-byte aligned, and overlaps no other argument.  Square domains only.  The line tables are the lossy route's: a
+ * first call on a square domain that has them to build is refused under stream capture (HN_ERR_STATE, nothing enqueued); later calls are capturable. */
+int hn_adjoint_grad_medium(hn_ctx* ctx, const float* lambda, const float* u, int src_batch, int batch, float* g_k_sq, float* g_k_sq_im /* NULL ok */,
+                           float* g_rho_grad /* [B,2,n,n] */, float* g_src /* NULL ok */, void* stream);
 
 /* ---- absorbing media in float64 (added within ABI v7: new entry points, nothing existing changes) ----
  * hn_residual_f64_lossy: res = L(wf) + (k_sq + i k_sq_im) wf - src in float64, hn_residual_f64's contract (res and / or rmse, the fixed-order
